@@ -9,10 +9,17 @@ de novo stutter EM and the genotype calls of BASELINE configs[2]).  STR loci are
 disjoint loci of one seeded set, no collective touches the data path.  Default: weak scaling (per-GPU work
 fixed, rank r takes loci [r*n, (r+1)*n)); --scaling strong splits the workload's loci over the ranks.
 `value` = alignments of all ranks x K / max-over-ranks wall time of the K timed steps, with inputs already
-resident in HBM; the host-inclusive figure (SURVEY §8d's metric taken literally: host arrays in, results out,
-through the streaming C-ABI) is reported beside it under "end_to_end".
+resident in HBM; `ms_per_step` = that wall time / K.
 
-Also printed in the same JSON line:
+A plain run sets up, warms up, times the K steps and prints the JSON line (metric, value, unit, ms_per_step, dtype,
+config, ...); nothing else.  --dump-outputs DIR also writes what the timed path computed in its last step (see
+dump_outputs).  --full adds every other measurement and check to the line, each taken after the timed steps: the
+host-inclusive figure (SURVEY §8d's metric taken literally: host arrays in, results out, through the streaming
+C-ABI) under "end_to_end", the stages around the forward pass, the per-kernel phase times and the blocks below,
+host-side timings, the workload breakdowns of c3 / c4, the pinned-child runs and, with N > 1, every rank's rate and
+the cross-device check of the ranks' results.
+
+Also printed in the same JSON line with --full:
   roofline      dominant kernel: ALGORITHMIC bytes per launch (SURVEY.md §8d formula, computed from the batch)
                 / average launch duration measured with HIP events on the launch stream, vs the 8 TB/s HBM peak;
                 traffic = L2<->fabric bytes from the committed rocprofv3 --pmc passes (profiles/).  The path is an
@@ -48,6 +55,22 @@ WORKLOADS = {
     "c4": (100, 5000, 32, 150, 60, 40, "BASELINE configs[3] per-locus shape (one GPU's shard): 100 loci x 1000 samples x 5 reads x 32 alleles; forward HMM + R x A^2 posteriors + genotype calls in the step"),
     "c5": (256, 200, 128, 250, 110, 100, "BASELINE configs[4] stress: 256 loci x 200 250bp reads x 128 alleles, ~100bp STR blocks"),
 }
+
+
+DUMP_BYTES = 60 << 20     # --dump-outputs: the data of all files together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float64 (the int32 outputs are exact in it).  An array longer than its share of
+    DUMP_BYTES is replaced by a fixed sample of its elements (indices drawn with SEED, kept in index order), written as <name>_sample.npy:
+    two builds run with the same arguments write the same elements and can be compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // 8 // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).ravel()
+        if a.size > cap:
+            a, name = a[np.sort(np.random.default_rng(SEED).choice(a.size, cap, replace=False))], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _cpu_worker(argv):
@@ -389,6 +412,10 @@ def main():
                     help="give the process N host CPUs: the library's host threads (HIPSTR_HOST_THREADS) AND the affinity mask of every thread of the "
                          "process (feeder, stream workers, collector included) — what one rank has on a node whose cores are shared by 8 ranks")
     ap.add_argument("--e2e-only", action="store_true", help="only the end-to-end (stream) measurement; prints its block as one JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement and check beyond the headline (end-to-end, pipeline stages, CPU baseline, per-kernel and roofline "
+                         "figures, host timings, workload breakdowns, pinned children, per-rank rates and the cross-device check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
     if args.host_threads > 0:
         # before any thread of the process exists (torch, the library's pool, the stream's workers): they inherit the mask
@@ -459,11 +486,12 @@ def main():
         raise SystemExit("upload failed: " + hmm.hipstr_last_error().decode())
     torch.cuda.synchronize()
     t_upload_cold = time.perf_counter() - t0          # first call of the process: device and pinned blocks come from the driver
-    hmm.hipstr_hmm_free(dev)
-    t0 = time.perf_counter()
-    dev = hmm.hipstr_hmm_upload(sb.ptr)
-    torch.cuda.synchronize()
-    t_upload = time.perf_counter() - t0               # steady state: blocks from the library's caches
+    if args.full:
+        hmm.hipstr_hmm_free(dev)
+        t0 = time.perf_counter()
+        dev = hmm.hipstr_hmm_upload(sb.ptr)
+        torch.cuda.synchronize()
+        t_upload = time.perf_counter() - t0           # steady state: blocks from the library's caches
     n_aln = C.c_int64(0); algo = C.c_int64(0); cells = C.c_int64(0)
     hmm.hipstr_hmm_workload(dev, C.byref(n_aln), C.byref(algo), C.byref(cells))
     hap_off = np.ctypeslib.as_array(sb.ptr.contents.hap_off, shape=(loci + 1,))
@@ -528,6 +556,7 @@ def main():
     if not pd:
         raise SystemExit("posterior upload failed: " + hmm.hipstr_last_error().decode())
     em_stats = {}
+    em_last = {}
 
     def step():
         if args.workload == "c3":
@@ -535,6 +564,7 @@ def main():
             tr, st_, it_, ll_ = capi.run_em(hmm, "hipstr_", **em_kw)
             em_stats["em_s"] = em_stats.get("em_s", 0.0) + time.perf_counter() - t_em
             em_stats["trained"] = int(tr.sum()); em_stats["iterations"] = int(it_.sum())
+            em_last.update(em_trained=tr, em_stutter_params=st_, em_iterations=it_, em_log_likelihood=ll_)
         if hmm.hipstr_hmm_align(dev, None) != 0 or hmm.hipstr_post_launch(pd, None) != 0:
             raise SystemExit("launch failed: " + hmm.hipstr_last_error().decode())
         if args.workload == "c4":
@@ -557,30 +587,47 @@ def main():
         step()
     fence()
     em_stats.clear()
-    hmm.hipstr_hmm_profile(dev, 1)
+    if args.full:
+        hmm.hipstr_hmm_profile(dev, 1)            # device events around every kernel group of the timed passes: the per-kernel figures
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    hmm.hipstr_hmm_profile(dev, 0)
-    ms = (C.c_float * (4 * args.steps))()
-    n_ms = hmm.hipstr_hmm_profile_read(dev, ms, args.steps)
-    phase_ms = np.array(ms[:4 * n_ms], dtype=np.float64).reshape(-1, 4).mean(axis=0) if n_ms > 0 else np.full(4, np.nan)
-    phase_names = ["hs_lead_kernel", "hs_str_kernel", "hs_trail_kernel", "hs_combine_kernel"]
-    dom = int(np.nanargmax(phase_ms)) if n_ms > 0 else 1
-    kernel_ms = float(phase_ms[dom])          # average duration of the dominant kernel (group) per pass
+    if args.full:
+        hmm.hipstr_hmm_profile(dev, 0)
+        ms = (C.c_float * (4 * args.steps))()
+        n_ms = hmm.hipstr_hmm_profile_read(dev, ms, args.steps)
+        phase_ms = np.array(ms[:4 * n_ms], dtype=np.float64).reshape(-1, 4).mean(axis=0) if n_ms > 0 else np.full(4, np.nan)
+        phase_names = ["hs_lead_kernel", "hs_str_kernel", "hs_trail_kernel", "hs_combine_kernel"]
+        dom = int(np.nanargmax(phase_ms)) if n_ms > 0 else 1
+        kernel_ms = float(phase_ms[dom])          # average duration of the dominant kernel (group) per pass
 
-    # --- a D2H of the results after the timed region (sanity + the PCIe-inclusive figure for DESIGN.md)
-    t0 = time.perf_counter()
-    probs = np.zeros(sb.n_out); seeds = np.zeros(sb.n_reads, np.int32)
-    assert hmm.hipstr_hmm_fetch(dev, probs.ctypes.data_as(capi._f64p), seeds.ctypes.data_as(capi._i32p)) == 0
-    t_fetch = time.perf_counter() - t0
-    if not os.environ.get("HIPSTR_BENCH_NOCHECK"):       # kernel ablation builds (timing only, results invalid) set this
-        assert np.all(np.isfinite(probs)) and np.all(probs <= 1e-10), "forward scores must be finite log-likelihoods <= 0"
+    if args.full or args.dump_outputs:
+        # --- a D2H of the results after the timed region (sanity + the PCIe-inclusive figure for DESIGN.md)
+        t0 = time.perf_counter()
+        probs = np.zeros(sb.n_out); seeds = np.zeros(sb.n_reads, np.int32)
+        assert hmm.hipstr_hmm_fetch(dev, probs.ctypes.data_as(capi._f64p), seeds.ctypes.data_as(capi._i32p)) == 0
+        t_fetch = time.perf_counter() - t0
+        if not os.environ.get("HIPSTR_BENCH_NOCHECK"):       # kernel ablation builds (timing only, results invalid) set this
+            assert np.all(np.isfinite(probs)) and np.all(probs <= 1e-10), "forward scores must be finite log-likelihoods <= 0"
+
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (rank 0's loci): the forward scores and seeds, then the
+        # genotype calls where the step makes them (c3, c4: the posteriors stay on the device), else the posteriors
+        outs = {"aln_log_probs": probs, "seeds": seeds}
+        if args.workload in ("c3", "c4"):
+            outs.update(zip((f for f, _ in capi.HipstrGtOut._fields_), gt_k))
+            outs.update(em_last)
+        else:
+            post = np.zeros(int(pb.post_off[-1])); tot = np.zeros(loci); gt = np.zeros(2 * loci, np.int32); lt = np.zeros(loci)
+            if hmm.hipstr_post_fetch(pd, post.ctypes.data_as(capi._f64p), tot.ctypes.data_as(capi._f64p), gt.ctypes.data_as(capi._i32p), lt.ctypes.data_as(capi._f64p)) != 0:
+                raise SystemExit("hipstr_post_fetch: " + hmm.hipstr_last_error().decode())
+            outs.update(log_post=post, sample_total_ll=tot, map_gt=gt, locus_total_ll=lt)
+        dump_outputs(args.dump_outputs, outs)
 
     per_rank = None; e2e_multi = None; rank_info = None; cross_check = None
-    if world > 1:
+    if world > 1 and args.full:
         dev_t = "cpu" if share else "cuda"
         # every rank's own resident rate, and the end-to-end rate (host arrays in -> results out through the stream) of all ranks at once
         mine = torch.tensor([float(n_aln.value) * args.steps / elapsed], dtype=torch.float64, device=dev_t)
@@ -627,6 +674,8 @@ def main():
             raise SystemExit("bench.py: results of " + "; ".join(verdict[0]) + " differ from rank 0's device on the same loci — no rate is reported")
         cross_check = {"loci_per_rank": len(sample), "ranks_checked_against_rank0": world - 1, "mismatches": 0,
                        "devices": [{k: c.get(k) for k in ("rank", "pci_bus_id", "numa_node", "device_name", "cpus_allowed")} for c in chk]}
+    if world > 1:
+        dev_t = "cpu" if share else "cuda"
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev_t)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
@@ -723,9 +772,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_aln * args.steps / elapsed
-        achieved = algo.value / (kernel_ms * 1e-3) / 1e9 if kernel_ms == kernel_ms else None
-        traffic, traffic_src = pmc_traffic(phase_names[dom].split("<")[0], n_aln.value)
-        valu = valu_block(dict(zip(phase_names, [float(x) for x in phase_ms])), n_aln.value) if n_ms > 0 else None
         out = {
             "metric": "read x allele HMM alignments/sec", "value": value, "unit": "alignments/s",
             "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -735,6 +781,12 @@ def main():
                        "alignments_per_step_per_gpu": n_aln.value, "sharding": "loci across ranks, no collective on the data path",
                        "str_allele_sides_by_kernel": str_kinds},
             "loci_per_sec": total_loci * args.steps / elapsed,
+        }
+    if rank == 0 and args.full:
+        achieved = algo.value / (kernel_ms * 1e-3) / 1e9 if kernel_ms == kernel_ms else None
+        traffic, traffic_src = pmc_traffic(phase_names[dom].split("<")[0], n_aln.value)
+        valu = valu_block(dict(zip(phase_names, [float(x) for x in phase_ms])), n_aln.value) if n_ms > 0 else None
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
                          "frac": (achieved / 8000.0) if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
                          "traffic_scope": "the dominant kernel's launches of one pass (FETCH_SIZE x 2 + WRITE_SIZE)",
@@ -764,7 +816,7 @@ def main():
             "valu": valu,
             "host": {"synth_s": t_gen, "prepare_upload_s": t_upload, "prepare_upload_first_call_s": t_upload_cold, "fetch_s": t_fetch,
                      "value_incl_prepare_pcie": total_aln / world / (t_upload + elapsed / args.steps + t_fetch) * world},
-        }
+        })
         if args.gpus == 1 and not args.no_pipeline:
             # passes: as many as the resident measurement, but at least ~120 M alignments' worth (about a second) — a stream that sees a few batches
             # measures its own fill and drain, not its rate (round 6: p30 under the 2-CPU pin 0.78-0.83 of resident over 31 passes, 0.87-0.94 over 150)
@@ -837,6 +889,7 @@ def main():
                         out["value_end_to_end_host_share_8gpu_p30"] = sh["alignments_per_s"]
                     except Exception as ex:
                         out["end_to_end_host_share_8gpu_p30"] = {"error": repr(ex)[:200]}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     hmm.hipstr_post_free(pd)
     hmm.hipstr_hmm_free(dev)

@@ -27,7 +27,7 @@ def _bench(args, nproc=1, port=29531):
 
 
 def test_single_gpu_line_has_every_contract_field():
-    d = _bench(["--steps", "2", "--warmup", "1", "--loci", "24", "--no-cpu-baseline"])
+    d = _bench(["--steps", "2", "--warmup", "1", "--loci", "24", "--no-cpu-baseline", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "end_to_end", "valu"):
         assert k in d, k
@@ -45,9 +45,31 @@ def test_single_gpu_line_has_every_contract_field():
     assert tp["fetch_x2"] >= tp["raw"] >= rf["traffic"] * 0.5 and tp["over_algorithmic_raw"] > 1
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline alone (the --full blocks are absent) over exactly --steps timed steps; --dump-outputs writes the
+    last step's forward scores, seeds and posteriors as float64 .npy files, the scores and seeds those of the oracle on the same loci."""
+    import numpy as np
+    from hipstr_amd import capi
+    d = _bench(["--steps", "3", "--warmup", "1", "--loci", "2", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    n_aln = d["config"]["alignments_per_step_per_gpu"]
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - n_aln) < 1e-6 * n_aln          # value = alignments x steps / (steps x ms_per_step)
+    for k in ("end_to_end", "pipeline", "cpu_baseline", "roofline", "roofline_fp64", "valu", "host"):
+        assert k not in d, k
+    files = {f.name[:-4]: np.load(str(f)) for f in tmp_path.glob("*.npy")}
+    assert set(files) == {"aln_log_probs", "seeds", "log_post", "sample_total_ll", "map_gt", "locus_total_ll"}, sorted(files)
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert sum(f.stat().st_size for f in tmp_path.glob("*.npy")) <= 64e6
+    sb = capi.SynthBatch(n_loci=2, reads_per_locus=500, n_str_alleles=32, read_len=150, flank_len=60, str_bp=40, seed=20260928)
+    want, wseeds = capi.run_align(capi.load_oracle(), "oracle_", sb.ptr, fill=0.0)
+    assert np.array_equal(files["seeds"], wseeds) and np.max(np.abs(files["aln_log_probs"] - want)) <= 1e-9
+    A_l = np.diff(np.ctypeslib.as_array(sb.ptr.contents.hap_off, shape=(3,)))
+    assert files["log_post"].size == int((A_l * A_l).sum()) and files["locus_total_ll"].size == 2 and np.all(np.isfinite(files["locus_total_ll"]))
+
+
 def test_cpu_baseline_runs_loci_of_the_timed_batch():
     """identical bytes go to the CPU and the GPU — the baseline's processes take loci [a, b) of the batch's own seeded set."""
-    d = _bench(["--steps", "1", "--warmup", "1", "--loci", "40", "--no-pipeline"])
+    d = _bench(["--steps", "1", "--warmup", "1", "--loci", "40", "--no-pipeline", "--full"])
     cb = d["cpu_baseline"]
     assert cb["same_bytes_as_gpu_batch"] and cb["seed"] == 20260928 and cb["value"] > 0 and cb["single_core"]["value"] > 0
     import re
@@ -57,8 +79,8 @@ def test_cpu_baseline_runs_loci_of_the_timed_batch():
 
 def test_two_ranks_weak_and_strong():
     one = _bench(["--steps", "2", "--warmup", "1", "--loci", "16", "--no-cpu-baseline", "--no-pipeline"])
-    weak = _bench(["--steps", "2", "--warmup", "1", "--loci", "16", "--no-cpu-baseline", "--no-pipeline"], nproc=2, port=29533)
-    strong = _bench(["--steps", "2", "--warmup", "1", "--loci", "16", "--scaling", "strong", "--no-cpu-baseline", "--no-pipeline"], nproc=2, port=29535)
+    weak = _bench(["--steps", "2", "--warmup", "1", "--loci", "16", "--no-cpu-baseline", "--no-pipeline", "--full"], nproc=2, port=29533)
+    strong = _bench(["--steps", "2", "--warmup", "1", "--loci", "16", "--scaling", "strong", "--no-cpu-baseline", "--no-pipeline", "--full"], nproc=2, port=29535)
     a1 = one["config"]["alignments_per_step_per_gpu"]
     assert weak["n_gpus"] == 2 and weak["scaling"] == "weak" and weak["config"]["loci_per_gpu"] == 16
     assert strong["scaling"] == "strong" and strong["config"]["loci_per_gpu"] == 8
@@ -77,7 +99,7 @@ def test_eight_ranks_on_one_gpu(scaling):
     """The driver's 8-GPU launch line (torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8) with the 8 ranks sharing GPU 0: one
     JSON line, rank-disjoint contiguous slices of the one seeded locus set, every rank's host threads = usable cores / 8 and its threads
     pinned to its own CPUs, the per-rank rates present, the caches trimmed at exit (rc 0 on every rank)."""
-    args = ["--steps", "2", "--warmup", "1", "--loci", "8", "--no-cpu-baseline"] + (["--scaling", "strong"] if scaling == "strong" else [])
+    args = ["--steps", "2", "--warmup", "1", "--loci", "8", "--no-cpu-baseline", "--full"] + (["--scaling", "strong"] if scaling == "strong" else [])
     d = _bench(args, nproc=8, port=29541 if scaling == "weak" else 29543)
     assert d["n_gpus"] == 8 and d["scaling"] == scaling and len(d["per_rank_alignments_per_s"]) == 8 and all(v > 0 for v in d["per_rank_alignments_per_s"])
     ranks = sorted(d["ranks"], key=lambda r: r["rank"])

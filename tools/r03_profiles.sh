@@ -12,7 +12,7 @@ done
 cd $R
 # the counters above are what bench.py reads back: copy them where it looks before the bench lines are taken
 for w in ns c5 p30 c4; do for f in sq_counters.json pmc_traffic.json; do cp $O/r03_${w}_$f profiles/ 2>/dev/null; done; done
-python bench.py > $O/r03_bench_ns.json 2> $O/bench_ns.err
-HIPSTR_SYNTH_IMPERFECT=1.0 python bench.py --no-cpu-baseline > $O/r03_bench_ns_imperfect1.0.json 2> $O/bench_imp.err
-for w in c5 p30 c4; do python bench.py --workload $w --no-cpu-baseline > $O/r03_bench_$w.json 2> $O/bench_$w.err; done
+python bench.py --full > $O/r03_bench_ns.json 2> $O/bench_ns.err
+HIPSTR_SYNTH_IMPERFECT=1.0 python bench.py --full --no-cpu-baseline > $O/r03_bench_ns_imperfect1.0.json 2> $O/bench_imp.err
+for w in c5 p30 c4; do python bench.py --full --workload $w --no-cpu-baseline > $O/r03_bench_$w.json 2> $O/bench_$w.err; done
 ls -la $O

@@ -6,13 +6,13 @@ timeout 1500 python -m pytest tests/test_hmm_gpu.py tests/test_limits_gpu.py tes
 for rep in 1 2; do
   for lib in prev new; do
     L=hipstr_amd/csrc/libhipstr_hmm.so; [ $lib = prev ] && L=hipstr_amd/csrc/libhipstr_hmm_prev.so
-    HIPSTR_HMM_LIB=$PWD/$L timeout 900 python bench.py --no-cpu-baseline --no-pipeline --steps 10 > $out/ns_${lib}_$rep.json 2> $out/ns_${lib}_$rep.err
+    HIPSTR_HMM_LIB=$PWD/$L timeout 900 python bench.py --full --no-cpu-baseline --no-pipeline --steps 10 > $out/ns_${lib}_$rep.json 2> $out/ns_${lib}_$rep.err
   done
 done
 for lib in prev new; do
   L=hipstr_amd/csrc/libhipstr_hmm.so; [ $lib = prev ] && L=hipstr_amd/csrc/libhipstr_hmm_prev.so
   for wl in p30 c2 c5; do
-    HIPSTR_HMM_LIB=$PWD/$L timeout 900 python bench.py --workload $wl --no-cpu-baseline --no-pipeline --steps 10 > $out/${wl}_${lib}.json 2> $out/${wl}_${lib}.err
+    HIPSTR_HMM_LIB=$PWD/$L timeout 900 python bench.py --full --workload $wl --no-cpu-baseline --no-pipeline --steps 10 > $out/${wl}_${lib}.json 2> $out/${wl}_${lib}.err
   done
 done
 cat $out/swap_probe.txt; cat $out/tests.txt

@@ -4,7 +4,7 @@ out=gpurun_out/${1:-r04_cmb2}; mkdir -p $out; shift
 for rep in 1 2; do
   for v in "$@"; do
     L=hipstr_amd/csrc/libhipstr_hmm_$v.so; [ $v = new ] && L=hipstr_amd/csrc/libhipstr_hmm.so
-    HIPSTR_HMM_LIB=$PWD/$L timeout 900 python bench.py --no-cpu-baseline --no-pipeline --steps 10 > $out/ns_${v}_$rep.json 2> $out/ns_${v}_$rep.err
+    HIPSTR_HMM_LIB=$PWD/$L timeout 900 python bench.py --full --no-cpu-baseline --no-pipeline --steps 10 > $out/ns_${v}_$rep.json 2> $out/ns_${v}_$rep.err
   done
 done
 python - $out <<'PY'

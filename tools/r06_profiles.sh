@@ -16,11 +16,11 @@ HIPSTR_SYNTH_INHERIT=2 pass inherit2 --loci 400
 cd $R
 # the counters above are what bench.py reads back: copy them where it looks before the bench lines are taken
 for w in ns c5 p30 c4 c2 c3 imperfect inherit2; do for f in sq_counters.json pmc_traffic.json; do cp $O/r06_${w}_$f profiles/ 2>/dev/null; done; done
-python bench.py > $O/r06_bench_ns.json 2> $O/bench_ns.err
-for w in c5 p30 c4 c2; do python bench.py --workload $w --no-cpu-baseline > $O/r06_bench_$w.json 2> $O/bench_$w.err; done
-python bench.py --workload c3 --no-cpu-baseline --no-pipeline --steps 3 > $O/r06_bench_c3.json 2> $O/bench_c3.err
-HIPSTR_SYNTH_IMPERFECT=1.0 python bench.py --no-cpu-baseline --no-pipeline > $O/r06_bench_ns_imperfect1.0.json 2> $O/bench_imp.err
-for k in 1 2 3; do HIPSTR_SYNTH_INHERIT=$k python bench.py --no-cpu-baseline --no-pipeline > $O/r06_bench_ns_inherit$k.json 2> $O/bench_inh$k.err; done
+python bench.py --full > $O/r06_bench_ns.json 2> $O/bench_ns.err
+for w in c5 p30 c4 c2; do python bench.py --full --workload $w --no-cpu-baseline > $O/r06_bench_$w.json 2> $O/bench_$w.err; done
+python bench.py --full --workload c3 --no-cpu-baseline --no-pipeline --steps 3 > $O/r06_bench_c3.json 2> $O/bench_c3.err
+HIPSTR_SYNTH_IMPERFECT=1.0 python bench.py --full --no-cpu-baseline --no-pipeline > $O/r06_bench_ns_imperfect1.0.json 2> $O/bench_imp.err
+for k in 1 2 3; do HIPSTR_SYNTH_INHERIT=$k python bench.py --full --no-cpu-baseline --no-pipeline > $O/r06_bench_ns_inherit$k.json 2> $O/bench_inh$k.err; done
 for w in p30 c2 ns; do
   python bench.py --workload $w --e2e-only --steps 5 --host-threads 2 > $O/r06_e2e_${w}_pin2.json 2> $O/e2e_${w}_pin2.err
   python bench.py --workload $w --e2e-only --steps 5 > $O/r06_e2e_${w}_all.json 2> $O/e2e_${w}_all.err
