@@ -565,7 +565,20 @@ def load_hmm():
     _sig(lib.hipstr_debug_stream_create, C.c_void_p, [])
     _sig(lib.hipstr_debug_stream_destroy, None, [C.c_void_p])
     _sig(lib.hipstr_debug_fetch_table, C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64])
+    _sig(lib.hipstr_debug_launch_plan, C.c_int, [_BP, C.c_double, C.c_char_p, C.c_int])
     return lib
+
+
+def launch_plan(lib, bptr, ws_gib=0.0):
+    """The launch plan hipstr_hmm_align would run for a batch (host only: hipstr_debug_launch_plan) as a dict; ws_gib > 0 sets the
+    workspace budget per workspace."""
+    import json
+    n = lib.hipstr_debug_launch_plan(bptr, ws_gib, None, 0)
+    if n < 0:
+        raise RuntimeError("hipstr_debug_launch_plan failed: " + lib.hipstr_last_error().decode())
+    buf = C.create_string_buffer(n + 1)
+    assert lib.hipstr_debug_launch_plan(bptr, ws_gib, buf, n + 1) == n
+    return json.loads(buf.value.decode())
 
 
 def _why(lib, prefix):

@@ -49,6 +49,9 @@ extern "C" size_t hs_str_group_lds_bytes(int max_B, int nd_cap, int with_ilog);
 extern "C" size_t hs_str_group_p_lds_bytes();
 extern "C" void hs_launch_lead2(unsigned n_active, unsigned n_wavefronts, hipStream_t st, const hs_dev_t* dp, int active_begin, int item_begin, int item_end, int chunk, int max_cols, int n_clear);
 extern "C" void hs_launch_trail(unsigned n_wavefronts, hipStream_t st, const hs_dev_t* dp, int item_begin, int item_end, int chunk, int max_cols, int max_rows);
+extern "C" int hs_flank_route(int trail, int n_items, int max_cols, int max_rows);
+extern "C" void hs_flank_shape(int trail, int route, int* R, int* W);
+extern "C" void hs_flank_limits(int32_t out[5]);
 
 namespace {
 
@@ -375,6 +378,58 @@ void* pin_alloc(Ctx* c, size_t bytes){ return c->pin_cache.get(bytes); }
 void  pin_free(Ctx* c, void* p){ c->pin_cache.put(p); }
 }  // namespace hipstr
 
+namespace hipstr {
+// Batch-wide facts the launch decisions of hipstr_hmm_align depend on (computed by the upload, and by hipstr_debug_launch_plan from the same code).
+struct LaunchFacts {
+  int band_cols = 1;             // the longest read side (at least 1): columns of the flank sweeps' boundary rows, picks the systolic form
+  int max_rows = 0;              // longest flank rowset of the batch (rows of a flank block): picks the band shape of the trailing-flank sweep
+  bool any_pw = false;           // some locus has alleles with piecewise simple lists (hs_str_group_kernel_pw)
+  bool any_rp = false;           // ... with lists replayed in the grouped layout (hs_str_group_kernel_rp)
+  bool any_short = false;        // some locus has tabulated alleles hs_str_group_kernel_p does not take (period above HS_GRP_MAXP)
+};
+static LaunchFacts launch_facts(const Prepared& P){
+  LaunchFacts f;
+  f.band_cols = P.max_side_len > 0 ? P.max_side_len : 1;
+  for (const hs_rowset_t& rs : P.rowsets) f.max_rows = std::max(f.max_rows, (int)rs.len);
+  for (const hs_locus_t& l : P.loci){
+    f.any_short |= (l.n_short[0] > 0 || l.n_short[1] > 0);
+    f.any_pw |= (l.n_pw[0] > l.n_tab[0] || l.n_pw[1] > l.n_tab[1]);
+    f.any_rp |= (l.n_rp[0] > l.n_pw[0] || l.n_rp[1] > l.n_pw[1]);
+  }
+  return f;
+}
+// A call of a locus or two: the interrupted alleles' kernels run beside the tabulated alleles' on the thread's second stream when a chunk
+// has at most this many STR items
+#define HS_SIDE_STREAM_ITEMS 256
+// The STR-block kernels one chunk launches — the one place it is decided: hipstr_hmm_align launches what it says, hipstr_debug_launch_plan
+// reports it.  HIPSTR_STR_GROUP=0: one workgroup per read for every tabulated allele (hs_str_kernel), for comparison.
+struct StrLaunch { bool per_read, nd, group_p, group, pw, rp, side_stream, long_sides, generic; };
+static StrLaunch str_launch(const Prepared& P, const Prepared::Chunk& ch, const LaunchFacts& f){
+  StrLaunch L;
+  const bool str_group = !(getenv("HIPSTR_STR_GROUP") && atoi(getenv("HIPSTR_STR_GROUP")) == 0);
+  const bool items = ch.str_end > ch.str_begin;
+  constexpr bool group_p = true;          // blocks of at least six repeat units (nearly all) through the kernel with a compile-time period
+  L.per_read = !str_group;
+  L.nd = str_group && items && group_p && P.ws_nd_size > 0;        // read-end deletion sums of the tabulated alleles
+  L.group_p = str_group && items && group_p;
+  L.group = str_group && items && (!group_p || f.any_short);       // (periods above HS_GRP_MAXP only, once hs_str_group_kernel_p is on)
+  L.pw = str_group && items && f.any_pw;
+  L.rp = str_group && items && f.any_rp;
+  L.side_stream = str_group && items && ch.str_end - ch.str_begin <= HS_SIDE_STREAM_ITEMS && group_p && (f.any_pw || f.any_rp);
+  L.long_sides = str_group && ch.n_long_sides > 0;                 // sides with more columns than a group holds: one workgroup per read
+  L.generic = true;                       // alleles without a closed form, and whatever hs_str_kernel marked HS_REDO
+  return L;
+}
+// workspace budget (doubles per workspace; there are two large ones): HIPSTR_WS_GIB, else 3 Gi doubles
+static int64_t ws_budget(double gib){
+  int64_t budget = (int64_t)3 << 30;
+  if (gib > 0) budget = (int64_t)(gib*134217728.0);
+  else if (getenv("HIPSTR_WS_GIB")) budget = (int64_t)(atof(getenv("HIPSTR_WS_GIB"))*134217728.0);
+  if (budget < 1024) budget = 1024;
+  return budget;
+}
+}  // namespace hipstr
+
 struct hipstr_dev_batch {
   Ctx* ctx = NULL;
   hipstr::Prepared prep;
@@ -382,11 +437,8 @@ struct hipstr_dev_batch {
   hs_dev_t* d_args = NULL;
   std::vector<void*> dev_blocks, pin_blocks;      // from the context's caches
   int grid_y = 1, max_alleles = 1, n_lead_items = 0, n_trail_items = 0, trail_waves = 1;
-  int max_rows = 0;              // longest flank rowset of the batch (rows of a flank block): picks the band shape of the trailing-flank sweep
+  hipstr::LaunchFacts facts;     // what the launch decisions depend on (band_cols, max_rows, any_pw / any_rp / any_short)
   size_t grp_lds_bytes = 0, grp_pw_lds_bytes = 0;
-  bool any_pw = false;           // some locus has alleles with piecewise simple lists (hs_str_group_kernel_pw)
-  bool any_rp = false;           // ... with lists replayed in the grouped layout (hs_str_group_kernel_rp)
-  bool any_short = false;        // some locus has tabulated alleles hs_str_group_kernel_p does not take (period above HS_GRP_MAXP)
   size_t lds_bytes = 0;
   hipEvent_t ev0 = NULL, ev1 = NULL;
   hipEvent_t ev_expand = NULL;            // the device-built tables are ready (recorded on the thread's aux stream; the first pass waits for it before the STR-block kernels)
@@ -537,10 +589,7 @@ hipstr_dev_batch_t* hipstr::upload_on(Ctx* ctx, const hipstr_batch_t* batch, con
   dev->h2d_stream = copy_stream;
   dev->stream = compute_stream;
   std::string err;
-  // workspace budget (doubles per workspace; there are two large ones): HIPSTR_WS_GIB, else a fifth of the free HBM, at most 24 GiB
-  int64_t budget = (int64_t)3 << 30;
-  if (getenv("HIPSTR_WS_GIB")) budget = (int64_t)(atof(getenv("HIPSTR_WS_GIB"))*134217728.0);
-  if (budget < 1024) budget = 1024;
+  const int64_t budget = hipstr::ws_budget(0);
   const auto t_prep0 = std::chrono::steady_clock::now();
   hipstr::adopt_recycled(dev->prep);
   if (hipstr::prepare_batch(batch, dev->prep, err, budget, seed_base)){ g_err = err; hipstr::recycle_prepared(dev->prep); delete dev; return NULL; }
@@ -618,10 +667,9 @@ hipstr_dev_batch_t* hipstr::upload_on(Ctx* ctx, const hipstr_batch_t* batch, con
   h.grp_recs = (const int32_t*)dalloc(sizeof(int32_t)*HS_GRP_REC_DWORDS*P.rec_descs.size());        // assembled on the device (hs_expand_recs_kernel)
   h.n_stropts = (int32_t)P.stropts.size(); h.n_recs = (int32_t)P.rec_descs.size(); h.f64_gen_base = (int64_t)P.n_f64();
   // trailing-flank kernel: persistent wavefronts, each with two band-boundary rows of [max side columns][64 lanes][M,D]
-  h.band_cols = P.max_side_len > 0 ? P.max_side_len : 1;
+  dev->facts = hipstr::launch_facts(P);
+  h.band_cols = dev->facts.band_cols;
   dev->trail_waves = (int)std::min<size_t>(P.trail_items.size() ? P.trail_items.size() : 1, 256 * 16);
-  dev->max_rows = 0;
-  for (const hs_rowset_t& rs : P.rowsets) dev->max_rows = std::max(dev->max_rows, (int)rs.len);
   h.ws_band = (double*)dalloc(sizeof(double)*(size_t)dev->trail_waves*h.band_cols*64*2);
   h.lts_rows = 1; h.ws_lts = NULL;          // (fields of the removed fused trailing-flank item: the argument block keeps its layout)
   h.n_active = (int32_t)P.active.size();
@@ -646,12 +694,6 @@ hipstr_dev_batch_t* hipstr::upload_on(Ctx* ctx, const hipstr_batch_t* batch, con
   dev->lds_bytes = hs_str_lds_bytes(h.lds_len, h.max_B);
   if (dev->lds_bytes > 160*1024){ g_err = "batch needs more than 160 KiB of LDS per workgroup"; hipstr_hmm_free(dev); return NULL; }
   h.grp_nd_cap = std::max(2, (P.grp_nd_cap + 1) & ~1);
-  dev->any_short = false;
-  for (const hs_locus_t& l : P.loci) dev->any_short |= (l.n_short[0] > 0 || l.n_short[1] > 0);
-  dev->any_pw = false;
-  for (const hs_locus_t& l : P.loci) dev->any_pw |= (l.n_pw[0] > l.n_tab[0] || l.n_pw[1] > l.n_tab[1]);
-  dev->any_rp = false;
-  for (const hs_locus_t& l : P.loci) dev->any_rp |= (l.n_rp[0] > l.n_pw[0] || l.n_rp[1] > l.n_pw[1]);
   dev->grp_lds_bytes = hs_str_group_lds_bytes(h.max_B, h.grp_nd_cap, 0);
   dev->grp_pw_lds_bytes = hs_str_group_lds_bytes(h.max_B, h.grp_nd_cap, 1);
   if (dev->grp_pw_lds_bytes > 48*1024){
@@ -874,38 +916,34 @@ int hipstr_hmm_align(hipstr_dev_batch_t* dev, void* hip_stream){
     // (once per stream: a later pass on ANOTHER stream of the caller's is not ordered behind the first one's wait)
     if (dev->ev_expand && (!dev->expand_joined || dev->expand_joined_on != st)){ HS_HIP(hipStreamWaitEvent(st, dev->ev_expand, 0)); dev->expand_joined = true; dev->expand_joined_on = st; }
     // tabulated alleles: reads of a locus side packed into workgroups (HIPSTR_STR_GROUP=0: one workgroup per read, for comparison)
-    const bool str_group = !(getenv("HIPSTR_STR_GROUP") && atoi(getenv("HIPSTR_STR_GROUP")) == 0);
-    if (!str_group) hipLaunchKernelGGL(hs_str_kernel, dim3(nact, dev->grid_y), dim3(128), dev->lds_bytes, st, dp, ch.active_begin, 0);
+    const hipstr::StrLaunch sl = hipstr::str_launch(dev->prep, ch, dev->facts);
+    if (sl.per_read) hipLaunchKernelGGL(hs_str_kernel, dim3(nact, dev->grid_y), dim3(128), dev->lds_bytes, st, dp, ch.active_begin, 0);
     else {
-      // blocks of at least six repeat units (nearly all) through the kernel with a compile-time period, the shorter ones as before
-      constexpr bool group_p = true;
       // A call of a locus or two: the interrupted alleles' kernels beside the tabulated alleles' (different alleles of the same reads: disjoint
       // outputs; the re-do marks both may set are the same value) on the thread's second stream — 18 us of a 180 us call
       hipStream_t st_pw = st; hipEvent_t ev_pw = NULL, ev_fork = NULL;
-      if (ch.str_end > ch.str_begin && ch.str_end - ch.str_begin <= 256 && group_p && (dev->any_pw || dev->any_rp)){
+      if (sl.side_stream){
         hipStream_t aux = thread_aux_stream(dev->ctx);
         ev_fork = aux ? dev->ctx->get_event(false) : NULL;
         ev_pw = ev_fork ? dev->ctx->get_event(false) : NULL;
         if (ev_pw) st_pw = aux; else { dev->ctx->put_event(ev_fork, false); ev_fork = NULL; }
       }
-      if (ch.str_end > ch.str_begin){
-        if (group_p && dev->prep.ws_nd_size > 0)       // read-end deletion sums of the tabulated alleles, every (row, column) a lane
-          hipLaunchKernelGGL(hs_nd_kernel, dim3(nact, 2), dim3(256), 0, st, dp, ch.active_begin);
-        if (ev_pw){      // (back to the pool once its wait is queued: the next user records it again)
-          const bool ok = hipEventRecord(ev_fork, st) == hipSuccess && hipStreamWaitEvent(st_pw, ev_fork, 0) == hipSuccess;
-          dev->ctx->put_event(ev_fork, false);
-          if (!ok){ dev->ctx->put_event(ev_pw, false); return fail("hipEventRecord / hipStreamWaitEvent failed"); }      // (nothing launched on the side stream yet)
-        }
-        if (group_p) hipLaunchKernelGGL(hs_str_group_kernel_p, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), hs_str_group_p_lds_bytes(), st, dp,
-                                        dev->n_lead_items + dev->n_trail_items + ch.str_begin);
-        if (!group_p || dev->any_short)      // (periods above HS_GRP_MAXP only, once hs_str_group_kernel_p is on)
-          hipLaunchKernelGGL(hs_str_group_kernel, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), dev->grp_lds_bytes, st, dp,
-                             dev->n_lead_items + dev->n_trail_items + ch.str_begin, group_p ? 1 : 0);
+      if (sl.nd)       // read-end deletion sums of the tabulated alleles, every (row, column) a lane
+        hipLaunchKernelGGL(hs_nd_kernel, dim3(nact, 2), dim3(256), 0, st, dp, ch.active_begin);
+      if (ev_pw){      // (back to the pool once its wait is queued: the next user records it again)
+        const bool ok = hipEventRecord(ev_fork, st) == hipSuccess && hipStreamWaitEvent(st_pw, ev_fork, 0) == hipSuccess;
+        dev->ctx->put_event(ev_fork, false);
+        if (!ok){ dev->ctx->put_event(ev_pw, false); return fail("hipEventRecord / hipStreamWaitEvent failed"); }      // (nothing launched on the side stream yet)
       }
-      if (dev->any_pw && ch.str_end > ch.str_begin)       // interrupted repeats: the piecewise simple lists' closed forms, grouped like the tabulated ones
+      if (sl.group_p) hipLaunchKernelGGL(hs_str_group_kernel_p, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), hs_str_group_p_lds_bytes(), st, dp,
+                                         dev->n_lead_items + dev->n_trail_items + ch.str_begin);
+      if (sl.group)      // (periods above HS_GRP_MAXP only, once hs_str_group_kernel_p is on)
+        hipLaunchKernelGGL(hs_str_group_kernel, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), dev->grp_lds_bytes, st, dp,
+                           dev->n_lead_items + dev->n_trail_items + ch.str_begin, sl.group_p ? 1 : 0);
+      if (sl.pw)       // interrupted repeats: the piecewise simple lists' closed forms, grouped like the tabulated ones
         hipLaunchKernelGGL(hs_str_group_kernel_pw, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), dev->grp_pw_lds_bytes, st_pw, dp,
                            dev->n_lead_items + dev->n_trail_items + ch.str_begin);
-      if (dev->any_rp && ch.str_end > ch.str_begin)       // three and more interruptions: lists without a closed form, replayed in the grouped layout
+      if (sl.rp)       // three and more interruptions: lists without a closed form, replayed in the grouped layout
         hipLaunchKernelGGL(hs_str_group_kernel_rp, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), dev->grp_pw_lds_bytes, st_pw, dp,
                            dev->n_lead_items + dev->n_trail_items + ch.str_begin);
       if (ev_pw){
@@ -916,15 +954,15 @@ int hipstr_hmm_align(hipstr_dev_batch_t* dev, void* hip_stream){
         dev->ctx->put_event(ev_pw, false);
         if (!ok){ hipStreamSynchronize(st_pw); return fail("hipEventRecord / hipStreamWaitEvent failed (side stream of the interrupted alleles' kernels)"); }
       }
-      if (ch.n_long_sides > 0)        // sides with more columns than a group holds: one workgroup per read as before
+      if (sl.long_sides)        // sides with more columns than a group holds: one workgroup per read as before
         hipLaunchKernelGGL(hs_str_kernel, dim3(nact, dev->grid_y), dim3(128), dev->lds_bytes, st, dp, ch.active_begin, 1);
     }
     // alleles without a tabulated closed form (interrupted repeats, very long blocks) and whatever hs_str_kernel marked HS_REDO
-    hipLaunchKernelGGL(hs_str_kernel_generic, dim3(nact, dev->grid_y), dim3(128), dev->lds_bytes, st, dp, ch.active_begin, str_group ? 1 : 0);
+    if (sl.generic) hipLaunchKernelGGL(hs_str_kernel_generic, dim3(nact, dev->grid_y), dim3(128), dev->lds_bytes, st, dp, ch.active_begin, sl.per_read ? 0 : 1);
     if (mark()) return 1;
     if (ch.trail_end > ch.trail_begin)     // trailing flanks: persistent wavefronts striding over (read side, allele group) items
       hs_launch_trail((unsigned)std::min(dev->trail_waves, ch.trail_end - ch.trail_begin), st, dp,
-                      dev->n_lead_items + ch.trail_begin, dev->n_lead_items + ch.trail_end, 2*chunk_no + 1, dev->h.band_cols, dev->max_rows);
+                      dev->n_lead_items + ch.trail_begin, dev->n_lead_items + ch.trail_end, 2*chunk_no + 1, dev->h.band_cols, dev->facts.max_rows);
     if (mark()) return 1;
     hipLaunchKernelGGL(hs_combine_kernel, dim3(nact), dim3(64*hs_combine_waves()), 0, st, dp, ch.active_begin);       // compute_aln_logprob
     if (mark()) return 1;
@@ -1213,6 +1251,135 @@ int hipstr_debug_str_groups(const hipstr_batch_t* batch, int32_t* side, int32_t*
     read_off[g + 1] = nr;
   }
   return ng;
+}
+
+// Diagnostics (host only): the launch plan of a batch as hipstr_hmm_align would run it, from the same decisions (hs_flank_route, str_launch,
+// hs_coop_bands, hs_combine_tier), as one JSON object.  Route names (the "routes" list of every chunk draws from kRoutes):
+static const char* const kRoutes[] = {
+  "lead_systolic", "lead_latency", "lead_default", "trail_systolic", "trail_latency", "trail_short", "trail_default",
+  "hs_str_group_kernel_p", "hs_str_group_kernel", "hs_str_group_kernel_pw", "hs_str_group_kernel_rp", "hs_str_kernel_long", "hs_str_kernel",
+  "hs_str_kernel_generic", "str_side_stream", "str_chunk_stream", "rp_list_closed_form", "rp_list_replay", "combine_one", "combine_1", "combine_2", "combine_3", "combine_4",
+  "plan_one_chunk", "plan_chunks" };
+int hipstr_debug_launch_plan(const hipstr_batch_t* batch, double ws_gib, char* json, int cap){
+  if (!batch) return fail("null batch");
+  hipstr::Prepared P; std::string err;
+  if (hipstr::prepare_batch(batch, P, err, hipstr::ws_budget(ws_gib))){ g_err = err; return -1; }
+  const hipstr::LaunchFacts f = hipstr::launch_facts(P);
+  int32_t lim[5]; hs_flank_limits(lim);
+  std::string o; char b[256];
+  auto put = [&](const char* fmt, auto... a){ snprintf(b, sizeof b, fmt, a...); o += b; };
+  auto shape = [&](const char* name, int trail, int route){ int R, W; hs_flank_shape(trail, route, &R, &W); put("\"%s\": [%d, %d], ", name, R, W); };
+  put("{\"thresholds\": {\"HS_SYS_ITEMS\": %d, \"HS_LAT_ITEMS\": %d, \"HS_SYS_MAXCOLS\": %d, \"HS_SHORT_TRAIL_ROWS\": %d, ", lim[0], lim[1], lim[2], lim[3]);
+  put("\"HS_GRP_MAXP\": %d, \"HS_GRP_MAX_BLOCK\": %d, \"HS_MAX_SIDE_LEN\": %d, \"HS_GRP_COLS\": %d, \"HS_PWK_MAX\": %d, \"HS_SIDE_STREAM_ITEMS\": %d, \"HS_CMB_MAX_FLANK\": %d, ",
+      HS_GRP_MAXP, HS_GRP_MAX_BLOCK, HS_MAX_SIDE_LEN, HS_GRP_COLS, HS_PWK_MAX, HS_SIDE_STREAM_ITEMS, 64*lim[4]);
+  o += "\"shapes\": {";
+  shape("lead_systolic", 0, HS_FLANK_SYSTOLIC); shape("lead_latency", 0, HS_FLANK_LATENCY); shape("lead_default", 0, HS_FLANK_DEFAULT);
+  shape("trail_systolic", 1, HS_FLANK_SYSTOLIC); shape("trail_latency", 1, HS_FLANK_LATENCY); shape("trail_short", 1, HS_FLANK_SHORT); shape("trail_default", 1, HS_FLANK_DEFAULT);
+  o.resize(o.size() - 2); o += "}}, \"routes\": [";
+  for (const char* r : kRoutes){ put("\"%s\", ", r); }
+  o.resize(o.size() - 2);
+  put("], \"max_cols\": %d, \"max_rows\": %d, \"chunks\": [", f.band_cols, f.max_rows);
+  static const char* const kLead[] = { "lead_systolic", "lead_latency", "", "lead_default" };
+  static const char* const kTrail[] = { "trail_systolic", "trail_latency", "trail_short", "trail_default" };
+  for (size_t ci = 0; ci < P.chunks.size(); ci++){
+    const hipstr::Prepared::Chunk& ch = P.chunks[ci];
+    std::vector<std::string> hit;
+    hit.push_back(P.chunks.size() == 1 ? "plan_one_chunk" : "plan_chunks");
+    put("%s{\"n_active\": %d, ", ci ? ", " : "", ch.active_end - ch.active_begin);
+    // flanks: the route of the launch and, per item in launch order, [rows after the first, rounds, bands of the last round, band heights]
+    // (systolic: [rows after the first, bands of 64 rows])
+    for (int trail = 0; trail < 2; trail++){
+      const int i0 = trail ? ch.trail_begin : ch.lead_begin, i1 = trail ? ch.trail_end : ch.lead_end;
+      const int route = hs_flank_route(trail, i1 - i0, f.band_cols, trail ? f.max_rows : 0);
+      const char* name = i1 > i0 ? (trail ? kTrail : kLead)[route] : "none";
+      if (i1 > i0) hit.push_back(name);
+      int R, W; hs_flank_shape(trail, route, &R, &W);
+      put("\"%s\": {\"route\": \"%s\", \"items\": %d, \"R\": %d, \"W\": %d, \"bands\": [", trail ? "trail" : "lead", name, i1 - i0, R, W);
+      for (int i = i0; i < i1; i++){
+        const hs_item_t& it = trail ? P.trail_items[i] : P.lead_items[i];
+        const int n_rows = P.rowsets[trail ? P.tgroups[it.slot].rowset : it.rowset].len - 1;
+        if (i > i0) o += ", ";
+        if (route == HS_FLANK_SYSTOLIC){ put("[%d, %d]", n_rows, (n_rows + 63) / 64); continue; }
+        if (n_rows == 0){ o += "[0, 0, 0, []]"; continue; }
+        const hs_coop_bands_t cb = hs_coop_bands(n_rows, R, W);
+        put("[%d, %d, %d, [%d", n_rows, cb.rounds, cb.nbands - (cb.rounds - 1)*W, cb.nr_rem < cb.nbands ? cb.nr_base : cb.nr_base + 1);
+        if (cb.nr_rem > 0 && cb.nr_rem < cb.nbands) put(", %d", cb.nr_base + 1);
+        o += "]]";
+      }
+      o += "]}, ";
+    }
+    // STR block: which kernels launch, and (active read side, realigned allele) pairs by the kernel that computes them
+    const hipstr::StrLaunch sl = hipstr::str_launch(P, ch, f);
+    int64_t n_p = 0, n_g = 0, n_pw = 0, n_rp = 0, n_long = 0, n_pr = 0, n_gen = 0;
+    // combine: (active read, realigned allele) pairs by form
+    int64_t tiers[5] = {0, 0, 0, 0, 0};
+    // visiting lists of the chunk's loci' realigned (allele, side) options by the form prep gave them (hs_stropt_t::shape): tabulated
+    // simple, piecewise (one or two interruptions), the K-level closed form (three to HS_PWK_MAX breaks), replayed entry by entry
+    int64_t lists[4] = {0, 0, 0, 0};
+    int last_locus = -1;
+    for (int a = ch.active_begin; a < ch.active_end; a++){
+      const hs_read_t& rd = P.reads[P.active[a]];
+      const hs_locus_t& loc = P.loci[rd.locus];
+      if (rd.locus != last_locus){
+        last_locus = rd.locus;
+        for (int k = 0; k < loc.n_alleles; k++){
+          const hs_allele_t& al = P.alleles[loc.hap_begin + k];
+          if (!al.realign) continue;
+          for (int side = 0; side < 2; side++){
+            const hs_stropt_t& so = P.stropts[al.str_opt[side]];
+            if (so.kind == 0) continue;
+            for (int q = 0; q <= HS_MAXREP; q++){
+              if ((q == HS_MAXREP ? so.B : so.B - (q+1)*so.period) < 0) continue;        // a deletion size that is never evaluated
+              const int sh = so.shape[q];
+              lists[sh >= 0 ? 0 : sh == HS_SHAPE_PIECEWISE ? 1 : sh == HS_SHAPE_PWK ? 2 : 3]++;
+            }
+          }
+        }
+      }
+      for (int side = 0; side < 2; side++){
+        const int n = side ? rd.len - rd.seed - 1 : rd.seed;
+        if (n <= 0) continue;
+        if (sl.per_read){ n_pr += loc.n_tab[side]; n_gen += loc.n_re - loc.n_tab[side]; continue; }
+        if (n > HS_GRP_COLS){ n_long += loc.n_tab[side]; n_gen += loc.n_re - loc.n_tab[side]; continue; }
+        n_g += loc.n_short[side]; n_p += loc.n_tab[side] - loc.n_short[side];
+        n_pw += loc.n_pw[side] - loc.n_tab[side]; n_rp += loc.n_rp[side] - loc.n_pw[side]; n_gen += loc.n_re - loc.n_rp[side];
+      }
+      for (int k = 0; k < loc.n_alleles; k++){
+        const hs_allele_t& al = P.alleles[loc.hap_begin + k];
+        if (al.realign) tiers[hs_combine_tier(al.n_flank, P.rowsets[al.lead_rows[0]].len, lim[4])]++;
+      }
+    }
+    const struct { const char* name; bool launched; int64_t pairs; } ks[] = {
+      { "hs_str_group_kernel_p", sl.group_p, n_p }, { "hs_str_group_kernel", sl.group, n_g }, { "hs_str_group_kernel_pw", sl.pw, n_pw },
+      { "hs_str_group_kernel_rp", sl.rp, n_rp }, { "hs_str_kernel_long", sl.long_sides, n_long }, { "hs_str_kernel", sl.per_read, n_pr },
+      { "hs_str_kernel_generic", sl.generic, n_gen } };
+    o += "\"str\": {\"launch\": [";
+    bool first = true;
+    if (sl.nd){ o += "\"hs_nd_kernel\""; first = false; }
+    for (const auto& k : ks) if (k.launched){ put("%s\"%s\"", first ? "" : ", ", k.name); first = false; }
+    o += "], \"pairs\": {";
+    for (size_t i = 0; i < sizeof ks / sizeof ks[0]; i++){
+      put("%s\"%s\": %lld", i ? ", " : "", ks[i].name, (long long)ks[i].pairs);
+      if (ks[i].launched && ks[i].pairs > 0) hit.push_back(ks[i].name);
+    }
+    const bool interrupted = sl.pw || sl.rp;
+    if (interrupted) hit.push_back(sl.side_stream ? "str_side_stream" : "str_chunk_stream");
+    if (sl.rp && n_rp > 0 && lists[2] > 0) hit.push_back("rp_list_closed_form");
+    if (sl.rp && n_rp > 0 && lists[3] > 0) hit.push_back("rp_list_replay");
+    put("}, \"lists\": {\"simple\": %lld, \"piecewise\": %lld, \"pwk\": %lld, \"replay\": %lld}, ", (long long)lists[0], (long long)lists[1], (long long)lists[2], (long long)lists[3]);
+    // the groups of hs_str_group_kernel*: per item [side, columns, reads]
+    o += "\"groups\": [";
+    for (int i = ch.str_begin; i < ch.str_end; i++) put("%s[%d, %d, %d]", i > ch.str_begin ? ", " : "", P.str_items[i].side, P.str_items[i].rowset, P.str_items[i].slot);
+    put("], \"items\": %d, \"side_stream\": %s, \"n_long_sides\": %d}, ", ch.str_end - ch.str_begin, sl.side_stream ? "true" : "false", ch.n_long_sides);
+    put("\"combine\": [%lld, %lld, %lld, %lld, %lld], \"routes\": [", (long long)tiers[0], (long long)tiers[1], (long long)tiers[2], (long long)tiers[3], (long long)tiers[4]);
+    static const char* const kCmb[] = { "combine_one", "combine_1", "combine_2", "combine_3", "combine_4" };
+    for (int t = 0; t < 5; t++) if (tiers[t] > 0) hit.push_back(kCmb[t]);
+    for (size_t i = 0; i < hit.size(); i++) put("%s\"%s\"", i ? ", " : "", hit[i].c_str());
+    o += "]}";
+  }
+  o += "]}";
+  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
+  return (int)o.size();
 }
 
 int hipstr_debug_simple_table(int bound, int U0, int tail, double entry[3]){

@@ -403,9 +403,8 @@ template <int R, int W, bool LEAD, bool EL = false>
 __device__ __forceinline__ void coop_rounds(const hs_dev_t& d, int w, int lane, bool live, int n, int nmax, const double* col, const hs_row_t* rows, int n_rows, int c0,
                                             const double* mr, double* bnd, double2 (*ring)[HS_RING*64], int* prog_s, int* gcol, double* lt, double* rowp, double* side_out, double2 (*ktabs)[24], double (*etabs)[2*HS_ETAB_PAR] = NULL, int npad = 64){
   // as many bands as there are wavefronts whenever the rows allow it (all wavefronts busy), more rounds only for blocks deeper than one round holds
-  const int rounds = (n_rows + R*W - 1) / (R*W);
-  const int nbands = min(n_rows, rounds*W);
-  const int nr_base = n_rows / nbands, nr_rem = n_rows - nr_base*nbands;
+  const hs_coop_bands_t cb = hs_coop_bands(n_rows, R, W);         // (layout.h: hipstr_debug_launch_plan reports the same bands)
+  const int rounds = cb.rounds, nbands = cb.nbands, nr_base = cb.nr_base, nr_rem = cb.nr_rem;
   hs_lds_i prog = (hs_lds_i)prog_s;
   for (int g = 0; g < rounds; g++){
     if (g > 0 && !gcol){
@@ -455,7 +454,9 @@ __device__ __forceinline__ void coop_rounds(const hs_dev_t& d, int w, int lane, 
 //   * every wavefront reads the record of item k when it gets there, sweeps, and goes on to item k + 1 without a barrier: the bands' column
 //     counters count through the items (coop_rounds, gcol), so the first band starts the next item while the last is still three columns
 //     behind in this one — the pipeline never drains.
-// The only barriers left are those between the rounds of a flank deeper than one round (HBM hand-over), passed by every wavefront alike.
+// No barrier is left, not even between the rounds of a flank deeper than one round: the last band of a round stores its boundary in the
+// workgroup's HBM scratch, drains the store and only then publishes the column in its counter (prog[W-1]); the next round's first band
+// waits for that counter column by column and reads the boundary from the scratch (coop_rounds with gcol, band_sweep_coop topg / wlast).
 // Same cells, same operations, same order per cell: bit-identical.
 struct TrailRec {          // what the sweeps of one item need; uniform words first
   int item_ok;             // 0: past the last item (the stream ends)
@@ -639,8 +640,12 @@ __global__ void __launch_bounds__(64*W, OCC) hs_lead_kernel_coop(const hs_dev_t*
 // is the latency shape only — and n + rows steps of one short dependent chain each.  The row constants (base, transition logs) are
 // per-lane registers, the per-column operands come from an LDS copy of the read side.  Same cells, same operations per cell as
 // band_sweep: bit-identical.  Flanks of more than 64 rows run in bands of 64 rows, the boundary row kept in LDS.
+#ifndef HS_SYS_MAXCOLS
 #define HS_SYS_MAXCOLS 256
-#define HS_SYS_ITEMS 96u
+#endif
+#ifndef HS_SYS_ITEMS
+#define HS_SYS_ITEMS 96u        // launches with at most this many flank items take the systolic form (hs_flank_route)
+#endif
 template <bool LEAD>
 __global__ void __launch_bounds__(64) hs_flank_systolic(const hs_dev_t* __restrict__ dp, int item_begin){
   const hs_dev_t& d = *dp;
@@ -2918,7 +2923,8 @@ hs_combine_kernel(const hs_dev_t* __restrict__ dp, int active_begin){
       const uint64_t members = todo & __ballot(alv.n_flank == N && alv.lead_rows[0] == lr && alv.trail_rows[0] == tr && alv.lead_slot[0] == slotL && alv.lead_slot[1] == slotR);
       todo &= ~members;
       const int lead_off = rdlane(rsl.off, f), F0 = rdlane(rsl.len, f), trail_off = rdlane(rst.off, f);
-      if (F0 < 1 || N - F0 < 1 || N > 64*HS_CMB_ROUNDS){
+      const int tier = hs_combine_tier(N, F0, HS_CMB_ROUNDS);       // (layout.h: hipstr_debug_launch_plan counts the same tiers)
+      if (tier == 0){
         int seen = 0;
         for (uint64_t mm = members; mm; mm &= mm - 1){
           const int kk = __builtin_ctzll(mm);
@@ -2927,10 +2933,10 @@ hs_combine_kernel(const hs_dev_t* __restrict__ dp, int active_begin){
         }
         continue;
       }
-      if (N <= 64)       combine_config<1>(d, vL, vR, lane, seed_c, seed_lc, seed_lw, N, lead_off, F0, trail_off, slotL, slotR, alv, members, kb, n_alleles, out_row);
-      else if (N <= 128) combine_config<2>(d, vL, vR, lane, seed_c, seed_lc, seed_lw, N, lead_off, F0, trail_off, slotL, slotR, alv, members, kb, n_alleles, out_row);
+      if (tier == 1)      combine_config<1>(d, vL, vR, lane, seed_c, seed_lc, seed_lw, N, lead_off, F0, trail_off, slotL, slotR, alv, members, kb, n_alleles, out_row);
+      else if (tier == 2) combine_config<2>(d, vL, vR, lane, seed_c, seed_lc, seed_lw, N, lead_off, F0, trail_off, slotL, slotR, alv, members, kb, n_alleles, out_row);
 #if HS_CMB_ROUNDS >= 4
-      else if (N <= 192) combine_config<3>(d, vL, vR, lane, seed_c, seed_lc, seed_lw, N, lead_off, F0, trail_off, slotL, slotR, alv, members, kb, n_alleles, out_row);
+      else if (tier == 3) combine_config<3>(d, vL, vR, lane, seed_c, seed_lc, seed_lw, N, lead_off, F0, trail_off, slotL, slotR, alv, members, kb, n_alleles, out_row);
       else               combine_config<4>(d, vL, vR, lane, seed_c, seed_lc, seed_lw, N, lead_off, F0, trail_off, slotL, slotR, alv, members, kb, n_alleles, out_row);
 #endif
     }
@@ -2950,38 +2956,72 @@ hs_combine_kernel(const hs_dev_t* __restrict__ dp, int active_begin){
 #endif
 extern "C" int hs_flank_waves_per_group(){ return HS_COOP_WAVES; }
 extern "C" int hs_combine_waves(){ return HS_CMB_WAVES; }
-// HIPSTR_FLANK_SYSTOLIC: 1 (default) = launches of at most HS_LAT_ITEMS flank items whose read sides fit HS_SYS_MAXCOLS columns take the
+// HIPSTR_FLANK_SYSTOLIC: 1 (default) = launches of at most HS_SYS_ITEMS flank items whose read sides fit HS_SYS_MAXCOLS columns take the
 // systolic kernels (a wavefront per alignment); 0 = never; 2 = every launch that fits (tests: the whole suite through this form)
 static int systolic_mode(){ const char* e = getenv("HIPSTR_FLANK_SYSTOLIC"); return e ? atoi(e) : 1; }      // (read per launch: tests switch it)
-static bool use_systolic(int item_begin, int item_end, int max_cols){
+// short trailing flanks (production panels: <= 35 bp): three bands of up to 12 rows fill their wavefronts better than four of 9 (p30 trailing
+// flank 4.25 -> 4.02 ms, profiles/r05_notes.md; at 60 rows the 4 x 15 shape is the best by 25 %).  Rows after the first of the batch's longest flank.
+#ifndef HS_SHORT_TRAIL_ROWS
+#define HS_SHORT_TRAIL_ROWS 36
+#endif
+#ifndef HS_SHORT_ROWS
+#define HS_SHORT_ROWS 12         // the short trailing shape: rows per band, bands (wavefronts) per round, wavefronts per SIMD
+#endif
+#ifndef HS_SHORT_WAVES
+#define HS_SHORT_WAVES 3
+#endif
+#ifndef HS_SHORT_OCC
+#define HS_SHORT_OCC 3
+#endif
+// Rows per band (R) and bands per round (W) of a flank shape; the systolic kernels run bands of 64 rows, one at a time.
+extern "C" void hs_flank_shape(int trail, int route, int* R, int* W){
+  switch (route){
+    case HS_FLANK_SYSTOLIC: *R = 64; *W = 1; break;
+    case HS_FLANK_LATENCY:  *R = HS_LAT_ROWS; *W = HS_LAT_WAVES; break;
+    case HS_FLANK_SHORT:    *R = trail ? HS_SHORT_ROWS : 0; *W = trail ? HS_SHORT_WAVES : 0; break;
+    default:                *R = HS_COOP_ROWS; *W = HS_COOP_WAVES; break;
+  }
+}
+// The flank shape of one launch of n_items leading (trail = 0) or trailing (1) flank items — the one place it is decided: hs_launch_lead2 /
+// hs_launch_trail launch what it returns and hipstr_debug_launch_plan (api.hip) reports it.  max_cols: the batch's longest read side,
+// max_rows: its longest flank rowset (trailing flanks only).
+extern "C" int hs_flank_route(int trail, int n_items, int max_cols, int max_rows){
   const int m = systolic_mode();
   // (a wavefront per alignment: up to 64 per item; beyond ~6000 of them the sweeps that share rows across lanes are faster again)
-  return m != 0 && max_cols <= HS_SYS_MAXCOLS && (m == 2 || (unsigned)(item_end - item_begin) <= HS_SYS_ITEMS);
+  if (m != 0 && max_cols <= HS_SYS_MAXCOLS && (m == 2 || (unsigned)n_items <= HS_SYS_ITEMS)) return HS_FLANK_SYSTOLIC;
+  // few items (a locus or two per call): the chip is far from full and what counts is the serial length of a sweep, so the bands are
+  // half as tall and twice as many (HS_LAT_WAVES x HS_LAT_ROWS: a step is shorter, the pipeline four steps longer): -10 % per sweep
+  if ((unsigned)n_items <= HS_LAT_ITEMS) return HS_FLANK_LATENCY;
+  if (trail && max_rows - 1 <= HS_SHORT_TRAIL_ROWS) return HS_FLANK_SHORT;
+  return HS_FLANK_DEFAULT;
+}
+// The thresholds of the decisions above as compiled into this object: HS_SYS_ITEMS, HS_LAT_ITEMS, HS_SYS_MAXCOLS, HS_SHORT_TRAIL_ROWS,
+// HS_CMB_ROUNDS (hs_combine_kernel: 64 x HS_CMB_ROUNDS flank bases at most in registers).
+extern "C" void hs_flank_limits(int32_t out[5]){
+  out[0] = (int32_t)HS_SYS_ITEMS; out[1] = (int32_t)HS_LAT_ITEMS; out[2] = HS_SYS_MAXCOLS; out[3] = HS_SHORT_TRAIL_ROWS; out[4] = HS_CMB_ROUNDS;
 }
 extern "C" void hs_launch_lead2(unsigned n_active, unsigned n_wavefronts, hipStream_t st, const hs_dev_t* dp, int active_begin, int item_begin, int item_end, int chunk, int max_cols, int n_clear){
   hipLaunchKernelGGL(hs_col_kernel, dim3(n_active), dim3(64), 0, st, dp, active_begin, n_clear);
   if (item_end <= item_begin) return;
-  if (use_systolic(item_begin, item_end, max_cols)){
-    hipLaunchKernelGGL((hs_flank_systolic<true>), dim3((unsigned)(item_end - item_begin), 64), dim3(64), 0, st, dp, item_begin);
-    return;
+  switch (hs_flank_route(0, item_end - item_begin, max_cols, 0)){
+    case HS_FLANK_SYSTOLIC:
+      hipLaunchKernelGGL((hs_flank_systolic<true>), dim3((unsigned)(item_end - item_begin), 64), dim3(64), 0, st, dp, item_begin); break;
+    case HS_FLANK_LATENCY:
+      hipLaunchKernelGGL((hs_lead_kernel_coop<HS_LAT_ROWS, HS_LAT_WAVES, 2>), dim3(std::max(1u, std::min(n_wavefronts, 256u))), dim3(64*HS_LAT_WAVES), 0, st, dp, item_begin, item_end, chunk); break;
+    default:
+      hipLaunchKernelGGL((hs_lead_kernel_coop<HS_COOP_ROWS, HS_COOP_WAVES, HS_COOP_OCC>), dim3(std::max(1u, std::min(n_wavefronts, 256u*HS_COOP_OCC*4/HS_COOP_WAVES))), dim3(64*HS_COOP_WAVES), 0, st, dp, item_begin, item_end, chunk); break;
   }
-  // few items (a locus or two per call): the chip is far from full and what counts is the serial length of a sweep, so the bands are
-  // half as tall and twice as many (HS_LAT_WAVES x HS_LAT_ROWS: a step is shorter, the pipeline four steps longer): -10 % per sweep
-  if ((unsigned)(item_end - item_begin) <= HS_LAT_ITEMS)
-    hipLaunchKernelGGL((hs_lead_kernel_coop<HS_LAT_ROWS, HS_LAT_WAVES, 2>), dim3(std::max(1u, std::min(n_wavefronts, 256u))), dim3(64*HS_LAT_WAVES), 0, st, dp, item_begin, item_end, chunk);
-  else
-    hipLaunchKernelGGL((hs_lead_kernel_coop<HS_COOP_ROWS, HS_COOP_WAVES, HS_COOP_OCC>), dim3(std::max(1u, std::min(n_wavefronts, 256u*HS_COOP_OCC*4/HS_COOP_WAVES))), dim3(64*HS_COOP_WAVES), 0, st, dp, item_begin, item_end, chunk);
 }
 extern "C" void hs_launch_trail(unsigned n_wavefronts, hipStream_t st, const hs_dev_t* dp, int item_begin, int item_end, int chunk, int max_cols, int max_rows){
-  if (item_end > item_begin && use_systolic(item_begin, item_end, max_cols)){
-    hipLaunchKernelGGL((hs_flank_systolic<false>), dim3((unsigned)(item_end - item_begin), 64), dim3(64), 0, st, dp, item_begin);
-    return;
+  if (item_end <= item_begin) return;
+  switch (hs_flank_route(1, item_end - item_begin, max_cols, max_rows)){
+    case HS_FLANK_SYSTOLIC:
+      hipLaunchKernelGGL((hs_flank_systolic<false>), dim3((unsigned)(item_end - item_begin), 64), dim3(64), 0, st, dp, item_begin); break;
+    case HS_FLANK_LATENCY:
+      hipLaunchKernelGGL((hs_trail_kernel_coop<HS_LAT_ROWS, HS_LAT_WAVES, 2>), dim3(std::max(1u, std::min(n_wavefronts, 256u))), dim3(64*HS_LAT_WAVES), 0, st, dp, item_begin, item_end, chunk); break;
+    case HS_FLANK_SHORT:
+      hipLaunchKernelGGL((hs_trail_kernel_coop<HS_SHORT_ROWS, HS_SHORT_WAVES, HS_SHORT_OCC>), dim3(std::max(1u, std::min(n_wavefronts, 256u*HS_SHORT_OCC*4/HS_SHORT_WAVES))), dim3(64*HS_SHORT_WAVES), 0, st, dp, item_begin, item_end, chunk); break;
+    default:
+      hipLaunchKernelGGL((hs_trail_kernel_coop<HS_COOP_ROWS, HS_COOP_WAVES, HS_COOP_OCC>), dim3(std::max(1u, std::min(n_wavefronts, 256u*HS_COOP_OCC*4/HS_COOP_WAVES))), dim3(64*HS_COOP_WAVES), 0, st, dp, item_begin, item_end, chunk); break;
   }
-  const bool lat = (unsigned)(item_end - item_begin) <= HS_LAT_ITEMS;
-  // short flanks (production panels: <= 35 bp): three bands of up to 12 rows fill their wavefronts better than four of 9 (p30 trailing flank
-  // 4.25 -> 4.02 ms, profiles/r05_notes.md; at 60 rows the 4 x 15 shape is the best by 25 %)
-  const bool shrt = max_rows - 1 <= 36;
-  if (lat)       hipLaunchKernelGGL((hs_trail_kernel_coop<HS_LAT_ROWS, HS_LAT_WAVES, 2>), dim3(std::max(1u, std::min(n_wavefronts, 256u))), dim3(64*HS_LAT_WAVES), 0, st, dp, item_begin, item_end, chunk);
-  else if (shrt) hipLaunchKernelGGL((hs_trail_kernel_coop<12, 3, 3>), dim3(std::max(1u, std::min(n_wavefronts, 256u*3*4/3))), dim3(64*3), 0, st, dp, item_begin, item_end, chunk);
-  else hipLaunchKernelGGL((hs_trail_kernel_coop<HS_COOP_ROWS, HS_COOP_WAVES, HS_COOP_OCC>), dim3(std::max(1u, std::min(n_wavefronts, 256u*HS_COOP_OCC*4/HS_COOP_WAVES))), dim3(64*HS_COOP_WAVES), 0, st, dp, item_begin, item_end, chunk);
 }

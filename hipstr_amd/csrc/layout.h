@@ -34,6 +34,11 @@
 #define HS_ND_TOTAL 192      // sum over the six deletion sizes of min(|D|, n) <= 21 p <= 189
 #define HS_WAVE_LDS (HS_ND_TOTAL + 24 + 2*HS_TAB_CAP)   // doubles of per-wavefront LDS of hs_str_kernel: nd | cstl | tab
 #define HS_LDS_LIMIT (160*1024)
+#if defined(__HIPCC__) || defined(__HIP__)
+#define HS_HD __host__ __device__
+#else
+#define HS_HD
+#endif
 // LDS bytes of one hs_str_kernel workgroup (both sides of a read) when the longest read has lds_len bases and the longest STR allele
 // max_B: the host refuses a locus whose reads and alleles would not fit (check_locus), before it shares a batch with others.
 static inline size_t hs_str_kernel_lds_bytes(int lds_len, int max_B){
@@ -252,3 +257,25 @@ struct hs_dev_t {
   int32_t            n_stropts, n_recs;
   int64_t            f64_gen_base;   // doubles: the f64 pool is [host-written part | generated part]
 };
+
+// ---- launch-route predicates shared by the kernels and the host's view of the launch plan (api.hip hipstr_debug_launch_plan)
+// The flank shapes hs_flank_route (hmm_kernels.hip) picks for a launch of leading or trailing flanks.
+enum { HS_FLANK_SYSTOLIC = 0, HS_FLANK_LATENCY = 1, HS_FLANK_SHORT = 2, HS_FLANK_DEFAULT = 3 };
+// The bands of one item of a coop flank sweep (coop_rounds): n_rows rows after the block's first row, R rows per band at most, W bands
+// per round.  As many bands as there are wavefronts whenever the rows allow it, more rounds only for blocks deeper than one round holds;
+// band b has nr_base + (b < nr_rem) rows.
+struct hs_coop_bands_t { int rounds, nbands, nr_base, nr_rem; };
+static HS_HD inline hs_coop_bands_t hs_coop_bands(int n_rows, int R, int W){
+  hs_coop_bands_t c;
+  c.rounds = (n_rows + R*W - 1) / (R*W);
+  c.nbands = n_rows < c.rounds*W ? n_rows : c.rounds*W;
+  c.nr_base = n_rows / c.nbands; c.nr_rem = n_rows - c.nr_base*c.nbands;
+  return c;
+}
+// Which form of hs_combine_kernel takes a flank configuration of n_flank bases whose leading flank rowset has lead_len rows: 0 = the
+// per-allele form (an empty leading or trailing flank, or more than 64 x rounds bases), else the register form with ceil(n_flank / 64)
+// rounds of 64 seed positions (combine_config<tier>).
+static HS_HD inline int hs_combine_tier(int n_flank, int lead_len, int rounds){
+  if (lead_len < 1 || n_flank - lead_len < 1 || n_flank > 64*rounds) return 0;
+  return (n_flank + 63) / 64;
+}

@@ -35,6 +35,16 @@ int hipstr_debug_prepare(const hipstr_batch_t* batch, int threads, double* secon
 int hipstr_debug_str_groups(const hipstr_batch_t* batch, int32_t* side, int32_t* columns, int32_t* read_off, int cap_groups,
                             int32_t* reads, int cap_reads, int32_t* max_columns);
 
+/* Diagnostics (host only): the launch plan hipstr_hmm_align would run for a batch, with a workspace budget of ws_gib GiB per workspace
+ * (<= 0: the upload's own, HIPSTR_WS_GIB or its default), from the same decisions the launches take — the flank shapes (and the
+ * HIPSTR_FLANK_SYSTOLIC mode in force), the coop sweeps' bands per item, the STR-block kernels, the combine forms — as one JSON object:
+ * "thresholds" (the limits compiled into the library, "shapes": [rows per band, bands per round] per flank shape), "routes" (every route
+ * name there is) and per chunk "lead" / "trail" (route, items, per item in launch order [rows, rounds, bands of the last round, band
+ * heights] or, systolic, [rows, bands of 64 rows]), "str" (kernels launched, (read side, allele) pairs per kernel, side stream, long
+ * sides), "combine" ((read, allele) pairs per form: per-allele, 1..4 rounds of 64) and "routes" (the ones the chunk takes).  Writes up to
+ * cap - 1 bytes and a NUL; returns the full length (-1 on error).  Used by tests/test_routes.py. */
+int hipstr_debug_launch_plan(const hipstr_batch_t* batch, double ws_gib, char* json, int cap);
+
 /* Diagnostics (host only): one entry {A, G, Bnd} of the tabulated closed form the STR kernel uses for a "simple" visiting
  * list (StutterAlignerClass.cpp:59-150 for a periodic block): with `bound` columns of the block in reach, a run of U0 equal
  * configurations at the block's right end and `tail` configurations in total, fast_log_sum_exp over the pushed values is

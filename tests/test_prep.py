@@ -34,6 +34,25 @@ def test_library_exports_every_declared_symbol(hmm_host):
         assert hasattr(hmm_host, n), "missing export " + n
 
 
+def test_build_tracks_every_included_header():
+    """hipstr_amd/build.py recompiles an object only when its source or a file of HIP_HEADERS is newer: every file a source of
+    HIP_SOURCES includes with #include "...", directly or through another header, resolved relative to the file that includes it, must be
+    in HIP_HEADERS — else an edit to it leaves the product's objects stale while the oracle, whose Makefile tracks it, is rebuilt."""
+    from hipstr_amd import build
+    csrc = build.CSRC
+    tracked = {os.path.normpath(os.path.join(csrc, h)) for h in build.HIP_HEADERS}
+    seen, todo = set(), [os.path.join(csrc, s) for s in build.HIP_SOURCES]
+    while todo:
+        f = todo.pop()
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), flags=re.M):
+            p = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+            assert os.path.exists(p), "%s includes %s, which does not exist" % (f, inc)
+            if p not in seen:
+                seen.add(p); todo.append(p)
+    missing = sorted(os.path.relpath(p, csrc) for p in seen - tracked)
+    assert not missing, "included but not in hipstr_amd/build.py HIP_HEADERS: " + ", ".join(missing)
+
+
 def test_no_cpu_fallback_without_device(hmm_host):
     """Without a GPU the compute entry points fail loudly instead of computing on the host."""
     import torch
