@@ -566,6 +566,9 @@ def load_hmm():
     _sig(lib.hipstr_debug_stream_destroy, None, [C.c_void_p])
     _sig(lib.hipstr_debug_fetch_table, C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64])
     _sig(lib.hipstr_debug_launch_plan, C.c_int, [_BP, C.c_double, C.c_char_p, C.c_int])
+    _sig(lib.hipstr_debug_trace_plan, C.c_int, [_BP, C.c_int32, _i32p, _i32p, _i32p, C.c_double, C.c_char_p, C.c_int])
+    _sig(lib.hipstr_debug_nw_plan, C.c_int, [C.POINTER(HipstrNwBatch), C.c_double, C.c_char_p, C.c_int])
+    _sig(lib.hipstr_debug_post_plan, C.c_int, [_PBP, C.c_char_p, C.c_int])
     return lib
 
 
@@ -579,6 +582,41 @@ def launch_plan(lib, bptr, ws_gib=0.0):
     buf = C.create_string_buffer(n + 1)
     assert lib.hipstr_debug_launch_plan(bptr, ws_gib, buf, n + 1) == n
     return json.loads(buf.value.decode())
+
+
+def _plan_json(lib, what, call):
+    """Two calls of a hipstr_debug_*_plan entry point: the length, then the JSON."""
+    import json
+    n = call(None, 0)
+    if n < 0:
+        raise RuntimeError("%s failed: %s" % (what, lib.hipstr_last_error().decode()))
+    buf = C.create_string_buffer(n + 1)
+    assert call(buf, n + 1) == n
+    return json.loads(buf.value.decode())
+
+
+def trace_plan(lib, bptr, req_read, req_allele, req_seed=None, ws_mib=0.0):
+    """What hipstr_hmm_trace(_seeded) would launch for a request list (host only: hipstr_debug_trace_plan) as a dict; ws_mib > 0 sets the
+    budget of decision matrices per chunk."""
+    rr = np.ascontiguousarray(np.asarray(req_read, np.int32)); aa = np.ascontiguousarray(np.asarray(req_allele, np.int32))
+    ss = None if req_seed is None else np.ascontiguousarray(np.asarray(req_seed, np.int32))
+    return _plan_json(lib, "hipstr_debug_trace_plan", lambda buf, cap: lib.hipstr_debug_trace_plan(
+        bptr, len(rr), rr.ctypes.data_as(_i32p), aa.ctypes.data_as(_i32p), _ptr(ss, _i32p), ws_mib, buf, cap))
+
+
+def nw_plan(lib, pairs, use_ref_end_penalty=False, ws_mib=0.0):
+    """The chunks and fill kernels hipstr_nw_align would launch for [(ref, read), ...] (host only: hipstr_debug_nw_plan) as a dict."""
+    refs = [r.encode() for r, _ in pairs]; reads = [q.encode() for _, q in pairs]
+    ro = np.concatenate([[0], np.cumsum([len(r) for r in refs])]).astype(np.int32)
+    qo = np.concatenate([[0], np.cumsum([len(q) for q in reads])]).astype(np.int32)
+    rb = b"".join(refs); qb = b"".join(reads)
+    nb = HipstrNwBatch(len(pairs), ro.ctypes.data_as(_i32p), rb, qo.ctypes.data_as(_i32p), qb, int(use_ref_end_penalty))
+    return _plan_json(lib, "hipstr_debug_nw_plan", lambda buf, cap: lib.hipstr_debug_nw_plan(C.byref(nb), ws_mib, buf, cap))
+
+
+def post_plan(lib, pb):
+    """The launch hipstr_post_launch would make for a PostBatch (host only: hipstr_debug_post_plan) as a dict."""
+    return _plan_json(lib, "hipstr_debug_post_plan", lambda buf, cap: lib.hipstr_debug_post_plan(pb.ptr, buf, cap))
 
 
 def _why(lib, prefix):

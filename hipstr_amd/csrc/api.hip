@@ -1425,9 +1425,9 @@ struct PostRun {
   }
 };
 
-int post_setup(const hipstr_post_batch_t* pb, const double* dev_ll, PostRun& R){
+// The (locus, sample) units of a posterior batch and the totals of its arrays (host only: hipstr_debug_post_plan builds the same units).
+int post_units(const hipstr_post_batch_t* pb, std::vector<hs_post_unit_t>& units, int64_t& n_post, int64_t& n_samp, int64_t& n_ll){
   const hipstr::HostTables& T = hipstr::host_tables();
-  Ctx* ctx = R.ctx;
   int64_t po = 0, so = 0, lo = 0;
   for (int l = 0; l < pb->n_loci; l++){
     const int A = pb->n_alleles[l], S = pb->n_samples[l];
@@ -1444,12 +1444,29 @@ int post_setup(const hipstr_post_batch_t* pb, const double* dev_ll, PostRun& R){
       u.read_begin = r; u.ll_off = lo + (int64_t)(r-r0)*A;
       while (r < r1 && pb->sample_label[r] == s) r++;
       u.n_reads = r - u.read_begin;
-      R.units.push_back(u);
+      units.push_back(u);
     }
     if (r != r1) return fail("reads of a locus must be grouped by ascending sample label (genotyper.h:112-119)");
     po += (int64_t)S*A*A; so += S; lo += (int64_t)(r1-r0)*A;
   }
-  R.n_post = po; R.n_samp = so; R.n_ll = lo; R.n_reads = pb->n_loci ? pb->read_off[pb->n_loci] : 0;
+  n_post = po; n_samp = so; n_ll = lo;
+  return 0;
+}
+
+// The launch of a run's units: the largest unit decides for all (hs_post_split, post_layout.h).
+struct PostLaunch { size_t n_units; int max_nd, split; };
+PostLaunch post_launch_of(const std::vector<hs_post_unit_t>& units){
+  PostLaunch L; L.n_units = units.size(); L.max_nd = 1;
+  for (const hs_post_unit_t& u : units) L.max_nd = std::max(L.max_nd, u.n_alleles*u.n_alleles);
+  L.split = units.empty() ? 1 : hs_post_split(L.max_nd, L.n_units);          // (no units: nothing is launched)
+  return L;
+}
+
+int post_setup(const hipstr_post_batch_t* pb, const double* dev_ll, PostRun& R){
+  const hipstr::HostTables& T = hipstr::host_tables();
+  Ctx* ctx = R.ctx;
+  if (post_units(pb, R.units, R.n_post, R.n_samp, R.n_ll)) return 1;
+  R.n_reads = pb->n_loci ? pb->read_off[pb->n_loci] : 0;
   memset(&R.h, 0, sizeof R.h);
   if (!dev_ll && !pb->log_aln_probs) return fail("no log_aln_probs given");
   {
@@ -1552,16 +1569,14 @@ int hipstr_post_launch(hipstr_post_dev_t* pd, void* hip_stream){
   {
     // few units with many diplotypes each (one sample per locus, 128 haplotypes): the accumulation of a unit is shared by several
     // workgroups, to ~2048 in all (post_kernels.hip; bit-identical either way)
-    const size_t n_units = pd->R.units.size();
-    int max_nd = 1;
-    for (const hs_post_unit_t& u : pd->R.units) max_nd = std::max(max_nd, u.n_alleles*u.n_alleles);
-    const int split = (int)std::min<size_t>((size_t)(max_nd + 255)/256, n_units < 1024 ? (2048 + n_units - 1)/n_units : 1);
-    constexpr bool no_split = false;
-    if (split > 1 && !no_split){
-      hipLaunchKernelGGL(hs_posterior_accumulate_kernel, dim3((unsigned)n_units, (unsigned)split), dim3(256), 0, st, (const hs_post_dev_t*)pd->R.d_args);
-      hipLaunchKernelGGL(hs_posterior_finish_kernel, dim3((unsigned)n_units), dim3(256), 0, st, (const hs_post_dev_t*)pd->R.d_args);
+    const PostLaunch L = post_launch_of(pd->R.units);
+    const size_t n_units = L.n_units;
+    const int split = L.split;
+    if (split > 1){
+      hipLaunchKernelGGL(hs_posterior_accumulate_kernel, dim3((unsigned)n_units, (unsigned)split), dim3(HS_POST_THREADS), 0, st, (const hs_post_dev_t*)pd->R.d_args);
+      hipLaunchKernelGGL(hs_posterior_finish_kernel, dim3((unsigned)n_units), dim3(HS_POST_THREADS), 0, st, (const hs_post_dev_t*)pd->R.d_args);
     } else
-      hipLaunchKernelGGL(hs_posterior_kernel, dim3((unsigned)n_units), dim3(256), 0, st, (const hs_post_dev_t*)pd->R.d_args);
+      hipLaunchKernelGGL(hs_posterior_kernel, dim3((unsigned)n_units), dim3(HS_POST_THREADS), 0, st, (const hs_post_dev_t*)pd->R.d_args);
   }
   HS_HIP(hipGetLastError());
   if (host_libm){
@@ -1589,6 +1604,53 @@ int hipstr_post_launch(hipstr_post_dev_t* pd, void* hip_stream){
   }
   return 0;
 }
+
+#ifndef HIPSTR_NO_DEBUG_ABI
+// Diagnostics (host only): the launch hipstr_post_launch would make for a posterior batch, from the same decisions (post_units,
+// post_launch_of, hs_post_in_registers, hs_post_reads_per_tile), as one JSON object.
+static const char* const kPostRoutes[] = {
+  "hs_posterior_kernel", "hs_posterior_accumulate_kernel+hs_posterior_finish_kernel", "post_registers", "post_chunked",
+  "post_one_tile", "post_many_tiles", "post_no_reads", "post_one_echunk", "post_many_echunks", "post_empty_share" };
+int hipstr_debug_post_plan(const hipstr_post_batch_t* pb, char* json, int cap){
+  if (!pb) return fail("null argument"), -1;
+  std::vector<hs_post_unit_t> units; int64_t n_post, n_samp, n_ll;
+  if (post_units(pb, units, n_post, n_samp, n_ll)) return -1;
+  const PostLaunch L = post_launch_of(units);
+  std::string o; char b[256];
+  auto put = [&](const char* fmt, auto... a){ snprintf(b, sizeof b, fmt, a...); o += b; };
+  put("{\"thresholds\": {\"HS_POST_THREADS\": %d, \"HS_POST_ECHUNK\": %d, \"HS_POST_REGS\": %d, \"HS_POST_SPLIT_WGS\": %d, \"HS_POST_SPLIT_MAX_UNITS\": %d}, \"routes\": [",
+      HS_POST_THREADS, HS_POST_ECHUNK, HS_POST_REGS, HS_POST_SPLIT_WGS, HS_POST_SPLIT_MAX_UNITS);
+  for (const char* r : kPostRoutes) put("\"%s\", ", r);
+  o.resize(o.size() - 2);
+  const bool split = !units.empty() && L.split > 1;
+  put("], \"n_units\": %d, \"max_nd\": %d, \"split\": %d, \"launch\": [", (int)L.n_units, L.max_nd, units.empty() ? 0 : L.split);
+  if (split) put("[\"hs_posterior_accumulate_kernel\", %d], [\"hs_posterior_finish_kernel\", %d]", (int)L.n_units*L.split, (int)L.n_units);
+  else if (!units.empty()) put("[\"hs_posterior_kernel\", %d]", (int)L.n_units);
+  // per unit: [alleles, reads, path (0 registers, 1 chunked), reads per tile (registers), tiles, chunks of exponentials (chunked),
+  // workgroups of a split launch whose share of the unit's diplotypes is empty]
+  o += "], \"units\": [";
+  bool hit[10] = {false};
+  if (!units.empty()) hit[split ? 1 : 0] = true;
+  for (size_t i = 0; i < units.size(); i++){
+    const hs_post_unit_t& u = units[i];
+    const int A = u.n_alleles, nd = A*A;
+    const bool regs = !split && hs_post_in_registers(nd);
+    const int rt = regs ? hs_post_reads_per_tile(A, u.n_reads) : 0, tiles = regs ? (u.n_reads + rt - 1)/rt : 0;
+    const int echunks = regs ? 0 : (nd + HS_POST_ECHUNK - 1)/HS_POST_ECHUNK;
+    const int used = (nd + HS_POST_THREADS - 1)/HS_POST_THREADS, empty = split ? std::max(0, L.split - used) : 0;
+    hit[regs ? 2 : 3] = true;
+    if (regs) hit[tiles == 0 ? 6 : tiles == 1 ? 4 : 5] = true; else hit[echunks > 1 ? 8 : 7] = true;
+    if (empty > 0) hit[9] = true;
+    put("%s[%d, %d, %d, %d, %d, %d, %d]", i ? ", " : "", A, u.n_reads, regs ? 0 : 1, rt, tiles, echunks, empty);
+  }
+  o += "], \"routes_hit\": [";
+  bool first = true;
+  for (int i = 0; i < 10; i++) if (hit[i]){ put("%s\"%s\"", first ? "" : ", ", kPostRoutes[i]); first = false; }
+  o += "]}";
+  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
+  return (int)o.size();
+}
+#endif  // HIPSTR_NO_DEBUG_ABI
 
 int hipstr_post_fetch(hipstr_post_dev_t* pd, double* log_post, double* sample_total_ll, int32_t* map_gt, double* locus_total_ll){
   if (!pd || !log_post || !sample_total_ll || !map_gt || !locus_total_ll) return fail("null argument");

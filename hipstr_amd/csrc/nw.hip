@@ -16,11 +16,14 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/hipstr_hmm.h"
+#include "../../include/hipstr_hmm_debug.h"
 #include "layout.h"
 #include "device_common.h"
 #include "api_internal.h"
@@ -28,6 +31,8 @@
 
 #define HS_NW_MAX_REF 4095
 #define HS_NW_MAX_READ 1536          // rows per lane come from {1,2,3,4,6,8,12,16,24}
+#define HS_NW_RUNGS 9
+#define HS_NW_BUDGET_MIB 256         // traceback bytes per chunk unless the call could need more (then the device is asked) or HIPSTR_NW_WS_MIB says
 
 struct hs_nw_pair_t {
   int32_t ref_off, L1, read_off, L2;
@@ -169,6 +174,41 @@ __global__ void __launch_bounds__(64) hs_nw_walk(const hs_nw_dev_t* __restrict__
 #define NW_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
   hipstr::api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
 
+// ---- launch decisions: the one place each is taken.  hipstr_nw_align calls them, hipstr_debug_nw_plan reports them
+// (tests/test_stage_routes.py pins a case on each side of every limit)
+const int kNwRows[HS_NW_RUNGS] = { 1, 2, 3, 4, 6, 8, 12, 16, 24 };       // rows per lane of the fill kernel instantiations
+// the rung of a read of L2 bases: the first whose 64 lanes x rows cover it (-1: beyond the last)
+int nw_rung(int L2){
+  const int need = (L2 + 63)/64;
+  for (int cl = 0; cl < HS_NW_RUNGS; cl++) if (need <= kNwRows[cl]) return cl;
+  return -1;
+}
+// why a pair is refused (NULL: it is taken)
+const char* nw_refusal(int L1, int L2){
+  if (L1 < 1 || L2 < 1) return "Needleman-Wunsch needs non-empty sequences";
+  if (L2 > HS_NW_MAX_READ) return "second sequence longer than 1536 bases is not supported";
+  if (L1 > HS_NW_MAX_REF) return "reference longer than 4095 bases is not supported";
+  return NULL;
+}
+static_assert(HS_NW_MAX_READ == 1536 && HS_NW_MAX_REF == 4095, "the refusal messages name the limits");
+int64_t nw_pair_bytes(int L1, int L2){ return (int64_t)L1*L2; }
+// the budget of a call that does not ask the device: the default, or HIPSTR_NW_WS_MIB
+bool nw_asks_device(int64_t all_bytes){ return all_bytes > ((int64_t)HS_NW_BUDGET_MIB << 20); }
+int64_t nw_env_budget(int64_t budget){
+  if (const char* e = getenv("HIPSTR_NW_WS_MIB")) budget = std::max<int64_t>(1, atoll(e)) << 20;
+  return budget;
+}
+// the chunk that starts at pair p0: pairs while they fit the budget, and always the first (a pair larger than the budget runs alone)
+template <typename Pairs> int nw_chunk_end(const Pairs& pairs, int p0, int n, int64_t budget){
+  int p1 = p0; int64_t tb = 0;
+  while (p1 < n){
+    const int64_t need = nw_pair_bytes(pairs[p1].L1, pairs[p1].L2);
+    if (p1 > p0 && tb + need > budget) break;
+    tb += need; p1++;
+  }
+  return p1;
+}
+
 struct NwBufs {
   std::vector<void*> p;
   hipstr::Ctx* ctx = NULL;          // blocks come from (and return to) the context's cache: no hipMalloc / hipFree per call
@@ -210,9 +250,7 @@ extern "C" int hipstr_nw_align(const hipstr_nw_batch_t* nb, hipstr_nw_out_t* o){
     hs_nw_pair_t& P = pairs[i];
     P.ref_off = nb->ref_off[i]; P.L1 = nb->ref_off[i+1] - nb->ref_off[i];
     P.read_off = nb->read_off[i]; P.L2 = nb->read_off[i+1] - nb->read_off[i];
-    if (P.L1 < 1 || P.L2 < 1) return api_fail("Needleman-Wunsch needs non-empty sequences");
-    if (P.L2 > HS_NW_MAX_READ) return api_fail("second sequence longer than 1536 bases is not supported");
-    if (P.L1 > HS_NW_MAX_REF) return api_fail("reference longer than 4095 bases is not supported");
+    if (const char* why = nw_refusal(P.L1, P.L2)) return api_fail(why);
   }
   hs_nw_dev_t h; memset(&h, 0, sizeof h);
   hipstr::HostArena seqs;                                     // the two sequence pools: one pinned block, one copy
@@ -224,37 +262,32 @@ extern "C" int hipstr_nw_align(const hipstr_nw_batch_t* nb, hipstr_nw_out_t* o){
   }
   h.end_penalty = nb->use_ref_end_penalty ? 1 : 0;
   // traceback bytes per chunk; the device is only asked how much it has free when the call could need more than 256 MiB
-  int64_t budget = (int64_t)256 << 20;
+  int64_t budget = (int64_t)HS_NW_BUDGET_MIB << 20;
   {
-    int64_t all = 0; for (int i = 0; i < n; i++) all += (int64_t)pairs[i].L1*pairs[i].L2;
-    if (all > budget){
+    int64_t all = 0; for (int i = 0; i < n; i++) all += nw_pair_bytes(pairs[i].L1, pairs[i].L2);
+    if (nw_asks_device(all)){
       size_t free_b = 0, total_b = 0;
       NW_HIP(hipMemGetInfo(&free_b, &total_b));
       budget = std::min<int64_t>((int64_t)8 << 30, (int64_t)(free_b / 4));
     }
   }
-  if (const char* e = getenv("HIPSTR_NW_WS_MIB")) budget = std::max<int64_t>(1, atoll(e)) << 20;
+  budget = nw_env_budget(budget);
   for (int p0 = 0; p0 < n; ){
-    int p1 = p0; int64_t tb = 0, lf = 0, ob = 0;
-    while (p1 < n){
-      const int64_t need = (int64_t)pairs[p1].L1*pairs[p1].L2;
-      if (p1 > p0 && tb + need > budget) break;
-      pairs[p1].trace_off = tb; tb += need;
-      pairs[p1].last_off = lf; lf += 3*(int64_t)pairs[p1].L1;
-      pairs[p1].ops_off = ob; ob += pairs[p1].L1 + pairs[p1].L2;
-      p1++;
+    const int p1 = nw_chunk_end(pairs, p0, n, budget);
+    int64_t tb = 0, lf = 0, ob = 0;
+    for (int i = p0; i < p1; i++){
+      pairs[i].trace_off = tb; tb += nw_pair_bytes(pairs[i].L1, pairs[i].L2);
+      pairs[i].last_off = lf; lf += 3*(int64_t)pairs[i].L1;
+      pairs[i].ops_off = ob; ob += pairs[i].L1 + pairs[i].L2;
     }
     const int np = p1 - p0;
-    static const int kRows[9] = { 1, 2, 3, 4, 6, 8, 12, 16, 24 };       // rows per lane of the fill kernel instantiations
-    std::vector<int32_t> items; int cls_begin[10];
-    for (int cl = 0; cl < 9; cl++){
+    const int* const kRows = kNwRows;
+    std::vector<int32_t> items; int cls_begin[HS_NW_RUNGS+1];
+    for (int cl = 0; cl < HS_NW_RUNGS; cl++){
       cls_begin[cl] = items.size();
-      for (int i = p0; i < p1; i++){
-        const int need = (pairs[i].L2 + 63)/64;
-        if (need <= kRows[cl] && (cl == 0 || need > kRows[cl-1])) items.push_back(i - p0);
-      }
+      for (int i = p0; i < p1; i++) if (nw_rung(pairs[i].L2) == cl) items.push_back(i - p0);
     }
-    cls_begin[9] = items.size();
+    cls_begin[HS_NW_RUNGS] = items.size();
     NwBufs ws;
     ws.runs_on(T.stream);
     hs_nw_dev_t hc = h;
@@ -273,7 +306,7 @@ extern "C" int hipstr_nw_align(const hipstr_nw_batch_t* nb, hipstr_nw_out_t* o){
     hc.pairs = ch.at<hs_nw_pair_t>(o_pairs); hc.items = ch.at<int32_t>(o_items);
     if (ch.send(T.stream)) return 1;
     const hs_nw_dev_t* d_args = ch.at<hs_nw_dev_t>(o_args);
-    for (int cl = 0; cl < 9; cl++){
+    for (int cl = 0; cl < HS_NW_RUNGS; cl++){
       const int cnt = cls_begin[cl+1] - cls_begin[cl];
       if (cnt == 0) continue;
 #define NW_LAUNCH(C_) hipLaunchKernelGGL(hs_nw_fill<C_>, dim3(cnt), dim3(64), 0, T.stream, d_args, cls_begin[cl])
@@ -329,6 +362,49 @@ extern "C" int hipstr_nw_align(const hipstr_nw_batch_t* nb, hipstr_nw_out_t* o){
   }
   return 0;
 }
+
+#ifndef HIPSTR_NO_DEBUG_ABI
+// Diagnostics (host only): the chunks and fill kernels hipstr_nw_align would launch, from the same decisions, as one JSON object.
+extern "C" int hipstr_debug_nw_plan(const hipstr_nw_batch_t* nb, double ws_mib, char* json, int cap){
+  using hipstr::api_fail;
+  if (!nb || nb->n_pairs < 0){ api_fail("null argument"); return -1; }
+  const int n = nb->n_pairs;
+  struct Pr { int L1, L2; };
+  std::vector<Pr> pairs(n);
+  int64_t all = 0;
+  for (int i = 0; i < n; i++){
+    pairs[i].L1 = nb->ref_off[i+1] - nb->ref_off[i]; pairs[i].L2 = nb->read_off[i+1] - nb->read_off[i];
+    if (const char* why = nw_refusal(pairs[i].L1, pairs[i].L2)){ api_fail(why); return -1; }
+    all += nw_pair_bytes(pairs[i].L1, pairs[i].L2);
+  }
+  // (a call that would ask the device for its free memory: the plan takes the budget it was given, else the default)
+  const int64_t budget = ws_mib > 0 ? (int64_t)(ws_mib*1048576.0) : nw_env_budget((int64_t)HS_NW_BUDGET_MIB << 20);
+  std::string o; char b[256];
+  auto put = [&](const char* fmt, auto... a){ snprintf(b, sizeof b, fmt, a...); o += b; };
+  put("{\"thresholds\": {\"HS_NW_MAX_REF\": %d, \"HS_NW_MAX_READ\": %d, \"HS_NW_BUDGET_MIB\": %d, \"rows\": [", HS_NW_MAX_REF, HS_NW_MAX_READ, HS_NW_BUDGET_MIB);
+  for (int cl = 0; cl < HS_NW_RUNGS; cl++) put("%s%d", cl ? ", " : "", kNwRows[cl]);
+  o += "]}, \"routes\": [";
+  for (int cl = 0; cl < HS_NW_RUNGS; cl++) put("\"hs_nw_fill<%d>\", ", kNwRows[cl]);
+  put("\"nw_one_chunk\", \"nw_chunks\", \"nw_pair_over_budget\"], \"budget\": %lld, \"asks_device\": %s, \"end_penalty\": %d, \"chunks\": [",
+      (long long)budget, nw_asks_device(all) ? "true" : "false", nb->use_ref_end_penalty ? 1 : 0);
+  int n_chunks = 0;
+  for (int p0 = 0; p0 < n; n_chunks++){
+    const int p1 = nw_chunk_end(pairs, p0, n, budget);
+    int64_t tb = 0; int cnt[HS_NW_RUNGS] = {0};
+    for (int i = p0; i < p1; i++){ tb += nw_pair_bytes(pairs[i].L1, pairs[i].L2); cnt[nw_rung(pairs[i].L2)]++; }
+    put("%s{\"p0\": %d, \"p1\": %d, \"bytes\": %lld, \"over_budget\": %s, \"rungs\": [", p0 ? ", " : "", p0, p1, (long long)tb, tb > budget ? "true" : "false");
+    for (int cl = 0; cl < HS_NW_RUNGS; cl++) put("%s%d", cl ? ", " : "", cnt[cl]);
+    o += "], \"launch\": [";
+    bool first = true;
+    for (int cl = 0; cl < HS_NW_RUNGS; cl++) if (cnt[cl]){ put("%s[\"hs_nw_fill<%d>\", %d]", first ? "" : ", ", kNwRows[cl], cnt[cl]); first = false; }
+    o += "]}";
+    p0 = p1;
+  }
+  put("], \"n_chunks\": %d}", n_chunks);
+  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
+  return (int)o.size();
+}
+#endif  // HIPSTR_NO_DEBUG_ABI
 
 namespace {
 // Haplotype::adjust_indels (Haplotype.cpp:8-56): move indels of the leading flank to the right, into / up to the repeat block

@@ -15,8 +15,7 @@
 #include "post_layout.h"
 #include "cr_math.h"
 
-#define HS_POST_ECHUNK 2048
-#define HS_POST_REGS 8            // diplotypes per thread a unit may have to stay in registers (256 x 8 = HS_POST_ECHUNK: its exponentials fit the LDS chunk)
+// (HS_POST_ECHUNK, HS_POST_REGS and the path / tile decisions: post_layout.h)
 
 namespace {
 
@@ -80,7 +79,7 @@ __device__ __forceinline__ void posterior_body(const hs_post_dev_t& d){
   // for the normalisation (40 KB of traffic per 1024-diplotype unit, a million units per EM round) and pays ~30 workgroup barriers in
   // its three tree reductions; here the reductions are wavefront shuffles plus one LDS exchange.  Same operations on the same values in the
   // same order (the sum of the exponentials is still thread 0's, in index order): bit-identical.
-  if (PHASE == 0 && nd <= 256*HS_POST_REGS && !d.raw){
+  if (PHASE == 0 && hs_post_in_registers(nd) && !d.raw){
 #ifdef HS_POST_TIME
     unsigned long long tk[6]; tk[0] = __builtin_amdgcn_s_memtime();
 #define HS_PT(i) tk[i] = __builtin_amdgcn_s_memtime()
@@ -123,7 +122,7 @@ __device__ __forceinline__ void posterior_body(const hs_post_dev_t& d){
       ij[k] = i | (j << 16);
     }
     {
-      const int RT = max(1, min(u.n_reads, HS_POST_ECHUNK / (2*A + 1)));      // reads per tile: two addends per (read, allele) + a weight per read
+      const int RT = hs_post_reads_per_tile(A, u.n_reads);                    // reads per tile: two addends per (read, allele) + a weight per read
       double* const sA1 = ebuf; double* const sA2 = ebuf + RT*A; double* const sW = ebuf + 2*RT*A;
       for (int r0 = 0; r0 < u.n_reads; r0 += RT){
         const int nr = min(RT, u.n_reads - r0);

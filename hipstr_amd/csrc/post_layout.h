@@ -1,6 +1,33 @@
 // post_layout.h — device-side description of a posterior batch (post_kernels.hip, api.hip).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+
+// ---- launch decisions of the posterior stage: the one place each is taken.  post_kernels.hip and hipstr_post_launch (api.hip) call them,
+// hipstr_debug_post_plan reports them (tests/test_stage_routes.py pins a case on each side of every limit)
+#define HS_POST_THREADS 256            // threads of a posterior workgroup
+#define HS_POST_ECHUNK 2048            // exponentials summed per LDS chunk; the register path's read tiles live in the same buffer
+#define HS_POST_REGS 8                 // diplotypes per thread a unit may have to stay in registers (256 x 8 = HS_POST_ECHUNK: its exponentials fit the LDS chunk)
+#define HS_POST_SPLIT_WGS 2048         // workgroups a split accumulation aims at
+#define HS_POST_SPLIT_MAX_UNITS 1024   // from this many units on the accumulation is never split
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define HS_POST_HD __host__ __device__
+#else
+#define HS_POST_HD
+#endif
+// a unit of nd = A^2 diplotypes keeps them in registers (one launch only: a split launch takes the chunked path for every unit)
+HS_POST_HD inline bool hs_post_in_registers(int nd){ return nd <= HS_POST_THREADS*HS_POST_REGS; }
+// reads per LDS tile of the register path: two addends per (read, allele) + a weight per read
+HS_POST_HD inline int hs_post_reads_per_tile(int A, int n_reads){
+  const int fit = HS_POST_ECHUNK / (2*A + 1), rt = n_reads < fit ? n_reads : fit;
+  return rt > 1 ? rt : 1;
+}
+// workgroups per unit of the accumulation (1 = hs_posterior_kernel alone): from the LARGEST unit, applied to every unit of the launch
+inline int hs_post_split(int max_nd, size_t n_units){
+  const size_t by_size = (size_t)(max_nd + HS_POST_THREADS - 1)/HS_POST_THREADS;
+  const size_t by_count = n_units < HS_POST_SPLIT_MAX_UNITS ? (HS_POST_SPLIT_WGS + n_units - 1)/n_units : 1;
+  return (int)(by_size < by_count ? by_size : by_count);
+}
 
 // One (locus, sample) pair: the unit a workgroup processes.
 struct hs_post_unit_t {

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "../../include/hipstr_hmm.h"
+#include "../../include/hipstr_hmm_debug.h"
 #include "layout.h"
 #include "device_common.h"
 #include "prep.h"
@@ -531,6 +533,9 @@ __device__ void trace_walk(const hs_tdev_t& d, int si, int B, int max_index, con
 }
 
 #define HS_WALK_LDS 24576          // bytes of decisions per side a walk keeps in LDS (150-bp reads x 60-row flanks: 9 KB)
+// decision bytes of a side, and whether hs_trace_walk copies them to LDS (hipstr_debug_trace_plan reports the same)
+__host__ __device__ inline int hs_trace_side_bytes(int F0, int F2, int n){ return (F0 + 1 + F2)*n; }
+__host__ __device__ inline bool hs_walk_in_lds(int bytes){ return bytes <= HS_WALK_LDS; }
 __global__ void __launch_bounds__(64) hs_trace_walk(const hs_tdev_t* __restrict__ dp, int req_begin){
   const hs_tdev_t& d = *dp;
   const int lane = threadIdx.x;
@@ -582,9 +587,9 @@ __global__ void __launch_bounds__(64) hs_trace_walk(const hs_tdev_t* __restrict_
 #pragma unroll
   for (int sd = 0; sd < 2; sd++){
     const hs_tside_t* S = SL + sd;
-    const int bytes = (uni(S->F0) + 1 + uni(S->F2))*uni(S->n);
+    const int bytes = hs_trace_side_bytes(uni(S->F0), uni(S->F2), uni(S->n));
     const uint8_t* g = d.dec + uni(S->dec_off);
-    if (bytes <= HS_WALK_LDS){
+    if (hs_walk_in_lds(bytes)){
       const uint4* g4 = (const uint4*)g;
       for (int i = lane; i < (bytes + 15)/16; i += 64) s_dec[sd][i] = g4[i];
       decp[sd] = (const uint8_t*)s_dec[sd];
@@ -621,6 +626,46 @@ struct DevBufs {
     return 0;
   }
 };
+
+// ---- launch decisions: the one place each is taken.  hipstr_hmm_trace_seeded calls them, hipstr_debug_trace_plan reports them
+// (tests/test_stage_routes.py pins a case on each side of every limit)
+#define HS_TRACE_STATIC_CLASSES 6        // column classes whose tables are static LDS (hs_trace_fill<1..6>, hs_trace_fill_mixed)
+#define HS_TRACE_MIXED_MAX_REQ 4096      // a chunk of more requests launches the static classes one by one
+#define HS_TRACE_BUDGET_MIB 256          // decision bytes per chunk unless the call could need more (then the device is asked) or HIPSTR_TRACE_WS_MIB says
+int trace_col_class(int n){ return (n + 63)/64; }                           // columns per lane of a side of n columns: 1 .. HS_MAX_COLS
+// the fill kernel of a class: hs_trace_fill<cl> up to HS_TRACE_STATIC_CLASSES, then hs_trace_fill_long<8 | 12 | 16>
+int trace_fill_cols(int cl){ return cl <= HS_TRACE_STATIC_CLASSES ? cl : (cl <= 8 ? 8 : (cl <= 12 ? 12 : 16)); }
+// small call, several static classes: one launch (hs_trace_fill_mixed)
+bool trace_mixed_launch(int n_static_classes, int nq){ return n_static_classes > 1 && nq <= HS_TRACE_MIXED_MAX_REQ; }
+// only the requested reads' bases travel when they are less than half of the batch's
+bool trace_compact_reads(int64_t wanted, int64_t total_bases){ return wanted > 0 && wanted*2 < total_bases; }
+const char* trace_side_refusal(int s, int len){
+  return (s > 64*HS_MAX_COLS || len-s-1 > 64*HS_MAX_COLS) ? "traceback of a read side longer than 1024 bases is not supported" : NULL;
+}
+static_assert(64*HS_MAX_COLS == 1024, "the refusal message names the limit");
+// workspace bytes of a side (16-byte pieces: hs_trace_walk copies a matrix to LDS in uint4s) and of a request
+int64_t trace_side_ws(int F0, int F2, int n){ return ((int64_t)(F0 + 1 + F2)*n + 15) & ~(int64_t)15; }
+bool trace_asks_device(int64_t rough_bytes){ return rough_bytes > ((int64_t)HS_TRACE_BUDGET_MIB << 20); }
+int64_t trace_env_budget(int64_t budget){
+  if (const char* e = getenv("HIPSTR_TRACE_WS_MIB")) budget = std::max<int64_t>(1, atoll(e)) << 20;
+  return budget;
+}
+// the chunk that starts at request q0: requests while their matrices fit the budget
+int trace_chunk_end(const std::vector<int64_t>& need, int q0, int64_t budget){
+  int q1 = q0; int64_t mat = 0;
+  while (q1 < (int)need.size() && mat + need[q1] <= budget){ mat += need[q1]; q1++; }
+  return q1;
+}
+// the seed of a request: the caller's or the host's; NULL or the refusal
+const char* trace_seed_of(const hipstr_batch_t* b, int l, int r, const int32_t* req_seed, int q, int& s){
+  const bool given = req_seed && req_seed[q] != HIPSTR_SEED_AUTO;       // trace_optimal_aln's seed_base argument (HapAligner.h:93)
+  s = given ? req_seed[q] : hipstr::calc_seed_base(b, l, r);
+  if (s == -2) return "Invalid alignment seed or unrecognized CIGAR char (HapAligner.cpp:309,316)";
+  if (s < 0) return "read without a seed base cannot be traced (HapAligner.cpp:586-594)";
+  const int len = b->base_off[r+1] - b->base_off[r];
+  if (given && (s < 1 || s > len - 2)) return "seed base must leave at least one base on either side (HapAligner.cpp:316)";
+  return trace_side_refusal(s, len);
+}
 
 // two side streams + their events per (host thread, device), created at first use and kept
 struct AllelePrep {
@@ -795,13 +840,8 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
     const int32_t* nopts = b->blk_nopts + 3*l;
     const int A = nopts[0]*nopts[1]*nopts[2];
     if (k < 0 || k >= A) return api_fail("request names an allele outside its locus");
-    const bool given = req_seed && req_seed[q] != HIPSTR_SEED_AUTO;       // trace_optimal_aln's seed_base argument (HapAligner.h:93)
-    const int s = given ? req_seed[q] : hipstr::calc_seed_base(b, l, r);
-    if (s == -2) return api_fail("Invalid alignment seed or unrecognized CIGAR char (HapAligner.cpp:309,316)");
-    if (s < 0) return api_fail("read without a seed base cannot be traced (HapAligner.cpp:586-594)");
-    const int len = b->base_off[r+1] - b->base_off[r];
-    if (given && (s < 1 || s > len - 2)) return api_fail("seed base must leave at least one base on either side (HapAligner.cpp:316)");
-    if (s > 64*HS_MAX_COLS || len-s-1 > 64*HS_MAX_COLS) return api_fail("traceback of a read side longer than 1024 bases is not supported");
+    int s;
+    if (const char* why = trace_seed_of(b, l, r, req_seed, q, s)) return api_fail(why);
     seeds[q] = s; req_locus[q] = l;
     const int64_t key = ((int64_t)l << 32) | (uint32_t)k;
     std::map<int64_t, int>::iterator hit = allele_slot.find(key);
@@ -848,7 +888,7 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
       const int r = req_read[q];
       if (at[r] < 0){ at[r] = (int32_t)wanted; wanted += b->base_off[r+1] - b->base_off[r]; }
     }
-    if (wanted > 0 && wanted*2 < (int64_t)total_bases){
+    if (trace_compact_reads(wanted, total_bases)){
       compact_reads = true;
       up_bases.resize((size_t)wanted); up_quals.resize((size_t)wanted);
       for (int q = 0; q < n_req; q++){
@@ -879,20 +919,20 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
   // ---- chunks of requests whose matrices fit the workspace budget
   // (the query costs as much as a small call's kernels: only a call whose matrices could exceed 256 MiB asks — an upper bound from the
   //  longest read and the flank lengths of the first allele is enough to tell)
-  int64_t budget = (int64_t)256 << 20;                                                   // bytes of decision matrices per chunk
+  int64_t budget = (int64_t)HS_TRACE_BUDGET_MIB << 20;                                   // bytes of decision matrices per chunk
   {
     int64_t rough = 0;
     for (int q = 0; q < n_req; q++){
       const int r = req_read[q]; const AllelePrep& ap = alleles[req_ap[q]];
       rough += (int64_t)(ap.seq[0][0].size() + ap.seq[0][2].size() + 2)*(b->base_off[r+1] - b->base_off[r]);
     }
-    if (rough > budget){
+    if (trace_asks_device(rough)){
       size_t free_b = 0, total_b = 0;
       TR_HIP(hipMemGetInfo(&free_b, &total_b));
       budget = std::min<int64_t>((int64_t)8 << 30, (int64_t)(free_b / 4));
     }
   }
-  if (const char* e = getenv("HIPSTR_TRACE_WS_MIB")) budget = std::max<int64_t>(1, atoll(e)) << 20;
+  budget = trace_env_budget(budget);
   std::vector<hs_tside_t> sides(2*(size_t)n_req);
   std::vector<int64_t> need(n_req);
   for (int q = 0; q < n_req; q++){
@@ -909,7 +949,7 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
       S.trail_off = ap.trail_off[sd]; S.F2 = ap.seq[sd][2].size();
       S.stropt = ap.stropt[sd];
       S.ops_cap = S.n + S.F0 + S.F2 + (int)ap.seq[sd][1].size() + 2*HS_MAXREP*b->period[req_locus[q]] + 16;
-      need[q] += ((int64_t)(S.F0 + 1 + S.F2)*S.n + 15) & ~(int64_t)15;
+      need[q] += trace_side_ws(S.F0, S.F2, S.n);
     }
     if (need[q] > budget) return api_fail("one traceback needs more workspace than the device offers");
   }
@@ -942,23 +982,23 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
   double ms_alloc = 0, ms_kernel = 0, ms_d2h = 0, ms_replay = 0;
   for (int q0 = 0; q0 < n_req; ){
     const auto c0 = now();
-    int q1 = q0; int64_t mat = 0; int64_t n_art = 0, n_ops = 0, n_lc = 0;
-    while (q1 < n_req && mat + need[q1] <= budget){
+    const int q1 = trace_chunk_end(need, q0, budget);
+    int64_t mat = 0; int64_t n_art = 0, n_ops = 0, n_lc = 0;
+    for (int q = q0; q < q1; q++){
       for (int sd = 0; sd < 2; sd++){
-        hs_tside_t& S = sides[2*q1+sd];
-        S.dec_off = mat; mat += ((int64_t)(S.F0 + 1 + S.F2)*S.n + 15) & ~(int64_t)15;       // (16-byte pieces: hs_trace_walk copies a matrix to LDS in uint4s)
+        hs_tside_t& S = sides[2*q+sd];
+        S.dec_off = mat; mat += trace_side_ws(S.F0, S.F2, S.n);
         S.lc_off = (int32_t)n_lc; n_lc += S.F0 + 1 + S.F2;
         S.art_off = (int32_t)n_art; n_art += 2*S.n;
         S.ops_off = (int32_t)n_ops; n_ops += S.ops_cap;
       }
-      q1++;
     }
     const int nq = q1 - q0;
     // launch order: sides grouped by columns-per-lane class
     std::vector<int32_t> items; int cls_begin[HS_MAX_COLS+1];
     for (int cl = 1; cl <= HS_MAX_COLS; cl++){
       cls_begin[cl-1] = items.size();
-      for (int si = 2*q0; si < 2*q1; si++) if ((sides[si].n + 63)/64 == cl) items.push_back(si - 2*q0);
+      for (int si = 2*q0; si < 2*q1; si++) if (trace_col_class(sides[si].n) == cl) items.push_back(si - 2*q0);
     }
     cls_begin[HS_MAX_COLS] = items.size();
     hipstr::HostArena ch_arena;                     // this chunk's sides, launch order and argument block
@@ -972,27 +1012,26 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
     const hs_tdev_t* d_args = ch_arena.at<hs_tdev_t>(o_args);
     const auto c1 = now();
     // the fill kernels of the column classes: one launch per class for calls of many loci, ONE launch for the requests of a locus or two (hs_trace_fill_mixed)
-    int n_cls = 0; for (int cl = 1; cl <= 6; cl++) n_cls += (cls_begin[cl] - cls_begin[cl-1]) > 0;
-    constexpr bool mixed_on = true;
-    const bool mixed = mixed_on && n_cls > 1 && nq <= 4096;        // small call, several classes: one launch (hs_trace_fill_mixed)
+    int n_cls = 0; for (int cl = 1; cl <= HS_TRACE_STATIC_CLASSES; cl++) n_cls += (cls_begin[cl] - cls_begin[cl-1]) > 0;
+    const bool mixed = trace_mixed_launch(n_cls, nq);
     if (mixed){
       hs_tcls_t cls;
-      for (int cl = 1; cl <= 6; cl++) cls.end[cl-1] = cls_begin[cl];
-      hipLaunchKernelGGL(hs_trace_fill_mixed, dim3(cls_begin[6]), dim3(64), 0, T.stream, d_args, cls);
+      for (int cl = 1; cl <= HS_TRACE_STATIC_CLASSES; cl++) cls.end[cl-1] = cls_begin[cl];
+      hipLaunchKernelGGL(hs_trace_fill_mixed, dim3(cls_begin[HS_TRACE_STATIC_CLASSES]), dim3(64), 0, T.stream, d_args, cls);
     }
-    for (int cl = mixed ? 7 : 1; cl <= HS_MAX_COLS; cl++){
+    for (int cl = mixed ? HS_TRACE_STATIC_CLASSES + 1 : 1; cl <= HS_MAX_COLS; cl++){
       const int cnt = cls_begin[cl] - cls_begin[cl-1];
       if (cnt == 0) continue;
       hipStream_t ks = T.stream;
-      switch (cl){
+      switch (trace_fill_cols(cl)){
         case 1: hipLaunchKernelGGL(hs_trace_fill<1>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
         case 2: hipLaunchKernelGGL(hs_trace_fill<2>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
         case 3: hipLaunchKernelGGL(hs_trace_fill<3>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
         case 4: hipLaunchKernelGGL(hs_trace_fill<4>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
         case 5: hipLaunchKernelGGL(hs_trace_fill<5>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
         case 6: hipLaunchKernelGGL(hs_trace_fill<6>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
-        case 7: case 8: if (launch_fill_long<8>(cnt, ks, d_args, cls_begin[cl-1])) return api_fail("hipFuncSetAttribute (traceback LDS) failed"); break;
-        case 9: case 10: case 11: case 12: if (launch_fill_long<12>(cnt, ks, d_args, cls_begin[cl-1])) return api_fail("hipFuncSetAttribute (traceback LDS) failed"); break;
+        case 8: if (launch_fill_long<8>(cnt, ks, d_args, cls_begin[cl-1])) return api_fail("hipFuncSetAttribute (traceback LDS) failed"); break;
+        case 12: if (launch_fill_long<12>(cnt, ks, d_args, cls_begin[cl-1])) return api_fail("hipFuncSetAttribute (traceback LDS) failed"); break;
         default: if (launch_fill_long<16>(cnt, ks, d_args, cls_begin[cl-1])) return api_fail("hipFuncSetAttribute (traceback LDS) failed"); break;
       }
     }
@@ -1156,3 +1195,108 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
             n_req, ms(t_begin, t_prep), ms(t_prep, t_static), ms_alloc, ms_kernel, ms_d2h, ms_replay, ms(t_begin, now()));
   return 0;
 }
+
+#ifndef HIPSTR_NO_DEBUG_ABI
+// Diagnostics (host only): the chunks, fill kernels and walk forms hipstr_hmm_trace_seeded would launch for a request list, from the same
+// decisions (trace_seed_of, trace_compact_reads, trace_side_ws, trace_chunk_end, trace_col_class, trace_mixed_launch, trace_fill_cols,
+// hs_walk_in_lds), as one JSON object.
+extern "C" int hipstr_debug_trace_plan(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                                       const int32_t* req_seed, double ws_mib, char* json, int cap){
+  using hipstr::api_fail;
+  auto bad = [](const char* why){ hipstr::api_fail(why); return -1; };
+  if (!b || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return bad("null argument");
+  if (b->n_loci < 1) return bad("hipstr_hmm_trace needs at least one locus");
+  { std::string err; if (hipstr::validate_tables(b, err)) return bad(err.c_str()); }
+  const int n_loci = b->n_loci, n_reads = b->read_off[n_loci];
+  std::vector<int32_t> opt_base(n_loci + 1, 0);
+  for (int l = 0; l < n_loci; l++){
+    int cnt = 0;
+    for (int k = 0; k < 3; k++){
+      if (b->blk_nopts[3*l+k] < 1) return bad("haplotype block without options");
+      cnt += b->blk_nopts[3*l+k];
+    }
+    opt_base[l+1] = opt_base[l] + cnt;
+  }
+  struct Rq { int nL, nR, F0, F2; };
+  std::vector<Rq> rq(n_req);
+  std::vector<int64_t> need(n_req);
+  std::vector<char> seen((size_t)n_reads, 0);
+  int64_t wanted = 0, rough = 0;
+  for (int q = 0; q < n_req; q++){
+    const int r = req_read[q], k = req_allele[q];
+    if (r < 0 || r >= n_reads) return bad("request names a read outside the batch");
+    const int l = (int)(std::upper_bound(b->read_off, b->read_off + n_loci + 1, r) - b->read_off) - 1;
+    const int32_t* nopts = b->blk_nopts + 3*l;
+    if (k < 0 || k >= nopts[0]*nopts[1]*nopts[2]) return bad("request names an allele outside its locus");
+    int s;
+    if (const char* why = trace_seed_of(b, l, r, req_seed, q, s)) return bad(why);
+    const int len = b->base_off[r+1] - b->base_off[r];
+    int32_t oi[3]; int F[3];
+    hipstr::allele_options(nopts, k, oi);
+    for (int x = 0, cur = opt_base[l]; x < 3; cur += nopts[x], x++) F[x] = b->opt_off[cur + oi[x] + 1] - b->opt_off[cur + oi[x]];
+    if (F[0] < 1 || F[2] < 1) return bad("empty flank sequence");
+    if (F[1] < 1) return bad("empty STR allele is not supported");
+    rq[q].nL = s; rq[q].nR = len - s - 1; rq[q].F0 = F[0]; rq[q].F2 = F[2];
+    need[q] = trace_side_ws(F[0], F[2], rq[q].nL) + trace_side_ws(F[2], F[0], rq[q].nR);
+    rough += (int64_t)(F[0] + F[2] + 2)*len;
+    if (!seen[r]){ seen[r] = 1; wanted += len; }
+  }
+  // (a call that would ask the device for its free memory: the plan takes the budget it was given, else the default)
+  const int64_t budget = ws_mib > 0 ? (int64_t)(ws_mib*1048576.0) : trace_env_budget((int64_t)HS_TRACE_BUDGET_MIB << 20);
+  for (int q = 0; q < n_req; q++) if (need[q] > budget) return bad("one traceback needs more workspace than the device offers");
+  const bool compact = n_req > 0 && trace_compact_reads(wanted, b->base_off[n_reads]);
+  std::string o; char buf[256];
+  auto put = [&](const char* fmt, auto... a){ snprintf(buf, sizeof buf, fmt, a...); o += buf; };
+  put("{\"thresholds\": {\"HS_MAX_COLS\": %d, \"HS_TRACE_STATIC_CLASSES\": %d, \"HS_TRACE_MIXED_MAX_REQ\": %d, \"HS_WALK_LDS\": %d, \"HS_TRACE_BUDGET_MIB\": %d, \"max_side\": %d, \"fill_cols\": [",
+      HS_MAX_COLS, HS_TRACE_STATIC_CLASSES, HS_TRACE_MIXED_MAX_REQ, HS_WALK_LDS, HS_TRACE_BUDGET_MIB, 64*HS_MAX_COLS);
+  for (int cl = 1; cl <= HS_MAX_COLS; cl++) put("%s%d", cl > 1 ? ", " : "", trace_fill_cols(cl));
+  o += "]}, \"routes\": [";
+  for (int cl = 1; cl <= HS_TRACE_STATIC_CLASSES; cl++) put("\"hs_trace_fill<%d>\", \"mixed<%d>\", ", cl, cl);
+  for (int cl = HS_TRACE_STATIC_CLASSES + 1, last = 0; cl <= HS_MAX_COLS; cl++) if (trace_fill_cols(cl) != last){ last = trace_fill_cols(cl); put("\"hs_trace_fill_long<%d>\", ", last); }
+  put("\"hs_trace_fill_mixed\", \"walk_lds\", \"walk_workspace\", \"reads_compact\", \"reads_whole\", \"trace_one_chunk\", \"trace_chunks\"], "
+      "\"compact_reads\": %s, \"wanted_bases\": %lld, \"total_bases\": %lld, \"budget\": %lld, \"asks_device\": %s, \"chunks\": [",
+      compact ? "true" : "false", (long long)wanted, (long long)b->base_off[n_reads], (long long)budget, trace_asks_device(rough) ? "true" : "false");
+  for (int q0 = 0; q0 < n_req; ){
+    const int q1 = trace_chunk_end(need, q0, budget), nq = q1 - q0;
+    int cnt[HS_MAX_COLS + 1] = {0}; int64_t mat = 0; int n_lds = 0, n_ws = 0;
+    for (int q = q0; q < q1; q++){ cnt[trace_col_class(rq[q].nL)]++; cnt[trace_col_class(rq[q].nR)]++; mat += need[q]; }
+    int n_cls = 0, n_static = 0;
+    for (int cl = 1; cl <= HS_TRACE_STATIC_CLASSES; cl++){ n_cls += cnt[cl] > 0; n_static += cnt[cl]; }
+    const bool mixed = trace_mixed_launch(n_cls, nq);
+    put("%s{\"q0\": %d, \"q1\": %d, \"bytes\": %lld, \"classes\": [", q0 ? ", " : "", q0, q1, (long long)mat);
+    for (int cl = 1; cl <= HS_MAX_COLS; cl++) put("%s%d", cl > 1 ? ", " : "", cnt[cl]);
+    put("], \"mixed\": %s, \"launch\": [", mixed ? "true" : "false");
+    bool first = true;
+    if (mixed){ put("[\"hs_trace_fill_mixed\", %d]", n_static); first = false; }
+    for (int cl = mixed ? HS_TRACE_STATIC_CLASSES + 1 : 1; cl <= HS_MAX_COLS; cl++){
+      if (!cnt[cl]) continue;
+      if (cl <= HS_TRACE_STATIC_CLASSES) put("%s[\"hs_trace_fill<%d>\", %d]", first ? "" : ", ", cl, cnt[cl]);
+      else put("%s[\"hs_trace_fill_long<%d>\", %d]", first ? "" : ", ", trace_fill_cols(cl), cnt[cl]);
+      first = false;
+    }
+    // per request: [left columns, right columns, flank rows + 1, left walk, right walk] (walk: 1 = decisions copied to LDS, 0 = read in the workspace)
+    put("%s[\"hs_trace_walk\", %d]], \"requests\": [", first ? "" : ", ", nq);
+    for (int q = q0; q < q1; q++){
+      const Rq& R = rq[q];
+      const bool wl = hs_walk_in_lds(hs_trace_side_bytes(R.F0, R.F2, R.nL)), wr = hs_walk_in_lds(hs_trace_side_bytes(R.F2, R.F0, R.nR));
+      n_lds += wl + wr; n_ws += !wl + !wr;
+      put("%s[%d, %d, %d, %d, %d]", q > q0 ? ", " : "", R.nL, R.nR, R.F0 + 1 + R.F2, wl ? 1 : 0, wr ? 1 : 0);
+    }
+    o += "], \"routes\": [";
+    put("\"%s\", \"%s\"", (q0 == 0 && q1 == n_req) ? "trace_one_chunk" : "trace_chunks", compact ? "reads_compact" : "reads_whole");
+    if (mixed) o += ", \"hs_trace_fill_mixed\"";
+    for (int cl = 1; cl <= HS_MAX_COLS; cl++){
+      if (!cnt[cl]) continue;
+      if (cl <= HS_TRACE_STATIC_CLASSES) put(mixed ? ", \"mixed<%d>\"" : ", \"hs_trace_fill<%d>\"", cl);
+      else if (cl == HS_TRACE_STATIC_CLASSES + 1 || trace_fill_cols(cl) != trace_fill_cols(cl-1) || !cnt[cl-1]) put(", \"hs_trace_fill_long<%d>\"", trace_fill_cols(cl));
+    }
+    if (n_lds) o += ", \"walk_lds\"";
+    if (n_ws) o += ", \"walk_workspace\"";
+    o += "]}";
+    q0 = q1;
+  }
+  o += "]}";
+  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
+  return (int)o.size();
+}
+#endif  // HIPSTR_NO_DEBUG_ABI

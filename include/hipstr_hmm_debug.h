@@ -45,6 +45,29 @@ int hipstr_debug_str_groups(const hipstr_batch_t* batch, int32_t* side, int32_t*
  * cap - 1 bytes and a NUL; returns the full length (-1 on error).  Used by tests/test_routes.py. */
 int hipstr_debug_launch_plan(const hipstr_batch_t* batch, double ws_gib, char* json, int cap);
 
+/* Diagnostics (host only): what hipstr_hmm_trace_seeded would launch for a request list (req_seed may be NULL), with a budget of ws_mib MiB
+ * of decision matrices per chunk (<= 0: the call's own default or HIPSTR_TRACE_WS_MIB; where the call would ask the device for its free
+ * memory the plan keeps that budget), from the same decisions the call takes, as one JSON object: "thresholds" (the compiled limits;
+ * "fill_cols": template argument of the fill kernel per column class 1..HS_MAX_COLS), "routes" (every route name there is),
+ * "compact_reads" (only the requested reads' bases are uploaded), and per chunk "q0" / "q1" (request range), "bytes", "classes" (sides per
+ * column class), "mixed" (hs_trace_fill_mixed takes the static classes), "launch" ([kernel, workgroups]), "requests" ([left columns, right
+ * columns, flank rows + 1, left walk, right walk]: walk 1 = decision bytes copied to LDS, 0 = read in the workspace) and "routes" (the ones
+ * the chunk takes; "mixed<C>": class C inside the mixed launch).  Writes up to cap - 1 bytes and a NUL; returns the full length (-1 on
+ * error).  Used by tests/test_stage_routes.py. */
+int hipstr_debug_trace_plan(const hipstr_batch_t* batch, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                            const int32_t* req_seed, double ws_mib, char* json, int cap);
+/* Diagnostics (host only): the chunks hipstr_nw_align would cut a batch into under a budget of ws_mib MiB of traceback bytes (<= 0: the
+ * call's own default or HIPSTR_NW_WS_MIB) and, per chunk, "p0" / "p1" (pair range), "bytes", "over_budget" (one pair larger than the
+ * budget, alone), "rungs" (pairs per rows-per-lane rung of "thresholds"."rows") and "launch" ([kernel, workgroups]).  Refused sizes fail
+ * as in the call.  Same conventions as hipstr_debug_trace_plan. */
+int hipstr_debug_nw_plan(const hipstr_nw_batch_t* batch, double ws_mib, char* json, int cap);
+/* Diagnostics (host only): the launch hipstr_post_launch would make for a posterior batch — "n_units", "max_nd" (diplotypes of the largest
+ * unit), "split" (workgroups per unit of the accumulation; > 1: hs_posterior_accumulate_kernel + hs_posterior_finish_kernel), "launch" and per
+ * unit [alleles, reads, path (0 = registers, 1 = chunked), reads per LDS tile, tiles, chunks of HS_POST_ECHUNK exponentials, workgroups of
+ * a split launch with an empty share], "routes_hit".  (HIPSTR_DEBUG_HOST_LIBM, which sends every unit down the chunked path, is not
+ * modelled.)  Same conventions as hipstr_debug_trace_plan. */
+int hipstr_debug_post_plan(const hipstr_post_batch_t* batch, char* json, int cap);
+
 /* Diagnostics (host only): one entry {A, G, Bnd} of the tabulated closed form the STR kernel uses for a "simple" visiting
  * list (StutterAlignerClass.cpp:59-150 for a periodic block): with `bound` columns of the block in reach, a run of U0 equal
  * configurations at the block's right end and `tail` configurations in total, fast_log_sum_exp over the pushed values is

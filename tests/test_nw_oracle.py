@@ -47,3 +47,13 @@ def test_oracle_matches_compiled_reference_on_fresh_cases(oracle):
         for pen in (False, True):
             pairs = nw_pairs(seed, n=25)
             assert capi.run_nw(oracle, "oracle_", pairs, pen) == capi.run_nw(ref, "ref_", pairs, pen)
+
+
+@pytest.mark.skipif(not os.path.exists(capi.REF_LIB), reason="compiled reference (oracle/_ref) not built")
+def test_oracle_matches_compiled_reference_at_the_route_boundaries(oracle, hmm_host):
+    """The rung-edge, limit, homopolymer and all-N pairs of tests/stage_route_cases.py under both end-penalty settings."""
+    import stage_route_cases as sc
+    ref = capi.load_ref()
+    for call in sc.nw_calls(sc.limits(hmm_host)["nw"])[:3]:
+        for pen in (False, True):
+            assert capi.run_nw(oracle, "oracle_", call.pairs, pen) == capi.run_nw(ref, "ref_", call.pairs, pen), call.name

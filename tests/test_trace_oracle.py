@@ -63,3 +63,19 @@ def test_oracle_trace_matches_compiled_reference(kw):
     want = capi.run_trace(ref, "ref_", sb.ptr, rr, aa, cap=1 << 20)
     got = capi.run_trace(ora, "oracle_", sb.ptr, rr, aa, h2r, cap=1 << 20)
     util.assert_traces_equal(got, want, str(kw))
+
+
+@pytest.mark.skipif(not os.path.exists(capi.REF_LIB), reason="compiled reference (oracle/_ref) not built")
+@pytest.mark.parametrize("name", ["boundary_sides", "single_class_3", "single_class_6", "walk_limit", "repack_+1", "chunking_whole"])
+def test_oracle_trace_matches_compiled_reference_at_the_route_boundaries(hmm_host, name):
+    """The boundary cases of tests/stage_route_cases.py (sides of 1, 64 | 65 ... 1024 columns with caller seeds, interrupted alleles, reads
+    that miss the STR block): the oracle the device is compared with there is itself the compiled reference's equal at these sizes."""
+    import stage_route_cases as sc
+    ora = capi.load_oracle(); ref = capi.load_ref()
+    T = sc.limits(hmm_host)["trace"]
+    call = {c.name: c for c in sc.trace_calls(hmm_host, T)}[name]
+    A = int(call.batch.arrays["hap_off"][1])
+    h2r = capi.ref_hap_aln_info(ref, call.batch.ptr, A)
+    want = capi.run_trace(ref, "ref_", call.batch.ptr, call.rr, call.aa, cap=1 << 21, req_seed=call.seeds)
+    got = capi.run_trace(ora, "oracle_", call.batch.ptr, call.rr, call.aa, h2r, cap=1 << 21, req_seed=call.seeds)
+    util.assert_traces_equal(got, want, name)
