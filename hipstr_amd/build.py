@@ -34,7 +34,7 @@ def build_hmm(force=False):
     out = os.path.join(CSRC, "libhipstr_hmm.so")
     hdrs = [os.path.join(CSRC, s) for s in HIP_HEADERS]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    extra = ["-D%s=%s" % (m, os.environ[e]) for m, e in (("HS_TRAIL_ROWS", "HIPSTR_TRAIL_ROWS"), ("HS_STR_WAVES", "HIPSTR_STR_WAVES")) if os.environ.get(e)]
+    extra = ["-D%s=%s" % (m, os.environ[e]) for m, e in (("HS_STR_WAVES", "HIPSTR_STR_WAVES"),) if os.environ.get(e)]
     objdir = os.path.join(ROOT, "build", "hmm_obj" + ("_" + "_".join(extra).replace("-D", "").replace("=", "") if extra else ""))
     os.makedirs(objdir, exist_ok=True)
     cflags = [f for f in HIPCC_FLAGS if f != "-shared"]

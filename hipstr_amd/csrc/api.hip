@@ -297,7 +297,7 @@ hipError_t hipstr::wait_stream(hipStream_t st){
   const auto t0 = std::chrono::steady_clock::now();
   bool slow = (mode == 2);
   // (round 6: an event recorded behind the stream's work and hipEventQuery — a hipStreamQuery that finds the stream busy leaves work for the
-  //  HSA runtime's event thread: 0.45 s of its CPU per 3 s of polling against 0.03 with an event, tools/r06_rt_probe.py; sixteen host threads
+  //  HSA runtime's event thread: 0.45 s of its CPU per 3 s of polling against 0.03 with an event, profiles/r06_runtime_thread_probe.txt; sixteen host threads
   //  of one-shot calls share that one thread)
   // (the event comes from this thread's context: only when that is the device the entry point bound — the stream's)
   Ctx* c = t_ctx;
@@ -403,21 +403,19 @@ static LaunchFacts launch_facts(const Prepared& P){
 #define HS_SIDE_STREAM_ITEMS 256
 // The STR-block kernels one chunk launches — the one place it is decided: hipstr_hmm_align launches what it says, hipstr_debug_launch_plan
 // reports it.  HIPSTR_STR_GROUP=0: one workgroup per read for every tabulated allele (hs_str_kernel), for comparison.
-struct StrLaunch { bool per_read, nd, group_p, group, pw, rp, side_stream, long_sides, generic; };
+struct StrLaunch { bool per_read, nd, group_p, group, pw, rp, side_stream, long_sides; };
 static StrLaunch str_launch(const Prepared& P, const Prepared::Chunk& ch, const LaunchFacts& f){
   StrLaunch L;
   const bool str_group = !(getenv("HIPSTR_STR_GROUP") && atoi(getenv("HIPSTR_STR_GROUP")) == 0);
   const bool items = ch.str_end > ch.str_begin;
-  constexpr bool group_p = true;          // blocks of at least six repeat units (nearly all) through the kernel with a compile-time period
   L.per_read = !str_group;
-  L.nd = str_group && items && group_p && P.ws_nd_size > 0;        // read-end deletion sums of the tabulated alleles
-  L.group_p = str_group && items && group_p;
-  L.group = str_group && items && (!group_p || f.any_short);       // (periods above HS_GRP_MAXP only, once hs_str_group_kernel_p is on)
+  L.nd = str_group && items && P.ws_nd_size > 0;                   // read-end deletion sums of the tabulated alleles
+  L.group_p = str_group && items;                                  // blocks of at least six repeat units (nearly all) through the kernel with a compile-time period
+  L.group = str_group && items && f.any_short;                     // periods above HS_GRP_MAXP only
   L.pw = str_group && items && f.any_pw;
   L.rp = str_group && items && f.any_rp;
-  L.side_stream = str_group && items && ch.str_end - ch.str_begin <= HS_SIDE_STREAM_ITEMS && group_p && (f.any_pw || f.any_rp);
+  L.side_stream = str_group && items && ch.str_end - ch.str_begin <= HS_SIDE_STREAM_ITEMS && (f.any_pw || f.any_rp);
   L.long_sides = str_group && ch.n_long_sides > 0;                 // sides with more columns than a group holds: one workgroup per read
-  L.generic = true;                       // alleles without a closed form, and whatever hs_str_kernel marked HS_REDO
   return L;
 }
 // workspace budget (doubles per workspace; there are two large ones): HIPSTR_WS_GIB, else 3 Gi doubles
@@ -749,8 +747,7 @@ hipstr_dev_batch_t* hipstr::upload_on(Ctx* ctx, const hipstr_batch_t* batch, con
   // The stream's batches take tens of milliseconds and their collectors must not burn a core waiting: hipEventSynchronize spins at 100 %
   // of a CPU on this stack whatever the event's flags (tools/wait_probe.hip: 41.7 ms of thread CPU per 41.7 ms of waiting, also with
   // hipEventBlockingSync), a query + usleep loop costs 0.6 ms (results_wait).
-  constexpr bool spin = false;
-  dev->sleepy_wait = reads_pinned && !spin;
+  dev->sleepy_wait = reads_pinned;
   dev->ev_h2d = ctx->get_event(false); dev->ev_done = ctx->get_event(false); dev->ev_d2h = ctx->get_event(false);
   if (!dev->ev0 || !dev->ev1 || !dev->ev_h2d || !dev->ev_done || !dev->ev_d2h){ g_err = "hipEventCreate failed"; hipstr_hmm_free(dev); return NULL; }
   HS_HIP_DEV(hipEventRecord(dev->ev_h2d, copy_stream));
@@ -785,7 +782,7 @@ int hipstr::fetch_begin(hipstr_dev_batch_t* dev, hipStream_t compute_stream, hip
   dev->d2h_stream = copy_stream;
   // Round 6: the copy back is NOT queued behind a hipStreamWaitEvent(copy_stream, ev_done).  A cross-stream wait for an event that tens of
   // milliseconds of kernels stand in front of is resolved by the HSA runtime's event thread ON THE CPU: it spins in the KFD's wait call until
-  // the event fires (tools/r06_rt_probe.py: 2.65 s of CPU per 3 s of such waits, nothing for the same kernels without the wait) — with a
+  // the event fires (profiles/r06_runtime_thread_probe.txt: 2.65 s of CPU per 3 s of such waits, nothing for the same kernels without the wait) — with a
   // stream running that was a core in use for as long as the device was busy, a third of a rank's two-CPU allowance.  The copy is queued by
   // whoever finds ev_done fired first: a worker passing by (fetch_poll) or the collector that waits for the results (results_wait).
   std::lock_guard<std::mutex> lg(dev->d2h_m);
@@ -937,9 +934,9 @@ int hipstr_hmm_align(hipstr_dev_batch_t* dev, void* hip_stream){
       }
       if (sl.group_p) hipLaunchKernelGGL(hs_str_group_kernel_p, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), hs_str_group_p_lds_bytes(), st, dp,
                                          dev->n_lead_items + dev->n_trail_items + ch.str_begin);
-      if (sl.group)      // (periods above HS_GRP_MAXP only, once hs_str_group_kernel_p is on)
+      if (sl.group)      // periods above HS_GRP_MAXP only (hs_str_group_kernel_p takes the others)
         hipLaunchKernelGGL(hs_str_group_kernel, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), dev->grp_lds_bytes, st, dp,
-                           dev->n_lead_items + dev->n_trail_items + ch.str_begin, sl.group_p ? 1 : 0);
+                           dev->n_lead_items + dev->n_trail_items + ch.str_begin, 1);
       if (sl.pw)       // interrupted repeats: the piecewise simple lists' closed forms, grouped like the tabulated ones
         hipLaunchKernelGGL(hs_str_group_kernel_pw, dim3(ch.str_end - ch.str_begin, dev->grid_y), dim3(HS_GRP_COLS), dev->grp_pw_lds_bytes, st_pw, dp,
                            dev->n_lead_items + dev->n_trail_items + ch.str_begin);
@@ -958,7 +955,7 @@ int hipstr_hmm_align(hipstr_dev_batch_t* dev, void* hip_stream){
         hipLaunchKernelGGL(hs_str_kernel, dim3(nact, dev->grid_y), dim3(128), dev->lds_bytes, st, dp, ch.active_begin, 1);
     }
     // alleles without a tabulated closed form (interrupted repeats, very long blocks) and whatever hs_str_kernel marked HS_REDO
-    if (sl.generic) hipLaunchKernelGGL(hs_str_kernel_generic, dim3(nact, dev->grid_y), dim3(128), dev->lds_bytes, st, dp, ch.active_begin, sl.per_read ? 0 : 1);
+    hipLaunchKernelGGL(hs_str_kernel_generic, dim3(nact, dev->grid_y), dim3(128), dev->lds_bytes, st, dp, ch.active_begin, sl.per_read ? 0 : 1);
     if (mark()) return 1;
     if (ch.trail_end > ch.trail_begin)     // trailing flanks: persistent wavefronts striding over (read side, allele group) items
       hs_launch_trail((unsigned)std::min(dev->trail_waves, ch.trail_end - ch.trail_begin), st, dp,
@@ -1352,7 +1349,7 @@ int hipstr_debug_launch_plan(const hipstr_batch_t* batch, double ws_gib, char* j
     const struct { const char* name; bool launched; int64_t pairs; } ks[] = {
       { "hs_str_group_kernel_p", sl.group_p, n_p }, { "hs_str_group_kernel", sl.group, n_g }, { "hs_str_group_kernel_pw", sl.pw, n_pw },
       { "hs_str_group_kernel_rp", sl.rp, n_rp }, { "hs_str_kernel_long", sl.long_sides, n_long }, { "hs_str_kernel", sl.per_read, n_pr },
-      { "hs_str_kernel_generic", sl.generic, n_gen } };
+      { "hs_str_kernel_generic", true, n_gen } };
     o += "\"str\": {\"launch\": [";
     bool first = true;
     if (sl.nd){ o += "\"hs_nd_kernel\""; first = false; }

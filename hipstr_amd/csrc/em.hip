@@ -917,15 +917,14 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
     hipLaunchKernelGGL(hs_em_units, dim3(nl), dim3(256), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
     unsigned bound_l = (unsigned)nl, bound_u = (unsigned)n_units;
     int rounds = 0;
-    constexpr bool em_serial = false;      // (the allele-frequency scans run beside the M-step on the side stream: 0.51 against 0.57 s per 10 000 loci, profiles/r05_notes.md)
     for (int r = 0; r <= eb->max_iter + 1; r++){
       const hs_em_dev_t* H = d_hb + (r & 1); const hs_post_dev_t* PH = d_pb + (r & 1);
       if (bound_l > 0){
         hipLaunchKernelGGL(hs_em_fill, dim3(bound_l), dim3(256), 0, T.stream, H);
         hipLaunchKernelGGL(hs_posterior_kernel, dim3(std::max(1u, bound_u)), dim3(256), 0, T.stream, PH);
         EM_HIP(hipEventRecord(side.ev_fork, T.stream));                  // posteriors are in place: the allele-frequency scans branch off
-        EM_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));
-        hipLaunchKernelGGL(hs_em_gt_priors, dim3(bound_l), dim3(256), 2*HS_EM_CHUNK*HS_EM_MAXA_LDS*sizeof(double), em_serial ? T.stream : side.stream, H);
+        EM_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));        // (beside the M-step on the side stream: 0.51 against 0.57 s per 10 000 loci in series, profiles/r05_notes.md)
+        hipLaunchKernelGGL(hs_em_gt_priors, dim3(bound_l), dim3(256), 2*HS_EM_CHUNK*HS_EM_MAXA_LDS*sizeof(double), side.stream, H);
         EM_HIP(hipEventRecord(side.ev_join, side.stream));
         hipLaunchKernelGGL(hs_em_gmax, dim3(bound_l), dim3(256), 0, T.stream, H);
         hipLaunchKernelGGL(hs_em_mstep_part<0>, dim3(bound_l, HS_EM_PARTS), dim3(256), 0, T.stream, H, (const double*)NULL);

@@ -19,9 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <mutex>
-#include <unordered_map>
 
 namespace hipstr {
 
@@ -99,16 +97,6 @@ Pool& pool(){ static Pool p; return p; }
 void parallel_for(int n, int max_threads, const std::function<void(int)>& fn){
   const int nt = std::max(1, std::min(n, max_threads));
   if (nt == 1){ for (int i = 0; i < n; i++) fn(i); return; }
-  constexpr bool no_pool = false;
-  if (no_pool){
-    std::atomic<int> next(0);
-    auto work = [&](){ for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i); };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (std::thread& t : th) t.join();
-    return;
-  }
   Pool& P = pool();
   P.ensure(std::max(host_threads(), nt) - 1);
   PoolJob job; job.fn = &fn; job.n = n; job.max_workers = nt - 1;
@@ -617,14 +605,13 @@ void emit_stropt(const char* blk, const int B, int period, const double pmf13[HS
     slot[0] = pack(k, ni_of(E[idx]));
     return true;
   };
-  constexpr bool group_replay = true, pwk_on = true;
   uint64_t pw[HS_MAXREP + 1][HS_PW_SLOTS];
   for (int k = 0; k <= HS_MAXREP; k++){ for (int i = 0; i < HS_PW_SLOTS; i++) pw[k][i] = 0; pw[k][0] = (uint64_t)(uint32_t)-1; }   // "not piecewise"
   uint64_t pwk[HS_MAXREP + 1][HS_PWK_SLOTS];
   for (int k = 0; k <= HS_MAXREP; k++){ for (int i = 0; i < HS_PWK_SLOTS; i++) pwk[k][i] = 0; pwk[k][0] = (uint64_t)(uint32_t)-1; }
   bool any_pwk = false;
   auto try_pwk = [&](int k, int off, int len, int limmax){
-    if (!pwk_on || so.shape[k] != -1 || limmax < 0) return;
+    if (so.shape[k] != -1 || limmax < 0) return;
     uint64_t tmp[HS_PWK_SLOTS];
     if (piecewise_k(off, len, limmax, tmp)){ memcpy(pwk[k], tmp, sizeof tmp); so.shape[k] = HS_SHAPE_PWK; any_pwk = true; }
   };
@@ -678,7 +665,7 @@ void emit_stropt(const char* blk, const int B, int period, const double pmf13[HS
   // (round 4: hs_str_group_kernel_pw also replays the lists that have no closed form — three and more interruptions — so an option with
   //  such lists stays in the grouped layout (kind 2) as long as its block is made of A/C/G/T; before round 4 they went to
   //  hs_str_kernel_generic)
-  if (any_pw || (any_replay && group_replay)){
+  if (any_pw || any_replay){
     const size_t at = out.f64pool.size();
     out.f64pool.resize(at + (HS_MAXREP + 1)*HS_PW_SLOTS);
     memcpy(out.f64pool.data() + at, pw, sizeof pw);
@@ -692,7 +679,6 @@ void emit_stropt(const char* blk, const int B, int period, const double pmf13[HS
   // tabulated closed form: only when every list the kernel can evaluate is simple and the entries fit the LDS budget
   so.tab_off = out.f64pool.size(); so.tab_len = 0;
   {
-    constexpr bool no_pw_group = false;
     bool ok = true; int total = 0;
     for (int i = 0; i < B; i++){ const char c = blk[i]; ok &= (c == 'A' || c == 'C' || c == 'G' || c == 'T'); }      // hs_str_group_kernel looks emissions up by base code
     ok &= (B >= period);                                                          // ... and lets ins_probs_ cycle through block bases only
@@ -701,8 +687,8 @@ void emit_stropt(const char* blk, const int B, int period, const double pmf13[HS
       const int tail = (k == HS_MAXREP) ? B : B - (k+1)*period;
       so.tab_base[k] = total;
       if (tail < 0) continue;                           // this deletion size is never evaluated
-      if (so.shape[k] == HS_SHAPE_PIECEWISE && !no_pw_group) continue;      // evaluated from its descriptor slots (hs_str_group_kernel_pw)
-      if ((so.shape[k] == -1 || so.shape[k] == HS_SHAPE_PWK) && group_replay && !no_pw_group) continue;      // replayed in the grouped layout (visit_eval_grp) or taken by the K-level closed form
+      if (so.shape[k] == HS_SHAPE_PIECEWISE) continue;      // evaluated from its descriptor slots (hs_str_group_kernel_pw)
+      if (so.shape[k] == -1 || so.shape[k] == HS_SHAPE_PWK) continue;      // replayed in the grouped layout (visit_eval_grp) or taken by the K-level closed form
       if (so.shape[k] < 0){ ok = false; break; }
       total += 2 + std::max(0, tail - so.shape[k]);
     }
@@ -727,44 +713,6 @@ void emit_stropt(const char* blk, const int B, int period, const double pmf13[HS
   }
   out.stropts.push_back(so);
   HS_SOLAP(4);
-}
-
-// Everything emit_stropt derives from (block, period, stutter model) — visiting lists, their shapes, the closed-form table, the 20
-// constants — is a function of those three alone, and the same STR options come back all the time: every round of
-// SeqStutterGenotyper::genotype() re-sends a locus with one or two alleles more (seq_stutter_genotyper.cpp:603-671), both sides of
-// a palindromic motif, neighbouring loci of a panel with the same motif.  A per-thread cache keyed by the three holds the option
-// record with its pool slices relative to their start; a hit appends copies (about 2 KB) instead of rebuilding them.
-struct StroptCached { hs_stropt_t so; std::vector<hs_visit_t> visits; std::vector<double> f64; std::vector<char> chars; };
-void emit_stropt_cached(const char* blk, int B, int period, const double* stutter, const double pmf13[HS_NART], Prepared& out, int pmf_off, int twin){
-  // (off by default since round 4: building an option now costs about what a hit did — a hash of ~100 bytes and 2 KB of copies;
-  //  the cache stays in the source for a caller that re-sends loci, switched off)
-  constexpr bool on = false;
-  if (!on || g_bnd_scale.load() != 1.0){ emit_stropt(blk, B, period, pmf13, out, true, pmf_off, twin); return; }      // (the cache keeps host-written tables only)
-  thread_local std::unordered_map<std::string, StroptCached> cache;
-  thread_local std::string key;
-  key.assign((const char*)stutter, 6*sizeof(double)); key.push_back((char)period); key.append(blk, B);
-  auto it = cache.find(key);
-  if (it == cache.end()){
-    const size_t v0 = out.visits.size(), f0 = out.f64pool.size(), c0 = out.chars.size();
-    emit_stropt(blk, B, period, pmf13, out, true);
-    if (cache.size() >= 8192) cache.clear();
-    StroptCached& e = cache[key];
-    e.so = out.stropts.back();
-    e.visits.assign(out.visits.begin() + v0, out.visits.end()); e.f64.assign(out.f64pool.begin() + f0, out.f64pool.end());
-    e.chars.assign(out.chars.begin() + c0, out.chars.end());
-    e.so.seq_off -= (int32_t)c0; e.so.f64_off -= (int32_t)f0; e.so.tab_off -= (int32_t)f0; e.so.ins_off -= (int32_t)v0;
-    for (int q = 0; q < HS_MAXREP; q++) e.so.del_off[q] -= (int32_t)v0;
-    return;
-  }
-  const StroptCached& e = it->second;
-  const int32_t v0 = (int32_t)out.visits.size(), f0 = (int32_t)out.f64pool.size(), c0 = (int32_t)out.chars.size();
-  out.visits.insert(out.visits.end(), e.visits.begin(), e.visits.end());
-  out.f64pool.insert(out.f64pool.end(), e.f64.begin(), e.f64.end());
-  out.chars.insert(out.chars.end(), e.chars.begin(), e.chars.end());
-  hs_stropt_t so = e.so;
-  so.seq_off += c0; so.f64_off += f0; so.tab_off += f0; so.ins_off += v0;
-  for (int q = 0; q < HS_MAXREP; q++) so.del_off[q] += v0;
-  out.stropts.push_back(so);
 }
 
 }  // namespace
@@ -931,7 +879,7 @@ static std::atomic<uint64_t> g_lap_cycles[8];
 static const bool g_lap_on = getenv("HIPSTR_PREP_PROFILE") != NULL;
 void prep_profile_print(){
   if (!g_lap_on) return;
-  static const char* const names[8] = { "options + strings", "STR options (emit_stropt_cached)", "boundary signatures", "allele loop (flank rows, reuse replay)", "STR order + records + read-end rows", "trailing-flank groups", "reads + seeds", "" };
+  static const char* const names[8] = { "options + strings", "STR options (emit_stropt)", "boundary signatures", "allele loop (flank rows, reuse replay)", "STR order + records + read-end rows", "trailing-flank groups", "reads + seeds", "" };
   uint64_t tot = 0; for (int i = 0; i < 7; i++) tot += g_lap_cycles[i];
   for (int i = 0; i < 7; i++){ fprintf(stderr, "prepare_locus: %-40s %6.1f %%\n", names[i], tot ? 100.0*g_lap_cycles[i]/tot : 0.0); g_lap_cycles[i] = 0; }
   static const char* const so_names[5] = { "constants (stutter pmf, priors)", "insertion list", "deletion lists", "list bookkeeping + descriptor slots", "closed-form table" };
@@ -1094,7 +1042,7 @@ static int prepare_locus(const hipstr_batch_t* b, int l, int opt_cursor, const P
   }
   for (int side = 0; side < 2; side++)
     for (int o = 0; o < nopts[1]; o++)
-      emit_stropt_cached(S.sblk[side][o].p, S.sblk[side][o].n, period, b->stutter + 6*l, pmf13, out, pmf_off, side ? so_base + o : -1);
+      emit_stropt(S.sblk[side][o].p, S.sblk[side][o].n, period, pmf13, out, true, pmf_off, side ? so_base + o : -1);
   HS_LAP(1);
   S.str_opt_of.resize(A);                            // STR option of every allele
   const bool one_flank = nopts[0] == 1 && nopts[2] == 1;          // (the usual locus: allele k is STR option k, the STR block is what changes)

@@ -240,10 +240,7 @@ struct hipstr_stream {
   // (the kernels of consecutive batches on alternating streams instead of the context's one: tried at the
   // end of round 4 against the 8 % a stream of 2 Mi batches loses to the resident rate (the tails and gaps of 60 kernels per pass instead
   // of 8): no effect, 129.5 ms per pass with 1, 2 and 3 streams — a persistent trailing-flank kernel holds every SIMD's registers until
-  // it ends.  What helped is fewer, larger batches (below).  One stream; the arrays below are what is left of the experiment.)
-  hipStream_t compute[4] = {NULL, NULL, NULL, NULL};
-  int n_compute = 0;
-  std::atomic<unsigned> launch_seq{0};
+  // it ends.  What helped is fewer, larger batches (below).  One compute stream: the context's.)
   int slots = 6;
   int64_t batch_work = (int64_t)2 << 20;       // (2 Mi pairs: a 30x batch's tables then stay within the last-level cache while they are built and packed)
   // ... for batches of MANY loci.  What the device sees is pairs: with heavy loci (the north-star shape: 16 000 pairs each) 2 Mi pairs are
@@ -340,7 +337,7 @@ void worker_loop(hipstr_stream* s, int n_workers){
         const int64_t next = !s->ready.empty() ? s->ready.front()->work : (s->pending ? s->pending->work : 0);
         // (a caller's own batch size does not multiply the memory in flight: slots x 2 Mi pairs as with the default — ~40 GB of workspaces at the
         //  north-star shape, twice that for loci of few alleles —, two batches at least.  Round 6: 8 slots x 8 Mi pairs of 8-allele loci ran the
-        //  device out of memory, tools/r06_rt_long.sh)
+        //  device out of memory, profiles/r06_notes.md)
         const int64_t cap = std::max((int64_t)s->slots * std::min(s->batch_work, (int64_t)2 << 20), 2 * s->batch_work);
         return w + next <= cap;
       };
@@ -353,7 +350,7 @@ void worker_loop(hipstr_stream* s, int n_workers){
     InFlight* f = new InFlight(); f->ob = ob; f->taken.assign(ob->tickets.size(), 0);
     const auto t0 = std::chrono::steady_clock::now();
     const double c0 = thread_cpu_now();
-    const hipStream_t cs = s->n_compute > 0 ? s->compute[s->launch_seq.fetch_add(1) % (unsigned)s->n_compute] : hipstr::ctx_stream(s->ctx);
+    const hipStream_t cs = hipstr::ctx_stream(s->ctx);
     f->dev = hipstr::upload_on(s->ctx, ob->finish(), ob->seed.data(), s->copy_stream, cs, true);
     if (!f->dev){ f->failed = true; f->err = hipstr_last_error(); }
     else if (hipstr_hmm_align(f->dev, NULL) != 0 || hipstr::fetch_begin(f->dev, cs, s->d2h_stream) != 0){
@@ -401,17 +398,6 @@ hipstr_stream_t* hipstr_stream_open(const hipstr_stream_opts_t* opts){
   }
   if (hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&s->d2h_stream, hipStreamNonBlocking) != hipSuccess){
     hipstr::api_fail("hipStreamCreate failed"); delete s; return NULL; }
-  {
-    int nc = 1;
-    if (nc > 1) for (int i = 0; i < nc; i++){
-      if (hipStreamCreateWithFlags(&s->compute[i], hipStreamNonBlocking) != hipSuccess){
-        hipstr::api_fail("hipStreamCreate failed");
-        for (int k = 0; k < s->n_compute; k++) hipStreamDestroy(s->compute[k]);
-        hipStreamDestroy(s->copy_stream); hipStreamDestroy(s->d2h_stream); delete s; return NULL;
-      }
-      s->n_compute = i + 1;
-    }
-  }
   memset(&s->stats, 0, sizeof s->stats);
   s->t_open = std::chrono::steady_clock::now();
   // Three workers by default (HIPSTR_STREAM_WORKERS): preparing a batch has serial stretches between its parallel ones (merging the
@@ -745,7 +731,6 @@ int hipstr_stream_close(hipstr_stream_t* s){
   hipstr::api_bind(s->ctx);
   for (InFlight* f : s->flying){ if (f->dev) hipstr::free_landed(f->dev, false); delete f->ob; delete f; }
   hipStreamSynchronize(s->copy_stream); hipStreamSynchronize(s->d2h_stream);
-  for (int i = 0; i < s->n_compute; i++){ hipStreamSynchronize(s->compute[i]); hipStreamDestroy(s->compute[i]); }
   for (OwnedBatch* ob : s->spare) delete ob;
   s->spare.clear();
   hipStreamDestroy(s->copy_stream); hipStreamDestroy(s->d2h_stream);

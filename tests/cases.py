@@ -86,7 +86,7 @@ def homopolymer_two_copy():
     which Haplotype::homopolymer_length's cross-block extension goes past its first neighbour (Haplotype.cpp:262-270 with HapBlock's carried
     counter, HapBlock.cpp:7-30: the table entry of a one-run block is 2 (n - 1), equal to n for n = 2), so the leading-flank rows next to
     'GG' depend on the far flank too — and alleles that start with a run of three share first base and run with it.  Interrupted and pure
-    alleles, three right and two left flank options (round 6: found by the fuzzers, tools/repro_r06_period1.py)."""
+    alleles, three right and two left flank options (round 6: found by the fuzzers, profiles/r06_repro_period1_before.txt)."""
     pre, suf = "TCAGGATCCATGCATTACGATCAG", "CTGATCGTAATGCATGGATCCTGA"
     lfs = [pre + "ACGTTGCAGG", pre + "ACGTTGCATG"]; rfs = ["GGTACCATGC" + suf, "TGTACCATGC" + suf, "GTTACCATGC" + suf]
     strs = ["GGGGGG", "GG", "GGGAGGGG", "GGG", "GGGGCGGGG", "GGTGG", "G" * 9]

@@ -115,7 +115,7 @@ def test_rows_next_to_a_two_copy_homopolymer_allele(hmm_host, oracle):
     """Haplotype::homopolymer_length stops its cross-block extension after one neighbour — unless that neighbour is one run whose table entry
     equals its length (Haplotype.cpp:262-270), which with HapBlock's carried counter (2 (n - 1) for a one-run block) is a TWO-base block: the
     two-copy allele of a homopolymer locus.  The leading-flank rows next to it then depend on the flank behind it as well, and they must not
-    be shared with an allele that merely starts with a run of three (found by tools/r06_fuzz_fresh.sh, round 6: the rows were cached by
+    be shared with an allele that merely starts with a run of three (found by tools/fuzz_fresh.sh, round 6: the rows were cached by
     (flank option, first base, run) alone)."""
     from util import simple_locus
     pre, suf = "TCAGGATCCATGCATTACGATCAG", "CTGATCGTAATGCATGGATCCTGA"

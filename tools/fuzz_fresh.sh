@@ -1,8 +1,8 @@
 #!/bin/bash
-# r06_fuzz_fresh.sh — every fuzzer of the repository once more with seeds none of the earlier sweeps used (base seed = $1), on the final
+# fuzz_fresh.sh — every fuzzer of the repository once more with seeds none of the earlier sweeps used (base seed = $1), on the final
 # library: forward path (plain / edges / big, 12 processes), traceback (plain / edges), posteriors + calls, stutter EM, NW + seeds + misc,
-# heterogeneous batches.  usage: tools/r06_fuzz_fresh.sh <base seed> [out]
-B=${1:-660000}; O=${2:-gpurun_out/r06_fuzz_fresh.txt}; mkdir -p $(dirname $O); : > $O
+# heterogeneous batches.  usage: tools/fuzz_fresh.sh <base seed> [out]
+B=${1:-660000}; O=${2:-build/fuzz_fresh.txt}; mkdir -p $(dirname $O); : > $O
 echo "base seed $B" >> $O
 wave(){   # label, count, command prefix (seed appended), suffix
   local label=$1 n=$2 pre=$3 suf=$4; local pids=()
