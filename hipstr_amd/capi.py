@@ -176,6 +176,94 @@ def run_gt_extract(lib, prefix, pb, n_variants, hap_to_allele, calc_gls=True, ca
     return out
 
 
+class HipstrAssignRequest(C.Structure):
+    _fields_ = [("seed", _i32p), ("reverse", _u8p), ("pool_index", _i32p), ("pool_off", _i32p), ("rule", C.c_int32), ("strand_tolerance", C.c_double)]
+
+
+class HipstrAssignOut(C.Structure):
+    _fields_ = [("best_hap", _i32p), ("read_strand", _i32p), ("log_phase_one", _f64p),
+                ("n_aligned", _i32p), ("n_snp", _i32p), ("n_strand_one", _i32p), ("n_strand_two", _i32p),
+                ("uniq_one", _i32p), ("uniq_two", _i32p), ("rv_uniq_one", _i32p), ("rv_uniq_two", _i32p),
+                ("phase1_reads", _f64p), ("phase2_reads", _f64p),
+                ("n_req", _i32p), ("req_read", _i32p), ("req_allele", _i32p), ("read_req", _i32p), ("cap_req", C.c_int32)]
+
+
+ASSIGN_VCF, ASSIGN_RETRACE = 0, 1
+ASSIGN_COUNTERS = ("n_aligned", "n_snp", "n_strand_one", "n_strand_two", "uniq_one", "uniq_two", "rv_uniq_one", "rv_uniq_two")
+NO_ML_BP = -2 ** 31
+UNTOUCHED = -7          # what run_assign fills the integer outputs with before the call (log_phase_one: NaN)
+
+
+def run_assign(lib, pd_or_pb, seed, reverse=None, pool_index=None, pool_off=None, rule=ASSIGN_VCF, strand_tolerance=0.0, cap_req=None,
+               n_reads=None, n_samp=None, dev_ll=None):
+    """hipstr_post_assign -> dict of arrays (+ "rc": 0, or 3 when cap_req was too small: then only "n_req" means anything).
+    pd_or_pb: a PostBatch (uploaded, launched, assigned and freed here; dev_ll = device pointer of the likelihoods or None) or a
+    hipstr_post_dev_t handle after hipstr_post_launch (then n_reads and n_samp say how long the outputs are).  Outputs the call leaves
+    untouched keep UNTOUCHED (integers) / NaN (log_phase_one).  Raises on any other failure."""
+    _sig(lib.hipstr_post_assign, C.c_int, [C.c_void_p, C.POINTER(HipstrAssignRequest), C.POINTER(HipstrAssignOut)])
+    own = isinstance(pd_or_pb, PostBatch)
+    if own:
+        n_reads = int(pd_or_pb.a["read_off"][-1]) if len(pd_or_pb.a["read_off"]) else 0
+        n_samp = int(pd_or_pb.samp_off[-1])
+    i32 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.int32))
+    k_in = dict(seed=i32(seed), reverse=None if reverse is None else np.ascontiguousarray(np.asarray(reverse, np.uint8)),
+                pool_index=i32(pool_index), pool_off=i32(pool_off))
+    rq = HipstrAssignRequest(_ptr(k_in["seed"], _i32p), _ptr(k_in["reverse"], _u8p), _ptr(k_in["pool_index"], _i32p), _ptr(k_in["pool_off"], _i32p),
+                             int(rule), float(strand_tolerance))
+    if cap_req is None:
+        cap_req = n_reads
+    k = dict(best_hap=np.full(max(n_reads, 1), UNTOUCHED, np.int32), read_strand=np.full(max(n_reads, 1), UNTOUCHED, np.int32),
+             log_phase_one=np.full(max(n_reads, 1), np.nan), phase1_reads=np.full(max(n_samp, 1), np.nan), phase2_reads=np.full(max(n_samp, 1), np.nan),
+             n_req=np.full(1, UNTOUCHED, np.int32), req_read=np.full(max(cap_req, 1), UNTOUCHED, np.int32),
+             req_allele=np.full(max(cap_req, 1), UNTOUCHED, np.int32), read_req=np.full(max(n_reads, 1), UNTOUCHED, np.int32))
+    for nm in ASSIGN_COUNTERS:
+        k[nm] = np.full(max(n_samp, 1), UNTOUCHED, np.int32)
+    o = HipstrAssignOut(*([k[f].ctypes.data_as(t) for f, t in HipstrAssignOut._fields_[:-1]] + [int(cap_req)]))
+    pd = pd_or_pb
+    if own:
+        pd = lib.hipstr_post_upload(pd_or_pb.ptr, dev_ll)
+        if not pd:
+            raise RuntimeError("hipstr_post_upload failed: " + lib.hipstr_last_error().decode())
+    try:
+        rc = lib.hipstr_post_launch(pd, None) if own else 0
+        if rc != 0:
+            raise RuntimeError("hipstr_post_launch failed: " + lib.hipstr_last_error().decode())
+        rc = lib.hipstr_post_assign(pd, C.byref(rq), C.byref(o))
+    finally:
+        if own:
+            lib.hipstr_post_free(pd)
+    if rc not in (0, 3):
+        raise RuntimeError("hipstr_post_assign failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    out = {nm: k[nm][:n_reads] for nm in ("best_hap", "read_strand", "log_phase_one", "read_req")}
+    for nm in ASSIGN_COUNTERS + ("phase1_reads", "phase2_reads"):
+        out[nm] = k[nm][:n_samp]
+    out["n_req"] = int(k["n_req"][0])
+    nq = out["n_req"] if (rc == 0 and pool_index is not None) else 0
+    out["req_read"] = k["req_read"][:nq]; out["req_allele"] = k["req_allele"][:nq]
+    out["rc"] = rc
+    return out
+
+
+def run_assign_trace_stats(lib, pb, read_req, trace, best_hap, hap_to_allele, allele_bp_diff, n_variants, region_start, region_stop):
+    """hipstr_assign_trace_stats (host only) -> (n_stutter[n_samp], n_flank_indel[n_samp], ml_bp[n_reads]).  trace: dict with the arrays
+    stutter_size, flank_ins, flank_del, aln_start, aln_stop per request (run_trace(..., unpack=False) returns such a dict)."""
+    _sig(lib.hipstr_assign_trace_stats, C.c_int, [_PBP, _i32p, C.POINTER(HipstrTraceOut)] + [_i32p] * 9)
+    i32 = lambda x: np.ascontiguousarray(np.asarray(x, np.int32))
+    t = HipstrTraceOut(); keep = {}
+    for nm in ("stutter_size", "flank_ins", "flank_del", "aln_start", "aln_stop"):
+        if trace.get(nm) is not None:
+            keep[nm] = i32(trace[nm]); setattr(t, nm, keep[nm].ctypes.data_as(_i32p))
+    n_reads = int(pb.a["read_off"][-1]) if len(pb.a["read_off"]) else 0
+    n_samp = int(pb.samp_off[-1])
+    a = [i32(x) for x in (read_req, best_hap, hap_to_allele, allele_bp_diff, n_variants, region_start, region_stop)]
+    ns = np.full(max(n_samp, 1), UNTOUCHED, np.int32); nf = np.full(max(n_samp, 1), UNTOUCHED, np.int32); ml = np.full(max(n_reads, 1), UNTOUCHED, np.int32)
+    p = lambda x: x.ctypes.data_as(_i32p)
+    rc = lib.hipstr_assign_trace_stats(pb.ptr, p(a[0]), C.byref(t), p(a[1]), p(a[2]), p(a[3]), p(a[4]), p(a[5]), p(a[6]), p(ns), p(nf), p(ml))
+    if rc != 0:
+        raise RuntimeError("hipstr_assign_trace_stats failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    return ns[:n_samp], nf[:n_samp], ml[:n_reads]
+
+
 class HipstrTraceOut(C.Structure):
     _fields_ = [("ll", _f64p), ("max_index", _i32p), ("hap_aln_off", _i32p), ("hap_aln", C.c_char_p), ("stutter_size", _i32p),
                 ("str_seq_off", _i32p), ("str_seq", C.c_char_p), ("flank_seq_off", _i32p), ("flank_seq", C.c_char_p),

@@ -37,6 +37,10 @@ extern "C" __global__ void hs_posterior_accumulate_kernel(const hs_post_dev_t* d
 extern "C" __global__ void hs_posterior_finish_kernel(const hs_post_dev_t* dp);
 extern "C" __global__ void hs_genotype_kernel(const hs_gt_dev_t* dp);
 extern "C" __global__ void hs_cr_math_kernel(int which, const double* x, double* y, int64_t n);
+extern "C" __global__ void hs_assign_kernel(const hs_assign_dev_t* dp);
+extern "C" __global__ void hs_assign_kernel_wg(const hs_assign_dev_t* dp);
+extern "C" __global__ void hs_assign_scan_kernel(const hs_assign_dev_t* dp);
+extern "C" __global__ void hs_assign_requests_kernel(const hs_assign_dev_t* dp);
 extern "C" size_t hs_str_lds_bytes(int lds_len, int max_B);
 extern "C" __global__ void hs_str_group_kernel(const hs_dev_t* dp, int item_begin, int short_only);
 extern "C" __global__ void hs_str_group_kernel_pw(const hs_dev_t* dp, int item_begin);
@@ -1529,7 +1533,7 @@ int post_setup(const hipstr_post_batch_t* pb, const double* dev_ll, PostRun& R){
 }
 }  // namespace
 
-struct hipstr_post_dev { PostRun R; std::vector<int32_t> n_samples, n_alleles; std::vector<uint8_t> haploid; bool foreign_stream = false; };
+struct hipstr_post_dev { PostRun R; std::vector<int32_t> n_samples, n_alleles; std::vector<uint8_t> haploid; bool foreign_stream = false; bool launched = false; };
 
 hipstr_post_dev_t* hipstr_post_upload(const hipstr_post_batch_t* pb, const double* dev_log_aln_probs){
   if (!pb){ g_err = "null argument"; return NULL; }
@@ -1548,7 +1552,7 @@ hipstr_post_dev_t* hipstr_post_upload(const hipstr_post_batch_t* pb, const doubl
 
 int hipstr_post_launch(hipstr_post_dev_t* pd, void* hip_stream){
   if (!pd) return fail("null argument");
-  if (pd->R.units.empty()) return 0;
+  if (pd->R.units.empty()){ pd->launched = true; return 0; }
   if (bind(pd->R.ctx)) return 1;
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : pd->R.stream;
   if (hip_stream && st != pd->R.stream) pd->foreign_stream = true;
@@ -1576,6 +1580,7 @@ int hipstr_post_launch(hipstr_post_dev_t* pd, void* hip_stream){
       hipLaunchKernelGGL(hs_posterior_kernel, dim3((unsigned)n_units), dim3(HS_POST_THREADS), 0, st, (const hs_post_dev_t*)pd->R.d_args);
   }
   HS_HIP(hipGetLastError());
+  pd->launched = true;
   if (host_libm){
     PostRun& R = pd->R;
     HS_HIP(hipstr::wait_stream(st));
@@ -1811,6 +1816,184 @@ int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hi
   if (rq->calc_pls && fetch_array(ctx, R.stream, out->pls, h.pls, (size_t)g*4)) return 1;
   if (rq->calc_phased_gls && fetch_array(ctx, R.stream, out->phased_gls, h.pgls, (size_t)pg*8)) return 1;
   lap("fetch");
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- read assignment
+namespace {
+// The loci of an assignment and its launch, from the posterior run's units (host only).
+struct AssignPlan { std::vector<hs_assign_locus_t> loci; std::vector<int32_t> unit_locus; int64_t tab_ints = 0; int max_unit_reads = 0, waves = 1; };
+int assign_plan(const hipstr_post_dev_t* pd, const hipstr_assign_request_t* rq, AssignPlan& P){
+  const PostRun& R = pd->R;
+  const size_t n_loci = pd->n_samples.size();
+  P.loci.resize(n_loci); P.unit_locus.resize(R.units.size());
+  size_t ui = 0; int rend = 0;
+  for (size_t l = 0; l < n_loci; l++){
+    hs_assign_locus_t& L = P.loci[l]; memset(&L, 0, sizeof L);
+    L.read_begin = rend; L.n_alleles = pd->n_alleles[l];
+    for (int s = 0; s < pd->n_samples[l]; s++, ui++){
+      const hs_post_unit_t& u = R.units[ui];
+      if (s == 0) L.read_begin = u.read_begin;
+      rend = u.read_begin + u.n_reads;
+      P.unit_locus[ui] = (int32_t)(l << 1) | (pd->haploid[l] ? 1 : 0);
+      P.max_unit_reads = std::max(P.max_unit_reads, u.n_reads);
+    }
+    L.n_reads = rend - L.read_begin;
+    if (rq->pool_index){
+      const int64_t np = (int64_t)rq->pool_off[l+1] - rq->pool_off[l];
+      if (np < 0) return fail("pool_off must not decrease");
+      const int64_t n_keys = np*L.n_alleles;
+      if (n_keys >= HS_ASSIGN_EMPTY) return fail("too many (pool, haplotype) pairs in a locus");
+      for (int r = L.read_begin; r < rend; r++)
+        if (rq->pool_index[r] < 0 || rq->pool_index[r] >= np) return fail("pool_index outside the pools of its locus");
+      int hashed = 0;
+      const int64_t slots = L.n_reads ? hs_assign_table_slots(n_keys, L.n_reads, &hashed) : 0;
+      if (slots >= HS_ASSIGN_EMPTY) return fail("too many reads in a locus");
+      L.slots = (int32_t)slots; L.hashed = hashed; L.pool_off = rq->pool_off[l];
+      L.tab_off = P.tab_ints; P.tab_ints += slots*(hashed ? 3 : 2);
+    }
+  }
+  P.waves = hs_assign_waves_per_unit(P.max_unit_reads);
+  return 0;
+}
+}  // namespace
+
+int hipstr_post_assign(hipstr_post_dev_t* pd, const hipstr_assign_request_t* rq, hipstr_assign_out_t* out){
+  if (!pd || !rq || !out || !rq->seed) return fail("null argument");
+  if (!out->best_hap || !out->read_strand || !out->log_phase_one || !out->n_aligned || !out->n_snp || !out->n_strand_one || !out->n_strand_two ||
+      !out->uniq_one || !out->uniq_two || !out->rv_uniq_one || !out->rv_uniq_two || !out->phase1_reads || !out->phase2_reads) return fail("null output array");
+  if (rq->rule != HIPSTR_ASSIGN_VCF && rq->rule != HIPSTR_ASSIGN_RETRACE) return fail("unknown assignment rule");
+  if (rq->pool_index && !rq->pool_off) return fail("pool_index given without pool_off");
+  if (rq->pool_index && (!out->n_req || !out->req_read || !out->req_allele || !out->read_req || out->cap_req < 0)) return fail("request-list output missing");
+  if (!(rq->strand_tolerance >= 0)) return fail("strand_tolerance must not be negative");
+  if (!pd->launched) return fail("hipstr_post_assign needs the posteriors: call hipstr_post_launch first");
+  PostRun& R = pd->R;
+  const hipstr::HostTables& T = hipstr::host_tables();
+  const bool req = rq->pool_index != NULL;
+  if (R.n_reads >= HS_ASSIGN_EMPTY) return fail("too many reads");
+  AssignPlan P;
+  if (assign_plan(pd, rq, P)) return 1;
+  if (req) *out->n_req = 0;
+  if (R.units.empty()) return 0;
+  if (bind(R.ctx)) return 1;
+  Ctx* ctx = R.ctx;
+  const size_t n = (size_t)R.n_reads, ns = (size_t)R.n_samp, nl = P.loci.size();
+  const size_t cap = req ? std::min((size_t)out->cap_req, n) : 0;          // (a read makes at most one request)
+
+  hipstr::HostArena ar;
+  const size_t o_loci = ar.add(P.loci.data(), nl*sizeof(hs_assign_locus_t)), o_ul = ar.add(P.unit_locus.data(), P.unit_locus.size()*4),
+               o_seed = ar.add(rq->seed, n*4), o_rev = rq->reverse ? ar.add(rq->reverse, n) : 0, o_pool = req ? ar.add(rq->pool_index, n*4) : 0;
+  hs_assign_dev_t h; memset(&h, 0, sizeof h);
+  const size_t o_args = ar.add(&h, sizeof h);
+  if (ar.reserve(ctx)) return 1;
+  // results, back to back (one copy home), then what stays on the device: counts and bases per locus, the first-occurrence tables
+  size_t tot = 0;
+  auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
+  const size_t r_nreq = take(4), r_best = take(n*4), r_strand = take(n*4), r_rreq = take(n*4), r_lpo = take(n*8), r_cnt = take(8*ns*4),
+               r_ph1 = take(ns*8), r_ph2 = take(ns*8), r_rr = take(cap*4), r_ra = take(cap*4);
+  const size_t res_bytes = tot;
+  const size_t d_count = take(nl*4), d_base = take(nl*4), d_tab = take((size_t)P.tab_ints*4);
+  struct Blocks { Ctx* c; hipStream_t st; char* dev = NULL; char* pin = NULL;
+                  ~Blocks(){ if (dev || pin) hipStreamSynchronize(st); if (dev) c->dev_cache.put(dev); if (pin) c->pin_cache.put(pin); } } B{ctx, R.stream};
+  B.dev = (char*)ctx->dev_cache.get(tot);
+  if (!B.dev) return 1;
+  B.pin = (char*)ctx->pin_cache.get(res_bytes);
+  if (!B.pin) return 1;
+  h.units = R.h.units; h.log_aln_probs = R.h.log_aln_probs; h.log_p1 = R.h.log_p1; h.log_p2 = R.h.log_p2; h.map_gt = R.h.map_gt;
+  h.unit_locus = ar.at<int32_t>(o_ul); h.loci = ar.at<hs_assign_locus_t>(o_loci); h.seed = ar.at<int32_t>(o_seed);
+  h.reverse = rq->reverse ? ar.at<uint8_t>(o_rev) : NULL; h.pool_index = req ? ar.at<int32_t>(o_pool) : NULL;
+  h.n_units = (int32_t)R.units.size(); h.n_loci = (int32_t)nl; h.rule = rq->rule; h.cap_req = (int32_t)cap;
+  h.log_half = T.log_half; h.strand_tolerance = rq->strand_tolerance == 0 ? 0.1 : rq->strand_tolerance;       // seq_stutter_genotyper.h:157
+  h.best_hap = (int32_t*)(B.dev + r_best); h.read_strand = (int32_t*)(B.dev + r_strand); h.read_req = (int32_t*)(B.dev + r_rreq);
+  h.log_phase_one = (double*)(B.dev + r_lpo); h.counters = (int32_t*)(B.dev + r_cnt); h.n_samp = (int32_t)ns;
+  h.phase1 = (double*)(B.dev + r_ph1); h.phase2 = (double*)(B.dev + r_ph2);
+  h.tab = (int32_t*)(B.dev + d_tab); h.locus_count = (int32_t*)(B.dev + d_count); h.locus_base = (int32_t*)(B.dev + d_base);
+  h.n_req = (int32_t*)(B.dev + r_nreq); h.req_read = (int32_t*)(B.dev + r_rr); h.req_allele = (int32_t*)(B.dev + r_ra);
+  if (pd->foreign_stream) HS_HIP(hipDeviceSynchronize());          // the posterior kernel may still be running on a stream of the caller's
+  hipStream_t st = R.stream;
+  if (ar.send(st)) return 1;
+  const hs_assign_dev_t* d_args = ar.at<hs_assign_dev_t>(o_args);
+  if (req){
+    HS_HIP(hipMemsetAsync(B.dev + d_count, 0, nl*4, st));
+    if (P.tab_ints) HS_HIP(hipMemsetAsync(B.dev + d_tab, 0x7f, (size_t)P.tab_ints*4, st));
+  }
+  const unsigned wgs = (unsigned)hs_assign_workgroups((int64_t)R.units.size(), P.waves);
+  if (P.waves == 1) hipLaunchKernelGGL(hs_assign_kernel, dim3(wgs), dim3(HS_ASSIGN_THREADS), 0, st, d_args);
+  else hipLaunchKernelGGL(hs_assign_kernel_wg, dim3(wgs), dim3(HS_ASSIGN_THREADS), 0, st, d_args);
+  if (req){
+    hipLaunchKernelGGL(hs_assign_scan_kernel, dim3(1), dim3(HS_ASSIGN_THREADS), 0, st, d_args);
+    hipLaunchKernelGGL(hs_assign_requests_kernel, dim3((unsigned)nl), dim3(HS_ASSIGN_THREADS), 0, st, d_args);
+  }
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(B.pin, B.dev, res_bytes, hipMemcpyDeviceToHost, st));
+  HS_HIP(hipstr::wait_stream(st));
+  const int32_t* bh = (const int32_t*)(B.pin + r_best);
+  if (req){
+    const int32_t n_req = *(const int32_t*)(B.pin + r_nreq);
+    *out->n_req = n_req;
+    if (n_req > out->cap_req){ fail("request arrays too small: *n_req holds the number needed"); return 3; }
+    memcpy(out->req_read, B.pin + r_rr, (size_t)n_req*4); memcpy(out->req_allele, B.pin + r_ra, (size_t)n_req*4);
+    memcpy(out->read_req, B.pin + r_rreq, n*4);
+  }
+  memcpy(out->best_hap, bh, n*4); memcpy(out->read_strand, B.pin + r_strand, n*4);
+  const double* lpo = (const double*)(B.pin + r_lpo);
+  for (size_t r = 0; r < n; r++) if (bh[r] >= 0) out->log_phase_one[r] = lpo[r];        // (skipped reads: untouched)
+  int32_t* const cnt[8] = { out->n_aligned, out->n_snp, out->n_strand_one, out->n_strand_two, out->uniq_one, out->uniq_two, out->rv_uniq_one, out->rv_uniq_two };
+  for (int k = 0; k < 8; k++) memcpy(cnt[k], B.pin + r_cnt + (size_t)k*ns*4, ns*4);
+  memcpy(out->phase1_reads, B.pin + r_ph1, ns*8); memcpy(out->phase2_reads, B.pin + r_ph2, ns*8);
+  return 0;
+}
+
+#ifndef HIPSTR_NO_DEBUG_ABI
+// Diagnostics (host only): the launch hipstr_post_assign would make for a posterior batch whose largest unit has max_unit_reads reads
+// and a locus of n_keys = pools x haplotypes keys and n_reads reads: out[0] wavefronts per unit, out[1] workgroups, out[2] table slots, out[3] hashed.
+int hipstr_debug_assign_plan(int32_t max_unit_reads, int64_t n_units, int64_t n_keys, int64_t n_reads, int64_t out[4]){
+  if (!out || max_unit_reads < 0 || n_units < 0 || n_keys < 0 || n_reads < 0) return fail("bad argument");
+  int hashed = 0;
+  out[0] = hs_assign_waves_per_unit(max_unit_reads); out[1] = hs_assign_workgroups(n_units, (int)out[0]);
+  out[2] = hs_assign_table_slots(n_keys, n_reads, &hashed); out[3] = hashed;
+  return 0;
+}
+#endif
+
+// Host only: the read counts that need the tracebacks (seq_stutter_genotyper.cpp:1124-1127, 1150-1154).
+int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read_req, const hipstr_trace_out_t* tr,
+                              const int32_t* best_hap, const int32_t* hap_to_allele, const int32_t* allele_bp_diff,
+                              const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop,
+                              int32_t* n_stutter, int32_t* n_flank_indel, int32_t* ml_bp){
+  if (!pb || !read_req || !tr || !best_hap || !hap_to_allele || !allele_bp_diff || !n_variants || !region_start || !region_stop ||
+      !n_stutter || !n_flank_indel || !ml_bp) return fail("null argument");
+  if (!tr->stutter_size || !tr->flank_ins || !tr->flank_del || !tr->aln_start || !tr->aln_stop) return fail("trace output without stutter_size / flank_ins / flank_del / aln_start / aln_stop");
+  if (pb->n_loci < 0 || (pb->n_loci && (!pb->n_alleles || !pb->n_samples || !pb->read_off || !pb->sample_label))) return fail("null argument");
+  int64_t so = 0, ao = 0, vo = 0;
+  for (int l = 0; l < pb->n_loci; l++){                    // everything checked before anything is written
+    const int A = pb->n_alleles[l], S = pb->n_samples[l], V = n_variants[l];
+    if (A < 1 || S < 0 || V < 1 || pb->read_off[l+1] < pb->read_off[l]) return fail("inconsistent locus tables");
+    for (int a = 0; a < A; a++) if (hap_to_allele[ao + a] < 0 || hap_to_allele[ao + a] >= V) return fail("hap_to_allele entry out of range");
+    for (int r = pb->read_off[l]; r < pb->read_off[l+1]; r++){
+      if (pb->sample_label[r] < 0 || pb->sample_label[r] >= S) return fail("sample_label out of range");
+      if (read_req[r] >= 0 && (best_hap[r] < 0 || best_hap[r] >= A)) return fail("best_hap out of range for a read with a request");
+    }
+    so += S; ao += A; vo += V;
+  }
+  const int n_reads = pb->n_loci ? pb->read_off[pb->n_loci] : 0;
+  for (int64_t s = 0; s < so; s++){ n_stutter[s] = 0; n_flank_indel[s] = 0; }
+  for (int r = 0; r < n_reads; r++) ml_bp[r] = HIPSTR_NO_ML_BP;
+  so = ao = vo = 0;
+  for (int l = 0; l < pb->n_loci; l++){
+    const int start_bound = region_start[l] > 4 ? region_start[l] - 4 : 0;
+    for (int r = pb->read_off[l]; r < pb->read_off[l+1]; r++){
+      const int q = read_req[r];
+      if (q < 0) continue;                                 // skipped read (:1080)
+      const int64_t s = so + pb->sample_label[r];
+      const bool str_data = tr->stutter_size[q] != HIPSTR_NO_STR_DATA;
+      if (str_data && tr->stutter_size[q] != 0) n_stutter[s]++;                        // has_stutter(), AlignmentTraceback.h:79-85
+      if (tr->flank_ins[q] != 0 || tr->flank_del[q] != 0) n_flank_indel[s]++;          // :1126
+      if (tr->aln_start[q] < start_bound && tr->aln_stop[q] > region_stop[l] + 4)      // :1152-1154
+        ml_bp[r] = allele_bp_diff[vo + hap_to_allele[ao + best_hap[r]]] + (str_data ? tr->stutter_size[q] : 0);
+    }
+    so += pb->n_samples[l]; ao += pb->n_alleles[l]; vo += n_variants[l];
+  }
   return 0;
 }
 

@@ -92,3 +92,60 @@ struct hs_gt_dev_t {
   double   log_thresh;
   int32_t  tot_given;            // HIPSTR_DEBUG_HOST_LIBM: `tot` (and log_unphased) come from the host
 };
+
+// ---- read assignment (assign.hip, hipstr_post_assign): SeqStutterGenotyper::write_vcf_record's per-read loop (seq_stutter_genotyper.cpp:1079-1157)
+// and retrace_alignments' pick (:805-841) on the resident MAP pairs.  The unit is hs_post_unit_t again; lanes are reads.
+#define HS_ASSIGN_THREADS 256          // threads of an assignment workgroup (four wavefronts)
+#define HS_ASSIGN_WAVE_READS 256       // a launch whose largest unit has at most this many reads gives every unit ONE wavefront, four units per workgroup
+#define HS_ASSIGN_DIRECT_MAX 4096      // a locus of up to this many (pool, haplotype) keys gets a direct first-occurrence table, a larger one a hashed table
+#define HS_ASSIGN_EMPTY 0x7f7f7f7f     // what a byte-wise fill with 0x7f leaves in the tables: above every read index and every key
+// wavefronts per unit of an assignment launch (1: four units share a workgroup, each loops over its reads 64 at a time; 4: a unit has the
+// workgroup and loops 256 at a time): from the LARGEST unit, applied to every unit of the launch, as hs_post_split is
+HS_POST_HD inline int hs_assign_waves_per_unit(int max_unit_reads){ return max_unit_reads <= HS_ASSIGN_WAVE_READS ? 1 : HS_ASSIGN_THREADS/64; }
+// workgroups of that launch
+HS_POST_HD inline int64_t hs_assign_workgroups(int64_t n_units, int waves_per_unit){
+  const int per_wg = HS_ASSIGN_THREADS/64/waves_per_unit;
+  return (n_units + per_wg - 1)/per_wg;
+}
+// slots of a locus' first-occurrence table: n_keys = pools x haplotypes entries addressed by the key itself, or — hashed — the power of two
+// from twice the locus' reads (a read adds at most one key: the table stays at most half full); *hashed says which
+HS_POST_HD inline int64_t hs_assign_table_slots(int64_t n_keys, int64_t n_reads, int* hashed){
+  if (n_keys <= HS_ASSIGN_DIRECT_MAX){ *hashed = 0; return n_keys; }
+  int64_t h = 64; while (h < 2*n_reads) h <<= 1;
+  *hashed = 1; return h;
+}
+
+// One locus of the request compaction.  Table of the locus at tab + tab_off: direct [first read: slots][request: slots],
+// hashed [key: slots][first read: slots][request: slots].
+struct hs_assign_locus_t {
+  int64_t tab_off;
+  int32_t slots, hashed;
+  int32_t read_begin, n_reads;     // un-pooled reads of the locus
+  int32_t n_alleles, pool_off;     // pool_off: hipstr_batch_t::read_off of the pooled batch (request = pool_off + pool index)
+};
+
+struct hs_assign_dev_t {
+  const hs_post_unit_t* units;     // the posterior run's
+  const double*  log_aln_probs;
+  const double*  log_p1;
+  const double*  log_p2;
+  const int32_t* map_gt;           // MAP haplotype pair per sample (hs_posterior_kernel)
+  const int32_t* unit_locus;       // [n_units] locus << 1 | haploid
+  const hs_assign_locus_t* loci;
+  const int32_t* seed;             // [n_reads]
+  const uint8_t* reverse;          // [n_reads] or NULL
+  const int32_t* pool_index;       // [n_reads] or NULL = no request list
+  int32_t  n_units, n_loci, rule, cap_req;
+  double   log_half, strand_tolerance;
+  // per read
+  int32_t* best_hap, *read_strand, *read_req;
+  double*  log_phase_one;
+  // per sample: n_aligned, n_snp, n_strand_one, n_strand_two, uniq_one, uniq_two, rv_uniq_one, rv_uniq_two back to back, [8][n_samp]
+  int32_t* counters;  int32_t n_samp;
+  double*  phase1, *phase2;
+  // request compaction
+  int32_t* tab;
+  int32_t* locus_count;            // [n_loci] distinct keys per locus (zeroed before the launch)
+  int32_t* locus_base;             // [n_loci] requests in front of the locus
+  int32_t* n_req, *req_read, *req_allele;
+};

@@ -473,6 +473,72 @@ int hipstr_hmm_trace(const hipstr_batch_t* batch, int32_t n_req, const int32_t* 
 int hipstr_hmm_trace_seeded(const hipstr_batch_t* batch, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                             const int32_t* req_seed, const char* const* hap_to_ref, hipstr_trace_out_t* out);
 
+/*
+ * Reads assigned to the MAP haplotypes and the per-sample read counts of a VCF record: the loop over the reads of
+ * SeqStutterGenotyper::write_vcf_record (seq_stutter_genotyper.cpp:1079-1157) with the phase totals of :1355-1356, and the pick of
+ * retrace_alignments (:805-841), on a resident hipstr_post_dev_t after hipstr_post_launch — the likelihood matrix is read where it
+ * lies (host array or device pointer given at upload), never fetched.  Per read, against its sample's MAP pair (hap_a, hap_b) = map_gt
+ * (== best_hap of hipstr_post_extract) and its row LL of log_aln_probs, every quantity in the reference's operation order:
+ *   log_phase_one = (LOG_ONE_HALF + log_p1) + LL[hap_a] - log_sum_exp((LOG_ONE_HALF + log_p1) + LL[hap_a], (LOG_ONE_HALF + log_p2) + LL[hap_b])
+ *                   (:1090-1091; the exact pair log-sum-exp of mathops.cpp:52-57 with correctly rounded exp / log)
+ *   read_strand   = 1 only if the locus is not haploid, hap_a != hap_b or |log_p1 - log_p2| > 1e-10, and with v1 = log_p1 + LL[hap_a],
+ *                   v2 = log_p2 + LL[hap_b]: |v1 - v2| > strand_tolerance and !(v1 > v2)   (:1095-1099); uniq_* / rv_uniq_* count the
+ *                   reads inside that tolerance branch by strand (:1100-1107)
+ *   best_hap      = HIPSTR_ASSIGN_VCF: read_strand == 0 ? hap_a : hap_b (:1113); HIPSTR_ASSIGN_RETRACE: the first argument of the pair
+ *                   log-sum-exp greater than the second ? hap_a : hap_b (:825).  The rule changes nothing else.
+ *   phase1_reads  = exp(log_sum_exp(log_phase_one of the sample's reads that were not skipped)) — mathops.cpp:64-70: the maximum, then the
+ *                   exponentials added IN READ ORDER — or 0 without such reads; phase2_reads = n_aligned - phase1_reads   (:1355-1356)
+ * A read with seed < 0 is skipped (:1080) and counts nowhere; so are the reads of a sample without a MAP pair (map_gt -1).
+ * Request list (with pool_index): request k is the k-th distinct (locus, pool_index, best_hap) met when the reads are walked in index
+ * order — the order trace_cache_ fills in (:1115-1122, :828-835) — as (req_read, req_allele) for hipstr_hmm_trace on the pooled batch;
+ * read_req[r] names the request of read r.  Returns 3 with *n_req set (nothing else promised) when n_req > cap_req, as hipstr_stream_next
+ * does for buffers that are too small.  Without pool_index the request outputs are left untouched.
+ * Device and pinned blocks come from the context's caches: no allocation in steady state.  The AB and FS p-values (cephes bdtr, htslib's
+ * kt_fisher_exact) stay with the host, computed from the counts returned here.
+ */
+#define HIPSTR_ASSIGN_VCF     0   /* write_vcf_record's rule, seq_stutter_genotyper.cpp:1094-1113 */
+#define HIPSTR_ASSIGN_RETRACE 1   /* retrace_alignments' rule, :823-825 */
+typedef struct hipstr_assign_request {
+  const int32_t* seed;        /* [n_reads] seed_positions_ of the un-pooled reads; < 0 = read skipped (:1080) */
+  const uint8_t* reverse;     /* [n_reads] Alignment::is_from_reverse_strand(), or NULL = none */
+  const int32_t* pool_index;  /* [n_reads] pool of the read within its locus (pool_index_), or NULL = no request list */
+  const int32_t* pool_off;    /* [n_loci+1] = hipstr_batch_t::read_off of the pooled batch; needed with pool_index */
+  int32_t rule;
+  double  strand_tolerance;   /* STRAND_TOLERANCE; 0 = the reference's 0.1 (seq_stutter_genotyper.h:157) */
+} hipstr_assign_request_t;
+typedef struct hipstr_assign_out {
+  /* per read */
+  int32_t* best_hap;          /* [n_reads] haplotype to trace on, -1 for a skipped read */
+  int32_t* read_strand;       /* [n_reads] 0 / 1 (:1095-1099), -1 for a skipped read */
+  double*  log_phase_one;     /* [n_reads] :1090-1091; untouched for skipped reads */
+  /* per sample, sample_total_ll's order */
+  int32_t* n_aligned, *n_snp, *n_strand_one, *n_strand_two;          /* :1135-1144 */
+  int32_t* uniq_one, *uniq_two, *rv_uniq_one, *rv_uniq_two;          /* :1100-1107 */
+  double*  phase1_reads, *phase2_reads;                              /* :1355-1356 */
+  /* trace requests: distinct (locus, pool, best_hap) in order of first occurrence by read index */
+  int32_t* n_req;             /* [1] */
+  int32_t* req_read;          /* [cap_req] pool_off[locus] + pool: hipstr_hmm_trace's req_read */
+  int32_t* req_allele;        /* [cap_req] */
+  int32_t* read_req;          /* [n_reads] request of the read, -1 for a skipped read */
+  int32_t  cap_req;
+} hipstr_assign_out_t;
+int hipstr_post_assign(hipstr_post_dev_t* pd, const hipstr_assign_request_t* rq, hipstr_assign_out_t* out);
+
+/* Host only (no device needed; works on a library that never opened one): the counts of the record that need the tracebacks, from
+ * hipstr_hmm_trace's output for the requests of hipstr_post_assign.  Per sample (sample_total_ll's order): n_stutter = reads whose request has
+ * a stutter_size that is neither HIPSTR_NO_STR_DATA nor 0 (has_stutter(), AlignmentTraceback.h:79-85; seq_stutter_genotyper.cpp:1124-1125),
+ * n_flank_indel = reads whose request has flank_ins != 0 || flank_del != 0 (:1126-1127).  Per read: ml_bp[r] =
+ * allele_bp_diff[hap_to_allele[best_hap[r]]] + total_stutter_size (0 without STR data, AlignmentTraceback.h:87-93) when the traced alignment
+ * spans the region by 5 bp — aln_start < (region_start > 4 ? region_start - 4 : 0) and aln_stop > region_stop + 4 (:1152-1154) — else
+ * HIPSTR_NO_ML_BP.  Reads without a request (read_req < 0) count nowhere.  hap_to_allele: [sum A_l] as in hipstr_gt_request_t;
+ * allele_bp_diff: [sum V_l], by variant; n_variants, region_start, region_stop: [n_loci].  Only n_loci, n_alleles, n_samples, read_off and
+ * sample_label of `pb` are read. */
+#define HIPSTR_NO_ML_BP INT32_MIN
+int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read_req /* [n_reads] */, const hipstr_trace_out_t* tr,
+                              const int32_t* best_hap, const int32_t* hap_to_allele /* [sum A_l] */, const int32_t* allele_bp_diff /* [sum V_l], by variant */,
+                              const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop /* [n_loci] */,
+                              int32_t* n_stutter, int32_t* n_flank_indel /* [n_samp] */, int32_t* ml_bp /* [n_reads] */);
+
 /* The diagnostics entry points (hipstr_debug_*: what the tests, the fuzzers and bench.py look inside the library with) are declared in
  * hipstr_hmm_debug.h — not part of the drop-in ABI; a build with -DHIPSTR_NO_DEBUG_ABI leaves them out of the library. */
 

@@ -67,6 +67,11 @@ int hipstr_debug_nw_plan(const hipstr_nw_batch_t* batch, double ws_mib, char* js
  * a split launch with an empty share], "routes_hit".  (HIPSTR_DEBUG_HOST_LIBM, which sends every unit down the chunked path, is not
  * modelled.)  Same conventions as hipstr_debug_trace_plan. */
 int hipstr_debug_post_plan(const hipstr_post_batch_t* batch, char* json, int cap);
+/* Diagnostics (host only): the launch decisions of hipstr_post_assign (post_layout.h) for a batch whose largest (locus, sample) unit has
+ * max_unit_reads reads and n_units units, and for a locus of n_keys = pools x haplotypes keys and n_reads reads: out[0] wavefronts per unit
+ * (1: four units share a workgroup; 4: a unit has the workgroup), out[1] workgroups, out[2] slots of the locus' first-occurrence table,
+ * out[3] 1 = hashed, 0 = direct. */
+int hipstr_debug_assign_plan(int32_t max_unit_reads, int64_t n_units, int64_t n_keys, int64_t n_reads, int64_t out[4]);
 
 /* Diagnostics (host only): one entry {A, G, Bnd} of the tabulated closed form the STR kernel uses for a "simple" visiting
  * list (StutterAlignerClass.cpp:59-150 for a periodic block): with `bound` columns of the block in reach, a run of U0 equal
