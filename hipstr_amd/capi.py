@@ -273,9 +273,13 @@ class HipstrTraceOut(C.Structure):
                 ("cap_chars", C.c_int32)]
 
 
-def run_trace(lib, prefix, bptr, req_read, req_allele, hap_to_ref=None, cap=1 << 16, timing=None, unpack=True, req_seed=None):
+TRACE_ASSEMBLE_DEVICE = 1      # HIPSTR_TRACE_ASSEMBLE_DEVICE
+
+
+def run_trace(lib, prefix, bptr, req_read, req_allele, hap_to_ref=None, cap=1 << 16, timing=None, unpack=True, req_seed=None, flags=None):
     """Call <prefix>trace on a one-locus batch; returns a list of dicts (one per request) with python-typed fields.
-    hap_to_ref: list of bytes (one per allele) or None.  The reference probe (prefix 'ref_') always stitches."""
+    hap_to_ref: list of bytes (one per allele) or None.  The reference probe (prefix 'ref_') always stitches.
+    flags: None, or the flags of <prefix>trace_ex (0 = host replay, TRACE_ASSEMBLE_DEVICE), which is then the entry point called."""
     n = len(req_read)
     o = HipstrTraceOut(); keep = {}
     def i32(name, m):
@@ -291,7 +295,7 @@ def run_trace(lib, prefix, bptr, req_read, req_allele, hap_to_ref=None, cap=1 <<
         chars(nm)
     o.cap_chars = cap
     rr = np.ascontiguousarray(np.asarray(req_read, np.int32)); aa = np.ascontiguousarray(np.asarray(req_allele, np.int32))
-    fn = getattr(lib, prefix + ("trace" if req_seed is None else "trace_seeded"))
+    fn = getattr(lib, prefix + ("trace_ex" if flags is not None else ("trace" if req_seed is None else "trace_seeded")))
     import time
     h2r = None
     if hap_to_ref is not None and prefix != "ref_":
@@ -301,7 +305,10 @@ def run_trace(lib, prefix, bptr, req_read, req_allele, hap_to_ref=None, cap=1 <<
     if req_seed is not None:        # trace_optimal_aln's seed_base argument (HapAligner.h:93)
         ss = np.ascontiguousarray(np.asarray(req_seed, np.int32)); keep["req_seed"] = ss
         extra, extra_t = [ss.ctypes.data_as(_i32p)], [_i32p]
-    if prefix == "ref_":
+    if flags is not None:
+        fn.restype = C.c_int; fn.argtypes = [_BP, C.c_int32, _i32p, _i32p, _i32p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(HipstrTraceOut)]
+        rc = fn(bptr, n, rr.ctypes.data_as(_i32p), aa.ctypes.data_as(_i32p), extra[0] if extra else None, h2r, int(flags), C.byref(o))
+    elif prefix == "ref_":
         fn.restype = C.c_int; fn.argtypes = [_BP, C.c_int32, _i32p, _i32p] + extra_t + [C.POINTER(HipstrTraceOut)]
         rc = fn(bptr, n, rr.ctypes.data_as(_i32p), aa.ctypes.data_as(_i32p), *(extra + [C.byref(o)]))
     else:
@@ -655,6 +662,7 @@ def load_hmm():
     _sig(lib.hipstr_debug_fetch_table, C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64])
     _sig(lib.hipstr_debug_launch_plan, C.c_int, [_BP, C.c_double, C.c_char_p, C.c_int])
     _sig(lib.hipstr_debug_trace_plan, C.c_int, [_BP, C.c_int32, _i32p, _i32p, _i32p, C.c_double, C.c_char_p, C.c_int])
+    _sig(lib.hipstr_debug_trace_assemble_plan, C.c_int, [_BP, C.c_int32, _i32p, _i32p, _i32p, C.POINTER(C.c_char_p), C.c_char_p, C.c_int])
     _sig(lib.hipstr_debug_nw_plan, C.c_int, [C.POINTER(HipstrNwBatch), C.c_double, C.c_char_p, C.c_int])
     _sig(lib.hipstr_debug_post_plan, C.c_int, [_PBP, C.c_char_p, C.c_int])
     return lib
@@ -690,6 +698,16 @@ def trace_plan(lib, bptr, req_read, req_allele, req_seed=None, ws_mib=0.0):
     ss = None if req_seed is None else np.ascontiguousarray(np.asarray(req_seed, np.int32))
     return _plan_json(lib, "hipstr_debug_trace_plan", lambda buf, cap: lib.hipstr_debug_trace_plan(
         bptr, len(rr), rr.ctypes.data_as(_i32p), aa.ctypes.data_as(_i32p), _ptr(ss, _i32p), ws_mib, buf, cap))
+
+
+def trace_assemble_plan(lib, bptr, req_read, req_allele, req_seed=None, hap_to_ref=None):
+    """The slots and the staging route hipstr_hmm_trace_ex(TRACE_ASSEMBLE_DEVICE) gives every request of a list (host only:
+    hipstr_debug_trace_assemble_plan) as a dict; "requests" rows are lists in the order of "fields"."""
+    rr = np.ascontiguousarray(np.asarray(req_read, np.int32)); aa = np.ascontiguousarray(np.asarray(req_allele, np.int32))
+    ss = None if req_seed is None else np.ascontiguousarray(np.asarray(req_seed, np.int32))
+    h2r = None if hap_to_ref is None else (C.c_char_p * len(hap_to_ref))(*hap_to_ref)
+    return _plan_json(lib, "hipstr_debug_trace_assemble_plan", lambda buf, cap: lib.hipstr_debug_trace_assemble_plan(
+        bptr, len(rr), rr.ctypes.data_as(_i32p), aa.ctypes.data_as(_i32p), _ptr(ss, _i32p), h2r, buf, cap))
 
 
 def nw_plan(lib, pairs, use_ref_end_penalty=False, ws_mib=0.0):

@@ -600,6 +600,394 @@ __global__ void __launch_bounds__(64) hs_trace_walk(const hs_tdev_t* __restrict_
   else if (lane == 1) trace_walk(d, 2*q+1, B, H-1-max_index, decp[1]);
 }
 
+// ------------------------------------------------------------------ records assembled on the device (hipstr_hmm_trace_ex)
+// The bookkeeping half of HapAligner::retrace (HapAligner.cpp:363-571, 642-707) and stitch_alignment_trace (AlignmentTraceback.cpp:7-52,
+// 55-144) from what hs_trace_walk left in the chunk's result block: the same replay as replay_side / the stitch loop of the host path, by
+// one lane per request out of LDS, then an exclusive scan per pool and a compaction into dense pools the host copies out whole.
+//   hs_trace_assemble  one wavefront per request: stages the two sides' ops, the read, its SNP-eligible flags (qual_correct of the device's
+//                      table against MIN_SNP_LOG_PROB_CORRECT), the flank bases (low byte of the rows) and the hap_to_ref string into LDS;
+//                      lane 0 replays.  Flank and STR sequences are runs of the read in read order (the left side's pieces are reversed
+//                      back, the right side walks a reversed read), so they leave as (start, length) and the compaction copies them from
+//                      the read; indels, SNPs, CIGAR pairs and the alignment string go to the request's slots, every write checked.
+//   hs_trace_scan      one wavefront per pool: running offsets over the chunk's requests, seeded with the earlier chunks' totals.
+//   hs_trace_compact   one wavefront per request: pieces into the dense pools, a lane per element.
+#define HS_ASM_LDS 8192            // bytes of staging per request the assemble kernel keeps in LDS (a 150-bp read with 60-base flanks: ~2 KB)
+#define HS_ASM_POOLS 7             // hap_aln, str_seq, flank_seq (two pieces per request), indel, snp, cigar, aln_str
+struct hs_areq_t {                 // one request of the assemble kernels
+  int32_t loc;                     // locus: row of blk_start / blk_end
+  int32_t h2r_off, h2r_len;        // its hap_to_ref string in the pool; length -1: no stitch
+  int32_t indel_cap, snp_cap, fa_cap;          // entries of its slots (fa_cap: stitched string, CIGAR pairs, alignment string)
+  int64_t indel_off, snp_off, fa_off;          // its slots in the staging arrays
+};
+struct hs_adev_t {
+  const hs_areq_t* reqs;
+  const int32_t *blk_start, *blk_end;          // [3*n_loci] each
+  const char* h2r;
+  int32_t *st_indel_pos, *st_indel_size, *st_snp_pos, *st_cig_len;      // staging, by slot
+  char *st_snp_base, *st_fa, *st_cig_op, *st_aln;
+  int32_t *lens, *excl, *rng, *fail;           // [8*nq] piece lengths / chunk-relative starts (pool p at hs_asm_pool_at(p, nq)), [3*nq] read offset of str_seq, flank 0, flank 2
+  int64_t* totals;                             // result block from here on: [HS_ASM_POOLS] running totals, then the first failed request
+  int32_t* first_fail;
+  int32_t *stutter_size, *flank_ins, *flank_del, *aln_start, *aln_stop;   // [nq]
+  int32_t* incl;                               // [8*nq] the caller's *_off[q+1]
+  int32_t *p_indel_pos, *p_indel_size, *p_snp_pos, *p_cig_len;           // dense pools of the chunk
+  char *p_hap_aln, *p_str_seq, *p_flank, *p_snp_base, *p_cig_op, *p_aln;
+  int64_t base[HS_ASM_POOLS];                  // totals of the earlier chunks
+  int64_t dense_cap[HS_ASM_POOLS];             // elements of each dense pool
+  int32_t nq;
+};
+__host__ __device__ inline int hs_asm_pool_at(int p, int nq){ return (p < 3 ? p : p + 1)*nq; }      // flank_seq has 2*nq entries
+__host__ __device__ inline int hs_asm_pool_n(int p, int nq){ return p == 2 ? 2*nq : nq; }
+// bytes a request stages: ops of both sides | read | SNP flags | flank bases of both orientations | hap_to_ref | stitched string
+__host__ __device__ inline int hs_asm_lds_bytes(int capL, int capR, int len, int F0, int F2, int hlen, int fa_cap){
+  return capL + capR + 2*len + 2*(F0 + F2) + (hlen > 0 ? hlen : 0) + fa_cap;
+}
+__host__ __device__ inline bool hs_asm_in_lds(int bytes){ return bytes <= HS_ASM_LDS; }
+
+__device__ __forceinline__ int wave_scan_i(int v){       // inclusive prefix sum over the wavefront: wave_sum_d's DPP steps, every lane kept
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false); v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false); v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
+  return v;
+}
+
+constexpr double DEV_MIN_SNP_LOG_PROB_CORRECT = -0.0043648054;     // HapAligner.cpp:24
+
+struct AsmView {                   // what the replay reads: the wavefront's LDS copies, or the originals in HBM
+  const char* ops[2]; int cnt[2];
+  const char* read;                // the read, forward
+  const uint8_t* good;             // per base: qual_correct > MIN_SNP_LOG_PROB_CORRECT; NULL: from the tables
+  const char* hc[2][2];            // flank bases per side: leading, trailing block; NULL: from the rows
+  const char* h2r;
+  char* fa;                        // stitched string, fa_cap bytes
+};
+
+__device__ void trace_assemble_serial(const hs_tdev_t& d, const hs_adev_t& a, int q, const AsmView& V){
+  const int MATCH = 0, DEL = 1, INS = 2, NONE = -1;
+  const hs_tside_t* SL = d.sides + 2*q;
+  const hs_areq_t R = a.reqs[q];
+  const int nq = a.nq;
+  const int len = SL->len, sb = SL->seed, base_off = SL->base_off;
+  const int F0 = SL->F0, F2 = SL->F2, B = d.stropts[SL->stropt].B, H = F0 + B + F2;
+  const int max_index = d.max_index[q];
+  bool ok = true;
+  int n_indel = 0, n_snp = 0, flank_ins = 0, flank_del = 0;
+  int stutter = HIPSTR_NO_STR_DATA, str_s = 0, str_n = 0;
+  int fl_s[2] = {0, 0}, fl_n[2] = {0, 0};                   // flank_seq(0), flank_seq(2) as runs of the read
+  auto add_flank = [&](int out_block, int s, int n){        // appends must continue the run: anything else is an inconsistent string
+    const int i = out_block >> 1;
+    if (n <= 0) return;
+    if (fl_n[i] == 0) fl_s[i] = s; else if (fl_s[i] + fl_n[i] != s) ok = false;
+    fl_n[i] += n;
+  };
+  auto push_indel = [&](int32_t pos, int32_t size){
+    if (n_indel < R.indel_cap){ a.st_indel_pos[R.indel_off + n_indel] = pos; a.st_indel_size[R.indel_off + n_indel] = size; } else ok = false;
+    n_indel++;
+  };
+  auto push_snp = [&](int32_t pos, char c){
+    if (n_snp < R.snp_cap){ a.st_snp_pos[R.snp_off + n_snp] = pos; a.st_snp_base[R.snp_off + n_snp] = c; } else ok = false;
+    n_snp++;
+  };
+  const int blen3[3] = { F0, B, F2 };
+  int seed_block = 0;
+  for (int x = 0, crd = max_index; x < 3; x++){ if (crd < blen3[x]){ seed_block = x; break; } crd -= blen3[x]; }
+  // left retrace, then the seed base joins the flank it sits in, then the right retrace (HapAligner.cpp:642-684)
+  for (int sd = 0; sd < 2 && ok; sd++){
+    const hs_tside_t* S = SL + sd;
+    const bool rev = sd != 0;
+    const int cnt = V.cnt[sd];
+    if (cnt < 0 || cnt > S->ops_cap){ ok = false; break; }
+    if (sd == 1 && seed_block != 1) add_flank(seed_block, sb, 1);
+    const int mx = sd ? H-1-max_index : max_index;
+    if (mx == 0) continue;                                  // this side is all soft clips
+    const int n = S->n;
+    const int sblen[3] = { S->F0, B, S->F2 };
+    int blk = 0, crd = mx;
+    for (int x = 0; x < 3; x++){ if (crd < sblen[x]){ blk = x; break; } crd -= sblen[x]; }
+    int block, base;
+    if (crd == 0){ block = blk-1; base = block >= 0 ? sblen[block]-1 : -1; } else { block = blk; base = crd-1; }
+    const int size = d.str_size[2*q+sd], apos = d.str_pos[2*q+sd];
+    const char* ops = V.ops[sd];
+    auto rdc = [&](int x){ return V.read[rev ? len-1-x : x]; };             // the side's read (reversed for the right problem)
+    int seq = n-1, k = 0;
+    bool done = false;
+    while (block >= 0 && ok && !done){
+      const int blen = sblen[block];
+      if (block == 1){
+        int i = max(0, min(seq+1, apos));
+        k += i;
+        if (size < 0) k += -size;
+        else { const int e = min(seq+1, apos+size); if (e > i){ k += e-i; i = e; } }
+        { const int e = min(blen+size, seq+1); if (e > i){ k += e-i; i = e; } }
+        stutter = size; str_n = i; str_s = rev ? len-1-seq : seq-i+1;       // rd[seq], rd[seq-1], ..: a run of the read either way
+        if (blen + size >= seq+1){ done = true; break; }                   // the read does not span the STR block
+        seq -= blen + size;
+      } else {
+        int prev = NONE;
+        const int fb = rev ? 2-block : block;                               // side_block_start
+        int32_t pos = ((!rev || fb == 1) ? a.blk_start[3*R.loc + fb] : a.blk_end[3*R.loc + fb]-1) + (rev ? -base : base);
+        const int32_t inc = rev ? 1 : -1;
+        int indel_seq = -1; int32_t indel_position = -1;
+        const int seq_hi = seq;
+        const int which = block == 0 ? 0 : 1;
+        const hs_row_t* rows = d.rows + (block == 0 ? S->lead_off : S->trail_off);
+        auto flush = [&](){ add_flank(fb, rev ? len-1-seq_hi : seq+1, seq_hi - seq); };
+        while (base >= 0 && seq >= 0){
+          if (k >= cnt){ ok = false; break; }
+          const char oc = ops[k++];
+          const int type = oc == 'M' ? MATCH : (oc == 'D' ? DEL : (oc == 'I' ? INS : NONE));
+          if (type == NONE){ ok = false; break; }
+          if (type != prev){
+            if (prev == DEL){
+              if (rev) push_indel(indel_position, indel_position - pos);
+              else     push_indel(pos+1, pos - indel_position);
+            } else if (prev == INS)
+              push_indel(indel_position + (rev ? 0 : 1), (int32_t)(indel_seq - seq));
+            if (type == DEL || type == INS){ indel_seq = seq; indel_position = pos; }
+            prev = type;
+          }
+          if (type == MATCH){
+            const char rc = rdc(seq);
+            const char hcv = V.hc[sd][which] ? V.hc[sd][which][base] : (char)(rows[base] & 0xff);
+            if (hcv != rc){
+              const int ri = rev ? len-1-seq : seq;
+              const bool good = V.good ? V.good[ri] != 0 : d.qual_correct[(uint8_t)d.quals[base_off + ri]] > DEV_MIN_SNP_LOG_PROB_CORRECT;
+              if (good) push_snp(pos, rc);
+            }
+            seq--; base--; pos += inc;
+          } else if (type == DEL){ flank_del++; base--; pos += inc; }
+          else { flank_ins++; seq--; }
+          if (seq == -1 || (base == -1 && block == 0)){
+            k += seq + 1;                      // soft clips
+            done = true;
+            break;
+          }
+        }
+        if (ok) flush();
+      }
+      if (done) break;
+      block--;
+      if (block >= 0) base = sblen[block] - 1;
+    }
+    if (k != cnt) ok = false;
+  }
+  const int cntL = V.cnt[0], cntR = V.cnt[1];
+  const int nfull = cntL + 1 + cntR;                        // hap_aln = reversed left ops + 'M' + right ops
+  int n_cig = 0, n_aln = 0;
+  int32_t start = 0, stop = 0;
+  if (ok && R.h2r_len >= 0){
+    // ---- stitch_alignment_trace (AlignmentTraceback.cpp:55-144)
+    const char* h2r = V.h2r; const int hlen = R.h2r_len;
+    auto fullc = [&](int i){ return i < cntL ? V.ops[0][cntL-1-i] : (i == cntL ? 'M' : V.ops[1][i-cntL-1]); };
+    int hap_index = max_index, hai = 0; int32_t seed_pos = a.blk_start[3*R.loc];
+    while (hap_index > 0 && hai < hlen){
+      const char c = h2r[hai];
+      if (c == 'M' || c == 'I') hap_index--;
+      if (c == 'M' || c == 'D') seed_pos++;
+      hai++;
+    }
+    while (hai < hlen && h2r[hai] == 'D') hai++;
+    int sbase = sb, rai = 0;
+    while (sbase > 0 && rai < nfull){
+      const char c = fullc(rai);
+      if (c == 'M' || c == 'I' || c == 'S') sbase--;
+      rai++;
+    }
+    while (rai < nfull && fullc(rai) == 'D') rai++;
+    // every character stitch_dir emits spends a read base or a hap_to_ref character: the left part is at most sb + hai long and is written
+    // backwards from there, which is the reversal the reference does afterwards
+    const int mid = sb + hai;
+    auto stitch_dir = [&](int h_index, int r_index, int inc, int wpos){      // AlignmentTraceback.cpp:7-52
+      int w = 0;
+      while (r_index >= 0 && r_index < nfull){
+        const char rc = fullc(r_index);
+        char out = 0;
+        if (rc == 'S'){ out = 'S'; r_index += inc; }
+        else {
+          if (h_index < 0 || h_index >= hlen) break;
+          const char hcv = h2r[h_index];
+          if (hcv == 'D'){
+            if (rc == 'I'){ out = 'M'; r_index += inc; h_index += inc; }
+            else { out = 'D'; h_index += inc; }
+          }
+          else if (rc == 'I'){ out = 'I'; r_index += inc; }
+          else if (rc == 'D'){
+            if (hcv == 'M') out = 'D';
+            r_index += inc; h_index += inc;
+          }
+          else { out = hcv; r_index += inc; h_index += inc; }
+        }
+        if (out){
+          const int p = wpos + inc*w;
+          if (p >= 0 && p < R.fa_cap) V.fa[p] = out; else ok = false;
+          w++;
+        }
+      }
+      return w;
+    };
+    const int nla = stitch_dir(hai-1, rai-1, -1, mid-1);
+    const int nra = stitch_dir(hai+1, rai+1, 1, mid+1);
+    if (mid < R.fa_cap) V.fa[mid] = 'M'; else ok = false;
+    if (ok){
+      const char* fa = V.fa + (mid - nla);
+      const int nfa = nla + 1 + nra;
+      start = stop = seed_pos;
+      bool lead = true; char cc = 0; int num = 0, ri = 0;
+      auto push_cig = [&](char c, int32_t m){
+        if (n_cig < R.fa_cap){ a.st_cig_op[R.fa_off + n_cig] = c; a.st_cig_len[R.fa_off + n_cig] = m; } else ok = false;
+        n_cig++;
+      };
+      auto push_aln = [&](char c){ if (n_aln < R.fa_cap) a.st_aln[R.fa_off + n_aln] = c; else ok = false; n_aln++; };
+      for (int i = 0; i < nfa; i++){
+        char ch = fa[i];
+        if (lead){ if (ch == 'I') ch = 'S'; else lead = false; }          // leading 'I' -> 'S'
+        if (ch == 'D' || ch == 'M'){ if (i < nla) start--; else if (i > nla) stop++; }
+        if (i == 0){ cc = ch; num = 1; }
+        else if (ch != cc){ push_cig(cc, num); cc = ch; num = 1; }
+        else num++;
+        if (ch == 'S') ri++;
+        else if (ch == 'M' || ch == 'I'){ if (ri < len) push_aln(V.read[ri]); else ok = false; ri++; }
+        else push_aln('-');
+      }
+      push_cig(cc, num);
+    }
+  }
+  if (str_s < 0 || str_s + str_n > len) ok = false;
+  for (int i = 0; i < 2; i++) if (fl_s[i] < 0 || fl_s[i] + fl_n[i] > len) ok = false;
+  if (!ok){ n_indel = n_snp = n_cig = n_aln = str_n = fl_n[0] = fl_n[1] = 0; }
+  a.fail[q] = ok ? 0 : 1;
+  a.lens[hs_asm_pool_at(0, nq) + q] = ok ? nfull : 0;
+  a.lens[hs_asm_pool_at(1, nq) + q] = str_n;
+  a.lens[hs_asm_pool_at(2, nq) + 2*q] = fl_n[0]; a.lens[hs_asm_pool_at(2, nq) + 2*q+1] = fl_n[1];
+  a.lens[hs_asm_pool_at(3, nq) + q] = n_indel;
+  a.lens[hs_asm_pool_at(4, nq) + q] = n_snp;
+  a.lens[hs_asm_pool_at(5, nq) + q] = n_cig;
+  a.lens[hs_asm_pool_at(6, nq) + q] = n_aln;
+  a.rng[q] = str_s; a.rng[nq + q] = fl_s[0]; a.rng[2*nq + q] = fl_s[1];
+  a.stutter_size[q] = stutter; a.flank_ins[q] = flank_ins; a.flank_del[q] = flank_del;
+  a.aln_start[q] = start; a.aln_stop[q] = stop;
+}
+
+__global__ void __launch_bounds__(64) hs_trace_assemble(const hs_tdev_t* __restrict__ dp, hs_adev_t a){
+  const hs_tdev_t& d = *dp;
+  const int lane = threadIdx.x;
+  const int q = blockIdx.x;
+  const hs_tside_t* SL = d.sides + 2*q;
+  const hs_areq_t* R = a.reqs + q;
+  const int len = uni(SL->len), base_off = uni(SL->base_off), hlen = uni(R->h2r_len), fa_cap = uni(R->fa_cap);
+  __shared__ char s_buf[HS_ASM_LDS];
+  AsmView V;
+  V.cnt[0] = uni(d.n_ops[2*q]); V.cnt[1] = uni(d.n_ops[2*q+1]);
+  if (hs_asm_in_lds(hs_asm_lds_bytes(uni(SL->ops_cap), uni(SL[1].ops_cap), len, uni(SL->F0), uni(SL->F2), hlen, fa_cap))){
+    // (pieces in hs_asm_lds_bytes' order, so they end inside s_buf; every copy is clamped to its piece)
+    int at = 0;
+    for (int sd = 0; sd < 2; sd++){
+      const hs_tside_t* S = SL + sd;
+      const int cap = uni(S->ops_cap), m = min(max(V.cnt[sd], 0), cap);
+      const char* g = d.ops + uni(S->ops_off);
+      for (int i = lane; i < m; i += 64) s_buf[at + i] = g[i];
+      V.ops[sd] = s_buf + at; at += cap;
+    }
+    for (int i = lane; i < len; i += 64){
+      s_buf[at + i] = d.bases[base_off + i];
+      s_buf[at + len + i] = d.qual_correct[(uint8_t)d.quals[base_off + i]] > DEV_MIN_SNP_LOG_PROB_CORRECT ? 1 : 0;
+    }
+    V.read = s_buf + at; V.good = (const uint8_t*)(s_buf + at + len); at += 2*len;
+    for (int sd = 0; sd < 2; sd++){
+      const hs_tside_t* S = SL + sd;
+      const int f0 = uni(S->F0), f2 = uni(S->F2);
+      const hs_row_t* lead = d.rows + uni(S->lead_off); const hs_row_t* trail = d.rows + uni(S->trail_off);
+      for (int i = lane; i < f0; i += 64) s_buf[at + i] = (char)(lead[i] & 0xff);
+      for (int i = lane; i < f2; i += 64) s_buf[at + f0 + i] = (char)(trail[i] & 0xff);
+      V.hc[sd][0] = s_buf + at; V.hc[sd][1] = s_buf + at + f0; at += f0 + f2;
+    }
+    if (hlen > 0){
+      const char* g = a.h2r + uni(R->h2r_off);
+      for (int i = lane; i < hlen; i += 64) s_buf[at + i] = g[i];
+    }
+    V.h2r = s_buf + at; at += max(hlen, 0);
+    V.fa = s_buf + at;
+  } else {
+    V.ops[0] = d.ops + uni(SL->ops_off); V.ops[1] = d.ops + uni(SL[1].ops_off);
+    V.read = d.bases + base_off; V.good = NULL;
+    V.hc[0][0] = V.hc[0][1] = V.hc[1][0] = V.hc[1][1] = NULL;
+    V.h2r = a.h2r + uni(R->h2r_off);
+    V.fa = a.st_fa + uni(R->fa_off);
+  }
+  wave_lds_sync();
+  if (lane == 0) trace_assemble_serial(d, a, q, V);
+}
+
+// running offsets of one pool per wavefront; wavefront HS_ASM_POOLS finds the first failed request
+__global__ void __launch_bounds__(64) hs_trace_scan(hs_adev_t a){
+  const int lane = threadIdx.x, p = blockIdx.x, nq = a.nq;
+  if (p == HS_ASM_POOLS){
+    int first = 0x7fffffff;
+    for (int i0 = 0; i0 < nq; i0 += 64){
+      const int i = i0 + lane;
+      first = min(first, wave_min_i((i < nq && a.fail[i]) ? i : 0x7fffffff));
+    }
+    if (lane == 0) *a.first_fail = first == 0x7fffffff ? -1 : first;
+    return;
+  }
+  const int n = hs_asm_pool_n(p, nq);
+  const int32_t* lens = a.lens + hs_asm_pool_at(p, nq);
+  int32_t* excl = a.excl + hs_asm_pool_at(p, nq);
+  int32_t* incl = a.incl + hs_asm_pool_at(p, nq);
+  int64_t carry = 0;                                        // chunk-relative
+  for (int i0 = 0; i0 < n; i0 += 64){
+    const int i = i0 + lane;
+    const int v = i < n ? lens[i] : 0;
+    const int s = wave_scan_i(v);
+    if (i < n){ excl[i] = (int32_t)(carry + s - v); incl[i] = (int32_t)(a.base[p] + carry + s); }
+    carry += rdlane(s, 63);
+  }
+  if (lane == 0) a.totals[p] = a.base[p] + carry;
+}
+
+__global__ void __launch_bounds__(64) hs_trace_compact(const hs_tdev_t* __restrict__ dp, hs_adev_t a){
+  const hs_tdev_t& d = *dp;
+  const int lane = threadIdx.x, q = blockIdx.x, nq = a.nq;
+  if (uni(a.fail[q])) return;
+  const hs_tside_t* SL = d.sides + 2*q;
+  const hs_areq_t* R = a.reqs + q;
+  auto len_of = [&](int p, int i){ return uni(a.lens[hs_asm_pool_at(p, nq) + i]); };
+  auto at_of = [&](int p, int i){ return (int64_t)uni(a.excl[hs_asm_pool_at(p, nq) + i]); };
+  // a piece that would end past its dense pool is dropped whole (cannot happen: a piece is at most its slot, the pools are the slots' sum)
+  auto fits = [&](int p, int64_t at, int n){ return at >= 0 && at + n <= a.dense_cap[p]; };
+  {
+    const int cntL = uni(d.n_ops[2*q]), n = len_of(0, q); const int64_t at = at_of(0, q);
+    const char* oL = d.ops + uni(SL->ops_off); const char* oR = d.ops + uni(SL[1].ops_off);
+    if (fits(0, at, n)) for (int i = lane; i < n; i += 64) a.p_hap_aln[at + i] = i < cntL ? oL[cntL-1-i] : (i == cntL ? 'M' : oR[i-cntL-1]);
+  }
+  const char* read = d.bases + uni(SL->base_off);
+  {
+    const int n = len_of(1, q), s = uni(a.rng[q]); const int64_t at = at_of(1, q);
+    if (fits(1, at, n)) for (int i = lane; i < n; i += 64) a.p_str_seq[at + i] = read[s + i];
+  }
+  for (int f = 0; f < 2; f++){
+    const int n = len_of(2, 2*q+f), s = uni(a.rng[(1+f)*nq + q]); const int64_t at = at_of(2, 2*q+f);
+    if (fits(2, at, n)) for (int i = lane; i < n; i += 64) a.p_flank[at + i] = read[s + i];
+  }
+  {
+    const int n = len_of(3, q); const int64_t at = at_of(3, q), from = uni(R->indel_off);
+    if (fits(3, at, n)) for (int i = lane; i < n; i += 64){ a.p_indel_pos[at + i] = a.st_indel_pos[from + i]; a.p_indel_size[at + i] = a.st_indel_size[from + i]; }
+  }
+  {
+    const int n = len_of(4, q); const int64_t at = at_of(4, q), from = uni(R->snp_off);
+    if (fits(4, at, n)) for (int i = lane; i < n; i += 64){ a.p_snp_pos[at + i] = a.st_snp_pos[from + i]; a.p_snp_base[at + i] = a.st_snp_base[from + i]; }
+  }
+  {
+    const int n = len_of(5, q); const int64_t at = at_of(5, q), from = uni(R->fa_off);
+    if (fits(5, at, n)) for (int i = lane; i < n; i += 64){ a.p_cig_op[at + i] = a.st_cig_op[from + i]; a.p_cig_len[at + i] = a.st_cig_len[from + i]; }
+  }
+  {
+    const int n = len_of(6, q); const int64_t at = at_of(6, q), from = uni(R->fa_off);
+    if (fits(6, at, n)) for (int i = lane; i < n; i += 64) a.p_aln[at + i] = a.st_aln[from + i];
+  }
+}
+
 // ------------------------------------------------------------------ host side
 #define TR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
   hipstr::api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
@@ -656,6 +1044,20 @@ int trace_chunk_end(const std::vector<int64_t>& need, int q0, int64_t budget){
   while (q1 < (int)need.size() && mat + need[q1] <= budget){ mat += need[q1]; q1++; }
   return q1;
 }
+// operation characters a side can emit: its read columns, the haplotype's rows and the largest artifact
+int trace_ops_cap(int n, int F0, int F2, int B, int period){ return n + F0 + F2 + B + 2*HS_MAXREP*period + 16; }
+// slots of a device-assembled request (hipstr_hmm_trace_ex), from bounds alone.  hap_aln: both sides' ops and the seed's 'M'.  seq: str_seq
+// and each flank_seq piece are runs of the read.  snp: one per read base at most.  indel: a record closes a run of 'I' or 'D'; in a flank
+// block runs alternate, every run that is not 'D' spends a read base, and a side walks two flank blocks, so there are at most len + 2 + 2
+// deletion runs and len insertion runs.  stitched (the stitched string, its CIGAR pairs and the alignment string): every character
+// stitch_dir emits spends a read base or a hap_to_ref character; 0 without hap_to_ref (hlen < 0).
+struct TraceAsmCaps { int hap_aln, seq, indel, snp, stitched, lds_bytes; };
+TraceAsmCaps trace_asm_caps(int capL, int capR, int len, int F0, int F2, int hlen){
+  TraceAsmCaps c;
+  c.hap_aln = capL + capR + 1; c.seq = len; c.indel = 2*len + 4; c.snp = len; c.stitched = hlen < 0 ? 0 : len + hlen;
+  c.lds_bytes = hs_asm_lds_bytes(capL, capR, len, F0, F2, hlen, c.stitched);
+  return c;
+}
 // the seed of a request: the caller's or the host's; NULL or the refusal
 const char* trace_seed_of(const hipstr_batch_t* b, int l, int r, const int32_t* req_seed, int q, int& s){
   const bool given = req_seed && req_seed[q] != HIPSTR_SEED_AUTO;       // trace_optimal_aln's seed_base argument (HapAligner.h:93)
@@ -671,6 +1073,7 @@ const char* trace_seed_of(const hipstr_batch_t* b, int l, int r, const int32_t* 
 struct AllelePrep {
   std::string seq[2][3];          // block sequences per orientation, in side order
   int lead_off[2], trail_off[2], stropt[2];
+  int32_t h2r_off = 0, h2r_len = -1;      // its hap_to_ref string in the pool a device-assembled call uploads
 };
 
 struct TraceAcc {                 // what AlignmentTrace accumulates (AlignmentTraceback.h:27-34)
@@ -792,6 +1195,9 @@ struct ReqOut {                    // one request's results, built by a worker t
 
 }  // namespace
 
+static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                      const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o);
+
 extern "C" int hipstr_hmm_trace(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                 const char* const* hap_to_ref, hipstr_trace_out_t* o){
   return hipstr_hmm_trace_seeded(b, n_req, req_read, req_allele, NULL, hap_to_ref, o);
@@ -799,7 +1205,20 @@ extern "C" int hipstr_hmm_trace(const hipstr_batch_t* b, int32_t n_req, const in
 
 extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                        const int32_t* req_seed, const char* const* hap_to_ref, hipstr_trace_out_t* o){
+  return trace_call(b, n_req, req_read, req_allele, req_seed, hap_to_ref, 0u, o);
+}
+
+extern "C" int hipstr_hmm_trace_ex(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                                   const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o){
+  if (flags & ~(uint32_t)HIPSTR_TRACE_ASSEMBLE_DEVICE) return hipstr::api_fail("hipstr_hmm_trace_ex: unknown flag bits");
+  return trace_call(b, n_req, req_read, req_allele, req_seed, hap_to_ref, flags, o);
+}
+
+// flags 0: the host replays the operation strings; HIPSTR_TRACE_ASSEMBLE_DEVICE: hs_trace_assemble / _scan / _compact build the records
+static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                      const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o){
   hipstr::ApiTimer prof_t(hipstr::PB_TRACE);
+  const bool on_device = (flags & HIPSTR_TRACE_ASSEMBLE_DEVICE) != 0;
   using hipstr::api_fail;
   if (!b || !o || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return api_fail("null argument");
   if (b->n_loci < 1) return api_fail("hipstr_hmm_trace needs at least one locus");
@@ -833,6 +1252,7 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
   std::map<int64_t, int> allele_slot;                    // (locus, allele) -> entry of `alleles`
   std::vector<AllelePrep> alleles;
   std::vector<int32_t> seeds(n_req), req_locus(n_req), req_ap(n_req);
+  std::string h2r_pool;                                  // device assembly: the hap_to_ref strings of the distinct (locus, allele) pairs requested
   for (int q = 0; q < n_req; q++){
     const int r = req_read[q], k = req_allele[q];
     if (r < 0 || r >= n_reads) return api_fail("request names a read outside the batch");
@@ -865,6 +1285,12 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
       ap.trail_off[sd] = rows.size(); rows.insert(rows.end(), trail.begin(), trail.end());
       ap.stropt[sd] = P.stropts.size();
       hipstr::append_stropt(ap.seq[sd][1], b->period[l], b->stutter + 6*l, P);
+    }
+    if (on_device && hap_to_ref){
+      const char* s2 = hap_to_ref[b->hap_off[l] + k];
+      ap.h2r_off = (int32_t)h2r_pool.size(); ap.h2r_len = (int32_t)strlen(s2);
+      h2r_pool.append(s2, (size_t)ap.h2r_len);
+      if (h2r_pool.size() > 0x7fffffff) return api_fail("too many requests for one call; split the request list");
     }
     req_ap[q] = allele_slot[key] = (int)alleles.size();
     alleles.push_back(ap);
@@ -904,7 +1330,11 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
   const char* const src_quals = compact_reads ? up_quals.data() : b->quals;
   const size_t n_up = compact_reads ? up_bases.size() : (size_t)total_bases;
   hipstr::HostArena st_arena;                     // every table of the call: one pinned block, one copy
+  hs_adev_t ad; memset(&ad, 0, sizeof ad);
   {
+    // device assembly: the block coordinates of every locus and the hap_to_ref pool travel with the tables
+    const size_t o_bs = on_device ? st_arena.add(b->blk_start, 3*(size_t)n_loci*sizeof(int32_t)) : 0, o_be = on_device ? st_arena.add(b->blk_end, 3*(size_t)n_loci*sizeof(int32_t)) : 0,
+                 o_h2r = on_device ? st_arena.add(h2r_pool.data(), h2r_pool.size()) : 0;
     const size_t o_rows = st_arena.add(rows.data(), rows.size()*sizeof(hs_row_t)), o_so = st_arena.add(P.stropts.data(), P.stropts.size()*sizeof(hs_stropt_t)),
                  o_vis = st_arena.add(P.visits.data(), P.visits.size()*sizeof(hs_visit_t)), o_f64 = st_arena.add(P.f64pool.data(), P.f64pool.size()*sizeof(double)),
                  o_chars = st_arena.add(P.chars.data(), P.chars.size()), o_bases = st_arena.add(src_bases, n_up), o_quals = st_arena.add(src_quals, n_up);
@@ -912,6 +1342,7 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
     if (st_arena.send(T.stream)) return 1;
     h.rows = st_arena.at<hs_row_t>(o_rows); h.stropts = st_arena.at<hs_stropt_t>(o_so); h.visits = st_arena.at<hs_visit_t>(o_vis);
     h.f64pool = st_arena.at<double>(o_f64); h.chars = st_arena.at<char>(o_chars); h.bases = st_arena.at<char>(o_bases); h.quals = st_arena.at<char>(o_quals);
+    if (on_device){ ad.blk_start = st_arena.at<int32_t>(o_bs); ad.blk_end = st_arena.at<int32_t>(o_be); ad.h2r = st_arena.at<char>(o_h2r); }
   }
   h.int_log = T.int_log; h.qual_correct = T.qual_correct; h.qual_error = T.qual_error; h.m2m = T.m2m; h.m2i = T.m2i;
   h.log_thresh = HT.log_thresh;
@@ -948,7 +1379,7 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
       S.lead_off = ap.lead_off[sd]; S.F0 = ap.seq[sd][0].size();
       S.trail_off = ap.trail_off[sd]; S.F2 = ap.seq[sd][2].size();
       S.stropt = ap.stropt[sd];
-      S.ops_cap = S.n + S.F0 + S.F2 + (int)ap.seq[sd][1].size() + 2*HS_MAXREP*b->period[req_locus[q]] + 16;
+      S.ops_cap = trace_ops_cap(S.n, S.F0, S.F2, (int)ap.seq[sd][1].size(), b->period[req_locus[q]]);
       need[q] += trace_side_ws(S.F0, S.F2, S.n);
     }
     if (need[q] > budget) return api_fail("one traceback needs more workspace than the device offers");
@@ -978,6 +1409,49 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
   hc.ll = (double*)(d_res + o_ll); hc.max_index = (int32_t*)(d_res + o_mxi); hc.n_ops = (int32_t*)(d_res + o_nops);
   hc.str_size = (int32_t*)(d_res + o_ssz); hc.str_pos = (int32_t*)(d_res + o_spos); hc.ops = d_res + o_ops;
 
+  // ---- device assembly: slots per request, staging and the result block sized for the largest chunk
+  std::vector<TraceAsmCaps> acaps;
+  int64_t mx_cap[5] = {0, 0, 0, 0, 0};                  // per chunk at most: hap_aln, seq, indel, snp, stitched entries
+  size_t ao_scal = 0, ao_incl = 0, ao_i32 = 0, ao_chr = 0, ao_end = 0;
+  char* d_out = NULL;
+  if (on_device){
+    acaps.resize(n_req);
+    for (int q = 0; q < n_req; q++){
+      const hs_tside_t& SL = sides[2*q];
+      acaps[q] = trace_asm_caps(SL.ops_cap, sides[2*q+1].ops_cap, SL.len, SL.F0, SL.F2, alleles[req_ap[q]].h2r_len);
+    }
+    for (int q0 = 0; q0 < n_req; ){
+      const int q1 = trace_chunk_end(need, q0, budget);
+      int64_t c[5] = {0, 0, 0, 0, 0};
+      for (int q = q0; q < q1; q++){ c[0] += acaps[q].hap_aln; c[1] += acaps[q].seq; c[2] += acaps[q].indel; c[3] += acaps[q].snp; c[4] += acaps[q].stitched; }
+      for (int i = 0; i < 5; i++) mx_cap[i] = std::max(mx_cap[i], c[i]);
+      q0 = q1;
+    }
+    for (int i = 0; i < 5; i++) if (2*mx_cap[i] > 0x7fffffff) return api_fail("too many requests for one call; split the request list");
+    const size_t nqm = (size_t)max_nq, n_in = (size_t)mx_cap[2], n_sn = (size_t)mx_cap[3], n_fa = (size_t)mx_cap[4];
+    if (dev.alloc(&ad.st_indel_pos, n_in) || dev.alloc(&ad.st_indel_size, n_in) || dev.alloc(&ad.st_snp_pos, n_sn) || dev.alloc(&ad.st_cig_len, n_fa) ||
+        dev.alloc(&ad.st_snp_base, n_sn) || dev.alloc(&ad.st_fa, n_fa) || dev.alloc(&ad.st_cig_op, n_fa) || dev.alloc(&ad.st_aln, n_fa) ||
+        dev.alloc(&ad.lens, 8*nqm) || dev.alloc(&ad.excl, 8*nqm) || dev.alloc(&ad.rng, 3*nqm) || dev.alloc(&ad.fail, nqm)) return 1;
+    // the result block, with the layout of the pinned block it is copied to: totals and the first failure | five scalars per request |
+    // the running offsets | int32 pools | char pools
+    ao_scal = 64; ao_incl = ao_scal + 5*nqm*4; ao_i32 = ao_incl + 8*nqm*4;
+    ao_chr = ao_i32 + (2*n_in + n_sn + n_fa)*4;
+    ao_end = ao_chr + (size_t)mx_cap[0] + 3*(size_t)mx_cap[1] + n_sn + 2*n_fa;
+    if (dev.alloc(&d_out, ao_end)) return 1;
+    ad.totals = (int64_t*)d_out; ad.first_fail = (int32_t*)(d_out + HS_ASM_POOLS*8);
+    int32_t* sc = (int32_t*)(d_out + ao_scal);
+    ad.stutter_size = sc; ad.flank_ins = sc + nqm; ad.flank_del = sc + 2*nqm; ad.aln_start = sc + 3*nqm; ad.aln_stop = sc + 4*nqm;
+    ad.incl = (int32_t*)(d_out + ao_incl);
+    int32_t* pi = (int32_t*)(d_out + ao_i32);
+    ad.p_indel_pos = pi; ad.p_indel_size = pi + n_in; ad.p_snp_pos = pi + 2*n_in; ad.p_cig_len = pi + 2*n_in + n_sn;
+    char* pc = d_out + ao_chr;
+    ad.p_hap_aln = pc; ad.p_str_seq = pc + mx_cap[0]; ad.p_flank = ad.p_str_seq + mx_cap[1]; ad.p_snp_base = ad.p_flank + 2*mx_cap[1];
+    ad.p_cig_op = ad.p_snp_base + n_sn; ad.p_aln = ad.p_cig_op + n_fa;
+    ad.dense_cap[0] = mx_cap[0]; ad.dense_cap[1] = mx_cap[1]; ad.dense_cap[2] = 2*mx_cap[1]; ad.dense_cap[3] = mx_cap[2]; ad.dense_cap[4] = mx_cap[3];
+    ad.dense_cap[5] = ad.dense_cap[6] = mx_cap[4];
+  }
+  int64_t pool_total[HS_ASM_POOLS] = {0, 0, 0, 0, 0, 0, 0};       // totals of the chunks done
+
   const auto t_static = now();
   double ms_alloc = 0, ms_kernel = 0, ms_d2h = 0, ms_replay = 0;
   for (int q0 = 0; q0 < n_req; ){
@@ -1003,8 +1477,20 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
     cls_begin[HS_MAX_COLS] = items.size();
     hipstr::HostArena ch_arena;                     // this chunk's sides, launch order and argument block
     hs_tdev_t hcc = hc;
+    std::vector<hs_areq_t> areqs;
+    if (on_device){
+      areqs.resize(nq);
+      int64_t at_in = 0, at_sn = 0, at_fa = 0;
+      for (int q = q0; q < q1; q++){
+        hs_areq_t& R = areqs[q-q0]; const AllelePrep& ap = alleles[req_ap[q]]; const TraceAsmCaps& c = acaps[q];
+        R.loc = req_locus[q]; R.h2r_off = ap.h2r_off; R.h2r_len = ap.h2r_len;
+        R.indel_cap = c.indel; R.snp_cap = c.snp; R.fa_cap = c.stitched;
+        R.indel_off = at_in; R.snp_off = at_sn; R.fa_off = at_fa;
+        at_in += c.indel; at_sn += c.snp; at_fa += c.stitched;
+      }
+    }
     const size_t o_sides = ch_arena.add(sides.data() + 2*q0, 2*(size_t)nq*sizeof(hs_tside_t)), o_items = ch_arena.add(items.data(), items.size()*sizeof(int32_t)),
-                 o_args = ch_arena.add(&hcc, sizeof hcc);
+                 o_args = ch_arena.add(&hcc, sizeof hcc), o_areq = on_device ? ch_arena.add(areqs.data(), areqs.size()*sizeof(hs_areq_t)) : 0;
     // (the argument block points into the arena it travels in: sizes first, then the pointers, then the copy)
     if (ch_arena.reserve(T.ctx)) return api_fail("out of device or pinned host memory");
     hcc.sides = ch_arena.at<hs_tside_t>(o_sides); hcc.items = ch_arena.at<int32_t>(o_items);
@@ -1036,6 +1522,73 @@ extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, c
       }
     }
     hipLaunchKernelGGL(hs_trace_walk, dim3(nq), dim3(64), 0, T.stream, d_args, 0);
+    if (on_device){
+      // ---- the records on the device: assemble, offsets, compaction; then the totals, then every pool and array in one copy each
+      hs_adev_t ac = ad;
+      ac.reqs = ch_arena.at<hs_areq_t>(o_areq); ac.nq = nq;
+      for (int p = 0; p < HS_ASM_POOLS; p++) ac.base[p] = pool_total[p];
+      hipEvent_t ev[2] = {NULL, NULL};
+      if (timing){ TR_HIP(hipEventCreate(&ev[0])); TR_HIP(hipEventCreate(&ev[1])); TR_HIP(hipEventRecord(ev[0], T.stream)); }
+      hipLaunchKernelGGL(hs_trace_assemble, dim3(nq), dim3(64), 0, T.stream, d_args, ac);
+      hipLaunchKernelGGL(hs_trace_scan, dim3(HS_ASM_POOLS + 1), dim3(64), 0, T.stream, ac);
+      hipLaunchKernelGGL(hs_trace_compact, dim3(nq), dim3(64), 0, T.stream, d_args, ac);
+      if (timing) TR_HIP(hipEventRecord(ev[1], T.stream));
+      TR_HIP(hipGetLastError());
+      const auto c2 = now();
+      char* hostblk = (char*)hipstr::pin_alloc(T.ctx, o_nops + ao_end);
+      if (!hostblk) return api_fail("out of pinned host memory");
+      struct PinGuard { hipstr::Ctx* c; void* p; ~PinGuard(){ hipstr::pin_free(c, p); } } pin_guard{T.ctx, hostblk};
+      char* hout = hostblk + o_nops;
+      TR_HIP(hipMemcpyAsync(hostblk, d_res, o_nops, hipMemcpyDeviceToHost, T.stream));                 // ll, max_index
+      TR_HIP(hipMemcpyAsync(hout, d_out, ao_i32, hipMemcpyDeviceToHost, T.stream));                    // totals, scalars, offsets
+      TR_HIP(hipstr::wait_stream(T.stream));
+      if (timing){
+        float kms = 0; TR_HIP(hipEventElapsedTime(&kms, ev[0], ev[1])); hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
+        fprintf(stderr, "  assemble + scan + compact of %d: %.3f ms on the device\n", nq, kms);
+      }
+      const int64_t* tot = (const int64_t*)hout;
+      const int32_t first_fail = *(const int32_t*)(hout + HS_ASM_POOLS*8);
+      const int32_t* incl = (const int32_t*)(hout + ao_incl);
+      const int64_t cap = o->cap_chars;
+      // the host path's order: request by request, an inconsistent operation string before a full pool
+      int first_full = -1;
+      { bool over = false; for (int p = 0; p < HS_ASM_POOLS; p++) over = over || tot[p] > cap;
+        if (over) for (int q = 0; q < nq && first_full < 0; q++) for (int p = 0; p < HS_ASM_POOLS; p++){
+          const int i = hs_asm_pool_at(p, nq) + (p == 2 ? 2*q+1 : q);
+          // (the offsets are 32-bit: one that wrapped is past any capacity too)
+          if (incl[i] > cap || incl[i] < 0){ first_full = q; break; }
+        }
+        if (over && first_full < 0) first_full = 0; }
+      if (first_fail >= 0 && (first_full < 0 || first_fail <= first_full)) return api_fail("internal error: inconsistent traceback operation string");
+      if (first_full >= 0) return api_fail("hipstr_trace_out_t pools are too small (cap_chars)");
+      const auto c3 = now();
+      struct Pool { int p; const void* dev; size_t esz; void* dst; };
+      const Pool pools[] = {
+        {0, ac.p_hap_aln, 1, o->hap_aln}, {1, ac.p_str_seq, 1, o->str_seq}, {2, ac.p_flank, 1, o->flank_seq},
+        {3, ac.p_indel_pos, 4, o->indel_pos}, {3, ac.p_indel_size, 4, o->indel_size}, {4, ac.p_snp_pos, 4, o->snp_pos}, {4, ac.p_snp_base, 1, o->snp_base},
+        {5, ac.p_cig_op, 1, o->cigar_op}, {5, ac.p_cig_len, 4, o->cigar_len}, {6, ac.p_aln, 1, o->aln_str} };
+      for (const Pool& pl : pools){
+        const size_t nb = (size_t)(tot[pl.p] - pool_total[pl.p])*pl.esz;
+        if (nb) TR_HIP(hipMemcpyAsync(hout + ((const char*)pl.dev - d_out), pl.dev, nb, hipMemcpyDeviceToHost, T.stream));
+      }
+      TR_HIP(hipstr::wait_stream(T.stream));
+      for (const Pool& pl : pools){
+        const size_t nb = (size_t)(tot[pl.p] - pool_total[pl.p])*pl.esz;
+        if (nb) memcpy((char*)pl.dst + (size_t)pool_total[pl.p]*pl.esz, hout + ((const char*)pl.dev - d_out), nb);
+      }
+      memcpy(o->ll + q0, hostblk + o_ll, (size_t)nq*8); memcpy(o->max_index + q0, hostblk + o_mxi, (size_t)nq*4);
+      const int32_t* sc = (const int32_t*)(hout + ao_scal);
+      int32_t* const scal_dst[5] = { o->stutter_size, o->flank_ins, o->flank_del, o->aln_start, o->aln_stop };
+      for (int i = 0; i < 5; i++) memcpy(scal_dst[i] + q0, sc + (size_t)i*max_nq, (size_t)nq*4);
+      int32_t* const off_dst[HS_ASM_POOLS] = { o->hap_aln_off, o->str_seq_off, o->flank_seq_off, o->indel_off, o->snp_off, o->cigar_off, o->aln_str_off };
+      for (int p = 0; p < HS_ASM_POOLS; p++)
+        memcpy(off_dst[p] + (p == 2 ? 2*q0 : q0) + 1, incl + hs_asm_pool_at(p, nq), (size_t)hs_asm_pool_n(p, nq)*4);
+      for (int p = 0; p < HS_ASM_POOLS; p++) pool_total[p] = tot[p];
+      q0 = q1;
+      const auto c4 = now();
+      ms_alloc += ms(c0, c1); ms_kernel += ms(c1, c2); ms_d2h += ms(c2, c3); ms_replay += ms(c3, c4);
+      continue;
+    }
     TR_HIP(hipGetLastError());
     const auto c2 = now();
     // results through one pinned block (a pageable destination costs a staging copy per call and per array), in one copy behind the kernels
@@ -1295,6 +1848,58 @@ extern "C" int hipstr_debug_trace_plan(const hipstr_batch_t* b, int32_t n_req, c
     o += "]}";
     q0 = q1;
   }
+  o += "]}";
+  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
+  return (int)o.size();
+}
+// Diagnostics (host only): the slots and the staging route of every request of a device-assembled call, from trace_ops_cap, trace_asm_caps
+// and hs_asm_in_lds — the functions hipstr_hmm_trace_ex and hs_trace_assemble call.
+extern "C" int hipstr_debug_trace_assemble_plan(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                                                const int32_t* req_seed, const char* const* hap_to_ref, char* json, int cap){
+  auto bad = [](const char* why){ hipstr::api_fail(why); return -1; };
+  if (!b || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return bad("null argument");
+  if (b->n_loci < 1) return bad("hipstr_hmm_trace needs at least one locus");
+  { std::string err; if (hipstr::validate_tables(b, err)) return bad(err.c_str()); }
+  const int n_loci = b->n_loci, n_reads = b->read_off[n_loci];
+  std::vector<int32_t> opt_base(n_loci + 1, 0);
+  for (int l = 0; l < n_loci; l++){
+    if (b->period[l] < 1 || b->period[l] > 9) return bad("STR period must be in [1,9] (stutter_model.h:38)");
+    int cnt = 0;
+    for (int k = 0; k < 3; k++){
+      if (b->blk_nopts[3*l+k] < 1) return bad("haplotype block without options");
+      cnt += b->blk_nopts[3*l+k];
+    }
+    opt_base[l+1] = opt_base[l] + cnt;
+  }
+  std::string o; char buf[256];
+  auto put = [&](const char* fmt, auto... a){ snprintf(buf, sizeof buf, fmt, a...); o += buf; };
+  put("{\"thresholds\": {\"HS_ASM_LDS\": %d}, \"routes\": [\"assemble_lds\", \"assemble_hbm\"], "
+      "\"fields\": [\"hap_aln\", \"seq\", \"indel\", \"snp\", \"stitched\", \"lds_bytes\", \"in_lds\"], \"requests\": [", HS_ASM_LDS);
+  int n_lds = 0, n_hbm = 0;
+  for (int q = 0; q < n_req; q++){
+    const int r = req_read[q], k = req_allele[q];
+    if (r < 0 || r >= n_reads) return bad("request names a read outside the batch");
+    const int l = (int)(std::upper_bound(b->read_off, b->read_off + n_loci + 1, r) - b->read_off) - 1;
+    const int32_t* nopts = b->blk_nopts + 3*l;
+    if (k < 0 || k >= nopts[0]*nopts[1]*nopts[2]) return bad("request names an allele outside its locus");
+    int s;
+    if (const char* why = trace_seed_of(b, l, r, req_seed, q, s)) return bad(why);
+    const int len = b->base_off[r+1] - b->base_off[r];
+    int32_t oi[3]; int F[3];
+    hipstr::allele_options(nopts, k, oi);
+    for (int x = 0, cur = opt_base[l]; x < 3; cur += nopts[x], x++) F[x] = b->opt_off[cur + oi[x] + 1] - b->opt_off[cur + oi[x]];
+    if (F[0] < 1 || F[2] < 1) return bad("empty flank sequence");
+    if (F[1] < 1) return bad("empty STR allele is not supported");
+    const int hlen = hap_to_ref ? (int)strlen(hap_to_ref[b->hap_off[l] + k]) : -1;
+    const TraceAsmCaps c = trace_asm_caps(trace_ops_cap(s, F[0], F[2], F[1], b->period[l]), trace_ops_cap(len - s - 1, F[2], F[0], F[1], b->period[l]),
+                                          len, F[0], F[2], hlen);
+    const bool lds = hs_asm_in_lds(c.lds_bytes);
+    n_lds += lds; n_hbm += !lds;
+    put("%s[%d, %d, %d, %d, %d, %d, %d]", q ? ", " : "", c.hap_aln, c.seq, c.indel, c.snp, c.stitched, c.lds_bytes, lds ? 1 : 0);
+  }
+  o += "], \"routes_hit\": [";
+  if (n_lds) o += "\"assemble_lds\"";
+  if (n_hbm) o += n_lds ? ", \"assemble_hbm\"" : "\"assemble_hbm\"";
   o += "]}";
   if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
   return (int)o.size();

@@ -472,6 +472,17 @@ int hipstr_hmm_trace(const hipstr_batch_t* batch, int32_t n_req, const int32_t* 
  * have it computed with calc_seed_base as process_reads does. */
 int hipstr_hmm_trace_seeded(const hipstr_batch_t* batch, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                             const int32_t* req_seed, const char* const* hap_to_ref, hipstr_trace_out_t* out);
+/* hipstr_hmm_trace_seeded with a choice of where the records are assembled.  flags == 0: exactly hipstr_hmm_trace_seeded — the device
+ * decides every move, host threads replay the operation strings into the fields above.  HIPSTR_TRACE_ASSEMBLE_DEVICE: the bookkeeping half
+ * of HapAligner::retrace (HapAligner.cpp:363-571, 642-707: flank and STR sequences, SNPs, indel records, flank_ins / flank_del, hap_aln) and
+ * stitch_alignment_trace (AlignmentTraceback.cpp:7-52, 55-144: seed position, the two stitch passes, leading 'I' -> 'S', start / stop, the
+ * run-length CIGAR, the alignment string) run on the device as well, one wavefront per request; per chunk the host reads the pools' totals,
+ * checks them against cap_chars and copies every pool and every offset / scalar array once into the caller's buffers.  Output, return
+ * values and messages are those of flags == 0, byte for byte.  Any other flag bit is refused. */
+#define HIPSTR_TRACE_ASSEMBLE_DEVICE 1u
+int hipstr_hmm_trace_ex(const hipstr_batch_t* batch, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                        const int32_t* req_seed /* or NULL */, const char* const* hap_to_ref /* or NULL */,
+                        uint32_t flags, hipstr_trace_out_t* out);
 
 /*
  * Reads assigned to the MAP haplotypes and the per-sample read counts of a VCF record: the loop over the reads of

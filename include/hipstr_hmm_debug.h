@@ -56,6 +56,14 @@ int hipstr_debug_launch_plan(const hipstr_batch_t* batch, double ws_gib, char* j
  * error).  Used by tests/test_stage_routes.py. */
 int hipstr_debug_trace_plan(const hipstr_batch_t* batch, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                             const int32_t* req_seed, double ws_mib, char* json, int cap);
+/* Diagnostics (host only): the slots hipstr_hmm_trace_ex(HIPSTR_TRACE_ASSEMBLE_DEVICE) gives every request of a list (req_seed and hap_to_ref
+ * may be NULL) and the route its staging takes, from the functions the call and hs_trace_assemble use: "thresholds" ("HS_ASM_LDS": bytes of
+ * staging a wavefront keeps in LDS), "routes" (every route name), "fields" (the columns of "requests"), "requests" (per request: entries of
+ * the hap_aln slot, of each sequence piece, of the indel and SNP pair lists, of the stitched string / CIGAR / alignment string, the bytes it
+ * would stage, 1 = staged in LDS / 0 = read in HBM) and "routes_hit".  Refusals as in the call.  Same conventions as hipstr_debug_trace_plan.
+ * Used by tests/test_trace_assemble_host.py. */
+int hipstr_debug_trace_assemble_plan(const hipstr_batch_t* batch, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                                     const int32_t* req_seed, const char* const* hap_to_ref, char* json, int cap);
 /* Diagnostics (host only): the chunks hipstr_nw_align would cut a batch into under a budget of ws_mib MiB of traceback bytes (<= 0: the
  * call's own default or HIPSTR_NW_WS_MIB) and, per chunk, "p0" / "p1" (pair range), "bytes", "over_budget" (one pair larger than the
  * budget, alone), "rungs" (pairs per rows-per-lane rung of "thresholds"."rows") and "launch" ([kernel, workgroups]).  Refused sizes fail

@@ -1,4 +1,5 @@
 """Randomised parity sweep of the traceback (GPU vs oracle) over generator shapes.  usage: python tools/fuzz_trace.py [n_configs] [seed] [edges]
+[--assemble host|device]   (device: hipstr_hmm_trace_ex with HIPSTR_TRACE_ASSEMBLE_DEVICE instead of the host replay)
 "edges": 63 ... 300 reads and 1 ... 160 alleles per locus (hundreds of requests per call: every column class in one launch), reads of
 8 ... 40 bases."""
 import os, sys
@@ -8,6 +9,11 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from hipstr_amd import capi
 import util
 
+FLAGS = None
+if "--assemble" in sys.argv:
+    i = sys.argv.index("--assemble"); mode = sys.argv[i + 1]; del sys.argv[i:i + 2]
+    assert mode in ("host", "device"), mode
+    FLAGS = capi.TRACE_ASSEMBLE_DEVICE if mode == "device" else None
 n_cfg = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 4321)
 hmm = capi.load_hmm(); ora = capi.load_oracle()
@@ -48,7 +54,7 @@ for c in range(n_cfg):
         continue
     h2r = capi.hap_aln_info(ora, "oracle_", sb.ptr)
     want = capi.run_trace(ora, "oracle_", sb.ptr, rr, aa, h2r, cap=1 << 21)
-    got = capi.run_trace(hmm, "hipstr_hmm_", sb.ptr, rr, aa, h2r, cap=1 << 21)
+    got = capi.run_trace(hmm, "hipstr_hmm_", sb.ptr, rr, aa, h2r, cap=1 << 21, flags=FLAGS)
     total += len(rr)
     if got != want:
         bad += 1
