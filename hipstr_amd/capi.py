@@ -324,6 +324,11 @@ def run_trace(lib, prefix, bptr, req_read, req_allele, hap_to_ref=None, cap=1 <<
         raise RuntimeError("%strace failed rc=%d%s" % (prefix, rc, why))
     if not unpack:
         return keep
+    return unpack_trace(keep, n)
+
+
+def unpack_trace(keep, n):
+    """The arrays and pools of run_trace(..., unpack=False) as run_trace's list of dicts, one per request."""
     raws = {nm: keep[nm].raw for nm in ("hap_aln", "str_seq", "flank_seq", "snp_base", "cigar_op", "aln_str")}     # .raw copies: once per pool
     def piece(pool, off, i):
         return raws[pool][keep[off][i]:keep[off][i + 1]].decode()
@@ -655,6 +660,7 @@ def load_hmm():
     _sig(lib.hipstr_debug_cr_math, C.c_int, [C.c_int, _f64p, _f64p, C.c_int64])
     _sig(lib.hipstr_debug_cache_get, C.c_void_p, [C.c_int64])
     _sig(lib.hipstr_debug_cache_put, None, [C.c_void_p])
+    _sig(lib.hipstr_debug_cache_poison, C.c_int64, [C.c_int])
     _sig(lib.hipstr_debug_cache_stats, C.c_int, [C.POINTER(C.c_int64)])
     _sig(lib.hipstr_debug_allele_kinds, C.c_int, [C.c_void_p, C.POINTER(C.c_int64)])
     _sig(lib.hipstr_debug_stream_create, C.c_void_p, [])

@@ -1120,6 +1120,31 @@ int hipstr_debug_cr_math(int which, const double* x, double* y, int64_t n){
 }
 void* hipstr_debug_cache_get(int64_t bytes){ Ctx* c = current_ctx(); if (!c || bind(c) || bytes < 0) return NULL; return c->dev_cache.get((size_t)bytes); }
 void hipstr_debug_cache_put(void* p){ Ctx* c = current_ctx(); if (c && p) c->dev_cache.put(p); }
+// Every byte of the calling thread's context's caches that the next get() may hand out — the free blocks and each chunk's not yet carved
+// tail — set to `byte`; a block that is out is never touched.  The device is idle first: a block goes back to the cache while the last
+// copy out of it may still be queued.
+int64_t hipstr_debug_cache_poison(int byte){
+  Ctx* c = current_ctx();
+  if (!c || bind(c)) return -1;
+  if (hipDeviceSynchronize() != hipSuccess){ fail("hipstr_debug_cache_poison: hipDeviceSynchronize failed"); return -1; }
+  int64_t filled = 0;
+  BlockCache* bc[2] = { &c->dev_cache, &c->pin_cache };
+  for (int k = 0; k < 2; k++){
+    std::lock_guard<std::mutex> g(bc[k]->m);
+    auto fill = [&](void* p, size_t n) -> bool {
+      if (n == 0) return true;
+      if (bc[k]->pinned) memset(p, byte, n);
+      else if (hipMemset(p, byte, n) != hipSuccess) return false;
+      filled += (int64_t)n;
+      return true;
+    };
+    for (const auto& fb : bc[k]->free_) if (!fill(fb.second, fb.first)){ fail("hipstr_debug_cache_poison: hipMemset failed"); return -1; }
+    for (const BlockCache::Chunk& ch : bc[k]->chunks)
+      if (!fill(ch.base + ch.used, ch.size - ch.used)){ fail("hipstr_debug_cache_poison: hipMemset failed"); return -1; }
+  }
+  if (hipDeviceSynchronize() != hipSuccess){ fail("hipstr_debug_cache_poison: hipDeviceSynchronize failed"); return -1; }
+  return filled;
+}
 int hipstr_debug_cache_stats(int64_t out[12]){
   Ctx* c = current_ctx();
   if (!c) return 1;

@@ -104,6 +104,12 @@ int hipstr_debug_cache_stats(int64_t out[12]);
 /* Diagnostics (tests): one block from / back to the calling thread's device block cache — what every upload does dozens of times. */
 void* hipstr_debug_cache_get(int64_t bytes);
 void hipstr_debug_cache_put(void* block);
+/* Diagnostics (tests): the memory the calling thread's device context's block caches may hand out next — every FREE block and every chunk's not
+ * yet carved tail, device (hipMemset) and pinned (memset) — filled with `byte`, after the device has gone idle; a block that is out is never
+ * touched.  The caches never clear a block, so a kernel that reads a word of its workspace it did not write gets whatever the block held
+ * before: after this call that is `byte` repeated, and results that change with `byte` show the read.  Returns the bytes filled (-1 on
+ * error, hipstr_last_error()).  Used by tests/test_poison_gpu.py. */
+int64_t hipstr_debug_cache_poison(int byte);
 /* Diagnostics (tests): the correctly rounded exp (which = 0) / log (1) of hipstr_amd/csrc/cr_math.h evaluated ON THE DEVICE, element by
  * element — the functions the posterior, genotype and EM kernels use in place of the device's own exp / log so that they reproduce
  * the host libm's bits. */

@@ -72,6 +72,8 @@ def restate(pb, LL, map_gt, seed, reverse=None, pool_index=None, pool_off=None, 
                 continue
             s = int(pb.samp_off[l]) + int(a["sample_label"][r])        # :1085
             ha, hb = int(map_gt[s][0]), int(map_gt[s][1])              # :1088-1089
+            if ha < 0 or hb < 0:                                       # no MAP pair (every diplotype -inf): the reference would index haplotype -1
+                continue                                               # here (in Python: silently the LAST allele); the library skips the sample's reads
             x1 = LOG_ONE_HALF + p1[r] + row[ha]; x2 = LOG_ONE_HALF + p2[r] + row[hb]
             total = _lse2(x1, x2, exp, log)                            # :1090
             lpo = LOG_ONE_HALF + p1[r] + row[ha] - total               # :1091
@@ -199,10 +201,13 @@ def test_chained_from_device_alignments(hmm, oracle):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2. wavefront / workgroup edges
-@pytest.mark.parametrize("sizes", [(0, 1, 63, 64, 65, 257), (0, 1, 63, 64, 65, 256)], ids=["workgroup_per_unit", "wavefront_per_unit"])
-def test_wavefront_and_workgroup_edges(hmm, oracle, sizes):
+EDGE_SIZES = {"workgroup_per_unit": (0, 1, 63, 64, 65, 257), "wavefront_per_unit": (0, 1, 63, 64, 65, 256)}
+
+
+def edges_inputs(sizes):
     """One locus, A = 3, samples on either side of the 64-lane and 256-thread chunks (257 reads: a unit has the workgroup; 256: the
-    launch gives every unit one wavefront); seeds < 0 scattered through, a sample whose reads are all skipped, skipped first and last reads."""
+    launch gives every unit one wavefront); seeds < 0 scattered through, a sample whose reads are all skipped, skipped first and last reads.
+    -> (PostBatch, flat LL, seed, reverse)."""
     rng = np.random.default_rng(5)
     samples = []
     for sz in sizes:
@@ -222,6 +227,12 @@ def test_wavefront_and_workgroup_edges(hmm, oracle, sizes):
     seed[off[3]] = -1; seed[off[4] - 1] = -1                                         # first and last read of the 64-read sample
     seed[off[4]] = -1; seed[off[6] - 1] = -1                                         # first of the 65-read sample, last of the largest
     reverse = rng.integers(0, 2, off[-1]).astype(np.uint8)
+    return pb, LL, seed, reverse
+
+
+@pytest.mark.parametrize("sizes", list(EDGE_SIZES.values()), ids=list(EDGE_SIZES))
+def test_wavefront_and_workgroup_edges(hmm, oracle, sizes):
+    pb, LL, seed, reverse = edges_inputs(sizes)
     mg = oracle_map(oracle, pb)
     for s in (3, 4, 5):
         assert sorted(mg[s]) == [0, 2]
@@ -229,6 +240,53 @@ def test_wavefront_and_workgroup_edges(hmm, oracle, sizes):
     want = check(got, pb, LL, mg, seed, "edges %r" % (sizes,), reverse=reverse)
     assert want["n_aligned"][0] == 0 and want["n_aligned"][2] == 0 and got["phase1_reads"][2] == 0 and got["phase2_reads"][2] == 0
     assert want["uniq_one"].sum() > 0 and want["uniq_two"].sum() > 0 and want["rv_uniq_one"].sum() > 0
+
+
+@pytest.mark.parametrize("n_big", [40, 257], ids=["wavefront_per_unit", "workgroup_per_unit"])
+def test_a_sample_without_a_map_pair_is_skipped(hmm, oracle, n_big):
+    """Three samples of one locus, A = 3; every likelihood of the middle one is -inf, so no diplotype of it is finite and its MAP pair is
+    (-1, -1) (hs_assign_kernel's no_map branch).  Its reads come out as skipped reads do and its counts are zero; its neighbours (one padded to 257
+    reads for the workgroup-per-unit launch) and the request list come out as from the batch without it."""
+    rng = np.random.default_rng(17)
+    def sample(n, h1, h2):
+        out = []
+        for i in range(n):
+            row = list(-25 - 5 * rng.random(3)); row[h1 if i % 2 == 0 else h2] = -1 - rng.random()
+            p = -rng.random(2) if i % 3 else (-0.3, -0.3)
+            out.append((float(p[0]), float(p[1]), [float(x) for x in row]))
+        return out
+    first, last = sample(9, 0, 2), sample(n_big, 1, 1)
+    middle = [(-0.2, -0.6, [-np.inf] * 3) for _ in range(5)]
+    pb, LL = make_pb([(3, [first, middle, last])])
+    n = 9 + 5 + n_big
+    seed = np.full(n, 4, np.int32); seed[[2, 20]] = -1
+    reverse = (np.arange(n) % 3 == 0).astype(np.uint8)
+    pool = (np.arange(n) % 6).astype(np.int32); pool[9:14] = [5, 0, 3, 3, 1]         # the middle sample shares its neighbours' pools
+    pool_off = np.array([0, 6], np.int32)
+    mg = oracle_map(oracle, pb)
+    assert tuple(mg[1]) == (-1, -1) and sorted(mg[0]) == [0, 2] and tuple(mg[2]) == (1, 1)
+    assert capi.post_plan(hmm, pb)["units"][2][1] == n_big
+    got = capi.run_assign(hmm, pb, seed, reverse=reverse, pool_index=pool, pool_off=pool_off)
+    want = check(got, pb, LL, mg, seed, "no MAP pair, %d reads beside it" % n_big, requests=True, reverse=reverse, pool_index=pool, pool_off=pool_off)
+    mid = slice(9, 14)
+    for k in ("best_hap", "read_strand", "read_req"):
+        assert np.all(got[k][mid] == -1) and np.all(want[k][mid] == -1), k
+    assert np.all(np.isnan(got["log_phase_one"][mid]))                               # untouched: what run_assign put there
+    for k in capi.ASSIGN_COUNTERS:
+        assert got[k][1] == 0, k
+    assert got["phase1_reads"][1] == 0 and got["phase2_reads"][1] == 0
+    keep = np.r_[0:9, 14:n]
+    pb2, _ = make_pb([(3, [first, last])])
+    alone = capi.run_assign(hmm, pb2, seed[keep], reverse=reverse[keep], pool_index=pool[keep], pool_off=pool_off)
+    assert alone["rc"] == 0 and got["n_req"] == alone["n_req"] > 0
+    for k in ("best_hap", "read_strand", "read_req"):
+        assert np.array_equal(got[k][keep], alone[k]), k
+    assert np.array_equal(got["log_phase_one"][keep].view(np.uint64), alone["log_phase_one"].view(np.uint64))
+    for k in capi.ASSIGN_COUNTERS:
+        assert np.array_equal(got[k][[0, 2]], alone[k]), k
+    for k in ("phase1_reads", "phase2_reads"):
+        assert np.array_equal(got[k][[0, 2]].view(np.uint64), alone[k].view(np.uint64)), k
+    assert np.array_equal(got["req_allele"], alone["req_allele"]) and np.array_equal(got["req_read"], alone["req_read"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3. every branch of :1096-1109
@@ -318,8 +376,9 @@ def test_rules_disagree_on_in_tolerance_heterozygous_reads(hmm, branch_batch):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 4. request list
-@pytest.fixture(scope="module")
-def request_batch(oracle):
+def request_inputs(oracle):
+    """Two loci whose request tables are a direct one (locus 0) and a hashed one (locus 1).
+    -> (PostBatch, flat LL, the oracle's MAP pairs, seed, pool_index, pool_off)."""
     rng = np.random.default_rng(9)
     fav = lambda A, h: [(-1.0 if k == h else -30.0) - float(rng.random()) for k in range(A)]
     # locus 0, A = 3: three samples that settle on haplotypes 0, 1 and {0, 2}; the pools are shared across the samples
@@ -334,6 +393,11 @@ def request_batch(oracle):
     n = int(pb.a["read_off"][-1])
     seed = np.full(n, 3, np.int32); seed[[1, 13, 15, 100]] = -1
     return pb, LL, oracle_map(oracle, pb), seed, np.array(pool0 + pool1, np.int32), np.array([0, 5, 1005], np.int32)
+
+
+@pytest.fixture(scope="module")
+def request_batch(oracle):
+    return request_inputs(oracle)
 
 
 @pytest.mark.parametrize("rule", [capi.ASSIGN_VCF, capi.ASSIGN_RETRACE])
