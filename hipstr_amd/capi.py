@@ -93,6 +93,26 @@ class HipstrEmBatch(C.Structure):
                 ("min_ll_abs_change", C.c_double), ("min_ll_frac_change", C.c_double)]
 
 
+def _em_batch(period, n_samples, read_off, sample_label, num_bps, log_p1, log_p2, haploid=None, ref_allele=0, max_iter=100,
+              min_ll_abs_change=0.01, min_ll_frac_change=0.001):
+    """(HipstrEmBatch, the arrays it points into, loci)."""
+    i32 = lambda x: np.ascontiguousarray(np.asarray(x, np.int32)); f64 = lambda x: np.ascontiguousarray(np.asarray(x, np.float64))
+    a = dict(period=i32(period), n_samples=i32(n_samples), read_off=i32(read_off), sample_label=i32(sample_label), num_bps=i32(num_bps),
+             log_p1=f64(log_p1), log_p2=f64(log_p2), haploid=None if haploid is None else np.ascontiguousarray(np.asarray(haploid, np.uint8)))
+    nl = len(a["period"])
+    eb = HipstrEmBatch(nl, a["period"].ctypes.data_as(_i32p), _ptr(a["haploid"], _u8p), a["n_samples"].ctypes.data_as(_i32p),
+                       a["read_off"].ctypes.data_as(_i32p), a["sample_label"].ctypes.data_as(_i32p), a["num_bps"].ctypes.data_as(_i32p),
+                       a["log_p1"].ctypes.data_as(_f64p), a["log_p2"].ctypes.data_as(_f64p), ref_allele, max_iter, min_ll_abs_change, min_ll_frac_change)
+    return eb, a, nl
+
+
+def em_plan(lib, **kw):
+    """The launch decisions hipstr_em_train takes for run_em's keyword arguments (host only: hipstr_debug_em_plan) as a dict; a batch the
+    call refuses raises with the call's message."""
+    eb, a, nl = _em_batch(**kw)
+    return _plan_json(lib, "hipstr_debug_em_plan", lambda buf, cap: lib.hipstr_debug_em_plan(C.byref(eb), buf, cap))
+
+
 def run_em(lib, prefix, period, n_samples, read_off, sample_label, num_bps, log_p1, log_p2, haploid=None, ref_allele=0, max_iter=100,
            min_ll_abs_change=0.01, min_ll_frac_change=0.001):
     """<prefix>em_train on a batch of loci -> (trained[n_loci] bool, stutter[n_loci, 6], n_iter[n_loci], final_ll[n_loci])."""
@@ -671,6 +691,7 @@ def load_hmm():
     _sig(lib.hipstr_debug_trace_assemble_plan, C.c_int, [_BP, C.c_int32, _i32p, _i32p, _i32p, C.POINTER(C.c_char_p), C.c_char_p, C.c_int])
     _sig(lib.hipstr_debug_nw_plan, C.c_int, [C.POINTER(HipstrNwBatch), C.c_double, C.c_char_p, C.c_int])
     _sig(lib.hipstr_debug_post_plan, C.c_int, [_PBP, C.c_char_p, C.c_int])
+    _sig(lib.hipstr_debug_em_plan, C.c_int, [C.POINTER(HipstrEmBatch), C.c_char_p, C.c_int])
     return lib
 
 

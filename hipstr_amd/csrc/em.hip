@@ -31,7 +31,9 @@
 #include <unistd.h>
 
 #include "../../include/hipstr_hmm.h"
+#include "../../include/hipstr_hmm_debug.h"
 #include "post_layout.h"
+#include "em_layout.h"
 #include "prep.h"
 #include "api_internal.h"
 #include "cr_math.h"
@@ -97,10 +99,7 @@ __device__ __forceinline__ int em_locus(const hs_em_dev_t& d){
   if (d.list) return ((int)blockIdx.x < d.counts[0]) ? d.list[blockIdx.x] : -1;
   return d.active[blockIdx.x] ? (int)blockIdx.x : -1;
 }
-#define HS_EM_PARTS 8          // workgroups per locus in the two big M-step reductions
-#define HS_EM_TILE 2048         // rows of a slice whose live rows are listed at a time (hs_em_mstep_part)
-#define HS_EM_CHUNK 32          // positions of the allele-frequency scans per round of prepared exponentials (em_gt_priors)
-#define HS_EM_MAXA_LDS 64      // alleles whose chains run side by side (lanes of the first wavefront); more alleles: several sweeps
+// (the sizes every kernel below is cut by — HS_EM_PARTS, HS_EM_TILE, HS_EM_CHUNK, HS_EM_MAXA_LDS ... — and the decisions taken from them: em_layout.h)
 
 namespace {
 
@@ -222,8 +221,8 @@ __device__ void em_gt_priors(const hs_em_dev_t& d, const hs_em_locus_t& L, int t
   // a thread per row adds them in allele order and takes the logarithm.
   extern __shared__ double hs_em_dyn[];
   {
-    const int Ap = A | 1;                                // odd row stride: the per-row walks of neighbouring threads fall into different banks
-    const int tile_rows = min(256, (int)((2*HS_EM_CHUNK*HS_EM_MAXA_LDS) / Ap));
+    const int Ap = hs_em_row_stride(A);                  // odd row stride: the per-row walks of neighbouring threads fall into different banks
+    const int tile_rows = hs_em_row_tile_rows(A);
     __shared__ double s_rm[256];
     __shared__ int s_fm[256];
     if (tile_rows >= 1){
@@ -242,7 +241,7 @@ __device__ void em_gt_priors(const hs_em_dev_t& d, const hs_em_locus_t& L, int t
         for (int e = tid; e < nr*A; e += 256){
           const int rr = e / A, j = e - rr*A;
           const double x_ = hs_em_dyn[rr*Ap + j] - s_rm[rr];
-          hs_em_dyn[rr*Ap + j] = (j > s_fm[rr] && x_ < -37.43) ? 0.0 : cr_exp(x_);
+          hs_em_dyn[rr*Ap + j] = (j > s_fm[rr] && x_ < HS_EM_TERM_FLOOR) ? 0.0 : cr_exp(x_);
         }
         __syncthreads();
         if (tid < nr){
@@ -284,9 +283,9 @@ __device__ void em_gt_priors(const hs_em_dev_t& d, const hs_em_locus_t& L, int t
   constexpr int NE = (CH*HS_EM_MAXA_LDS + 255)/256;      // a thread's share of a chunk's (position, allele) pairs
   double* const Ebuf = hs_em_dyn;                         // [CH][na]: the maximum in front of the step, then the step's exponential
   double* const Vbuf = hs_em_dyn + CH*HS_EM_MAXA_LDS;    // [CH][na]: the values (the walks are dependent chains and must not wait for L2 at every step)
-  const int64_t n1 = S, n2 = (int64_t)S*A, ntot = n1 + n2;
+  const int64_t n1 = S, ntot = hs_em_chain_len(S, A);
   for (int a0 = 0; a0 < A; a0 += HS_EM_MAXA_LDS){
-    const int na = min(HS_EM_MAXA_LDS, A - a0);
+    const int na = hs_em_sweep_alleles(A, a0);
     double m = -DBL_MAX/2, t = 0.0;                      // lane a - a0 < na of the first wavefront: the chain's state
     // a thread's pairs are the same in every chunk: position i (of the chunk) and allele al of pair e = tid + 256 q
     int pi[NE], pidx[NE];
@@ -294,7 +293,7 @@ __device__ void em_gt_priors(const hs_em_dev_t& d, const hs_em_locus_t& L, int t
     for (int q = 0; q < NE; q++){ const int e = tid + 256*q; const int i = e / na; pi[q] = i; pidx[q] = i*na + (e - i*na); }
     double nxt[NE];
     auto fetch = [&](int64_t c0){                        // this thread's share of the chunk at c0: requested here, used after the next barrier but one
-      const int cn = (int)min((int64_t)CH, ntot - c0);
+      const int cn = hs_em_chunk_len(ntot, c0);
 #pragma unroll
       for (int q = 0; q < NE; q++) if (pi[q] < cn){
         const int64_t ci = c0 + pi[q]; const int a = a0 + (pidx[q] - pi[q]*na);
@@ -303,7 +302,7 @@ __device__ void em_gt_priors(const hs_em_dev_t& d, const hs_em_locus_t& L, int t
     };
     fetch(0);
     for (int64_t c0 = 0; c0 < ntot; c0 += CH){
-      const int cn = (int)min((int64_t)CH, ntot - c0);
+      const int cn = hs_em_chunk_len(ntot, c0);
 #pragma unroll
       for (int q = 0; q < NE; q++) if (pi[q] < cn) Vbuf[pidx[q]] = nxt[q];
       __syncthreads();
@@ -335,7 +334,7 @@ __device__ void em_gt_priors(const hs_em_dev_t& d, const hs_em_locus_t& L, int t
       for (int q = 0; q < NE; q++) if (pi[q] < cn){      // (3)
         const double lv = Vbuf[pidx[q]], mb = Ebuf[pidx[q]];
         double ex;
-        if (lv <= mb){ const double x_ = lv - mb; ex = (x_ < -37.43) ? -1.0 : cr_exp(x_); }       // -1: "below 2^-54" (see the walk)
+        if (lv <= mb){ const double x_ = lv - mb; ex = (x_ < HS_EM_TERM_FLOOR) ? -1.0 : cr_exp(x_); }       // -1: "below 2^-54" (see the walk)
         else ex = cr_exp(mb - lv);                        // the factor of the total gathered under the old maximum
         Ebuf[pidx[q]] = ex;
       }
@@ -399,8 +398,8 @@ __global__ void __launch_bounds__(256) hs_em_gmax(const hs_em_dev_t* __restrict_
   const int A = L.A, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const double* post = d.post + L.post_off;
   double* g = d.gmax + L.sa_off;
-  if (A <= 64){
-    for (int s_ = w; s_ < L.S; s_ += 4){
+  if (hs_em_gmax_wave(A)){
+    for (int s_ = w; s_ < L.S; s_ += HS_EM_GMAX_WAVES){
       const double* gp = post + (int64_t)s_*A*A;
       double colmax = -DBL_MAX, mine = -DBL_MAX;              // lane j: max over a of gp[a][j];  lane a: max over j of gp[a][j]
       for (int a = 0; a < A; a++){
@@ -450,7 +449,7 @@ __global__ void __launch_bounds__(256) hs_em_mstep_part(const hs_em_dev_t* __res
   // (a, j) and phase 1 of (j, a) — feed the same two vectors (the category and diffs vector of (r, a), hs_em_fill), so the
   // seven-way choice is made once per (r, a) and the walk itself is branch-free.
   const int total = L.R*A;
-  const int x0 = (int)((int64_t)total*k_part/HS_EM_PARTS), x1 = (int)((int64_t)total*(k_part + 1)/HS_EM_PARTS);
+  const int x0 = hs_em_slice_begin(total, k_part), x1 = hs_em_slice_begin(total, k_part + 1);
   // Round 5: most (read, source allele) rows cannot matter and are recognised without walking them.  Every term of a row is
   //   f = log P(diplotype | sample) + log P(phase | read, diplotype)  <=  G + c,   G = gmax[sample][a] (hs_em_gmax: the sample's best diplotype
   // that holds allele a), c = 4e-6 (the phase term is <= 0 up to the float log-sum-exp's approximation error: its bit-trick log dips to
@@ -461,7 +460,7 @@ __global__ void __launch_bounds__(256) hs_em_mstep_part(const hs_em_dev_t* __res
   // into a list per tile of HS_EM_TILE rows, so that the walk keeps every lane busy.  Same maxima, same sums (of float terms, in double:
   // exact in any order).
   const double* gmax = d.gmax + L.sa_off;
-  constexpr double PH_C = 4.0e-6;
+  constexpr double PH_C = HS_EM_PRUNE_C;
   __shared__ int s_rows[HS_EM_TILE];
   __shared__ int s_cnt;
   for (int t0 = x0; t0 < x1; t0 += HS_EM_TILE){
@@ -608,9 +607,9 @@ __device__ __forceinline__ double em_lse2_exact(double a, double b){      // mat
 }
 
 // init_stutter_model (:59-62) and the loop's starting state, a thread per locus
-__global__ void __launch_bounds__(256) hs_em_init(const hs_em_dev_t* __restrict__ dp){
+__global__ void __launch_bounds__(HS_EM_INIT_THREADS) hs_em_init(const hs_em_dev_t* __restrict__ dp){
   const hs_em_dev_t& d = *dp;
-  const int l = blockIdx.x*256 + threadIdx.x;
+  const int l = blockIdx.x*HS_EM_INIT_THREADS + threadIdx.x;
   if (l >= d.n_loci) return;
   const double init[6] = { 0.9, 0.1, 0.1, 0.8, 0.01, 0.01 };
   for (int k = 0; k < 6; k++) d.sp[6*l + k] = init[k];
@@ -664,20 +663,20 @@ __global__ void __launch_bounds__(64) hs_em_finish(const hs_em_dev_t* __restrict
 }
 
 // The loci still training, ascending, and where their (locus, sample) units go: one workgroup, an exclusive scan over the loci in chunks.
-__global__ void __launch_bounds__(1024) hs_em_compact(const hs_em_dev_t* __restrict__ dp){
+__global__ void __launch_bounds__(HS_EM_COMPACT_THREADS) hs_em_compact(const hs_em_dev_t* __restrict__ dp){
   const hs_em_dev_t& d = *dp;
   const int tid = threadIdx.x;
-  __shared__ int sc_n[1024], sc_u[1024];
+  __shared__ int sc_n[HS_EM_COMPACT_THREADS], sc_u[HS_EM_COMPACT_THREADS];
   __shared__ int base_n, base_u;
   if (tid == 0){ base_n = 0; base_u = 0; }
   __syncthreads();
-  for (int l0 = 0; l0 < d.n_loci; l0 += 1024){
+  for (int l0 = 0; l0 < d.n_loci; l0 += HS_EM_COMPACT_THREADS){
     const int l = l0 + tid;
     const int on = (l < d.n_loci && d.state[l] == 0) ? 1 : 0;
     const int nu = on ? d.loci[l].S : 0;
     sc_n[tid] = on; sc_u[tid] = nu;
     __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1){               // inclusive scan (Hillis-Steele)
+    for (int off = 1; off < HS_EM_COMPACT_THREADS; off <<= 1){               // inclusive scan (Hillis-Steele)
       const int a = (tid >= off) ? sc_n[tid - off] : 0, b = (tid >= off) ? sc_u[tid - off] : 0;
       __syncthreads();
       sc_n[tid] += a; sc_u[tid] += b;
@@ -688,17 +687,17 @@ __global__ void __launch_bounds__(1024) hs_em_compact(const hs_em_dev_t* __restr
       d.next_unit_begin[l] = base_u + sc_u[tid] - nu;
     }
     __syncthreads();
-    if (tid == 1023){ base_n += sc_n[1023]; base_u += sc_u[1023]; }
+    if (tid == HS_EM_COMPACT_THREADS - 1){ base_n += sc_n[HS_EM_COMPACT_THREADS - 1]; base_u += sc_u[HS_EM_COMPACT_THREADS - 1]; }
     __syncthreads();
   }
   if (tid == 0){ d.next_counts[0] = base_n; d.next_counts[1] = base_u; }
 }
-__global__ void __launch_bounds__(256) hs_em_units(const hs_em_dev_t* __restrict__ dp){
+__global__ void __launch_bounds__(HS_EM_UNITS_THREADS) hs_em_units(const hs_em_dev_t* __restrict__ dp){
   const hs_em_dev_t& d = *dp;
   if ((int)blockIdx.x >= d.next_counts[0]) return;
   const int l = d.next_list[blockIdx.x];
   const int S = d.loci[l].S, b = d.next_unit_begin[l], u0 = d.unit_first[l];
-  for (int s = threadIdx.x; s < S; s += 256) d.next_units[b + s] = u0 + s;
+  for (int s = threadIdx.x; s < S; s += HS_EM_UNITS_THREADS) d.next_units[b + s] = u0 + s;
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
@@ -751,35 +750,33 @@ double h_fast_lse2(double a, double b, double thr){
 }
 double h_lse2(double a, double b){ return a > b ? a + log(1 + exp(b - a)) : b + log(1 + exp(a - b)); }       // mathops.cpp:52-57
 
-}  // namespace
+// |effective difference| of an observed size against an allele size, as hs_em_fill forms it (the index into the table of integer
+// logarithms), in 64 bits: the size difference itself may not fit an int
+inline int64_t em_abs_eff(int64_t ob, int64_t allele, int period){
+  const int64_t bd = ob - allele;
+  const int64_t eff = (bd % period != 0) ? bd - bd/period : bd/period;
+  return eff < 0 ? -eff : eff;
+}
 
-extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
-  hipstr::ApiTimer prof_t(hipstr::PB_EM_TRAIN);
-  using hipstr::api_fail;
-  if (!eb || !trained || !stutter || !n_iter || !final_ll) return api_fail("null argument");
-  const int nl = eb->n_loci;
-  if (nl < 0) return api_fail("negative locus count");
-  if (nl == 0) return 0;
-  hipstr::ApiTables T;
-  if (hipstr::api_device_tables(&T)) return 1;
-  const hipstr::HostTables& HT = hipstr::host_tables();
-  const int n_reads = eb->read_off[nl];
-  const bool timing = getenv("HIPSTR_TIMING") != NULL;
-  const bool host_loop = getenv("HIPSTR_EM_HOST_LOOP") && atoi(getenv("HIPSTR_EM_HOST_LOOP")) != 0;       // the round-4 loop: host libm, every locus in every round
-  auto t_prev = std::chrono::steady_clock::now();
-  double t_gpu = 0.0, t_host = 0.0;
-  auto lap = [&](const char* what, double* into){
-    const auto now = std::chrono::steady_clock::now();
-    const double dt = std::chrono::duration<double>(now - t_prev).count();
-    t_prev = now;
-    if (into) *into += dt; else if (timing) fprintf(stderr, "hipstr_em_train: %s %.3f ms\n", what, 1e3*dt);
-  };
-
-  // ---- alleles, read -> allele index, initial allele frequencies (em_stutter_genotyper.h:55-100, .cpp:10-20)
-  std::vector<hs_em_locus_t> loci(nl);
+// What hipstr_em_train knows about a batch before the first device call (em_stutter_genotyper.h:55-100, .cpp:10-20): per locus the allele
+// sizes, the reads' allele indices, the initial allele frequencies and its offsets into the device arrays; the (locus, sample) units of the
+// posterior kernel.  Every refusal of an input is decided here — hipstr_debug_em_plan runs the same function.
+struct EmPrep {
+  std::vector<hs_em_locus_t> loci;
   std::vector<hs_post_unit_t> units;
-  std::vector<int32_t> bps, obs(n_reads), unit_locus;
+  std::vector<int32_t> bps, obs, unit_locus;
   std::vector<double> gtp;
+  int64_t post_off = 0, ll_off = 0, prior_off = 0, sa_off = 0; int samp_off = 0;
+};
+int em_prepare(const hipstr_em_batch_t* eb, bool host_loop, EmPrep& P){
+  using hipstr::api_fail;
+  const int nl = eb->n_loci;
+  const int n_reads = eb->read_off[nl];
+  const int64_t n_logs = (int64_t)hipstr::host_tables().int_log.size();      // entries of the table of integer logarithms (mathops.cpp:13-21)
+  std::vector<hs_em_locus_t>& loci = P.loci; std::vector<hs_post_unit_t>& units = P.units;
+  std::vector<int32_t>& bps = P.bps; std::vector<int32_t>& obs = P.obs; std::vector<int32_t>& unit_locus = P.unit_locus;
+  std::vector<double>& gtp = P.gtp;
+  loci.assign(nl, hs_em_locus_t()); obs.assign(n_reads, 0);
   // per locus, independent of the others (host threads): allele sizes, the reads' allele indices, the initial allele frequencies
   struct LocusPrep { std::vector<int> sizes; std::vector<double> gtp; std::vector<int32_t> reads_of_sample; const char* err = NULL; };
   std::vector<LocusPrep> lp(nl);
@@ -794,7 +791,19 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
     sizes.erase(std::unique(sizes.begin(), sizes.end()), sizes.end());
     sizes.insert(sizes.begin(), eb->ref_allele);
     const int A = (int)sizes.size();
-    if (A + 1 >= 10000){ Q.err = "too many distinct allele sizes"; return; }
+    if (A + 1 >= n_logs){ Q.err = "too many distinct allele sizes"; return; }
+    // Every (observed size, allele) pair looks its effective difference up in the table of integer logarithms (hs_em_fill; the reference
+    // does the same, em_stutter_genotyper.cpp:76-104 with mathops.cpp:13-21): beyond the table there is no answer.  |eff| <= |difference|,
+    // so a span of the sizes (the reference allele included, observed or not) below the table's length settles it with one subtraction.
+    {
+      int64_t lo = sizes[0], hi = sizes[0];
+      if (A > 1){ lo = std::min<int64_t>(lo, sizes[1]); hi = std::max<int64_t>(hi, sizes[A-1]); }
+      if (hi - lo >= n_logs){
+        for (int i = 0; i < A && !Q.err; i++) for (int j = i + 1; j < A; j++)       // (|eff| is the same either way round)
+          if (em_abs_eff(sizes[j], sizes[i], eb->period[l]) >= n_logs){ Q.err = "allele sizes too far apart (effective difference beyond the table of integer logarithms, mathops.cpp:13-21)"; break; }
+        if (Q.err) return;
+      }
+    }
     Q.reads_of_sample.assign(S, 0);
     int prev = 0;
     for (int r = r0; r < r1; r++){
@@ -837,7 +846,41 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
     }
     post_off += (int64_t)S*A*A; ll_off += (int64_t)R*A; prior_off += (int64_t)A*A; samp_off += S; sa_off += (int64_t)S*A;
   }
-  std::vector<LocusPrep>().swap(lp);
+  P.post_off = post_off; P.ll_off = ll_off; P.prior_off = prior_off; P.sa_off = sa_off; P.samp_off = samp_off;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
+  hipstr::ApiTimer prof_t(hipstr::PB_EM_TRAIN);
+  using hipstr::api_fail;
+  if (!eb || !trained || !stutter || !n_iter || !final_ll) return api_fail("null argument");
+  const int nl = eb->n_loci;
+  if (nl < 0) return api_fail("negative locus count");
+  if (nl == 0) return 0;
+  hipstr::ApiTables T;
+  if (hipstr::api_device_tables(&T)) return 1;
+  const hipstr::HostTables& HT = hipstr::host_tables();
+  const int n_reads = eb->read_off[nl];
+  const bool timing = getenv("HIPSTR_TIMING") != NULL;
+  const bool host_loop = getenv("HIPSTR_EM_HOST_LOOP") && atoi(getenv("HIPSTR_EM_HOST_LOOP")) != 0;       // the round-4 loop: host libm, every locus in every round
+  auto t_prev = std::chrono::steady_clock::now();
+  double t_gpu = 0.0, t_host = 0.0;
+  auto lap = [&](const char* what, double* into){
+    const auto now = std::chrono::steady_clock::now();
+    const double dt = std::chrono::duration<double>(now - t_prev).count();
+    t_prev = now;
+    if (into) *into += dt; else if (timing) fprintf(stderr, "hipstr_em_train: %s %.3f ms\n", what, 1e3*dt);
+  };
+
+  // ---- alleles, read -> allele index, initial allele frequencies, (locus, sample) units; the refusals
+  EmPrep P;
+  if (em_prepare(eb, host_loop, P)) return 1;
+  std::vector<hs_em_locus_t>& loci = P.loci; std::vector<hs_post_unit_t>& units = P.units;
+  std::vector<int32_t>& bps = P.bps; std::vector<int32_t>& obs = P.obs; std::vector<int32_t>& unit_locus = P.unit_locus;
+  std::vector<double>& gtp = P.gtp;
+  const int64_t post_off = P.post_off, ll_off = P.ll_off, prior_off = P.prior_off, sa_off = P.sa_off; const int samp_off = P.samp_off;
   lap("alleles and units", NULL);
   // ---- device state
   EmBufs dev;
@@ -910,21 +953,21 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
       }
     };
     lap("device-loop state", NULL);
-    const unsigned g_loci = (unsigned)((nl + 255)/256);
+    const unsigned g_loci = hs_em_init_blocks(nl);
     // the starting state, and the lists of round 0 (written through block 1, whose "next" set is block 0's current one)
-    hipLaunchKernelGGL(hs_em_init, dim3(g_loci), dim3(256), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
-    hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(1024), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
-    hipLaunchKernelGGL(hs_em_units, dim3(nl), dim3(256), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
+    hipLaunchKernelGGL(hs_em_init, dim3(g_loci), dim3(HS_EM_INIT_THREADS), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
+    hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(HS_EM_COMPACT_THREADS), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
+    hipLaunchKernelGGL(hs_em_units, dim3(nl), dim3(HS_EM_UNITS_THREADS), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
     unsigned bound_l = (unsigned)nl, bound_u = (unsigned)n_units;
     int rounds = 0;
-    for (int r = 0; r <= eb->max_iter + 1; r++){
+    for (int r = 0; r <= hs_em_last_round(eb->max_iter); r++){
       const hs_em_dev_t* H = d_hb + (r & 1); const hs_post_dev_t* PH = d_pb + (r & 1);
       if (bound_l > 0){
         hipLaunchKernelGGL(hs_em_fill, dim3(bound_l), dim3(256), 0, T.stream, H);
         hipLaunchKernelGGL(hs_posterior_kernel, dim3(std::max(1u, bound_u)), dim3(256), 0, T.stream, PH);
         EM_HIP(hipEventRecord(side.ev_fork, T.stream));                  // posteriors are in place: the allele-frequency scans branch off
         EM_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));        // (beside the M-step on the side stream: 0.51 against 0.57 s per 10 000 loci in series, profiles/r05_notes.md)
-        hipLaunchKernelGGL(hs_em_gt_priors, dim3(bound_l), dim3(256), 2*HS_EM_CHUNK*HS_EM_MAXA_LDS*sizeof(double), side.stream, H);
+        hipLaunchKernelGGL(hs_em_gt_priors, dim3(bound_l), dim3(HS_EM_THREADS), hs_em_lds_doubles()*sizeof(double), side.stream, H);
         EM_HIP(hipEventRecord(side.ev_join, side.stream));
         hipLaunchKernelGGL(hs_em_gmax, dim3(bound_l), dim3(256), 0, T.stream, H);
         hipLaunchKernelGGL(hs_em_mstep_part<0>, dim3(bound_l, HS_EM_PARTS), dim3(256), 0, T.stream, H, (const double*)NULL);
@@ -932,8 +975,8 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
         hipLaunchKernelGGL(hs_em_mstep_part<1>, dim3(bound_l, HS_EM_PARTS), dim3(256), 0, T.stream, H, (const double*)d_keep);
         hipLaunchKernelGGL(hs_em_finish, dim3(bound_l), dim3(64), 0, T.stream, H, (const double*)d_keep);
         EM_HIP(hipStreamWaitEvent(T.stream, side.ev_join, 0));            // the next round's hs_em_fill reads the new allele frequencies
-        hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(1024), 0, T.stream, H);
-        hipLaunchKernelGGL(hs_em_units, dim3(bound_l), dim3(256), 0, T.stream, H);
+        hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(HS_EM_COMPACT_THREADS), 0, T.stream, H);
+        hipLaunchKernelGGL(hs_em_units, dim3(bound_l), dim3(HS_EM_UNITS_THREADS), 0, T.stream, H);
         rounds++;
       }
       EM_HIP(hipMemcpyAsync(pin.p + 2*(r % NBUF), d_counts[(r & 1) ^ 1], 2*sizeof(int32_t), hipMemcpyDeviceToHost, T.stream));
@@ -995,7 +1038,7 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
     hipLaunchKernelGGL(hs_posterior_kernel, dim3((unsigned)units.size()), dim3(256), 0, T.stream, (const hs_post_dev_t*)d_ph);
     EM_HIP(hipEventRecord(side.ev_fork, T.stream));                      // posteriors are in place: the allele-frequency scans branch off
     EM_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));
-    hipLaunchKernelGGL(hs_em_gt_priors, dim3(nl), dim3(256), 2*HS_EM_CHUNK*HS_EM_MAXA_LDS*sizeof(double), side.stream, d_h);
+    hipLaunchKernelGGL(hs_em_gt_priors, dim3(nl), dim3(HS_EM_THREADS), hs_em_lds_doubles()*sizeof(double), side.stream, d_h);
     EM_HIP(hipEventRecord(side.ev_join, side.stream));
     hipLaunchKernelGGL(hs_em_gmax, dim3(nl), dim3(256), 0, T.stream, d_h);
     hipLaunchKernelGGL(hs_em_mstep_part<0>, dim3(nl, HS_EM_PARTS), dim3(256), 0, T.stream, d_h, (const double*)NULL);
@@ -1041,3 +1084,90 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
   }
   return 0;
 }
+
+#ifndef HIPSTR_NO_DEBUG_ABI
+// Diagnostics (host only): the launch decisions hipstr_em_train takes for a batch, from the same preparation (em_prepare: the refusals are
+// the call's) and the same functions (em_layout.h; post_layout.h for the posterior kernel's path), as one JSON object.
+static const char* const kEmRoutes[] = {
+  "gmax_wave", "gmax_thread", "rows_tile_full", "rows_tile_reduced", "rows_direct", "sweeps_1", "sweeps_2", "sweeps_3plus",
+  "scan_last_chunk_full", "scan_last_chunk_partial", "slices_all_filled", "slices_some_empty", "slices_no_rows", "slice_one_tile",
+  "slice_many_tiles", "post_registers", "post_chunked", "post_no_reads", "post_one_tile", "post_many_tiles", "init_one_block",
+  "init_many_blocks", "compact_one_chunk", "compact_many_chunks", "units_one_pass", "units_strided" };
+enum { EM_N_ROUTES = sizeof kEmRoutes / sizeof kEmRoutes[0] };
+extern "C" int hipstr_debug_em_plan(const hipstr_em_batch_t* eb, char* json, int cap){
+  using hipstr::api_fail;
+  if (!eb) return api_fail("null argument"), -1;
+  const int nl = eb->n_loci;
+  if (nl < 0) return api_fail("negative locus count"), -1;
+  EmPrep P;
+  if (nl > 0 && em_prepare(eb, false, P)) return -1;
+  std::string o; char b[512];
+  auto put = [&](const char* fmt, auto... a){ snprintf(b, sizeof b, fmt, a...); o += b; };
+  put("{\"thresholds\": {\"HS_EM_THREADS\": %d, \"HS_EM_PARTS\": %d, \"HS_EM_TILE\": %d, \"HS_EM_CHUNK\": %d, \"HS_EM_MAXA_LDS\": %d, \"HS_EM_GMAX_WAVE_MAXA\": %d, "
+      "\"HS_EM_GMAX_WAVES\": %d, \"HS_EM_INIT_THREADS\": %d, \"HS_EM_COMPACT_THREADS\": %d, \"HS_EM_UNITS_THREADS\": %d, \"HS_EM_PRUNE_C\": %.17g, "
+      "\"HS_EM_TERM_FLOOR\": %.17g, \"lds_doubles\": %d, \"int_log_len\": %d, \"last_round\": %d, \"HS_POST_THREADS\": %d, \"HS_POST_REGS\": %d, \"HS_POST_ECHUNK\": %d}, \"routes\": [",
+      HS_EM_THREADS, HS_EM_PARTS, HS_EM_TILE, HS_EM_CHUNK, HS_EM_MAXA_LDS, HS_EM_GMAX_WAVE_MAXA, HS_EM_GMAX_WAVES, HS_EM_INIT_THREADS, HS_EM_COMPACT_THREADS,
+      HS_EM_UNITS_THREADS, (double)HS_EM_PRUNE_C, (double)HS_EM_TERM_FLOOR, hs_em_lds_doubles(), (int)hipstr::host_tables().int_log.size(),
+      hs_em_last_round(eb->max_iter), HS_POST_THREADS, HS_POST_REGS, HS_POST_ECHUNK);
+  for (const char* r : kEmRoutes) put("\"%s\", ", r);
+  o.resize(o.size() - 2);
+  o += "], \"loci\": [";
+  bool hit[EM_N_ROUTES] = {false};
+  int max_S = 0;
+  size_t u0 = 0;
+  for (int l = 0; l < nl; l++){
+    const hs_em_locus_t& L = P.loci[l];
+    const int A = L.A, S = L.S, R = L.R;
+    max_S = std::max(max_S, S);
+    const bool wave = hs_em_gmax_wave(A);
+    hit[wave ? 0 : 1] = true;
+    // rows (sample, allele_1) of the posteriors per LDS tile
+    const int tr = hs_em_row_tile_rows(A);
+    const int64_t rows = (int64_t)S*A;
+    const int64_t row_tiles = tr >= 1 ? (rows + tr - 1)/tr : 0;
+    const int last_tile = tr >= 1 ? (int)(rows - (row_tiles - 1)*tr) : 0;
+    hit[tr < 1 ? 4 : tr == HS_EM_THREADS ? 2 : 3] = true;
+    // sweeps of HS_EM_MAXA_LDS chains; chunks of a chain
+    const int sweeps = hs_em_sweeps(A);
+    int last_sweep = 0; for (int a0 = 0; a0 < A; a0 += HS_EM_MAXA_LDS) last_sweep = hs_em_sweep_alleles(A, a0);
+    hit[sweeps == 1 ? 5 : sweeps == 2 ? 6 : 7] = true;
+    const int64_t ntot = hs_em_chain_len(S, A);
+    int64_t chunks = 0; int last_chunk = 0;
+    for (int64_t c0 = 0; c0 < ntot; c0 += HS_EM_CHUNK){ chunks++; last_chunk = hs_em_chunk_len(ntot, c0); }
+    hit[last_chunk == HS_EM_CHUNK ? 8 : 9] = true;
+    // slices of the R*A (read, source allele) rows
+    const int total = R*A;
+    int smin = INT32_MAX, smax = 0, empty = 0;
+    for (int k = 0; k < HS_EM_PARTS; k++){
+      const int n = hs_em_slice_begin(total, k + 1) - hs_em_slice_begin(total, k);
+      smin = std::min(smin, n); smax = std::max(smax, n); if (n == 0) empty++;
+    }
+    const int tiles = (smax + HS_EM_TILE - 1)/HS_EM_TILE;
+    hit[empty == 0 ? 10 : empty == HS_EM_PARTS ? 12 : 11] = true;
+    if (tiles >= 1) hit[tiles == 1 ? 13 : 14] = true;
+    // the posterior kernel on the locus' largest unit: one launch of hs_posterior_kernel (sym_prior), never split
+    int ur = 0;
+    for (int s = 0; s < S; s++) ur = std::max(ur, (int)P.units[u0 + s].n_reads);
+    u0 += S;
+    const bool regs = hs_post_in_registers(A*A);
+    const int rt = regs ? hs_post_reads_per_tile(A, ur) : 0, ptiles = regs ? (ur + rt - 1)/rt : 0;
+    hit[regs ? 15 : 16] = true;
+    if (ur == 0) hit[17] = true; else if (regs) hit[ptiles == 1 ? 18 : 19] = true;
+    put("%s{\"A\": %d, \"S\": %d, \"R\": %d, \"period\": %d, \"haploid\": %d, \"gmax\": \"%s\", \"row_tile\": ", l ? ", " : "", A, S, R, L.period, L.haploid, wave ? "wave" : "thread");
+    if (tr >= 1) put("%d", tr); else o += "\"direct\"";
+    put(", \"row_tiles\": %lld, \"last_row_tile\": %d, \"sweeps\": %d, \"last_sweep\": %d, \"scan_chunks\": %lld, \"scan_last\": %d, \"slice_rows\": [%d, %d], "
+        "\"empty_slices\": %d, \"slice_tiles\": %d, \"post\": [\"%s\", %d, %d, %d]}", (long long)row_tiles, last_tile, sweeps, last_sweep, (long long)chunks, last_chunk,
+        smin, smax, empty, tiles, regs ? "registers" : "chunked", ur, rt, ptiles);
+  }
+  const unsigned ib = nl > 0 ? hs_em_init_blocks(nl) : 0; const int cc = nl > 0 ? hs_em_compact_chunks(nl) : 0;
+  const int passes = (max_S + HS_EM_UNITS_THREADS - 1)/HS_EM_UNITS_THREADS;
+  if (nl > 0){ hit[ib == 1 ? 20 : 21] = true; hit[cc == 1 ? 22 : 23] = true; hit[passes <= 1 ? 24 : 25] = true; }
+  put("], \"n_loci\": %d, \"init_blocks\": %u, \"compact_chunks\": %d, \"compact_last_chunk\": %d, \"max_S\": %d, \"units_passes\": %d, \"routes_hit\": [",
+      nl, ib, cc, nl > 0 ? nl - (cc - 1)*HS_EM_COMPACT_THREADS : 0, max_S, passes);
+  bool first = true;
+  for (int i = 0; i < EM_N_ROUTES; i++) if (hit[i]){ put("%s\"%s\"", first ? "" : ", ", kEmRoutes[i]); first = false; }
+  o += "]}";
+  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
+  return (int)o.size();
+}
+#endif  // HIPSTR_NO_DEBUG_ABI

@@ -3,12 +3,15 @@ de novo stutter EM, and (reference window, read) pairs for Needleman-Wunsch."""
 import numpy as np
 
 
-def em_case(seed, n_loci=3, samples=(8, 30), reads_per_sample=(2, 9), haploid_rate=0.25, snp_rate=0.3, allele_counts=None):
-    """allele_counts: optional per-locus number of true alleles (default: 2..5 drawn per locus)."""
+def em_case(seed, n_loci=3, samples=(8, 30), reads_per_sample=(2, 9), haploid_rate=0.25, snp_rate=0.3, allele_counts=None, all_periods=False,
+            empty_sample_rate=0.0):
+    """allele_counts: optional per-locus number of true alleles (default: 2..5 drawn per locus).  all_periods: periods 1..9, uniformly,
+    instead of 2..6; empty_sample_rate: chance that a sample has no read at all.  The two defaults reproduce the draws of every seed in
+    use exactly (the golden vectors and bench.py depend on them): neither takes a number from the generator unless it is switched on."""
     rng = np.random.default_rng(seed)
     period, n_samples, read_off, lab, bps, p1, p2, hap = [], [], [0], [], [], [], [], []
     for l in range(n_loci):
-        p = int(rng.choice([2, 3, 4, 5, 6], p=[.35, .2, .3, .1, .05]))
+        p = int(rng.integers(1, 10)) if all_periods else int(rng.choice([2, 3, 4, 5, 6], p=[.35, .2, .3, .1, .05]))
         S = int(rng.integers(samples[0], samples[1] + 1))
         h = rng.random() < haploid_rate
         if allele_counts is None:
@@ -22,6 +25,8 @@ def em_case(seed, n_loci=3, samples=(8, 30), reads_per_sample=(2, 9), haploid_ra
             g = rng.choice(alleles, size=2)
             if h:
                 g[1] = g[0]
+            if empty_sample_rate > 0 and rng.random() < empty_sample_rate:
+                continue
             for _ in range(int(rng.integers(reads_per_sample[0], reads_per_sample[1] + 1))):
                 strand = int(rng.integers(2))
                 size = int(g[strand])

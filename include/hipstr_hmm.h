@@ -383,7 +383,12 @@ typedef struct hipstr_em_batch {
 } hipstr_em_batch_t;
 /* trained[l]   = the return value of train();
  * stutter[6*l] = inframe geom, up, down, outframe geom, up, down of get_stutter_model() after train();
- * n_iter[l]    = E-steps performed;  final_ll[l] = the last E-step's total log-likelihood. */
+ * n_iter[l]    = E-steps performed;  final_ll[l] = the last E-step's total log-likelihood.
+ * Refused (non-zero return, hipstr_last_error(); nothing is launched): a period outside 1..9, a locus without samples, reads not grouped by
+ * ascending sample label, 9998 or more distinct sizes at a locus, and a locus two of whose allele sizes (the observed sizes and ref_allele,
+ * observed or not) lie so far apart that their effective difference — d / period for a difference d in frame, d - d / period (truncating)
+ * out of frame — reaches the 10 000 entries of the table of integer logarithms: the reference indexes INT_LOGS[10000] with it
+ * (mathops.cpp:13-21) and has no answer there either. */
 int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll);
 
 /*

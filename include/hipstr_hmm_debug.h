@@ -75,6 +75,16 @@ int hipstr_debug_nw_plan(const hipstr_nw_batch_t* batch, double ws_mib, char* js
  * a split launch with an empty share], "routes_hit".  (HIPSTR_DEBUG_HOST_LIBM, which sends every unit down the chunked path, is not
  * modelled.)  Same conventions as hipstr_debug_trace_plan. */
 int hipstr_debug_post_plan(const hipstr_post_batch_t* batch, char* json, int cap);
+/* Diagnostics (host only): the launch decisions hipstr_em_train takes for a batch, after the same per-locus preparation and validation (a
+ * batch the call refuses fails the plan with the same hipstr_last_error()): "thresholds" (hipstr_amd/csrc/em_layout.h's limits, "int_log_len"
+ * = entries of the table of integer logarithms, "last_round" = last value of the host's round counter for the batch's max_iter), "routes"
+ * (every route name), per locus "A", "S", "R", "gmax" ("wave" / "thread"), "row_tile" (posterior rows per LDS tile, or "direct"), "row_tiles",
+ * "last_row_tile", "sweeps" and "last_sweep" (alleles of the last one), "scan_chunks" and "scan_last" (positions of the last chunk of a chain
+ * of S + S A), "slice_rows" ([fewest, most] rows of the HS_EM_PARTS slices of the R A rows), "empty_slices", "slice_tiles" (tiles of
+ * HS_EM_TILE rows of the fullest slice), "post" ([path of the posterior kernel, reads of the locus' largest unit, reads per LDS tile, tiles],
+ * post_layout.h); for the batch "init_blocks", "compact_chunks", "compact_last_chunk", "max_S", "units_passes" and "routes_hit".  Same
+ * conventions as hipstr_debug_trace_plan.  Used by tests/test_em_routes.py. */
+int hipstr_debug_em_plan(const hipstr_em_batch_t* batch, char* json, int cap);
 /* Diagnostics (host only): the launch decisions of hipstr_post_assign (post_layout.h) for a batch whose largest (locus, sample) unit has
  * max_unit_reads reads and n_units units, and for a locus of n_keys = pools x haplotypes keys and n_reads reads: out[0] wavefronts per unit
  * (1: four units share a workgroup; 4: a unit has the workgroup), out[1] workgroups, out[2] slots of the locus' first-occurrence table,

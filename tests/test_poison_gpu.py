@@ -352,3 +352,13 @@ def test_stream_created_after_a_poison(hmm, oracle):
         same_bits(got[i], one, "stream, batch %d against the one-shot call" % i)
         want = capi.run_align(oracle, "oracle_", p.ptr, fill=FILL)
         assert np.array_equal(got[i][1], want[1]) and np.array_equal(got[i][0], want[0]), "stream, batch %d against the oracle" % i
+
+
+@pytest.mark.parametrize("name", ["no_reads_between_S3", "samples_without_reads", "alleles_M+1"])
+def test_em_idle_scratch(hmm, oracle, name):
+    """tests/em_route_cases.py: a locus without reads between two ordinary ones, samples without reads, and one allele more than a sweep of
+    the allele-frequency scans holds (the second sweep uses one lane's worth of the LDS tiles; the rest idles) — where a stale read would show."""
+    import em_route_cases as ec
+    kw = ec.cases(ec.limits(hmm))[name].kw
+    _em_case(hmm, oracle, kw, None, "EM route case " + name)
+

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Randomised stutter-EM parity at the kernels' size boundaries (allele sizes around a wavefront's 64 lanes and its multiples, one sample ...
 hundreds, samples with one read ... dozens, haploid loci, batches mixing all of these so that the compaction sees loci leave in every
-order): hipstr_em_train against the oracle evaluated with the same correctly rounded exp / log, every output bit for bit (trained
+order; periods 1 to 9 and, in one configuration of four, samples without reads): hipstr_em_train against the oracle evaluated with the same correctly rounded exp / log, every output bit for bit (trained
 flags, six parameters, iteration counts, final log-likelihood).    usage: tools/fuzz_em.py [configs] [seed]"""
 import os, sys
 import numpy as np
@@ -15,11 +15,12 @@ def run(n_cfg, seed, hmm, ora):
     for c in range(n_cfg):
         nl = int(rng.integers(1, 9))
         shape = int(rng.integers(4))
-        if shape == 0:   kw = em_case(int(rng.integers(1 << 30)), n_loci=nl, samples=(1, 6), reads_per_sample=(1, 40))
+        more = dict(all_periods=True, empty_sample_rate=0.15 if rng.random() < 0.25 else 0.0)
+        if shape == 0:   kw = em_case(int(rng.integers(1 << 30)), n_loci=nl, samples=(1, 6), reads_per_sample=(1, 40), **more)
         elif shape == 1: kw = em_case(int(rng.integers(1 << 30)), n_loci=nl, samples=(60, 90), reads_per_sample=(2, 5), haploid_rate=0.0,
-                                      allele_counts=[int(rng.choice([30, 60, 64, 66, 80])) for _ in range(nl)])
-        elif shape == 2: kw = em_case(int(rng.integers(1 << 30)), n_loci=nl, samples=(200, 330), reads_per_sample=(1, 3), allele_counts=[int(rng.integers(2, 9)) for _ in range(nl)])
-        else:            kw = em_case(int(rng.integers(1 << 30)), n_loci=nl, samples=(3, 50), reads_per_sample=(1, 12), haploid_rate=0.5, snp_rate=0.8)
+                                      allele_counts=[int(rng.choice([30, 60, 64, 66, 80])) for _ in range(nl)], **more)
+        elif shape == 2: kw = em_case(int(rng.integers(1 << 30)), n_loci=nl, samples=(200, 330), reads_per_sample=(1, 3), allele_counts=[int(rng.integers(2, 9)) for _ in range(nl)], **more)
+        else:            kw = em_case(int(rng.integers(1 << 30)), n_loci=nl, samples=(3, 50), reads_per_sample=(1, 12), haploid_rate=0.5, snp_rate=0.8, **more)
         kw["max_iter"] = int(rng.choice([100, 100, 7, 1]))
         got = capi.run_em(hmm, "hipstr_", **kw)
         with capi.oracle_cr_math(ora):
