@@ -284,6 +284,68 @@ def run_assign_trace_stats(lib, pb, read_req, trace, best_hap, hap_to_allele, al
     return ns[:n_samp], nf[:n_samp], ml[:n_reads]
 
 
+class HipstrReadLayout(C.Structure):
+    _fields_ = [("n_loci", C.c_int32), ("n_alleles", _i32p), ("read_off", _i32p), ("pool_index", _i32p), ("second_mate", _u8p)]
+
+
+class ReadMatrix:
+    """hipstr_rm_*: the read x haplotype matrix of a batch of loci resident on the device (include/hipstr_hmm.h).  Every call raises
+    with hipstr_last_error() when the library refuses it."""
+
+    def __init__(self, lib, n_alleles, read_off, pool_index, second_mate=None, init_ll=None, init_seeds=None):
+        self.lib = lib; self.h = None
+        i32 = lambda x: np.ascontiguousarray(np.asarray(x, np.int32))
+        self.n_alleles = i32(n_alleles); self.read_off = i32(read_off)
+        keep = [self.n_alleles, self.read_off, i32(pool_index), None if second_mate is None else np.ascontiguousarray(np.asarray(second_mate, np.uint8)),
+                None if init_ll is None else np.ascontiguousarray(np.asarray(init_ll, np.float64)), None if init_seeds is None else i32(init_seeds)]
+        lay = HipstrReadLayout(len(self.n_alleles), _ptr(keep[0], _i32p), _ptr(keep[1], _i32p), _ptr(keep[2], _i32p), _ptr(keep[3], _u8p))
+        self.h = lib.hipstr_rm_create(C.byref(lay), _ptr(keep[4], _f64p), _ptr(keep[5], _i32p))
+        if not self.h:
+            raise RuntimeError("hipstr_rm_create failed: " + lib.hipstr_last_error().decode())
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError("%s failed rc=%d: %s" % (what, rc, self.lib.hipstr_last_error().decode()))
+
+    def scatter(self, dev, copy_read=None):
+        c = None if copy_read is None else np.ascontiguousarray(np.asarray(copy_read, np.uint8))
+        self._check(self.lib.hipstr_rm_scatter(self.h, dev, _ptr(c, _u8p)), "hipstr_rm_scatter")
+
+    def remap(self, new_n_alleles, allele_mapping):
+        na = np.ascontiguousarray(np.asarray(new_n_alleles, np.int32)); am = np.ascontiguousarray(np.asarray(allele_mapping, np.int32))
+        self._check(self.lib.hipstr_rm_remap(self.h, _ptr(na, _i32p), _ptr(am, _i32p)), "hipstr_rm_remap")
+        self.n_alleles = na
+
+    @property
+    def dev_ll(self):
+        return self.lib.hipstr_rm_dev_log_aln_probs(self.h)
+
+    def fetch(self):
+        """(log_aln_probs, seeds) as they lie on the device."""
+        R = np.diff(self.read_off).astype(np.int64)
+        ll = np.zeros(max(int((R * self.n_alleles).sum()), 1)); seeds = np.zeros(max(int(R.sum()), 1), np.int32)
+        self._check(self.lib.hipstr_rm_fetch(self.h, ll.ctypes.data_as(_f64p), seeds.ctypes.data_as(_i32p)), "hipstr_rm_fetch")
+        return ll[:int((R * self.n_alleles).sum())], seeds[:int(R.sum())]
+
+    def close(self):
+        if self.h:
+            self.lib.hipstr_rm_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rm_plan(lib, n_alleles, n_items):
+    """hipstr_debug_rm_plan (host only) as a dict: the route of a locus of n_alleles haplotypes and n_items mate groups / rows."""
+    out = np.zeros(5, np.int64)
+    if lib.hipstr_debug_rm_plan(int(n_alleles), int(n_items), out.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
+        raise RuntimeError("hipstr_debug_rm_plan failed: " + lib.hipstr_last_error().decode())
+    return dict(route="wide" if out[0] else "narrow", lanes=int(out[1]), items_per_wave=int(out[2]), waves=int(out[3]), column_steps=int(out[4]))
+
+
 class HipstrTraceOut(C.Structure):
     _fields_ = [("ll", _f64p), ("max_index", _i32p), ("hap_aln_off", _i32p), ("hap_aln", C.c_char_p), ("stutter_size", _i32p),
                 ("str_seq_off", _i32p), ("str_seq", C.c_char_p), ("flank_seq_off", _i32p), ("flank_seq", C.c_char_p),
@@ -692,6 +754,13 @@ def load_hmm():
     _sig(lib.hipstr_debug_nw_plan, C.c_int, [C.POINTER(HipstrNwBatch), C.c_double, C.c_char_p, C.c_int])
     _sig(lib.hipstr_debug_post_plan, C.c_int, [_PBP, C.c_char_p, C.c_int])
     _sig(lib.hipstr_debug_em_plan, C.c_int, [C.POINTER(HipstrEmBatch), C.c_char_p, C.c_int])
+    _sig(lib.hipstr_rm_create, C.c_void_p, [C.POINTER(HipstrReadLayout), _f64p, _i32p])
+    _sig(lib.hipstr_rm_scatter, C.c_int, [C.c_void_p, C.c_void_p, _u8p])
+    _sig(lib.hipstr_rm_remap, C.c_int, [C.c_void_p, _i32p, _i32p])
+    _sig(lib.hipstr_rm_dev_log_aln_probs, C.c_void_p, [C.c_void_p])
+    _sig(lib.hipstr_rm_fetch, C.c_int, [C.c_void_p, _f64p, _i32p])
+    _sig(lib.hipstr_rm_free, None, [C.c_void_p])
+    _sig(lib.hipstr_debug_rm_plan, C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)])
     return lib
 
 

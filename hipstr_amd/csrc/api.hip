@@ -25,6 +25,7 @@
 #include "../../include/hipstr_hmm_debug.h"
 #include "layout.h"
 #include "post_layout.h"
+#include "readmat_layout.h"
 #include "prep.h"
 #include "api_internal.h"
 
@@ -41,6 +42,9 @@ extern "C" __global__ void hs_assign_kernel(const hs_assign_dev_t* dp);
 extern "C" __global__ void hs_assign_kernel_wg(const hs_assign_dev_t* dp);
 extern "C" __global__ void hs_assign_scan_kernel(const hs_assign_dev_t* dp);
 extern "C" __global__ void hs_assign_requests_kernel(const hs_assign_dev_t* dp);
+extern "C" __global__ void hs_rm_scatter_kernel(const hs_rm_scatter_t d);
+extern "C" __global__ void hs_rm_remap_kernel(const hs_rm_remap_t d);
+extern "C" __global__ void hs_rm_fill_kernel(double* p, int64_t n, double v);
 extern "C" size_t hs_str_lds_bytes(int lds_len, int max_B);
 extern "C" __global__ void hs_str_group_kernel(const hs_dev_t* dp, int item_begin, int short_only);
 extern "C" __global__ void hs_str_group_kernel_pw(const hs_dev_t* dp, int item_begin);
@@ -451,6 +455,7 @@ struct hipstr_dev_batch {
   hipStream_t h2d_stream = NULL, d2h_stream = NULL;
   double* host_out = NULL;                  // pinned copy of aln_probs (fetch_begin)
   bool profiling = false, foreign_stream = false, sleepy_wait = false;
+  bool aligned = false;                     // hipstr_hmm_align has queued a pass: aln_probs holds (or will hold, in stream order) a forward pass' rows
   bool d2h_pending = false;            // fetch_begin: the copy back is queued once ev_done has fired (fetch_poll / results_wait), not behind a cross-stream wait
   std::mutex d2h_m;
   std::vector<hipEvent_t> prof_pool;        // reusable events; every pass records 5 per chunk (phase boundaries)
@@ -882,6 +887,7 @@ int hipstr_hmm_align(hipstr_dev_batch_t* dev, void* hip_stream){
   if (bind(dev->ctx)) return 1;
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : dev->stream;
   if (hip_stream && (hipStream_t)hip_stream != dev->stream) dev->foreign_stream = true;
+  dev->aligned = true;
   // the tables were sent on another stream.  Also with nothing to align: what follows on `st` (the copy back, the events that release the
   // batch's blocks to the cache) must come after the upload that is still writing into those blocks
   // (round 6, the stream's batches — the caller is a worker thread with a batch's time to spare: the two events a batch's kernels depend on, the
@@ -1429,6 +1435,8 @@ int hipstr_post_offsets(const hipstr_post_batch_t* pb, int64_t* post_off, int64_
 }
 
 namespace {
+// `ll` is a resident read matrix (hipstr_rm_*) whose last scatter / remap was queued on another stream than `st`: `st` waits for it
+int rm_order_behind(const double* ll, hipStream_t st);
 struct PostRun {
   Ctx* ctx = NULL;
   hipStream_t stream = NULL;        // the creating thread's stream
@@ -1583,6 +1591,7 @@ int hipstr_post_launch(hipstr_post_dev_t* pd, void* hip_stream){
   if (hip_stream && st != pd->R.stream) pd->foreign_stream = true;
   // a small run's inputs and argument block were sent asynchronously on the run's own stream: a launch elsewhere comes after them
   if (st != pd->R.stream && pd->R.ev_up) HS_HIP(hipStreamWaitEvent(st, pd->R.ev_up, 0));
+  if (rm_order_behind(pd->R.h.log_aln_probs, st)) return 1;
   // HIPSTR_DEBUG_HOST_LIBM=1 (tests/test_genotypes_gpu.py): the three places where the device's exp / log enter — the per-sample
   // log-sum-exp over the diplotypes, the streaming log-sum-exps per genotype and the exact pair log-sum-exp of the unphased posterior —
   // are evaluated on the host with its libm, in the reference's order, on the device's accumulated values.  It shows where the
@@ -1936,6 +1945,7 @@ int hipstr_post_assign(hipstr_post_dev_t* pd, const hipstr_assign_request_t* rq,
   h.n_req = (int32_t*)(B.dev + r_nreq); h.req_read = (int32_t*)(B.dev + r_rr); h.req_allele = (int32_t*)(B.dev + r_ra);
   if (pd->foreign_stream) HS_HIP(hipDeviceSynchronize());          // the posterior kernel may still be running on a stream of the caller's
   hipStream_t st = R.stream;
+  if (rm_order_behind(R.h.log_aln_probs, st)) return 1;
   if (ar.send(st)) return 1;
   const hs_assign_dev_t* d_args = ar.at<hs_assign_dev_t>(o_args);
   if (req){
@@ -2021,6 +2031,313 @@ int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read
   }
   return 0;
 }
+
+// ----------------------------------------------------------------------------- resident read x haplotype matrix
+// log_aln_probs_ of a batch of loci kept on the device between the rounds of SeqStutterGenotyper::genotype (hipstr_hmm.h: hipstr_rm_*).
+// The layout (reads per locus, pool of every read, mates) is fixed at creation: the mate groups and each read's pool go to the device once;
+// the haplotype counts change with hipstr_rm_remap, and with them the wavefront list of the scatter (readmat_layout.h).
+struct hipstr_read_matrix {
+  Ctx* ctx = NULL;
+  hipStream_t stream = NULL;                   // the creating thread's stream: every kernel and copy of the matrix is queued here
+  int32_t n_loci = 0; int64_t n_reads = 0, n_ll = 0, n_groups = 0, n_waves = 0;
+  std::vector<int32_t> n_alleles, read_off, pool_index, pool_max, group_off;      // pool_max: largest pool_index of a locus (-1: no reads)
+  std::vector<int64_t> mat_off;
+  double* d_ll = NULL; int32_t* d_seeds = NULL;
+  char* d_static = NULL; size_t o_groups = 0, o_pool = 0, o_waves = 0;            // mate groups | pool_index | wavefront list, device
+  char* d_stage = NULL; char* pin_stage = NULL; size_t stage_bytes = 0;           // what a scatter sends: locus records | copy_read | realign_hap flags
+  hipEvent_t ev_stage = NULL, ev_done = NULL;  // the staging block's last copy has left it / the matrix' last kernel has run
+  bool stage_sent = false;
+};
+
+namespace {
+std::mutex g_rm_m;
+std::map<const double*, hipstr_read_matrix*> g_rm;       // by device pointer of the matrix (hipstr_rm_dev_log_aln_probs)
+
+int rm_order_behind(const double* ll, hipStream_t st){
+  std::lock_guard<std::mutex> g(g_rm_m);
+  auto it = g_rm.find(ll);
+  if (it == g_rm.end() || it->second->stream == st) return 0;
+  HS_HIP(hipStreamWaitEvent(st, it->second->ev_done, 0));
+  return 0;
+}
+
+int ilog2(int w){ int k = 0; while ((1 << k) < w) k++; return k; }
+
+// the wavefront list of a launch whose locus l has count[l] work items of A[l] columns
+void rm_waves(const std::vector<int32_t>& A, const int64_t* count, std::vector<hs_rm_wave_t>& out){
+  out.clear();
+  for (size_t l = 0; l < A.size(); l++){
+    const int per = hs_rm_items_per_wave(A[l]);
+    for (int64_t f = 0; f < count[l]; f += per) out.push_back(hs_rm_wave_t{(int32_t)l, (int32_t)f});
+  }
+}
+
+size_t rm_stage_bytes(const hipstr_read_matrix* rm){
+  size_t sumA = 0; for (int32_t a : rm->n_alleles) sumA += (size_t)a;
+  return (((size_t)rm->n_loci*sizeof(hs_rm_locus_t) + 255) & ~(size_t)255) + (((size_t)rm->n_reads + 255) & ~(size_t)255) + sumA + 256;
+}
+
+// host arrays -> device through a pinned block of the cache, on the matrix' stream; returns when the copy has landed
+int rm_send(hipstr_read_matrix* rm, void* dst, const void* src, size_t bytes){
+  if (!bytes) return 0;
+  char* pin = (char*)rm->ctx->pin_cache.get(bytes);
+  if (!pin) return 1;
+  memcpy(pin, src, bytes);
+  const bool ok = hipMemcpyAsync(dst, pin, bytes, hipMemcpyHostToDevice, rm->stream) == hipSuccess && hipstr::wait_stream(rm->stream) == hipSuccess;
+  rm->ctx->pin_cache.put(pin);
+  return ok ? 0 : fail("host-to-device copy failed");
+}
+
+void rm_release(hipstr_read_matrix* rm){
+  if (!rm) return;
+  { std::lock_guard<std::mutex> g(g_rm_m); if (rm->d_ll) g_rm.erase(rm->d_ll); }
+  if (rm->ctx && bind(rm->ctx) == 0){
+    hipStreamSynchronize(rm->stream);          // the blocks are handed to the next user
+    rm->ctx->dev_cache.put(rm->d_ll); rm->ctx->dev_cache.put(rm->d_seeds); rm->ctx->dev_cache.put(rm->d_static); rm->ctx->dev_cache.put(rm->d_stage);
+    rm->ctx->pin_cache.put(rm->pin_stage);
+  }
+  if (rm->ctx){ rm->ctx->put_event(rm->ev_stage, false); rm->ctx->put_event(rm->ev_done, false); }
+  delete rm;
+}
+}  // namespace
+
+hipstr_read_matrix_t* hipstr_rm_create(const hipstr_read_layout_t* lay, const double* init_ll, const int32_t* init_seeds){
+  if (!lay || lay->n_loci < 0 || (lay->n_loci > 0 && (!lay->n_alleles || !lay->read_off))){ g_err = "null argument or negative locus count"; return NULL; }
+  const int nl = lay->n_loci;
+  if (nl > 0 && lay->read_off[0] != 0){ g_err = "read_off must start at 0"; return NULL; }
+  int64_t n_ll = 0;
+  for (int l = 0; l < nl; l++){
+    if (lay->n_alleles[l] < 1 || lay->n_alleles[l] + 1 >= 10000){ g_err = "allele count out of range"; return NULL; }
+    if (lay->read_off[l+1] < lay->read_off[l]){ g_err = "read_off must be ascending (negative read count)"; return NULL; }
+    n_ll += (int64_t)(lay->read_off[l+1] - lay->read_off[l])*lay->n_alleles[l];
+  }
+  const int64_t R = nl ? lay->read_off[nl] : 0;
+  if (R > 0 && !lay->pool_index){ g_err = "null pool_index"; return NULL; }
+  std::vector<uint32_t> groups; std::vector<int32_t> group_off(nl + 1, 0), pool_max(nl, -1);
+  for (int l = 0; l < nl; l++){
+    const int r0 = lay->read_off[l], r1 = lay->read_off[l+1];
+    for (int i = r0; i < r1; i++){
+      if (lay->pool_index[i] < 0){ g_err = "pool_index must not be negative"; return NULL; }
+      pool_max[l] = std::max(pool_max[l], lay->pool_index[i]);
+      if (lay->second_mate && lay->second_mate[i]){
+        if (i == r0){ g_err = "second_mate set on the first read of a locus: its first mate would be a read of another locus"; return NULL; }
+        if (lay->second_mate[i-1]){ g_err = "second_mate set on two consecutive reads"; return NULL; }
+      }
+    }
+    for (int i = r0; i < r1; ){        // a read alone, or a first mate with the second mate behind it (seq_stutter_genotyper.cpp:555-556)
+      const bool pair = lay->second_mate && i + 1 < r1 && lay->second_mate[i+1];
+      groups.push_back((uint32_t)i | (pair ? HS_RM_PAIR : 0u));
+      i += pair ? 2 : 1;
+    }
+    group_off[l+1] = (int32_t)groups.size();
+  }
+  Ctx* ctx = hipstr::api_current_ctx();
+  if (!ctx) return NULL;
+  hipstr_read_matrix_t* rm = new hipstr_read_matrix_t();
+  rm->ctx = ctx; rm->stream = thread_stream(ctx);
+  rm->n_loci = nl; rm->n_reads = R; rm->n_ll = n_ll; rm->n_groups = (int64_t)groups.size();
+  rm->n_alleles.assign(lay->n_alleles, lay->n_alleles + nl); rm->read_off.assign(lay->read_off, lay->read_off + (nl ? nl + 1 : 0));
+  if (!nl) rm->read_off.assign(1, 0);
+  rm->pool_index.assign(lay->pool_index, lay->pool_index + R); rm->pool_max.swap(pool_max); rm->group_off.swap(group_off);
+  rm->mat_off.assign(nl + 1, 0);
+  for (int l = 0; l < nl; l++) rm->mat_off[l+1] = rm->mat_off[l] + (int64_t)(rm->read_off[l+1] - rm->read_off[l])*rm->n_alleles[l];
+  std::vector<hs_rm_wave_t> waves;
+  { std::vector<int64_t> cnt(nl); for (int l = 0; l < nl; l++) cnt[l] = rm->group_off[l+1] - rm->group_off[l]; rm_waves(rm->n_alleles, cnt.data(), waves); }
+  rm->n_waves = (int64_t)waves.size();
+  // mate groups | pool_index | wavefront list (room for one wavefront per group: what any later haplotype count can need)
+  const size_t G = groups.size();
+  rm->o_groups = 0; rm->o_pool = (G*4 + 255) & ~(size_t)255; rm->o_waves = (rm->o_pool + (size_t)R*4 + 255) & ~(size_t)255;
+  const size_t static_bytes = rm->o_waves + G*sizeof(hs_rm_wave_t) + 256;
+  rm->stage_bytes = rm_stage_bytes(rm);
+  rm->d_ll = (double*)ctx->dev_cache.get((size_t)(n_ll ? n_ll : 1)*sizeof(double));
+  rm->d_seeds = (int32_t*)ctx->dev_cache.get((size_t)(R ? R : 1)*sizeof(int32_t));
+  rm->d_static = (char*)ctx->dev_cache.get(static_bytes);
+  rm->d_stage = (char*)ctx->dev_cache.get(rm->stage_bytes);
+  rm->pin_stage = (char*)ctx->pin_cache.get(rm->stage_bytes);
+  rm->ev_stage = ctx->get_event(false); rm->ev_done = ctx->get_event(false);
+  bool ok = rm->d_ll && rm->d_seeds && rm->d_static && rm->d_stage && rm->pin_stage;
+  if (ok && (!rm->ev_stage || !rm->ev_done)){ ok = false; g_err = "hipEventCreate failed"; }
+  if (ok){
+    std::vector<char> img(static_bytes, 0);
+    if (G) memcpy(img.data() + rm->o_groups, groups.data(), G*4);
+    if (R) memcpy(img.data() + rm->o_pool, rm->pool_index.data(), (size_t)R*4);
+    if (!waves.empty()) memcpy(img.data() + rm->o_waves, waves.data(), waves.size()*sizeof(hs_rm_wave_t));
+    ok = rm_send(rm, rm->d_static, img.data(), static_bytes) == 0;
+  }
+  hipError_t e = hipSuccess;
+  if (ok && n_ll){
+    if (init_ll) e = hipMemcpyAsync(rm->d_ll, init_ll, (size_t)n_ll*sizeof(double), hipMemcpyHostToDevice, rm->stream);
+    else {          // columns nobody has aligned yet (seq_stutter_genotyper.cpp:374)
+      const unsigned wgs = (unsigned)std::min<int64_t>((n_ll + HS_RM_THREADS - 1)/HS_RM_THREADS, 2048);
+      hipLaunchKernelGGL(hs_rm_fill_kernel, dim3(wgs), dim3(HS_RM_THREADS), 0, rm->stream, rm->d_ll, n_ll, HS_RM_UNALIGNED);
+      e = hipGetLastError();
+    }
+  }
+  if (ok && e == hipSuccess && R)
+    e = init_seeds ? hipMemcpyAsync(rm->d_seeds, init_seeds, (size_t)R*sizeof(int32_t), hipMemcpyHostToDevice, rm->stream)
+                   : hipMemsetAsync(rm->d_seeds, 0xff, (size_t)R*sizeof(int32_t), rm->stream);         // -1
+  if (ok && e == hipSuccess) e = hipEventRecord(rm->ev_done, rm->stream);
+  if (ok && e == hipSuccess) e = hipstr::wait_stream(rm->stream);      // the sources are the caller's arrays: done with them before returning
+  if (ok && e != hipSuccess){ ok = false; g_err = std::string("hipstr_rm_create: ") + hipGetErrorString(e); }
+  if (!ok){ rm_release(rm); return NULL; }
+  { std::lock_guard<std::mutex> g(g_rm_m); g_rm[rm->d_ll] = rm; }
+  return rm;
+}
+
+int hipstr_rm_scatter(hipstr_read_matrix_t* rm, hipstr_dev_batch_t* dev, const uint8_t* copy_read){
+  if (!rm || !dev) return fail("null argument");
+  if (rm->ctx != dev->ctx) return fail("the matrix and the batch belong to different devices");
+  if (!dev->aligned) return fail("hipstr_rm_scatter needs a forward pass: call hipstr_hmm_align on the batch first");
+  const hipstr::Prepared& P = dev->prep;
+  static_assert(sizeof(hs_read_t) == 16, "hs_rm_scatter_kernel reads the seed as the third dword of a 16-byte record");
+  if ((int64_t)P.loci.size() != rm->n_loci) return fail("n_loci of the matrix disagrees with the batch");
+  bool all_pools = true;
+  for (int l = 0; l < rm->n_loci; l++){
+    const hs_locus_t& loc = P.loci[l];
+    if (loc.n_alleles != rm->n_alleles[l]) return fail("n_alleles of locus " + std::to_string(l) + " disagrees with the batch");
+    if (rm->pool_max[l] >= loc.n_reads) return fail("pool_index outside the pooled reads of locus " + std::to_string(l));
+  }
+  for (uint8_t f : P.realign_read) if (!f){ all_pools = false; break; }
+  if (!all_pools)      // the reference would copy a row process_reads never wrote (seq_stutter_genotyper.cpp:526-542)
+    for (int l = 0; l < rm->n_loci; l++)
+      for (int i = rm->read_off[l]; i < rm->read_off[l+1]; i++)
+        if ((!copy_read || copy_read[i]) && !P.realign_read[P.loci[l].read_begin + rm->pool_index[i]])
+          return fail("copy_read set for read " + std::to_string(i) + " whose pool was not realigned");
+  if (bind(rm->ctx)) return 1;
+  Ctx* ctx = rm->ctx;
+  hipStream_t st = rm->stream;
+  // ---- what this scatter sends: locus records | copy_read | realign_hap flags of the loci with a partial mask
+  if (rm->stage_sent) HS_HIP(hipEventSynchronize(rm->ev_stage));      // the previous scatter's copy has left the pinned block
+  const size_t o_copy = ((size_t)rm->n_loci*sizeof(hs_rm_locus_t) + 255) & ~(size_t)255, o_mask = o_copy + (((size_t)rm->n_reads + 255) & ~(size_t)255);
+  hs_rm_locus_t* lr = (hs_rm_locus_t*)rm->pin_stage;
+  size_t mask_used = 0;
+  for (int l = 0; l < rm->n_loci; l++){
+    const hs_locus_t& loc = P.loci[l];
+    hs_rm_locus_t& o = lr[l];
+    o.mat_off = rm->mat_off[l]; o.src_off = loc.out_off; o.n_alleles = loc.n_alleles; o.lanes_log2 = ilog2(hs_rm_item_lanes(loc.n_alleles));
+    o.read_begin = rm->read_off[l]; o.pool_begin = loc.read_begin; o.group_begin = rm->group_off[l]; o.n_groups = rm->group_off[l+1] - rm->group_off[l];
+    o.mask_off = -1; o.pad = 0;
+    if (loc.n_re != loc.n_alleles){
+      o.mask_off = (int32_t)mask_used;
+      memcpy(rm->pin_stage + o_mask + mask_used, P.realign_hap.data() + loc.hap_begin, (size_t)loc.n_alleles);
+      mask_used += (size_t)loc.n_alleles;
+    }
+  }
+  if (copy_read && rm->n_reads) memcpy(rm->pin_stage + o_copy, copy_read, (size_t)rm->n_reads);
+  // ---- behind the batch's last pass
+  if (dev->foreign_stream) HS_HIP(hipDeviceSynchronize());            // a pass was launched on a stream of the caller's
+  else if (dev->stream != st){
+    hipEvent_t ev = ctx->get_event(false);
+    if (!ev) return fail("hipEventCreate failed");
+    const bool ok = hipEventRecord(ev, dev->stream) == hipSuccess && hipStreamWaitEvent(st, ev, 0) == hipSuccess;
+    ctx->put_event(ev, false);          // (its wait is queued: the event may be recorded again by its next user)
+    if (!ok) return fail("hipEventRecord / hipStreamWaitEvent failed");
+  }
+  HS_HIP(hipMemcpyAsync(rm->d_stage, rm->pin_stage, o_mask + mask_used + 1, hipMemcpyHostToDevice, st));
+  HS_HIP(hipEventRecord(rm->ev_stage, st));
+  rm->stage_sent = true;
+  if (rm->n_waves > 0){
+    hs_rm_scatter_t a; memset(&a, 0, sizeof a);
+    a.waves = (const hs_rm_wave_t*)(rm->d_static + rm->o_waves); a.loci = (const hs_rm_locus_t*)rm->d_stage;
+    a.groups = (const uint32_t*)(rm->d_static + rm->o_groups); a.pool_index = (const int32_t*)(rm->d_static + rm->o_pool);
+    a.copy_read = copy_read ? (const uint8_t*)(rm->d_stage + o_copy) : NULL; a.mask = (const uint8_t*)(rm->d_stage + o_mask);
+    a.src = dev->h.aln_probs; a.pool_reads = (const int32_t*)dev->h.reads; a.ll = rm->d_ll; a.seeds = rm->d_seeds; a.n_waves = rm->n_waves;
+    hipLaunchKernelGGL(hs_rm_scatter_kernel, dim3((unsigned)((rm->n_waves + HS_RM_THREADS/64 - 1)/(HS_RM_THREADS/64))), dim3(HS_RM_THREADS), 0, st, a);
+    HS_HIP(hipGetLastError());
+  }
+  HS_HIP(hipEventRecord(rm->ev_done, st));
+  // the batch's blocks are read by a kernel on the matrix' stream: hipstr_hmm_free waits for the batch's own stream only
+  if (!dev->foreign_stream && dev->stream != st) HS_HIP(hipStreamWaitEvent(dev->stream, rm->ev_done, 0));
+  return 0;
+}
+
+int hipstr_rm_remap(hipstr_read_matrix_t* rm, const int32_t* new_n_alleles, const int32_t* allele_mapping){
+  if (!rm || (rm->n_loci > 0 && (!new_n_alleles || !allele_mapping))) return fail("null argument");
+  const int nl = rm->n_loci;
+  std::vector<int32_t> newA(new_n_alleles, new_n_alleles + nl), inv;
+  std::vector<hs_rm_remap_locus_t> loci(nl);
+  std::vector<int64_t> new_off(nl + 1, 0), rows(nl);
+  size_t old_base = 0;
+  for (int l = 0; l < nl; l++){
+    if (newA[l] < 1 || newA[l] + 1 >= 10000) return fail("allele count out of range");
+    const size_t ib = inv.size();
+    inv.resize(ib + (size_t)newA[l], -1);
+    for (int j = 0; j < rm->n_alleles[l]; j++){
+      const int m = allele_mapping[old_base + j];
+      if (m == -1) continue;
+      if (m < 0 || m >= newA[l]) return fail("allele_mapping entry out of range at locus " + std::to_string(l));
+      if (inv[ib + m] != -1) return fail("two old columns mapped to one new column at locus " + std::to_string(l));
+      inv[ib + m] = j;
+    }
+    rows[l] = rm->read_off[l+1] - rm->read_off[l];
+    new_off[l+1] = new_off[l] + rows[l]*newA[l];
+    hs_rm_remap_locus_t& o = loci[l];
+    o.old_off = rm->mat_off[l]; o.new_off = new_off[l]; o.old_A = rm->n_alleles[l]; o.new_A = newA[l];
+    o.lanes_log2 = ilog2(hs_rm_item_lanes(newA[l])); o.n_reads = (int32_t)rows[l]; o.inv_off = (int32_t)ib; o.pad = 0;
+    old_base += (size_t)rm->n_alleles[l];
+  }
+  if (bind(rm->ctx)) return 1;
+  Ctx* ctx = rm->ctx;
+  hipStream_t st = rm->stream;
+  std::vector<hs_rm_wave_t> waves, swaves;          // of this launch (rows), of the scatters to come (mate groups under the new counts)
+  rm_waves(newA, rows.data(), waves);
+  { std::vector<int64_t> cnt(nl); for (int l = 0; l < nl; l++) cnt[l] = rm->group_off[l+1] - rm->group_off[l]; rm_waves(newA, cnt.data(), swaves); }
+  const int64_t n_new = new_off[nl];
+  double* nll = (double*)ctx->dev_cache.get((size_t)(n_new ? n_new : 1)*sizeof(double));
+  if (!nll) return 1;
+  {
+    hipstr::HostArena ar;             // (waits for the stream when it goes)
+    const size_t o_loci = ar.add(loci.data(), loci.size()*sizeof(hs_rm_remap_locus_t)), o_inv = ar.add(inv.data(), inv.size()*4),
+                 o_w = ar.add(waves.data(), waves.size()*sizeof(hs_rm_wave_t)), o_sw = ar.add(swaves.data(), swaves.size()*sizeof(hs_rm_wave_t));
+    bool ok = ar.reserve(ctx) == 0 && ar.send(st) == 0;
+    if (ok && !waves.empty()){
+      hs_rm_remap_t a; memset(&a, 0, sizeof a);
+      a.waves = ar.at<hs_rm_wave_t>(o_w); a.loci = ar.at<hs_rm_remap_locus_t>(o_loci); a.inv = ar.at<int32_t>(o_inv);
+      a.old_ll = rm->d_ll; a.new_ll = nll; a.n_waves = (int64_t)waves.size();
+      hipLaunchKernelGGL(hs_rm_remap_kernel, dim3((unsigned)((waves.size() + HS_RM_THREADS/64 - 1)/(HS_RM_THREADS/64))), dim3(HS_RM_THREADS), 0, st, a);
+      ok = hipGetLastError() == hipSuccess;
+    }
+    if (ok && !swaves.empty())
+      ok = hipMemcpyAsync(rm->d_static + rm->o_waves, ar.at<char>(o_sw), swaves.size()*sizeof(hs_rm_wave_t), hipMemcpyDeviceToDevice, st) == hipSuccess;
+    if (ok) ok = hipEventRecord(rm->ev_done, st) == hipSuccess && hipstr::wait_stream(st) == hipSuccess;
+    if (!ok){ hipStreamSynchronize(st); ctx->dev_cache.put(nll); return g_err.empty() ? fail("hipstr_rm_remap: launch failed") : 1; }
+  }
+  { std::lock_guard<std::mutex> g(g_rm_m); g_rm.erase(rm->d_ll); g_rm[nll] = rm; }
+  ctx->dev_cache.put(rm->d_ll);          // (the stream is idle: nothing reads the old matrix any more)
+  rm->d_ll = nll; rm->n_ll = n_new; rm->n_alleles.swap(newA); rm->mat_off.swap(new_off); rm->n_waves = (int64_t)swaves.size();
+  const size_t need = rm_stage_bytes(rm);
+  if (need > rm->stage_bytes){           // more haplotype flags than the staging blocks hold
+    char* d = (char*)ctx->dev_cache.get(need); char* p = (char*)ctx->pin_cache.get(need);
+    if (!d || !p){ ctx->dev_cache.put(d); ctx->pin_cache.put(p); return 1; }
+    ctx->dev_cache.put(rm->d_stage); ctx->pin_cache.put(rm->pin_stage);
+    rm->d_stage = d; rm->pin_stage = p; rm->stage_bytes = need; rm->stage_sent = false;
+  }
+  return 0;
+}
+
+const double* hipstr_rm_dev_log_aln_probs(hipstr_read_matrix_t* rm){ return rm ? rm->d_ll : NULL; }
+
+int hipstr_rm_fetch(hipstr_read_matrix_t* rm, double* ll, int32_t* seeds){
+  if (!rm) return fail("null argument");
+  if (bind(rm->ctx)) return 1;
+  HS_HIP(hipstr::wait_stream(rm->stream));
+  if (ll && fetch_array(rm->ctx, rm->stream, ll, rm->d_ll, (size_t)rm->n_ll*sizeof(double))) return 1;
+  if (seeds && fetch_array(rm->ctx, rm->stream, seeds, rm->d_seeds, (size_t)rm->n_reads*sizeof(int32_t))) return 1;
+  return 0;
+}
+
+void hipstr_rm_free(hipstr_read_matrix_t* rm){ rm_release(rm); }
+
+#ifndef HIPSTR_NO_DEBUG_ABI
+// Diagnostics (host only): the route the matrix kernels give a locus of n_alleles haplotypes and n_items work items (mate groups of a
+// scatter, rows of a remap), from readmat_layout.h's functions.
+int hipstr_debug_rm_plan(int32_t n_alleles, int64_t n_items, int64_t out[5]){
+  if (!out || n_alleles < 1 || n_items < 0) return fail("bad argument");
+  out[0] = n_alleles > HS_RM_NARROW_MAX ? 1 : 0; out[1] = hs_rm_item_lanes(n_alleles); out[2] = hs_rm_items_per_wave(n_alleles);
+  out[3] = hs_rm_waves(n_alleles, n_items); out[4] = hs_rm_column_steps(n_alleles);
+  return 0;
+}
+#endif
 
 int hipstr_post_run(const hipstr_post_batch_t* pb, const double* dev_log_aln_probs,
                     double* log_post, double* sample_total_ll, int32_t* map_gt, double* locus_total_ll){

@@ -165,7 +165,8 @@ int hipstr_hmm_fetch(hipstr_dev_batch_t* dev, double* aln_probs, int32_t* seeds)
 /* Device pointer to the batch's aln_probs buffer (same layout), for chaining
  * into hipstr_post_run without a host round trip.  The device buffer holds 0 where the host contract
  * says "untouched" (reads or alleles that were not realigned): chain it only for batches that realign
- * everything, or merge on the host (hipstr_hmm_fetch) when earlier values must survive. */
+ * everything and whose reads are their own pools; hipstr_rm_scatter (below) expands a pooled batch's rows to its reads and merges
+ * them into what earlier rounds left, on the device. */
 double* hipstr_hmm_dev_aln_probs(hipstr_dev_batch_t* dev);
 
 /* One-shot convenience = upload + align + fetch + free: the drop-in for
@@ -554,6 +555,57 @@ int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read
                               const int32_t* best_hap, const int32_t* hap_to_allele /* [sum A_l] */, const int32_t* allele_bp_diff /* [sum V_l], by variant */,
                               const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop /* [n_loci] */,
                               int32_t* n_stutter, int32_t* n_flank_indel /* [n_samp] */, int32_t* ml_bp /* [n_reads] */);
+
+/*
+ * The read x haplotype matrix of a batch of loci, resident on the device between the rounds of SeqStutterGenotyper::genotype
+ * (seq_stutter_genotyper.cpp:603-671): log_aln_probs_ (R x A per locus, un-pooled reads; genotyper.h:33) and seed_positions_, in the layout
+ * of hipstr_post_batch_t::log_aln_probs.  The forward pass writes one row per POOLED read (hipstr_hmm_align, P x A); the posteriors, the
+ * genotype calls and hipstr_post_assign read one row per read.  The calls below keep the matrix where it lies: one batch can go
+ *   align -> hipstr_rm_scatter -> hipstr_post_upload(pb with log_aln_probs = NULL, hipstr_rm_dev_log_aln_probs(rm)) -> launch / assign -> traces
+ *   -> new alleles: hipstr_rm_remap -> align only those -> hipstr_rm_scatter -> posteriors ...
+ * without the matrix leaving the device.  The layout — reads per locus, each read's pool (pool_index_, read_pooler.cpp:3-20), the second
+ * mates (second_mate_, seq_stutter_genotyper.cpp:499-507) — is fixed at creation and copied; the haplotype counts change with hipstr_rm_remap.
+ * Device and pinned blocks come from the context's caches: no allocation in steady state.
+ */
+typedef struct hipstr_read_matrix hipstr_read_matrix_t;
+typedef struct hipstr_read_layout {
+  int32_t        n_loci;
+  const int32_t* n_alleles;    /* [n_loci]   A_l                                                              */
+  const int32_t* read_off;     /* [n_loci+1] prefix sums of the un-pooled reads (== hipstr_post_batch_t)      */
+  const int32_t* pool_index;   /* [n_reads]  pool of the read within its locus (pool_index_)                  */
+  const uint8_t* second_mate;  /* [n_reads]  second_mate_, or NULL = none                                     */
+} hipstr_read_layout_t;
+/* init_ll: [sum R_l*A_l] or NULL = every entry -100000, the value the reference gives columns it has not aligned yet
+ * (seq_stutter_genotyper.cpp:374); init_seeds: [n_reads] or NULL = every seed -1.  Refused (NULL + hipstr_last_error()): negative counts,
+ * read_off that does not ascend from 0, a negative pool_index, second_mate set on the first read of a locus (its first mate, read i-1 of
+ * :555, would belong to another locus) or on two consecutive reads — the reference produces neither. */
+hipstr_read_matrix_t* hipstr_rm_create(const hipstr_read_layout_t* layout, const double* init_ll, const int32_t* init_seeds);
+/* The second half of SeqStutterGenotyper::calc_hap_aln_probs (seq_stutter_genotyper.cpp:530-564) on a batch hipstr_hmm_align has run on
+ * (the first half, :522-528, is upload + align).  For every read i with copy_read[i] (NULL = all): seeds[i] = the seed of its pool, and
+ * M[i][j] = the pool's row for every haplotype j the batch realigned (its realign_hap; :532-543); then for every second mate i with
+ * copy_read[i], rows i-1 and i both become M[i-1][j] + M[i][j] for the realigned j (:551-564) — row i-1 as it then lies: freshly copied if
+ * copy_read[i-1], the resident value otherwise.  Everything else keeps its value.  A pool without a seed contributes its row of zeros
+ * (HapAligner.cpp:333-337).  Asynchronous, ordered behind the batch's last pass; hipstr_post_launch / hipstr_post_assign on a run that was
+ * given the matrix' pointer are ordered behind the scatter without the caller synchronising, as long as everything runs on the library's
+ * own streams (a pass launched on a stream of the caller's makes this call wait for the device instead).  The caller keeps a posterior run
+ * on the matrix from being launched while a scatter of ANOTHER thread is being queued.
+ * Refused (non-zero + hipstr_last_error(), nothing launched): a batch that was never aligned, n_loci or a locus' n_alleles that disagrees
+ * with the batch, a pool_index outside the batch's pooled reads of that locus, copy_read[i] set for a read whose pool was not realigned
+ * (the reference would copy memory process_reads never wrote, :526-542). */
+int  hipstr_rm_scatter(hipstr_read_matrix_t* rm, hipstr_dev_batch_t* dev, const uint8_t* copy_read /* [n_reads] or NULL = all */);
+/* The column re-layout of SeqStutterGenotyper::add_and_remove_alleles (seq_stutter_genotyper.cpp:371-386), per locus: a new matrix of
+ * new_n_alleles[l] columns filled with -100000, old column j copied to column allele_mapping[j] where that is >= 0 (allele_mapping:
+ * [sum of the OLD A_l], locus after locus; -1 = the haplotype is gone).  Seeds are unchanged.  THE DEVICE POINTER CHANGES: a
+ * hipstr_post_dev_t built on the old pointer must be freed before this call, and hipstr_rm_dev_log_aln_probs asked again after it.
+ * Returns when the new matrix is complete.  Refused: a count below 1, a mapping entry outside [-1, new A_l), two old columns mapped to
+ * one new column. */
+int  hipstr_rm_remap(hipstr_read_matrix_t* rm, const int32_t* new_n_alleles, const int32_t* allele_mapping);
+/* Device pointer of the matrix, for hipstr_post_upload / hipstr_post_run (layout of hipstr_post_batch_t::log_aln_probs). */
+const double* hipstr_rm_dev_log_aln_probs(hipstr_read_matrix_t* rm);
+/* Copies the matrix and / or the seeds back (either may be NULL), after everything queued on the matrix has run. */
+int  hipstr_rm_fetch(hipstr_read_matrix_t* rm, double* ll /* [sum R_l*A_l] */, int32_t* seeds /* [n_reads] */);
+/* Every hipstr_post_dev_t built on the matrix' pointer must have been freed. */
+void hipstr_rm_free(hipstr_read_matrix_t* rm);
 
 /* The diagnostics entry points (hipstr_debug_*: what the tests, the fuzzers and bench.py look inside the library with) are declared in
  * hipstr_hmm_debug.h — not part of the drop-in ABI; a build with -DHIPSTR_NO_DEBUG_ABI leaves them out of the library. */

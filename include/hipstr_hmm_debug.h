@@ -91,6 +91,12 @@ int hipstr_debug_em_plan(const hipstr_em_batch_t* batch, char* json, int cap);
  * out[3] 1 = hashed, 0 = direct. */
 int hipstr_debug_assign_plan(int32_t max_unit_reads, int64_t n_units, int64_t n_keys, int64_t n_reads, int64_t out[4]);
 
+/* Diagnostics (host only): the route hipstr_rm_scatter / hipstr_rm_remap give a locus of n_alleles haplotypes with n_items work items (mate groups
+ * of a scatter, rows of a remap; hipstr_amd/csrc/readmat_layout.h): out[0] 0 = narrow (n_alleles <= 32: several items packed into a wavefront),
+ * 1 = wide (an item has the wavefront), out[1] lanes per item, out[2] items per wavefront, out[3] wavefronts of the locus, out[4] column
+ * steps per lane (wide: ceil(n_alleles / 64)). */
+int hipstr_debug_rm_plan(int32_t n_alleles, int64_t n_items, int64_t out[5]);
+
 /* Diagnostics (host only): one entry {A, G, Bnd} of the tabulated closed form the STR kernel uses for a "simple" visiting
  * list (StutterAlignerClass.cpp:59-150 for a periodic block): with `bound` columns of the block in reach, a run of U0 equal
  * configurations at the block's right end and `tail` configurations in total, fast_log_sum_exp over the pushed values is
