@@ -355,6 +355,108 @@ class HipstrTraceOut(C.Structure):
                 ("cap_chars", C.c_int32)]
 
 
+class HipstrCensusRequest(C.Structure):
+    _fields_ = [("pooled", C.POINTER(HipstrBatch)), ("seed", _i32p), ("read_req", _i32p), ("n_req", C.c_int32), ("req_read", _i32p),
+                ("trace", C.POINTER(HipstrTraceOut)), ("hap_to_allele", _i32p * 3), ("sample_uncallable", _u8p), ("min_reads", C.c_int32),
+                ("min_frac", C.c_double)]
+
+
+class HipstrCensusOut(C.Structure):
+    _fields_ = [("cand_off", _i32p), ("cand_req", _i32p), ("cand_seq_off", _i32p), ("cand_seq", C.c_char_p), ("new_n_haps", C.POINTER(C.c_int64)),
+                ("n_spanning", _i32p), ("n_span_stutter", _i32p), ("called", _u8p), ("spanned", _u8p), ("cap_cand", C.c_int32), ("cap_chars", C.c_int32)]
+
+
+CENSUS_ROUTES = ("wave", "lds", "global")
+CENSUS_FILL = 0xAA      # what run_census fills called / spanned with before the call
+
+
+def census_trace(aln_start, aln_stop, stutter_size, str_seqs):
+    """Hand-made trace fields for run_census: str_seqs is a list of bytes, one per request."""
+    off = np.concatenate([[0], np.cumsum([len(x) for x in str_seqs])]).astype(np.int32) if len(str_seqs) else np.zeros(1, np.int32)
+    return dict(aln_start=aln_start, aln_stop=aln_stop, stutter_size=stutter_size, str_seq_off=off, str_seq=b"".join(str_seqs))
+
+
+def run_census(lib, pd_or_pb, bptr, seed, read_req, req_read, trace, hap_to_allele=(None, None, None), sample_uncallable=None, min_reads=0,
+               min_frac=0.0, cap_cand=None, cap_chars=None, n_samp=None, dev_ll=None):
+    """hipstr_post_census -> dict: "rc" (0, or 3 when cap_cand / cap_chars was too small: then only "cand_off" means anything), "cand_off",
+    "cand_req", "cand" (per locus the list of candidate strings, bytes), "new_n_haps", "n_spanning", "n_span_stutter", "called", "spanned"
+    (uint8 per option; CENSUS_FILL where the call wrote nothing).  pd_or_pb: a PostBatch (uploaded, launched and freed here; dev_ll = device
+    pointer of the likelihoods or None) or a hipstr_post_dev_t handle after hipstr_post_launch (then n_samp says how long the per-sample
+    outputs are).  bptr: the pooled batch (Batch.ptr / SynthBatch.ptr).  trace: dict with aln_start, aln_stop, stutter_size, str_seq_off and
+    str_seq (bytes, or run_trace(..., unpack=False)'s buffer).  Raises on any other failure."""
+    _sig(lib.hipstr_post_census, C.c_int, [C.c_void_p, C.POINTER(HipstrCensusRequest), C.POINTER(HipstrCensusOut)])
+    own = isinstance(pd_or_pb, PostBatch)
+    if own:
+        n_samp = int(pd_or_pb.samp_off[-1])
+    b = bptr.contents if hasattr(bptr, "contents") else (bptr._obj if hasattr(bptr, "_obj") else bptr)
+    nl = int(b.n_loci)
+    nopts = np.ctypeslib.as_array(b.blk_nopts, shape=(3 * nl,)) if nl else np.zeros(0, np.int32)
+    n_opts = int(nopts.sum())
+    i32 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.int32))
+    keep = dict(seed=i32(seed), read_req=i32(read_req), req_read=i32(req_read))
+    n_req = 0 if keep["req_read"] is None else len(keep["req_read"])
+    t = HipstrTraceOut()
+    for nm in ("aln_start", "aln_stop", "stutter_size", "str_seq_off"):
+        if trace is not None and trace.get(nm) is not None:
+            keep[nm] = i32(trace[nm]); setattr(t, nm, keep[nm].ctypes.data_as(_i32p))
+    if trace is not None and trace.get("str_seq") is not None:
+        keep["str_seq"] = trace["str_seq"]
+        t.str_seq = keep["str_seq"] if isinstance(keep["str_seq"], bytes) else C.cast(keep["str_seq"], C.c_char_p)
+    h2a = [i32(x) for x in hap_to_allele]
+    unc = None if sample_uncallable is None else np.ascontiguousarray(np.asarray(sample_uncallable, np.uint8))
+    rq = HipstrCensusRequest(C.cast(bptr, C.POINTER(HipstrBatch)) if not hasattr(bptr, "_obj") else C.pointer(bptr._obj), _ptr(keep["seed"], _i32p),
+                             _ptr(keep["read_req"], _i32p), n_req, _ptr(keep["req_read"], _i32p), C.pointer(t) if trace is not None else None,
+                             (_i32p * 3)(*[_ptr(x, _i32p) for x in h2a]), _ptr(unc, _u8p), int(min_reads), float(min_frac))
+    if cap_cand is None:
+        cap_cand = n_req
+    if cap_chars is None:
+        cap_chars = int(keep["str_seq_off"][-1]) if "str_seq_off" in keep and len(keep["str_seq_off"]) else 0
+    k = dict(cand_off=np.full(nl + 1, UNTOUCHED, np.int32), cand_req=np.full(max(cap_cand, 1), UNTOUCHED, np.int32),
+             cand_seq_off=np.full(max(cap_cand, 0) + 1, UNTOUCHED, np.int32), new_n_haps=np.full(max(nl, 1), UNTOUCHED, np.int64),
+             n_spanning=np.full(max(n_samp, 1), UNTOUCHED, np.int32), n_span_stutter=np.full(max(n_samp, 1), UNTOUCHED, np.int32),
+             called=np.full(max(n_opts, 1), CENSUS_FILL, np.uint8), spanned=np.full(max(n_opts, 1), CENSUS_FILL, np.uint8))
+    seq = C.create_string_buffer(max(cap_chars, 1))
+    o = HipstrCensusOut(k["cand_off"].ctypes.data_as(_i32p), k["cand_req"].ctypes.data_as(_i32p), k["cand_seq_off"].ctypes.data_as(_i32p),
+                        C.cast(seq, C.c_char_p), k["new_n_haps"].ctypes.data_as(C.POINTER(C.c_int64)), k["n_spanning"].ctypes.data_as(_i32p),
+                        k["n_span_stutter"].ctypes.data_as(_i32p), k["called"].ctypes.data_as(_u8p), k["spanned"].ctypes.data_as(_u8p),
+                        int(cap_cand), int(cap_chars))
+    pd = pd_or_pb
+    if own:
+        pd = lib.hipstr_post_upload(pd_or_pb.ptr, dev_ll)
+        if not pd:
+            raise RuntimeError("hipstr_post_upload failed: " + lib.hipstr_last_error().decode())
+    try:
+        rc = lib.hipstr_post_launch(pd, None) if own else 0
+        if rc != 0:
+            raise RuntimeError("hipstr_post_launch failed: " + lib.hipstr_last_error().decode())
+        rc = lib.hipstr_post_census(pd, C.byref(rq), C.byref(o))
+    finally:
+        if own:
+            lib.hipstr_post_free(pd)
+    if rc not in (0, 3):
+        raise RuntimeError("hipstr_post_census failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    out = dict(rc=rc, cand_off=k["cand_off"], new_n_haps=k["new_n_haps"][:nl], n_spanning=k["n_spanning"][:n_samp],
+               n_span_stutter=k["n_span_stutter"][:n_samp], called=k["called"][:n_opts], spanned=k["spanned"][:n_opts])
+    nc = int(k["cand_off"][nl]) if rc == 0 else 0
+    out["cand_req"] = k["cand_req"][:nc]
+    raw = seq.raw
+    flat = [raw[k["cand_seq_off"][i]:k["cand_seq_off"][i + 1]] for i in range(nc)]
+    out["cand"] = [flat[k["cand_off"][l]:k["cand_off"][l + 1]] for l in range(nl)] if rc == 0 else None
+    return out
+
+
+def census_plan(lib, n_req, n_reads):
+    """hipstr_debug_census_plan (host only) as a dict: the route of a locus of n_req requests and n_reads un-pooled reads and the compiled
+    limits of hipstr_amd/csrc/census_layout.h."""
+    _sig(lib.hipstr_debug_census_plan, C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)])
+    out = np.zeros(10, np.int64)
+    if lib.hipstr_debug_census_plan(int(n_req), int(n_reads), out.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
+        raise RuntimeError("hipstr_debug_census_plan failed: " + lib.hipstr_last_error().decode())
+    return dict(route=CENSUS_ROUTES[int(out[0])], ws_ints=int(out[1]), lanes=int(out[2]), loci_per_workgroup=int(out[3]), global_ints=int(out[4]),
+                thresholds=dict(HS_CENSUS_WAVE_REQS=int(out[5]), HS_CENSUS_WAVE_READS=int(out[6]), HS_CENSUS_LDS_INTS=int(out[7]),
+                                HS_CENSUS_THREADS=int(out[8]), HS_CENSUS_REQ_INTS=int(out[9])))
+
+
 TRACE_ASSEMBLE_DEVICE = 1      # HIPSTR_TRACE_ASSEMBLE_DEVICE
 
 

@@ -26,6 +26,7 @@
 #include "layout.h"
 #include "post_layout.h"
 #include "readmat_layout.h"
+#include "census_layout.h"
 #include "prep.h"
 #include "api_internal.h"
 
@@ -42,6 +43,11 @@ extern "C" __global__ void hs_assign_kernel(const hs_assign_dev_t* dp);
 extern "C" __global__ void hs_assign_kernel_wg(const hs_assign_dev_t* dp);
 extern "C" __global__ void hs_assign_scan_kernel(const hs_assign_dev_t* dp);
 extern "C" __global__ void hs_assign_requests_kernel(const hs_assign_dev_t* dp);
+extern "C" __global__ void hs_census_wave_kernel(const hs_census_dev_t* dp);
+extern "C" __global__ void hs_census_lds_kernel(const hs_census_dev_t* dp);
+extern "C" __global__ void hs_census_global_kernel(const hs_census_dev_t* dp);
+extern "C" __global__ void hs_census_scan_kernel(const hs_census_dev_t* dp);
+extern "C" __global__ void hs_census_emit_kernel(const hs_census_dev_t* dp);
 extern "C" __global__ void hs_rm_scatter_kernel(const hs_rm_scatter_t d);
 extern "C" __global__ void hs_rm_remap_kernel(const hs_rm_remap_t d);
 extern "C" __global__ void hs_rm_fill_kernel(double* p, int64_t n, double v);
@@ -1987,6 +1993,219 @@ int hipstr_debug_assign_plan(int32_t max_unit_reads, int64_t n_units, int64_t n_
   int hashed = 0;
   out[0] = hs_assign_waves_per_unit(max_unit_reads); out[1] = hs_assign_workgroups(n_units, (int)out[0]);
   out[2] = hs_assign_table_slots(n_keys, n_reads, &hashed); out[3] = hashed;
+  return 0;
+}
+#endif
+
+// ----------------------------------------------------------------------------- allele census
+namespace {
+// The loci of a census, their routes and everything the host derives for the device (host only); every refusal of hipstr_post_census.
+struct CensusPlan {
+  std::vector<hs_census_locus_t> loci;
+  std::vector<int32_t> list[3], read_samp, req_locus, o1_off;
+  std::string o1_seq;
+  int64_t ws_ints = 0, n_opts = 0, n_haps = 0;
+};
+int census_plan(const hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, CensusPlan& P){
+  const PostRun& R = pd->R;
+  const hipstr_batch_t* b = rq->pooled;
+  const size_t nl = pd->n_samples.size();
+  if ((size_t)b->n_loci != nl) return fail("hipstr_post_census: pooled->n_loci differs from the posterior batch's");
+  const hipstr_trace_out_t* tr = rq->trace;
+  const int32_t nq_all = rq->n_req;
+  // requests: grouped by locus, in locus order
+  P.req_locus.resize((size_t)nq_all);
+  std::vector<int32_t> req_begin(nl + 1, 0);
+  {
+    size_t l = 0;
+    const int32_t n_pooled = nl ? b->read_off[nl] : 0;
+    for (int32_t k = 0; k < nq_all; k++){
+      const int32_t pr = rq->req_read[k];
+      if (pr < 0 || pr >= n_pooled) return fail("hipstr_post_census: req_read outside the pooled reads");
+      while (l < nl && pr >= b->read_off[l+1]){ l++; req_begin[l] = k; }
+      if (pr < b->read_off[l]) return fail("hipstr_post_census: requests must be grouped by locus, in locus order");
+      P.req_locus[k] = (int32_t)l;
+    }
+    for (l++; l <= nl; l++) req_begin[l] = nq_all;
+    if (nq_all){
+      if (tr->str_seq_off[0] < 0) return fail("hipstr_post_census: str_seq_off must not be negative");
+      for (int32_t k = 0; k < nq_all; k++) if (tr->str_seq_off[k+1] < tr->str_seq_off[k]) return fail("hipstr_post_census: str_seq_off must not decrease");
+      if (tr->str_seq_off[nq_all] > 0 && !tr->str_seq) return fail("hipstr_post_census: trace output without str_seq");
+    }
+  }
+  P.loci.resize(nl); P.read_samp.assign((size_t)R.n_reads, 0); P.o1_off.push_back(0);
+  size_t ui = 0; int rend = 0; int64_t opt = 0;
+  for (size_t l = 0; l < nl; l++){
+    hs_census_locus_t& L = P.loci[l]; memset(&L, 0, sizeof L);
+    const int A = pd->n_alleles[l];
+    if ((int64_t)b->hap_off[l+1] - b->hap_off[l] != A) return fail("hipstr_post_census: pooled->hap_off disagrees with the posterior batch's allele counts");
+    L.n_alleles = A; L.hap_begin = b->hap_off[l]; L.haploid = pd->haploid[l] ? 1 : 0;
+    L.read_begin = rend; L.samp_begin = ui < R.units.size() ? R.units[ui].samp_index : (int32_t)R.n_samp; L.n_samp = pd->n_samples[l];
+    for (int s = 0; s < pd->n_samples[l]; s++, ui++){
+      const hs_post_unit_t& u = R.units[ui];
+      if (s == 0){ L.read_begin = u.read_begin; L.ll_off = u.ll_off; }
+      rend = u.read_begin + u.n_reads;
+      for (int r = u.read_begin; r < rend; r++) P.read_samp[r] = u.samp_index;
+    }
+    L.n_reads = rend - L.read_begin;
+    L.req_begin = req_begin[l]; L.n_req = req_begin[l+1] - req_begin[l];
+    L.blk_start = b->blk_start[3*l + 1]; L.blk_end = b->blk_end[3*l + 1];
+    for (int k = 0; k < 3; k++){
+      const int no = b->blk_nopts[3*l + k];
+      if (no < 1) return fail("hipstr_post_census: a block without options");
+      for (int o = 0; o < no; o++) if (b->opt_off[opt + o + 1] < b->opt_off[opt + o]) return fail("hipstr_post_census: opt_off must not decrease");
+      L.opt_begin[k] = (int32_t)opt; L.n_opts[k] = no;
+      if (k == 1){
+        L.o1_begin = (int32_t)P.o1_off.size() - 1;
+        for (int o = 0; o < no; o++){
+          P.o1_seq.append(b->seq + b->opt_off[opt + o], (size_t)(b->opt_off[opt + o + 1] - b->opt_off[opt + o]));
+          P.o1_off.push_back((int32_t)P.o1_seq.size());
+        }
+      }
+      opt += no;
+      if (rq->hap_to_allele[k])
+        for (int h = 0; h < A; h++){
+          const int32_t v = rq->hap_to_allele[k][L.hap_begin + h];
+          if (v < 0 || v >= no) return fail("hipstr_post_census: hap_to_allele entry outside its block's options");
+        }
+    }
+    if ((int64_t)L.n_samp*std::max(L.n_req, 1) >= INT32_MAX) return fail("hipstr_post_census: too many (sample, request) pairs in a locus");
+    for (int r = L.read_begin; r < rend; r++){
+      const int32_t k = rq->read_req[r];
+      if (k < -1 || k >= nq_all) return fail("hipstr_post_census: read_req outside [-1, n_req)");
+      if (k < 0) continue;
+      if (P.req_locus[k] != (int32_t)l) return fail("hipstr_post_census: a read's request belongs to another locus");
+      if (rq->seed[r] >= 0 && tr->aln_start[k] < L.blk_start && tr->aln_stop[k] > L.blk_end && tr->stutter_size[k] == HIPSTR_NO_STR_DATA)
+        return fail("hipstr_post_census: a spanning request without STR data (AlignmentTrace::stutter_size asserts)");
+    }
+    const int route = hs_census_route(L.n_req, L.n_reads);
+    if (route == HS_CENSUS_ROUTE_GLOBAL){ L.ws_off = P.ws_ints; P.ws_ints += hs_census_ws_stride(L.n_req, L.n_reads); }
+    P.list[route].push_back((int32_t)l);
+  }
+  P.n_opts = opt; P.n_haps = nl ? b->hap_off[nl] : 0;
+  return 0;
+}
+}  // namespace
+
+int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, hipstr_census_out_t* out){
+  if (!pd || !rq || !out || !rq->pooled || !rq->seed || !rq->read_req) return fail("null argument");
+  const hipstr_batch_t* b = rq->pooled;
+  if (b->n_loci < 0 || (b->n_loci && (!b->blk_start || !b->blk_end || !b->blk_nopts || !b->opt_off || !b->seq || !b->hap_off || !b->read_off))) return fail("null argument");
+  if (rq->n_req < 0) return fail("hipstr_post_census: negative n_req");
+  if (rq->n_req && (!rq->req_read || !rq->trace || !rq->trace->aln_start || !rq->trace->aln_stop || !rq->trace->stutter_size || !rq->trace->str_seq_off))
+    return fail("hipstr_post_census: trace output without aln_start / aln_stop / stutter_size / str_seq_off");
+  const bool any_h2a = rq->hap_to_allele[0] || rq->hap_to_allele[1] || rq->hap_to_allele[2];
+  if (!out->cand_off || !out->cand_seq_off || !out->new_n_haps || !out->n_spanning || !out->n_span_stutter || out->cap_cand < 0 || out->cap_chars < 0 ||
+      (out->cap_cand && !out->cand_req) || (out->cap_chars && !out->cand_seq) || (any_h2a && !out->called) || (rq->hap_to_allele[1] && !out->spanned))
+    return fail("null output array");
+  if (rq->min_reads < 0 || !(rq->min_frac >= 0)) return fail("hipstr_post_census: min_reads and min_frac must not be negative");
+  if (!pd->launched) return fail("hipstr_post_census needs the posteriors: call hipstr_post_launch first");
+  PostRun& R = pd->R;
+  CensusPlan P;
+  if (census_plan(pd, rq, P)) return 1;
+  const size_t nl = P.loci.size(), n = (size_t)R.n_reads, ns = (size_t)R.n_samp, nq = (size_t)rq->n_req, no = (size_t)P.n_opts, nh = (size_t)P.n_haps;
+  const hipstr_trace_out_t* tr = rq->trace;
+  if (bind(R.ctx)) return 1;
+  Ctx* ctx = R.ctx;
+  const size_t cap = std::min((size_t)out->cap_cand, nq);                 // (a request makes at most one candidate)
+
+  hipstr::HostArena ar;
+  const size_t o_loci = ar.add(P.loci.data(), nl*sizeof(hs_census_locus_t)),
+               o_list[3] = { ar.add(P.list[0].data(), P.list[0].size()*4), ar.add(P.list[1].data(), P.list[1].size()*4), ar.add(P.list[2].data(), P.list[2].size()*4) },
+               o_seed = ar.add(rq->seed, n*4), o_rreq = ar.add(rq->read_req, n*4), o_rsamp = ar.add(P.read_samp.data(), n*4),
+               o_start = ar.add(nq ? tr->aln_start : NULL, nq*4), o_stop = ar.add(nq ? tr->aln_stop : NULL, nq*4), o_stut = ar.add(nq ? tr->stutter_size : NULL, nq*4),
+               o_soff = ar.add(nq ? tr->str_seq_off : NULL, nq ? (nq + 1)*4 : 0), o_sseq = ar.add(nq ? tr->str_seq : NULL, nq ? (size_t)tr->str_seq_off[nq] : 0),
+               o_rloc = ar.add(P.req_locus.data(), nq*4), o_o1off = ar.add(P.o1_off.data(), P.o1_off.size()*4), o_o1seq = ar.add(P.o1_seq.data(), P.o1_seq.size()),
+               o_h2a[3] = { ar.add(rq->hap_to_allele[0], rq->hap_to_allele[0] ? nh*4 : 0), ar.add(rq->hap_to_allele[1], rq->hap_to_allele[1] ? nh*4 : 0),
+                            ar.add(rq->hap_to_allele[2], rq->hap_to_allele[2] ? nh*4 : 0) },
+               o_unc = ar.add(rq->sample_uncallable, rq->sample_uncallable ? ns : 0);
+  hs_census_dev_t h; memset(&h, 0, sizeof h);
+  const size_t o_args = ar.add(&h, sizeof h);
+  if (ar.reserve(ctx)) return 1;
+  // results, back to back (one copy home), then what stays on the device
+  size_t tot = 0;
+  auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
+  const size_t r_coff = take((nl + 1)*4), r_creq = take(cap*4), r_nsp = take(ns*4), r_nss = take(ns*4), r_called = take(no), r_spanned = take(no);
+  const size_t res_bytes = tot;
+  const size_t d_count = take(nl*4), d_has = take(ns), d_rank = take(nq*4), d_ws = take((size_t)P.ws_ints*4);
+  struct Blocks { Ctx* c; hipStream_t st; char* dev = NULL; char* pin = NULL;
+                  ~Blocks(){ if (dev || pin) hipStreamSynchronize(st); if (dev) c->dev_cache.put(dev); if (pin) c->pin_cache.put(pin); } } B{ctx, R.stream};
+  B.dev = (char*)ctx->dev_cache.get(tot);
+  if (!B.dev) return 1;
+  B.pin = (char*)ctx->pin_cache.get(res_bytes);
+  if (!B.pin) return 1;
+  h.loci = ar.at<hs_census_locus_t>(o_loci);
+  for (int k = 0; k < 3; k++){
+    h.list[k] = ar.at<int32_t>(o_list[k]); h.n_list[k] = (int32_t)P.list[k].size();
+    h.h2a[k] = rq->hap_to_allele[k] ? ar.at<int32_t>(o_h2a[k]) : NULL;
+  }
+  h.n_loci = (int32_t)nl; h.n_req = (int32_t)nq; h.cap_cand = (int32_t)cap;
+  h.log_aln_probs = R.h.log_aln_probs; h.log_p1 = R.h.log_p1; h.log_p2 = R.h.log_p2; h.map_gt = R.h.map_gt;
+  h.seed = ar.at<int32_t>(o_seed); h.read_req = ar.at<int32_t>(o_rreq); h.read_samp = ar.at<int32_t>(o_rsamp);
+  h.aln_start = ar.at<int32_t>(o_start); h.aln_stop = ar.at<int32_t>(o_stop); h.stutter_size = ar.at<int32_t>(o_stut);
+  h.str_seq_off = ar.at<int32_t>(o_soff); h.str_seq = ar.at<char>(o_sseq); h.req_locus = ar.at<int32_t>(o_rloc);
+  h.o1_off = ar.at<int32_t>(o_o1off); h.o1_seq = ar.at<char>(o_o1seq);
+  h.uncallable = rq->sample_uncallable ? ar.at<uint8_t>(o_unc) : NULL;
+  h.min_reads = rq->min_reads == 0 ? 2 : rq->min_reads; h.min_frac = rq->min_frac == 0 ? 0.15 : rq->min_frac;      // seq_stutter_genotyper.cpp:869
+  h.cand_off = (int32_t*)(B.dev + r_coff); h.cand_req = (int32_t*)(B.dev + r_creq);
+  h.n_spanning = (int32_t*)(B.dev + r_nsp); h.n_span_stutter = (int32_t*)(B.dev + r_nss);
+  h.called = (uint8_t*)(B.dev + r_called); h.spanned = (uint8_t*)(B.dev + r_spanned);
+  h.cand_count = (int32_t*)(B.dev + d_count); h.has_read = (uint8_t*)(B.dev + d_has); h.req_rank = (int32_t*)(B.dev + d_rank); h.ws = (int32_t*)(B.dev + d_ws);
+  if (pd->foreign_stream) HS_HIP(hipDeviceSynchronize());          // the posterior kernel may still be running on a stream of the caller's
+  hipStream_t st = R.stream;
+  if (rm_order_behind(R.h.log_aln_probs, st)) return 1;
+  if (ar.send(st)) return 1;
+  const hs_census_dev_t* d_args = ar.at<hs_census_dev_t>(o_args);
+  HS_HIP(hipMemsetAsync(B.dev + r_nsp, 0, res_bytes - r_nsp, st));                 // the counts and the marks
+  HS_HIP(hipMemsetAsync(B.dev + d_count, 0, d_rank - d_count, st));                // candidates per locus, the samples' flags
+  if (!P.list[0].empty()) hipLaunchKernelGGL(hs_census_wave_kernel, dim3((unsigned)hs_census_workgroups(0, (int64_t)P.list[0].size())), dim3(HS_CENSUS_THREADS), 0, st, d_args);
+  if (!P.list[1].empty()) hipLaunchKernelGGL(hs_census_lds_kernel, dim3((unsigned)P.list[1].size()), dim3(HS_CENSUS_THREADS), 0, st, d_args);
+  if (!P.list[2].empty()) hipLaunchKernelGGL(hs_census_global_kernel, dim3((unsigned)P.list[2].size()), dim3(HS_CENSUS_THREADS), 0, st, d_args);
+  hipLaunchKernelGGL(hs_census_scan_kernel, dim3(1), dim3(HS_CENSUS_THREADS), 0, st, d_args);
+  if (nq) hipLaunchKernelGGL(hs_census_emit_kernel, dim3((unsigned)((nq + HS_CENSUS_THREADS - 1)/HS_CENSUS_THREADS)), dim3(HS_CENSUS_THREADS), 0, st, d_args);
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(B.pin, B.dev, res_bytes, hipMemcpyDeviceToHost, st));
+  HS_HIP(hipstr::wait_stream(st));
+  const int32_t* coff = (const int32_t*)(B.pin + r_coff);
+  const int32_t* creq = (const int32_t*)(B.pin + r_creq);
+  memcpy(out->cand_off, coff, (nl + 1)*4);
+  const int32_t n_cand = coff[nl];
+  if (n_cand > out->cap_cand){ fail("candidate arrays too small: cand_off[n_loci] holds the number needed"); return 3; }
+  int64_t chars = 0;
+  for (int32_t k = 0; k < n_cand; k++) chars += tr->str_seq_off[creq[k] + 1] - tr->str_seq_off[creq[k]];
+  if (chars > out->cap_chars){ fail("candidate string pool too small: cap_chars of str_seq_off[n_req] always holds it"); return 3; }
+  // the candidates' strings are the caller's own bytes: copied here from trace->str_seq in the order the device fixed
+  out->cand_seq_off[0] = 0;
+  for (int32_t k = 0; k < n_cand; k++){
+    const int32_t q = creq[k], len = tr->str_seq_off[q+1] - tr->str_seq_off[q];
+    out->cand_req[k] = q;
+    if (len) memcpy(out->cand_seq + out->cand_seq_off[k], tr->str_seq + tr->str_seq_off[q], (size_t)len);
+    out->cand_seq_off[k+1] = out->cand_seq_off[k] + len;
+  }
+  for (size_t l = 0; l < nl; l++){                                                // :583-584, integer division as written
+    const int64_t n1 = P.loci[l].n_opts[1];
+    out->new_n_haps[l] = (int64_t)P.loci[l].n_alleles / n1 * (n1 + (coff[l+1] - coff[l]));
+  }
+  memcpy(out->n_spanning, B.pin + r_nsp, ns*4); memcpy(out->n_span_stutter, B.pin + r_nss, ns*4);
+  for (size_t l = 0; l < nl; l++)
+    for (int k = 0; k < 3; k++)
+      if (rq->hap_to_allele[k]){
+        const hs_census_locus_t& L = P.loci[l];
+        memcpy(out->called + L.opt_begin[k], B.pin + r_called + L.opt_begin[k], (size_t)L.n_opts[k]);
+        if (k == 1) memcpy(out->spanned + L.opt_begin[k], B.pin + r_spanned + L.opt_begin[k], (size_t)L.n_opts[k]);
+      }
+  return 0;
+}
+
+#ifndef HIPSTR_NO_DEBUG_ABI
+// Diagnostics (host only): the route hipstr_post_census gives a locus of n_req requests and n_reads un-pooled reads (census_layout.h).
+int hipstr_debug_census_plan(int64_t n_req, int64_t n_reads, int64_t out[10]){
+  if (!out || n_req < 0 || n_reads < 0) return fail("bad argument");
+  const int route = hs_census_route(n_req, n_reads);
+  out[0] = route; out[1] = hs_census_ws_ints(n_req, n_reads);
+  out[2] = route == HS_CENSUS_ROUTE_WAVE ? 64 : HS_CENSUS_THREADS; out[3] = route == HS_CENSUS_ROUTE_WAVE ? HS_CENSUS_THREADS/64 : 1;
+  out[4] = route == HS_CENSUS_ROUTE_GLOBAL ? hs_census_ws_stride(n_req, n_reads) : 0;
+  out[5] = HS_CENSUS_WAVE_REQS; out[6] = HS_CENSUS_WAVE_READS; out[7] = HS_CENSUS_LDS_INTS; out[8] = HS_CENSUS_THREADS; out[9] = HS_CENSUS_REQ_INTS;
   return 0;
 }
 #endif

@@ -557,6 +557,69 @@ int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read
                               int32_t* n_stutter, int32_t* n_flank_indel /* [n_samp] */, int32_t* ml_bp /* [n_reads] */);
 
 /*
+ * The allele census between two rounds of SeqStutterGenotyper::genotype (seq_stutter_genotyper.cpp:603-671): what decides the next round's
+ * allele set, on a resident hipstr_post_dev_t after hipstr_post_launch — the likelihood matrix is read where it lies (host array or device
+ * pointer given at upload, e.g. hipstr_rm_dev_log_aln_probs), never fetched.  Two functions of the reference in one call:
+ *   get_stutter_candidate_alleles (:843-879, driven by id_and_align_to_stutter_alleles :570-601) -> cand_*, new_n_haps, n_spanning, n_span_stutter
+ *   get_unused_alleles (:229-315; called at :649, :658 and :207)                                 -> called, spanned
+ * A read HAS A TRACE iff seed >= 0 and read_req >= 0 (traced_alns[r] != NULL); its trace SPANS block 1 iff aln_start < blk_start and
+ * aln_stop > blk_end of its request, both strict (:856-857, :274-275).
+ * Candidates: over the reads with a spanning trace n_spanning[s]++ for the read's sample s (:860) and, if the request's stutter_size != 0,
+ *   the count of the pair (s, CONTENT of the request's str_seq) goes up by one (:858-859) — the key is the string, not the request: requests
+ *   of different pools or haplotypes with equal str_seq feed one count, the same string in two samples is two counts.  A pair qualifies iff
+ *   count >= min_reads and 1.0*count/n_spanning[s] >= min_frac (:869: one double division, compared as written) and block 1 does not hold the
+ *   string among its options (HapBlock::contains, :870).  A locus' candidates are the qualifying strings, each once, in
+ *   orderByLengthAndSequence order (stringops.cpp:35-39: by length, then bytewise; :582); the empty string is a legal key.
+ * Called: for every sample that has a read with seed >= 0, is not sample_uncallable and has a MAP pair (map_gt not -1), the options of hap_a
+ *   and of hap_b are marked (:293-301), for every block with a hap_to_allele.  UNLIKE THE REFERENCE (:255-256) blocks with one option are
+ *   written too: their option 0 simply ends up 0 or 1.
+ * Spanned (block 1 only): per read with a spanning trace whose request has stutter_size == 0: best = hap_a; if the locus is not haploid and
+ *   hap_a != hap_b, with v1 = log_p1 + LL[hap_a], v2 = log_p2 + LL[hap_b] (no LOG_ONE_HALF): if fabs(v1 - v2) > 1e-10 (TOLERANCE,
+ *   mathops.cpp:10) best = v1 > v2 ? hap_a : hap_b (:280-284 — a third tie rule, neither HIPSTR_ASSIGN_VCF's nor HIPSTR_ASSIGN_RETRACE's);
+ *   spanned[hap_to_allele[1][best]] = 1.  Reads of a sample without a MAP pair mark nothing.
+ * called / spanned are zeroed by the call for the blocks it writes and left untouched for blocks whose hap_to_allele is NULL; the caller applies
+ * allele_index >= 1 and the check_* choice of :305-311.  Building the new Haplotype and allele_mapping from the candidates stays with the caller.
+ * Refused (non-zero, hipstr_last_error(); checked on the host before any launch, nothing is written): a run that was not launched, pooled->n_loci
+ * that differs from the run's, hap_off that disagrees with the run's allele counts, read_req outside [-1, n_req), a read whose request belongs to
+ * another locus, requests not grouped by locus in locus order (hipstr_post_assign emits them so), str_seq_off that decreases, a hap_to_allele
+ * entry outside its block's options, a spanning request with stutter_size == HIPSTR_NO_STR_DATA used by a read with a seed
+ * (AlignmentTrace::stutter_size asserts there).
+ * Returns 3 when cap_cand or cap_chars is too small: cand_off is filled (cand_off[n_loci] = candidates needed; cap_chars = str_seq_off[n_req]
+ * always suffices), nothing else is promised — hipstr_post_assign's convention.
+ * Only the five trace fields, the per-read and per-request indices, hap_to_allele and block 1's option strings are uploaded; the candidates'
+ * bytes are copied on the host from trace->str_seq in the order the device fixed.  Device and pinned blocks come from the context's caches: no
+ * allocation in steady state.
+ */
+typedef struct hipstr_census_request {
+  const hipstr_batch_t* pooled;     /* the round's pooled batch: only n_loci, blk_start, blk_end, blk_nopts, opt_off, seq, hap_off, read_off are read */
+  const int32_t* seed;              /* [n_reads] seed_positions_ of the un-pooled reads; < 0 = traced_alns[r] == NULL */
+  const int32_t* read_req;          /* [n_reads] request of the read: hipstr_post_assign(HIPSTR_ASSIGN_RETRACE)'s read_req; -1 for a skipped read */
+  int32_t        n_req;
+  const int32_t* req_read;          /* [n_req] as given to hipstr_hmm_trace: fixes every request's locus */
+  const hipstr_trace_out_t* trace;  /* only aln_start, aln_stop, stutter_size, str_seq_off, str_seq are read (host arrays) */
+  const int32_t* hap_to_allele[3];  /* per block: [sum A_l] haps_to_alleles(block) (:219-227), or NULL = this block's flags are not wanted */
+  const uint8_t* sample_uncallable; /* [n_samp] !call_sample_[s].empty(), or NULL = every sample callable */
+  int32_t  min_reads;               /* 0 = the reference's 2     (:869) */
+  double   min_frac;                /* 0 = the reference's 0.15  (:869) */
+} hipstr_census_request_t;
+typedef struct hipstr_census_out {
+  /* stutter candidates of block 1, per locus, unique, in orderByLengthAndSequence order */
+  int32_t* cand_off;       /* [n_loci+1] */
+  int32_t* cand_req;       /* [cap_cand] the lowest-numbered request of the locus whose str_seq is this candidate */
+  int32_t* cand_seq_off;   /* [cap_cand+1] */
+  char*    cand_seq;       /* [cap_chars] */
+  int64_t* new_n_haps;     /* [n_loci] num_combs / nopts(1) * (nopts(1) + candidates)  (:583-584, integer division as written) */
+  /* per sample, sample_total_ll's order */
+  int32_t* n_spanning;     /* [n_samp] sample_counts (:860) */
+  int32_t* n_span_stutter; /* [n_samp] spanning reads with stutter_size != 0 */
+  /* per option, opt_off's enumeration (locus-major, block-major, option-minor); untouched for blocks whose hap_to_allele is NULL */
+  uint8_t* called;         /* [n_opts] :293-301 */
+  uint8_t* spanned;        /* [n_opts] :265-291; written for block 1 only */
+  int32_t  cap_cand, cap_chars;
+} hipstr_census_out_t;
+int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, hipstr_census_out_t* out);
+
+/*
  * The read x haplotype matrix of a batch of loci, resident on the device between the rounds of SeqStutterGenotyper::genotype
  * (seq_stutter_genotyper.cpp:603-671): log_aln_probs_ (R x A per locus, un-pooled reads; genotyper.h:33) and seed_positions_, in the layout
  * of hipstr_post_batch_t::log_aln_probs.  The forward pass writes one row per POOLED read (hipstr_hmm_align, P x A); the posteriors, the

@@ -97,6 +97,14 @@ int hipstr_debug_assign_plan(int32_t max_unit_reads, int64_t n_units, int64_t n_
  * steps per lane (wide: ceil(n_alleles / 64)). */
 int hipstr_debug_rm_plan(int32_t n_alleles, int64_t n_items, int64_t out[5]);
 
+/* Diagnostics (host only): the route hipstr_post_census gives a locus of n_req requests and n_reads un-pooled reads
+ * (hipstr_amd/csrc/census_layout.h): out[0] 0 = a wavefront per locus (four loci per workgroup, workspace in LDS), 1 = a workgroup per locus
+ * with the workspace in LDS, 2 = a workgroup per locus with the workspace in a global block; out[1] dwords of the locus' workspace, out[2]
+ * lanes of the locus, out[3] loci per workgroup, out[4] dwords the locus takes of the global block (route 2, else 0); then the compiled
+ * limits: out[5] HS_CENSUS_WAVE_REQS, out[6] HS_CENSUS_WAVE_READS, out[7] HS_CENSUS_LDS_INTS, out[8] HS_CENSUS_THREADS, out[9]
+ * HS_CENSUS_REQ_INTS.  Used by tests/test_census_plan.py. */
+int hipstr_debug_census_plan(int64_t n_req, int64_t n_reads, int64_t out[10]);
+
 /* Diagnostics (host only): one entry {A, G, Bnd} of the tabulated closed form the STR kernel uses for a "simple" visiting
  * list (StutterAlignerClass.cpp:59-150 for a periodic block): with `bound` columns of the block in reach, a run of U0 equal
  * configurations at the block's right end and `tail` configurations in total, fast_log_sum_exp over the pushed values is
