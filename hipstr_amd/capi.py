@@ -377,14 +377,17 @@ def census_trace(aln_start, aln_stop, stutter_size, str_seqs):
 
 
 def run_census(lib, pd_or_pb, bptr, seed, read_req, req_read, trace, hap_to_allele=(None, None, None), sample_uncallable=None, min_reads=0,
-               min_frac=0.0, cap_cand=None, cap_chars=None, n_samp=None, dev_ll=None):
+               min_frac=0.0, cap_cand=None, cap_chars=None, n_samp=None, dev_ll=None, td=None):
     """hipstr_post_census -> dict: "rc" (0, or 3 when cap_cand / cap_chars was too small: then only "cand_off" means anything), "cand_off",
     "cand_req", "cand" (per locus the list of candidate strings, bytes), "new_n_haps", "n_spanning", "n_span_stutter", "called", "spanned"
     (uint8 per option; CENSUS_FILL where the call wrote nothing).  pd_or_pb: a PostBatch (uploaded, launched and freed here; dev_ll = device
     pointer of the likelihoods or None) or a hipstr_post_dev_t handle after hipstr_post_launch (then n_samp says how long the per-sample
     outputs are).  bptr: the pooled batch (Batch.ptr / SynthBatch.ptr).  trace: dict with aln_start, aln_stop, stutter_size, str_seq_off and
-    str_seq (bytes, or run_trace(..., unpack=False)'s buffer).  Raises on any other failure."""
+    str_seq (bytes, or run_trace(..., unpack=False)'s buffer).  td: a TraceDev instead of `trace` (then None): hipstr_post_census_dev reads
+    the five fields from the resident result.  Raises on any other failure."""
     _sig(lib.hipstr_post_census, C.c_int, [C.c_void_p, C.POINTER(HipstrCensusRequest), C.POINTER(HipstrCensusOut)])
+    _sig(lib.hipstr_post_census_dev, C.c_int, [C.c_void_p, C.POINTER(HipstrCensusRequest), C.c_void_p, C.POINTER(HipstrCensusOut)])
+    fn_name = "hipstr_post_census" if td is None else "hipstr_post_census_dev"
     own = isinstance(pd_or_pb, PostBatch)
     if own:
         n_samp = int(pd_or_pb.samp_off[-1])
@@ -409,6 +412,8 @@ def run_census(lib, pd_or_pb, bptr, seed, read_req, req_read, trace, hap_to_alle
                              (_i32p * 3)(*[_ptr(x, _i32p) for x in h2a]), _ptr(unc, _u8p), int(min_reads), float(min_frac))
     if cap_cand is None:
         cap_cand = n_req
+    if cap_chars is None and td is not None:
+        cap_chars = int(td.sizes()[1][1])
     if cap_chars is None:
         cap_chars = int(keep["str_seq_off"][-1]) if "str_seq_off" in keep and len(keep["str_seq_off"]) else 0
     k = dict(cand_off=np.full(nl + 1, UNTOUCHED, np.int32), cand_req=np.full(max(cap_cand, 1), UNTOUCHED, np.int32),
@@ -429,12 +434,14 @@ def run_census(lib, pd_or_pb, bptr, seed, read_req, req_read, trace, hap_to_alle
         rc = lib.hipstr_post_launch(pd, None) if own else 0
         if rc != 0:
             raise RuntimeError("hipstr_post_launch failed: " + lib.hipstr_last_error().decode())
-        rc = lib.hipstr_post_census(pd, C.byref(rq), C.byref(o))
+        rc = lib.hipstr_post_census(pd, C.byref(rq), C.byref(o)) if td is None else lib.hipstr_post_census_dev(pd, C.byref(rq), td.h, C.byref(o))
     finally:
         if own:
             lib.hipstr_post_free(pd)
     if rc not in (0, 3):
-        raise RuntimeError("hipstr_post_census failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+        e = RuntimeError("%s failed rc=%d: %s" % (fn_name, rc, lib.hipstr_last_error().decode()))
+        e.outputs = dict(k, cand_seq=seq.raw)          # what the refused call left in the output arrays (pre-filled above)
+        raise e
     out = dict(rc=rc, cand_off=k["cand_off"], new_n_haps=k["new_n_haps"][:nl], n_spanning=k["n_spanning"][:n_samp],
                n_span_stutter=k["n_span_stutter"][:n_samp], called=k["called"][:n_opts], spanned=k["spanned"][:n_opts])
     nc = int(k["cand_off"][nl]) if rc == 0 else 0
@@ -443,6 +450,139 @@ def run_census(lib, pd_or_pb, bptr, seed, read_req, req_read, trace, hap_to_alle
     flat = [raw[k["cand_seq_off"][i]:k["cand_seq_off"][i + 1]] for i in range(nc)]
     out["cand"] = [flat[k["cand_off"][l]:k["cand_off"][l + 1]] for l in range(nl)] if rc == 0 else None
     return out
+
+
+# ---- the resident traceback result (hipstr_hmm_trace_resident, hipstr_trace_dev_*): the constants are include/hipstr_hmm.h's HIPSTR_TRACE_F_*
+TRACE_F_SCALARS, TRACE_F_HAP_ALN, TRACE_F_STR_SEQ, TRACE_F_FLANKS, TRACE_F_INDELS, TRACE_F_SNPS, TRACE_F_STITCH, TRACE_F_ALL = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x7f
+# the arrays of every group: (name, kind, pool) — kind "f8" / "i4" per request, "off" an offset array, "i4p" / "chr" a pool array of pool `pool`
+TRACE_GROUPS = {
+    TRACE_F_SCALARS: [("ll", "f8", None), ("max_index", "i4", None), ("stutter_size", "i4", None), ("flank_ins", "i4", None), ("flank_del", "i4", None),
+                      ("aln_start", "i4", None), ("aln_stop", "i4", None)],
+    TRACE_F_HAP_ALN: [("hap_aln_off", "off", 0), ("hap_aln", "chr", 0)],
+    TRACE_F_STR_SEQ: [("str_seq_off", "off", 1), ("str_seq", "chr", 1)],
+    TRACE_F_FLANKS: [("flank_seq_off", "off", 2), ("flank_seq", "chr", 2)],
+    TRACE_F_INDELS: [("indel_off", "off", 3), ("indel_pos", "i4p", 3), ("indel_size", "i4p", 3)],
+    TRACE_F_SNPS: [("snp_off", "off", 4), ("snp_pos", "i4p", 4), ("snp_base", "chr", 4)],
+    TRACE_F_STITCH: [("cigar_off", "off", 5), ("cigar_op", "chr", 5), ("cigar_len", "i4p", 5), ("aln_str_off", "off", 6), ("aln_str", "chr", 6)],
+}
+TRACE_SENTINEL = 0x5A        # what trace_dev_fetch fills every byte of every array with before the call
+
+
+def _trace_dev_sigs(lib):
+    _sig(lib.hipstr_hmm_trace_resident, C.c_int, [_BP, C.c_int32, _i32p, _i32p, _i32p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)])
+    _sig(lib.hipstr_trace_dev_sizes, C.c_int, [C.c_void_p, _i32p, C.POINTER(C.c_int64)])
+    _sig(lib.hipstr_trace_dev_fetch, C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(HipstrTraceOut)])
+    _sig(lib.hipstr_trace_dev_free, None, [C.c_void_p])
+    _sig(lib.hipstr_debug_trace_dev_from_host, C.c_int, [C.POINTER(HipstrTraceOut), C.c_int32, C.POINTER(C.c_void_p)])
+    _sig(lib.hipstr_assign_trace_stats_dev, C.c_int, [_PBP, _i32p, C.c_void_p] + [_i32p] * 9)
+
+
+class TraceDev:
+    """A hipstr_trace_dev_t handle; close() frees it."""
+
+    def __init__(self, lib, h):
+        self.lib, self.h = lib, h
+
+    def sizes(self):
+        """(n_req, totals[7]) of hipstr_trace_dev_sizes."""
+        n = np.zeros(1, np.int32); tot = np.zeros(7, np.int64)
+        if self.lib.hipstr_trace_dev_sizes(self.h, n.ctypes.data_as(_i32p), tot.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
+            raise RuntimeError("hipstr_trace_dev_sizes failed: " + self.lib.hipstr_last_error().decode())
+        return int(n[0]), tot
+
+    def close(self):
+        if self.h:
+            self.lib.hipstr_trace_dev_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def run_trace_resident(lib, bptr, req_read, req_allele, hap_to_ref=None, req_seed=None, flags=0):
+    """hipstr_hmm_trace_resident -> TraceDev.  Raises with hipstr_last_error() when the call fails (the handle it left must then be NULL)."""
+    _trace_dev_sigs(lib)
+    rr = np.ascontiguousarray(np.asarray(req_read, np.int32)); aa = np.ascontiguousarray(np.asarray(req_allele, np.int32))
+    ss = None if req_seed is None else np.ascontiguousarray(np.asarray(req_seed, np.int32))
+    h2r = None if hap_to_ref is None else (C.c_char_p * len(hap_to_ref))(*hap_to_ref)
+    h = C.c_void_p(0xdead)           # (the call has to clear it on failure)
+    rc = lib.hipstr_hmm_trace_resident(bptr, len(rr), _ptr(rr, _i32p), _ptr(aa, _i32p), _ptr(ss, _i32p), h2r, int(flags), C.byref(h))
+    if rc != 0:
+        assert not h.value, "hipstr_hmm_trace_resident failed and left a handle"
+        raise RuntimeError("hipstr_hmm_trace_resident failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    assert h.value
+    return TraceDev(lib, h.value)
+
+
+def trace_dev_fetch(lib, td, fields=TRACE_F_ALL, cap=None, null_others=False):
+    """hipstr_trace_dev_fetch -> the dict of run_trace(..., unpack=False): numpy arrays and string buffers, every byte TRACE_SENTINEL before
+    the call.  cap: out->cap_chars (default: the largest pool, so everything fits); the buffers always hold the largest pool.  null_others:
+    the arrays of the groups not chosen are passed as NULL (they are still in the dict, untouched).  Raises when the call fails, with the dict
+    as the exception's `keep`."""
+    _trace_dev_sigs(lib)
+    n, tot = td.sizes()
+    room = max(int(tot.max()), 1)
+    o = HipstrTraceOut(); keep = {}
+    for bit, arrays in TRACE_GROUPS.items():
+        for nm, kind, pool in arrays:
+            if kind == "chr":
+                a = C.create_string_buffer(bytes([TRACE_SENTINEL]) * room, room)
+                ptr = C.cast(a, C.c_char_p)
+            else:
+                m = {"f8": n, "i4": n, "off": (2 * n if pool == 2 else n) + 1, "i4p": room}[kind]
+                a = np.frombuffer(bytes([TRACE_SENTINEL]) * (max(m, 1) * (8 if kind == "f8" else 4)), np.float64 if kind == "f8" else np.int32).copy()
+                ptr = a.ctypes.data_as(_f64p if kind == "f8" else _i32p)
+            keep[nm] = a
+            if (fields & bit) or not null_others:
+                setattr(o, nm, ptr)
+    o.cap_chars = int(room if cap is None else cap)
+    rc = lib.hipstr_trace_dev_fetch(td.h, int(fields), C.byref(o))
+    if rc != 0:
+        e = RuntimeError("hipstr_trace_dev_fetch failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+        e.keep = keep
+        raise e
+    return keep
+
+
+def trace_dev_from_host(lib, trace, n_req):
+    """hipstr_debug_trace_dev_from_host -> TraceDev.  trace: dict of hipstr_trace_out_t's arrays (integers: sequences; pools: bytes or a string
+    buffer); what is missing or None is an absent array."""
+    _trace_dev_sigs(lib)
+    t = HipstrTraceOut(); keep = []
+    for arrays in TRACE_GROUPS.values():
+        for nm, kind, pool in arrays:
+            v = trace.get(nm)
+            if v is None:
+                continue
+            if kind == "chr":
+                setattr(t, nm, v if isinstance(v, bytes) else C.cast(v, C.c_char_p)); keep.append(v)
+            else:
+                a = np.ascontiguousarray(np.asarray(v, np.float64 if kind == "f8" else np.int32)); keep.append(a)
+                setattr(t, nm, a.ctypes.data_as(_f64p if kind == "f8" else _i32p))
+    h = C.c_void_p(0xdead)
+    rc = lib.hipstr_debug_trace_dev_from_host(C.byref(t), int(n_req), C.byref(h))
+    if rc != 0:
+        assert not h.value
+        raise RuntimeError("hipstr_debug_trace_dev_from_host failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    return TraceDev(lib, h.value)
+
+
+def assign_trace_stats_dev(lib, pb, read_req, td, best_hap, hap_to_allele, allele_bp_diff, n_variants, region_start, region_stop):
+    """hipstr_assign_trace_stats_dev -> (n_stutter[n_samp], n_flank_indel[n_samp], ml_bp[n_reads]); the shape of run_assign_trace_stats with a
+    TraceDev in the trace's place."""
+    _trace_dev_sigs(lib)
+    i32 = lambda x: np.ascontiguousarray(np.asarray(x, np.int32))
+    n_reads = int(pb.a["read_off"][-1]) if len(pb.a["read_off"]) else 0
+    n_samp = int(pb.samp_off[-1])
+    a = [i32(x) for x in (read_req, best_hap, hap_to_allele, allele_bp_diff, n_variants, region_start, region_stop)]
+    ns = np.full(max(n_samp, 1), UNTOUCHED, np.int32); nf = np.full(max(n_samp, 1), UNTOUCHED, np.int32); ml = np.full(max(n_reads, 1), UNTOUCHED, np.int32)
+    p = lambda x: x.ctypes.data_as(_i32p)
+    rc = lib.hipstr_assign_trace_stats_dev(pb.ptr, p(a[0]), td.h, p(a[1]), p(a[2]), p(a[3]), p(a[4]), p(a[5]), p(a[6]), p(ns), p(nf), p(ml))
+    if rc != 0:
+        raise RuntimeError("hipstr_assign_trace_stats_dev failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    return ns[:n_samp], nf[:n_samp], ml[:n_reads]
 
 
 def census_plan(lib, n_req, n_reads):
@@ -863,6 +1003,8 @@ def load_hmm():
     _sig(lib.hipstr_rm_fetch, C.c_int, [C.c_void_p, _f64p, _i32p])
     _sig(lib.hipstr_rm_free, None, [C.c_void_p])
     _sig(lib.hipstr_debug_rm_plan, C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)])
+    _trace_dev_sigs(lib)
+    _sig(lib.hipstr_post_census_dev, C.c_int, [C.c_void_p, C.POINTER(HipstrCensusRequest), C.c_void_p, C.POINTER(HipstrCensusOut)])
     return lib
 
 

@@ -48,6 +48,9 @@ extern "C" __global__ void hs_census_lds_kernel(const hs_census_dev_t* dp);
 extern "C" __global__ void hs_census_global_kernel(const hs_census_dev_t* dp);
 extern "C" __global__ void hs_census_scan_kernel(const hs_census_dev_t* dp);
 extern "C" __global__ void hs_census_emit_kernel(const hs_census_dev_t* dp);
+extern "C" __global__ void hs_census_check_kernel(const hs_census_dev_t* dp);
+extern "C" __global__ void hs_census_gather_kernel(const hs_census_dev_t* dp);
+extern "C" __global__ void hs_trace_stats_kernel(const hs_tstat_dev_t* dp);
 extern "C" __global__ void hs_rm_scatter_kernel(const hs_rm_scatter_t d);
 extern "C" __global__ void hs_rm_remap_kernel(const hs_rm_remap_t d);
 extern "C" __global__ void hs_rm_fill_kernel(double* p, int64_t n, double v);
@@ -2006,12 +2009,12 @@ struct CensusPlan {
   std::string o1_seq;
   int64_t ws_ints = 0, n_opts = 0, n_haps = 0;
 };
-int census_plan(const hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, CensusPlan& P){
+// tr: the trace's host arrays, or NULL when they lie on the device (hipstr_post_census_dev: the checks of their values run there)
+int census_plan(const hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const hipstr_trace_out_t* tr, CensusPlan& P){
   const PostRun& R = pd->R;
   const hipstr_batch_t* b = rq->pooled;
   const size_t nl = pd->n_samples.size();
   if ((size_t)b->n_loci != nl) return fail("hipstr_post_census: pooled->n_loci differs from the posterior batch's");
-  const hipstr_trace_out_t* tr = rq->trace;
   const int32_t nq_all = rq->n_req;
   // requests: grouped by locus, in locus order
   P.req_locus.resize((size_t)nq_all);
@@ -2027,7 +2030,7 @@ int census_plan(const hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, 
       P.req_locus[k] = (int32_t)l;
     }
     for (l++; l <= nl; l++) req_begin[l] = nq_all;
-    if (nq_all){
+    if (nq_all && tr){
       if (tr->str_seq_off[0] < 0) return fail("hipstr_post_census: str_seq_off must not be negative");
       for (int32_t k = 0; k < nq_all; k++) if (tr->str_seq_off[k+1] < tr->str_seq_off[k]) return fail("hipstr_post_census: str_seq_off must not decrease");
       if (tr->str_seq_off[nq_all] > 0 && !tr->str_seq) return fail("hipstr_post_census: trace output without str_seq");
@@ -2075,7 +2078,7 @@ int census_plan(const hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, 
       if (k < -1 || k >= nq_all) return fail("hipstr_post_census: read_req outside [-1, n_req)");
       if (k < 0) continue;
       if (P.req_locus[k] != (int32_t)l) return fail("hipstr_post_census: a read's request belongs to another locus");
-      if (rq->seed[r] >= 0 && tr->aln_start[k] < L.blk_start && tr->aln_stop[k] > L.blk_end && tr->stutter_size[k] == HIPSTR_NO_STR_DATA)
+      if (tr && rq->seed[r] >= 0 && tr->aln_start[k] < L.blk_start && tr->aln_stop[k] > L.blk_end && tr->stutter_size[k] == HIPSTR_NO_STR_DATA)
         return fail("hipstr_post_census: a spanning request without STR data (AlignmentTrace::stutter_size asserts)");
     }
     const int route = hs_census_route(L.n_req, L.n_reads);
@@ -2087,12 +2090,18 @@ int census_plan(const hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, 
 }
 }  // namespace
 
-int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, hipstr_census_out_t* out){
-  if (!pd || !rq || !out || !rq->pooled || !rq->seed || !rq->read_req) return fail("null argument");
+namespace {
+// hipstr_post_census (td == NULL: the five trace fields are rq->trace's host arrays) and hipstr_post_census_dev (dev: they lie in td): one
+// plan, the same launches, one copy home.  Only the source of the five fields and of the candidates' bytes differs.
+int census_call(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const hipstr_trace_dev* td, bool dev, hipstr_census_out_t* out){
+  if (dev && rq && rq->trace) return fail("hipstr_post_census_dev: rq->trace must be NULL (the trace fields are the handle's)");
+  if (!pd || !rq || !out || (dev && !td) || !rq->pooled || !rq->seed || !rq->read_req) return fail("null argument");
   const hipstr_batch_t* b = rq->pooled;
   if (b->n_loci < 0 || (b->n_loci && (!b->blk_start || !b->blk_end || !b->blk_nopts || !b->opt_off || !b->seq || !b->hap_off || !b->read_off))) return fail("null argument");
   if (rq->n_req < 0) return fail("hipstr_post_census: negative n_req");
-  if (rq->n_req && (!rq->req_read || !rq->trace || !rq->trace->aln_start || !rq->trace->aln_stop || !rq->trace->stutter_size || !rq->trace->str_seq_off))
+  if (dev && rq->n_req != td->n_req) return fail("hipstr_post_census_dev: rq->n_req differs from the trace handle's");
+  if (rq->n_req && (!rq->req_read || (dev ? (!td->scal[3] || !td->scal[4] || !td->scal[0] || !td->off[1])
+                                          : (!rq->trace || !rq->trace->aln_start || !rq->trace->aln_stop || !rq->trace->stutter_size || !rq->trace->str_seq_off))))
     return fail("hipstr_post_census: trace output without aln_start / aln_stop / stutter_size / str_seq_off");
   const bool any_h2a = rq->hap_to_allele[0] || rq->hap_to_allele[1] || rq->hap_to_allele[2];
   if (!out->cand_off || !out->cand_seq_off || !out->new_n_haps || !out->n_spanning || !out->n_span_stutter || out->cap_cand < 0 || out->cap_chars < 0 ||
@@ -2101,10 +2110,11 @@ int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq,
   if (rq->min_reads < 0 || !(rq->min_frac >= 0)) return fail("hipstr_post_census: min_reads and min_frac must not be negative");
   if (!pd->launched) return fail("hipstr_post_census needs the posteriors: call hipstr_post_launch first");
   PostRun& R = pd->R;
+  if (dev && td->ctx != R.ctx) return fail("hipstr_post_census_dev: the trace handle lives on another device than the posteriors");
+  const hipstr_trace_out_t* tr = dev ? NULL : rq->trace;
   CensusPlan P;
-  if (census_plan(pd, rq, P)) return 1;
+  if (census_plan(pd, rq, tr, P)) return 1;
   const size_t nl = P.loci.size(), n = (size_t)R.n_reads, ns = (size_t)R.n_samp, nq = (size_t)rq->n_req, no = (size_t)P.n_opts, nh = (size_t)P.n_haps;
-  const hipstr_trace_out_t* tr = rq->trace;
   if (bind(R.ctx)) return 1;
   Ctx* ctx = R.ctx;
   const size_t cap = std::min((size_t)out->cap_cand, nq);                 // (a request makes at most one candidate)
@@ -2113,8 +2123,10 @@ int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq,
   const size_t o_loci = ar.add(P.loci.data(), nl*sizeof(hs_census_locus_t)),
                o_list[3] = { ar.add(P.list[0].data(), P.list[0].size()*4), ar.add(P.list[1].data(), P.list[1].size()*4), ar.add(P.list[2].data(), P.list[2].size()*4) },
                o_seed = ar.add(rq->seed, n*4), o_rreq = ar.add(rq->read_req, n*4), o_rsamp = ar.add(P.read_samp.data(), n*4),
-               o_start = ar.add(nq ? tr->aln_start : NULL, nq*4), o_stop = ar.add(nq ? tr->aln_stop : NULL, nq*4), o_stut = ar.add(nq ? tr->stutter_size : NULL, nq*4),
-               o_soff = ar.add(nq ? tr->str_seq_off : NULL, nq ? (nq + 1)*4 : 0), o_sseq = ar.add(nq ? tr->str_seq : NULL, nq ? (size_t)tr->str_seq_off[nq] : 0),
+               // the five trace fields travel only when they are the host's
+               o_start = ar.add(nq && tr ? tr->aln_start : NULL, tr ? nq*4 : 0), o_stop = ar.add(nq && tr ? tr->aln_stop : NULL, tr ? nq*4 : 0),
+               o_stut = ar.add(nq && tr ? tr->stutter_size : NULL, tr ? nq*4 : 0), o_soff = ar.add(nq && tr ? tr->str_seq_off : NULL, nq && tr ? (nq + 1)*4 : 0),
+               o_sseq = ar.add(nq && tr ? tr->str_seq : NULL, nq && tr ? (size_t)tr->str_seq_off[nq] : 0),
                o_rloc = ar.add(P.req_locus.data(), nq*4), o_o1off = ar.add(P.o1_off.data(), P.o1_off.size()*4), o_o1seq = ar.add(P.o1_seq.data(), P.o1_seq.size()),
                o_h2a[3] = { ar.add(rq->hap_to_allele[0], rq->hap_to_allele[0] ? nh*4 : 0), ar.add(rq->hap_to_allele[1], rq->hap_to_allele[1] ? nh*4 : 0),
                             ar.add(rq->hap_to_allele[2], rq->hap_to_allele[2] ? nh*4 : 0) },
@@ -2126,7 +2138,11 @@ int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq,
   size_t tot = 0;
   auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
   const size_t r_coff = take((nl + 1)*4), r_creq = take(cap*4), r_nsp = take(ns*4), r_nss = take(ns*4), r_called = take(no), r_spanned = take(no);
+  // (resident trace fields: what the check found, the candidates' offsets and byte count; their bytes last: only those in use come home)
+  const size_t dev_chars = dev ? (size_t)std::min<int64_t>(out->cap_chars, td->totals[1]) : 0;
+  const size_t r_check = dev ? take(8) : 0, r_cchars = dev ? take(8) : 0, r_csoff = dev ? take((cap + 1)*4) : 0;
   const size_t res_bytes = tot;
+  const size_t r_cseq = dev ? take(dev_chars) : 0;
   const size_t d_count = take(nl*4), d_has = take(ns), d_rank = take(nq*4), d_ws = take((size_t)P.ws_ints*4);
   struct Blocks { Ctx* c; hipStream_t st; char* dev = NULL; char* pin = NULL;
                   ~Blocks(){ if (dev || pin) hipStreamSynchronize(st); if (dev) c->dev_cache.put(dev); if (pin) c->pin_cache.put(pin); } } B{ctx, R.stream};
@@ -2142,8 +2158,15 @@ int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq,
   h.n_loci = (int32_t)nl; h.n_req = (int32_t)nq; h.cap_cand = (int32_t)cap;
   h.log_aln_probs = R.h.log_aln_probs; h.log_p1 = R.h.log_p1; h.log_p2 = R.h.log_p2; h.map_gt = R.h.map_gt;
   h.seed = ar.at<int32_t>(o_seed); h.read_req = ar.at<int32_t>(o_rreq); h.read_samp = ar.at<int32_t>(o_rsamp);
-  h.aln_start = ar.at<int32_t>(o_start); h.aln_stop = ar.at<int32_t>(o_stop); h.stutter_size = ar.at<int32_t>(o_stut);
-  h.str_seq_off = ar.at<int32_t>(o_soff); h.str_seq = ar.at<char>(o_sseq); h.req_locus = ar.at<int32_t>(o_rloc);
+  if (dev){
+    h.aln_start = td->scal[3]; h.aln_stop = td->scal[4]; h.stutter_size = td->scal[0]; h.str_seq_off = td->off[1]; h.str_seq = td->arr[1];
+    h.check = (int32_t*)(B.dev + r_check); h.n_reads = (int32_t)n; h.check_offsets = td->checked ? 0 : 1; h.str_total = td->totals[1];
+    h.cand_seq_off = (int32_t*)(B.dev + r_csoff); h.cand_seq = B.dev + r_cseq; h.cand_chars = (int64_t*)(B.dev + r_cchars); h.cap_chars = out->cap_chars;
+  } else {
+    h.aln_start = ar.at<int32_t>(o_start); h.aln_stop = ar.at<int32_t>(o_stop); h.stutter_size = ar.at<int32_t>(o_stut);
+    h.str_seq_off = ar.at<int32_t>(o_soff); h.str_seq = ar.at<char>(o_sseq);
+  }
+  h.req_locus = ar.at<int32_t>(o_rloc);
   h.o1_off = ar.at<int32_t>(o_o1off); h.o1_seq = ar.at<char>(o_o1seq);
   h.uncallable = rq->sample_uncallable ? ar.at<uint8_t>(o_unc) : NULL;
   h.min_reads = rq->min_reads == 0 ? 2 : rq->min_reads; h.min_frac = rq->min_frac == 0 ? 0.15 : rq->min_frac;      // seq_stutter_genotyper.cpp:869
@@ -2156,31 +2179,63 @@ int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq,
   if (rm_order_behind(R.h.log_aln_probs, st)) return 1;
   if (ar.send(st)) return 1;
   const hs_census_dev_t* d_args = ar.at<hs_census_dev_t>(o_args);
-  HS_HIP(hipMemsetAsync(B.dev + r_nsp, 0, res_bytes - r_nsp, st));                 // the counts and the marks
+  if (dev && nq){
+    // the checks of the trace's values; offsets that are not known to ascend are judged before any kernel follows them into str_seq
+    hipLaunchKernelGGL(hs_census_check_kernel, dim3(1), dim3(HS_CENSUS_THREADS), 0, st, d_args);
+    if (h.check_offsets){
+      HS_HIP(hipGetLastError());
+      HS_HIP(hipMemcpyAsync(B.pin + r_check, B.dev + r_check, 8, hipMemcpyDeviceToHost, st));
+      HS_HIP(hipstr::wait_stream(st));
+      const int bad = *(const int32_t*)(B.pin + r_check);
+      if (bad & HS_CENSUS_BAD_NEGATIVE) return fail("hipstr_post_census: str_seq_off must not be negative");
+      if (bad & HS_CENSUS_BAD_DECREASE) return fail("hipstr_post_census: str_seq_off must not decrease");
+    }
+  }
+  HS_HIP(hipMemsetAsync(B.dev + r_nsp, 0, (dev ? r_check : res_bytes) - r_nsp, st));          // the counts and the marks
   HS_HIP(hipMemsetAsync(B.dev + d_count, 0, d_rank - d_count, st));                // candidates per locus, the samples' flags
   if (!P.list[0].empty()) hipLaunchKernelGGL(hs_census_wave_kernel, dim3((unsigned)hs_census_workgroups(0, (int64_t)P.list[0].size())), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   if (!P.list[1].empty()) hipLaunchKernelGGL(hs_census_lds_kernel, dim3((unsigned)P.list[1].size()), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   if (!P.list[2].empty()) hipLaunchKernelGGL(hs_census_global_kernel, dim3((unsigned)P.list[2].size()), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   hipLaunchKernelGGL(hs_census_scan_kernel, dim3(1), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   if (nq) hipLaunchKernelGGL(hs_census_emit_kernel, dim3((unsigned)((nq + HS_CENSUS_THREADS - 1)/HS_CENSUS_THREADS)), dim3(HS_CENSUS_THREADS), 0, st, d_args);
+  if (dev && nq) hipLaunchKernelGGL(hs_census_gather_kernel, dim3(1), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   HS_HIP(hipGetLastError());
   HS_HIP(hipMemcpyAsync(B.pin, B.dev, res_bytes, hipMemcpyDeviceToHost, st));
   HS_HIP(hipstr::wait_stream(st));
   const int32_t* coff = (const int32_t*)(B.pin + r_coff);
   const int32_t* creq = (const int32_t*)(B.pin + r_creq);
+  if (dev && nq && (*(const int32_t*)(B.pin + r_check) & HS_CENSUS_BAD_NO_STR))
+    return fail("hipstr_post_census: a spanning request without STR data (AlignmentTrace::stutter_size asserts)");
   memcpy(out->cand_off, coff, (nl + 1)*4);
   const int32_t n_cand = coff[nl];
   if (n_cand > out->cap_cand){ fail("candidate arrays too small: cand_off[n_loci] holds the number needed"); return 3; }
   int64_t chars = 0;
-  for (int32_t k = 0; k < n_cand; k++) chars += tr->str_seq_off[creq[k] + 1] - tr->str_seq_off[creq[k]];
+  if (dev) chars = nq ? *(const int64_t*)(B.pin + r_cchars) : 0;
+  else for (int32_t k = 0; k < n_cand; k++) chars += tr->str_seq_off[creq[k] + 1] - tr->str_seq_off[creq[k]];
   if (chars > out->cap_chars){ fail("candidate string pool too small: cap_chars of str_seq_off[n_req] always holds it"); return 3; }
   // the candidates' strings are the caller's own bytes: copied here from trace->str_seq in the order the device fixed
+  if (dev){
+    // ... or gathered on the device in that order: the bytes in use come home in a copy of their own
+    out->cand_seq_off[0] = 0;
+    if (nq) memcpy(out->cand_seq_off, B.pin + r_csoff, ((size_t)n_cand + 1)*4);
+    if (n_cand) memcpy(out->cand_req, creq, (size_t)n_cand*4);
+    if (chars){
+      char* pin_seq = (char*)ctx->pin_cache.get((size_t)chars);
+      if (!pin_seq) return 1;
+      const bool ok = hipMemcpyAsync(pin_seq, B.dev + r_cseq, (size_t)chars, hipMemcpyDeviceToHost, st) == hipSuccess && hipstr::wait_stream(st) == hipSuccess;
+      if (ok) memcpy(out->cand_seq, pin_seq, (size_t)chars);
+      else hipStreamSynchronize(st);
+      ctx->pin_cache.put(pin_seq);
+      if (!ok) return fail("device-to-host copy failed");
+    }
+  } else {
   out->cand_seq_off[0] = 0;
   for (int32_t k = 0; k < n_cand; k++){
     const int32_t q = creq[k], len = tr->str_seq_off[q+1] - tr->str_seq_off[q];
     out->cand_req[k] = q;
     if (len) memcpy(out->cand_seq + out->cand_seq_off[k], tr->str_seq + tr->str_seq_off[q], (size_t)len);
     out->cand_seq_off[k+1] = out->cand_seq_off[k] + len;
+  }
   }
   for (size_t l = 0; l < nl; l++){                                                // :583-584, integer division as written
     const int64_t n1 = P.loci[l].n_opts[1];
@@ -2195,6 +2250,14 @@ int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq,
         if (k == 1) memcpy(out->spanned + L.opt_begin[k], B.pin + r_spanned + L.opt_begin[k], (size_t)L.n_opts[k]);
       }
   return 0;
+}
+}  // namespace
+
+int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, hipstr_census_out_t* out){
+  return census_call(pd, rq, NULL, false, out);
+}
+int hipstr_post_census_dev(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const hipstr_trace_dev_t* td, hipstr_census_out_t* out){
+  return census_call(pd, rq, td, true, out);
 }
 
 #ifndef HIPSTR_NO_DEBUG_ABI
@@ -2248,6 +2311,74 @@ int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read
     }
     so += pb->n_samples[l]; ao += pb->n_alleles[l]; vo += n_variants[l];
   }
+  return 0;
+}
+
+static_assert(HS_TSTAT_NO_STR_DATA == HIPSTR_NO_STR_DATA && HS_CENSUS_NO_STR_DATA == HIPSTR_NO_STR_DATA && HS_TSTAT_NO_ML_BP == HIPSTR_NO_ML_BP,
+              "the kernels' copies of the public constants");
+// The same counts with the five scalars read from a resident traceback result, on its device (assign.hip: hs_trace_stats_kernel).  The
+// host's table checks are those above, before any launch; the units are the runs of reads of one sample.
+int hipstr_assign_trace_stats_dev(const hipstr_post_batch_t* pb, const int32_t* read_req, const hipstr_trace_dev_t* td,
+                                  const int32_t* best_hap, const int32_t* hap_to_allele, const int32_t* allele_bp_diff,
+                                  const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop,
+                                  int32_t* n_stutter, int32_t* n_flank_indel, int32_t* ml_bp){
+  if (!pb || !read_req || !td || !best_hap || !hap_to_allele || !allele_bp_diff || !n_variants || !region_start || !region_stop ||
+      !n_stutter || !n_flank_indel || !ml_bp) return fail("null argument");
+  if (!td->scal[0] || !td->scal[1] || !td->scal[2] || !td->scal[3] || !td->scal[4]) return fail("trace output without stutter_size / flank_ins / flank_del / aln_start / aln_stop");
+  if (pb->n_loci < 0 || (pb->n_loci && (!pb->n_alleles || !pb->n_samples || !pb->read_off || !pb->sample_label))) return fail("null argument");
+  std::vector<hs_tstat_unit_t> units; std::vector<hs_tstat_locus_t> loci((size_t)pb->n_loci);
+  int64_t so = 0, ao = 0, vo = 0;
+  for (int l = 0; l < pb->n_loci; l++){                    // everything checked before anything is written or launched
+    const int A = pb->n_alleles[l], S = pb->n_samples[l], V = n_variants[l];
+    if (A < 1 || S < 0 || V < 1 || pb->read_off[l+1] < pb->read_off[l]) return fail("inconsistent locus tables");
+    for (int a = 0; a < A; a++) if (hap_to_allele[ao + a] < 0 || hap_to_allele[ao + a] >= V) return fail("hap_to_allele entry out of range");
+    for (int r = pb->read_off[l]; r < pb->read_off[l+1]; r++){
+      if (pb->sample_label[r] < 0 || pb->sample_label[r] >= S) return fail("sample_label out of range");
+      if (read_req[r] >= 0 && (best_hap[r] < 0 || best_hap[r] >= A)) return fail("best_hap out of range for a read with a request");
+      if (read_req[r] >= td->n_req) return fail("read_req outside the trace handle's requests");
+      if (r > pb->read_off[l] && pb->sample_label[r] == pb->sample_label[r-1]) units.back().n_reads++;
+      else units.push_back(hs_tstat_unit_t{r, 1, (int32_t)(so + pb->sample_label[r]), l});
+    }
+    hs_tstat_locus_t& L = loci[l];
+    L.hap_begin = ao; L.var_begin = vo;
+    L.start_bound = region_start[l] > 4 ? region_start[l] - 4 : 0; L.stop_bound = region_stop[l] + 4;
+    so += S; ao += A; vo += V;
+  }
+  const size_t n = pb->n_loci ? (size_t)pb->read_off[pb->n_loci] : 0, ns = (size_t)so;
+  if (units.empty()){                                      // no read: nothing for the device to do
+    for (size_t s = 0; s < ns; s++){ n_stutter[s] = 0; n_flank_indel[s] = 0; }
+    return 0;
+  }
+  Ctx* ctx = td->ctx;
+  if (bind(ctx)) return 1;
+  hipStream_t st = td->stream;
+  hipstr::HostArena ar;
+  const size_t o_units = ar.add(units.data(), units.size()*sizeof(hs_tstat_unit_t)), o_loci = ar.add(loci.data(), loci.size()*sizeof(hs_tstat_locus_t)),
+               o_rreq = ar.add(read_req, n*4), o_best = ar.add(best_hap, n*4), o_h2a = ar.add(hap_to_allele, (size_t)ao*4), o_bp = ar.add(allele_bp_diff, (size_t)vo*4);
+  hs_tstat_dev_t h; memset(&h, 0, sizeof h);
+  const size_t o_args = ar.add(&h, sizeof h);
+  if (ar.reserve(ctx)) return 1;
+  size_t tot = 0;
+  auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
+  const size_t r_st = take(ns*4), r_fi = take(ns*4), r_ml = take(n*4);
+  struct Blocks { Ctx* c; hipStream_t st; char* dev = NULL; char* pin = NULL;
+                  ~Blocks(){ if (dev || pin) hipStreamSynchronize(st); if (dev) c->dev_cache.put(dev); if (pin) c->pin_cache.put(pin); } } B{ctx, st};
+  B.dev = (char*)ctx->dev_cache.get(tot);
+  if (!B.dev) return 1;
+  B.pin = (char*)ctx->pin_cache.get(tot);
+  if (!B.pin) return 1;
+  h.units = ar.at<hs_tstat_unit_t>(o_units); h.loci = ar.at<hs_tstat_locus_t>(o_loci); h.n_units = (int32_t)units.size();
+  h.read_req = ar.at<int32_t>(o_rreq); h.best_hap = ar.at<int32_t>(o_best); h.hap_to_allele = ar.at<int32_t>(o_h2a); h.allele_bp_diff = ar.at<int32_t>(o_bp);
+  h.stutter_size = td->scal[0]; h.flank_ins = td->scal[1]; h.flank_del = td->scal[2]; h.aln_start = td->scal[3]; h.aln_stop = td->scal[4];
+  h.n_stutter = (int32_t*)(B.dev + r_st); h.n_flank_indel = (int32_t*)(B.dev + r_fi); h.ml_bp = (int32_t*)(B.dev + r_ml);
+  if (ar.send(st)) return 1;
+  const hs_tstat_dev_t* d_args = ar.at<hs_tstat_dev_t>(o_args);
+  HS_HIP(hipMemsetAsync(B.dev + r_st, 0, r_ml - r_st, st));                        // the samples' counts
+  hipLaunchKernelGGL(hs_trace_stats_kernel, dim3((unsigned)hs_assign_workgroups((int64_t)units.size(), 1)), dim3(HS_ASSIGN_THREADS), 0, st, d_args);
+  HS_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(B.pin, B.dev, tot, hipMemcpyDeviceToHost, st));
+  HS_HIP(hipstr::wait_stream(st));
+  memcpy(n_stutter, B.pin + r_st, ns*4); memcpy(n_flank_indel, B.pin + r_fi, ns*4); memcpy(ml_bp, B.pin + r_ml, n*4);
   return 0;
 }
 

@@ -95,3 +95,22 @@ hipStream_t ctx_stream(Ctx* c);
 int ctx_device(Ctx* c);
 
 }  // namespace hipstr
+
+// ---- a resident traceback result (trace.hip: hipstr_hmm_trace_resident; read by hipstr_post_census_dev and hipstr_assign_trace_stats_dev
+// in api.hip).  Every array is a piece of ONE block of the context's device cache, laid out by TraceDevLayout (trace.hip): the arrays of
+// hipstr_trace_out_t, offsets with their leading 0, pools dense.  Read-only once the creating call has returned (it waits for its stream).
+#define HS_TRACE_DEV_POOLS 7          // hap_aln, str_seq, flank_seq, indel, snp, cigar, aln_str: hipstr_trace_out_t's order
+#define HS_TRACE_DEV_ARRAYS 10        // the pools' arrays: hap_aln, str_seq, flank_seq, indel_pos, indel_size, snp_pos, snp_base, cigar_op, cigar_len, aln_str
+struct hipstr_trace_dev {
+  hipstr::Ctx* ctx = NULL;
+  hipStream_t stream = NULL;          // the creating thread's stream: fetches and the read counts are queued here
+  int32_t n_req = 0;
+  int64_t totals[HS_TRACE_DEV_POOLS] = {0, 0, 0, 0, 0, 0, 0};
+  uint32_t groups = 0;                // HIPSTR_TRACE_F_* present (a handle of hipstr_debug_trace_dev_from_host may lack some)
+  bool checked = false;               // made by hipstr_hmm_trace_resident: the offsets ascend by construction
+  char* block = NULL;
+  double* ll = NULL; int32_t* max_index = NULL;
+  int32_t* scal[5] = {NULL, NULL, NULL, NULL, NULL};          // stutter_size, flank_ins, flank_del, aln_start, aln_stop
+  int32_t* off[HS_TRACE_DEV_POOLS] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+  char* arr[HS_TRACE_DEV_ARRAYS] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
+};

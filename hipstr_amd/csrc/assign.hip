@@ -234,3 +234,38 @@ extern "C" __global__ void __launch_bounds__(HS_ASSIGN_THREADS) hs_assign_reques
     if (slot >= 0) d.read_req[g] = reqid[slot];             // a key's first read lies in this chunk or an earlier one
   }
 }
+
+// Read counts that need the tracebacks, from a resident traceback result (post_layout.h: hs_tstat_*): a wavefront per run of reads of one
+// sample, its reads 64 at a time; the per-sample counts are ballots + population counts, added to the sample once per run.
+extern "C" __global__ void __launch_bounds__(HS_ASSIGN_THREADS) hs_trace_stats_kernel(const hs_tstat_dev_t* __restrict__ dp){
+  const hs_tstat_dev_t& d = *dp;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t ub = (int64_t)blockIdx.x*(HS_ASSIGN_THREADS/64) + wave;
+  if (ub >= d.n_units) return;                              // (a whole wavefront; nothing below synchronises the workgroup)
+  const hs_tstat_unit_t u = d.units[ub];
+  const hs_tstat_locus_t L = d.loci[u.locus];
+  int n_st = 0, n_fi = 0;                                   // uniform over the lanes
+  for (int r0 = 0; r0 < u.n_reads; r0 += 64){
+    const int r = r0 + lane;
+    const bool in = r < u.n_reads;
+    const int g = u.read_begin + (in ? r : 0);
+    const int q = in ? d.read_req[g] : -1;                  // a read without a request counts nowhere (:1080)
+    bool st = false, fi = false;
+    int ml = HS_TSTAT_NO_ML_BP;
+    if (q >= 0){
+      const int ss = d.stutter_size[q];
+      const bool str_data = ss != HS_TSTAT_NO_STR_DATA;
+      st = str_data && ss != 0;                             // has_stutter(), AlignmentTraceback.h:79-85
+      fi = d.flank_ins[q] != 0 || d.flank_del[q] != 0;      // :1126
+      if (d.aln_start[q] < L.start_bound && d.aln_stop[q] > L.stop_bound)      // :1152-1154
+        ml = d.allele_bp_diff[L.var_begin + d.hap_to_allele[L.hap_begin + d.best_hap[g]]] + (str_data ? ss : 0);
+    }
+    if (in) d.ml_bp[g] = ml;
+    n_st += __popcll(__ballot(st));
+    n_fi += __popcll(__ballot(fi));
+  }
+  if (lane == 0){
+    if (n_st) atomicAdd(&d.n_stutter[u.samp], n_st);
+    if (n_fi) atomicAdd(&d.n_flank_indel[u.samp], n_fi);
+  }
+}

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "census_layout.h"
+#include "device_common.h"
 
 namespace {
 
@@ -179,4 +180,76 @@ extern "C" __global__ void __launch_bounds__(HS_CENSUS_THREADS) hs_census_emit_k
   if (rank < 0) return;
   const int64_t k = (int64_t)d.cand_off[d.req_locus[Q]] + rank;
   if (k < d.cap_cand) d.cand_req[k] = (int32_t)Q;
+}
+
+// ---- the trace fields of a resident traceback result (hipstr_post_census_dev)
+// The two checks of hipstr_post_census that read the trace's values, one workgroup: the offsets of str_seq (requests are the lanes) and the
+// spanning request without STR data (reads are the lanes).  Thread 0 stores what was found and the lowest offending read.
+extern "C" __global__ void __launch_bounds__(HS_CENSUS_THREADS) hs_census_check_kernel(const hs_census_dev_t* __restrict__ dp){
+  const hs_census_dev_t& d = *dp;
+  __shared__ int s_bad, s_read;
+  const int tid = threadIdx.x;
+  if (tid == 0){ s_bad = 0; s_read = 0x7fffffff; }
+  __syncthreads();
+  int bad = 0, first = 0x7fffffff;
+  if (d.check_offsets && d.n_req > 0){
+    for (int q = tid; q < d.n_req; q += HS_CENSUS_THREADS) if (d.str_seq_off[q+1] < d.str_seq_off[q]) bad |= HS_CENSUS_BAD_DECREASE;
+    if (tid == 0 && d.str_seq_off[0] < 0) bad |= HS_CENSUS_BAD_NEGATIVE;
+    if (tid == 0 && d.str_seq_off[d.n_req] > d.str_total) bad |= HS_CENSUS_BAD_DECREASE;
+  }
+  for (int r = tid; r < d.n_reads; r += HS_CENSUS_THREADS){
+    const int k = d.read_req[r];
+    if (k < 0 || d.seed[r] < 0) continue;
+    const hs_census_locus_t& L = d.loci[d.req_locus[k]];
+    if (d.aln_start[k] < L.blk_start && d.aln_stop[k] > L.blk_end && d.stutter_size[k] == HS_CENSUS_NO_STR_DATA) first = min(first, r);
+  }
+  first = wave_min_i(first);
+  bad = (__ballot((bad & HS_CENSUS_BAD_NEGATIVE) != 0) ? HS_CENSUS_BAD_NEGATIVE : 0) | (__ballot((bad & HS_CENSUS_BAD_DECREASE) != 0) ? HS_CENSUS_BAD_DECREASE : 0);
+  if ((tid & 63) == 0){
+    if (bad) atomicOr(&s_bad, bad);
+    if (first != 0x7fffffff) atomicMin(&s_read, first);
+  }
+  __syncthreads();
+  if (tid == 0){
+    d.check[0] = s_bad | (s_read != 0x7fffffff ? HS_CENSUS_BAD_NO_STR : 0);
+    d.check[1] = s_read;
+  }
+}
+
+// The candidates' strings, after hs_census_emit_kernel has fixed cand_req: one workgroup scans the candidates' lengths into cand_seq_off (a
+// thread sums a contiguous share, thread 0 chains the shares) — the total is what cap_chars is checked against — then a wavefront per
+// candidate copies its bytes from str_seq, a lane per byte.  More candidates than cap_cand: none is looked at (return code 3 either way).
+extern "C" __global__ void __launch_bounds__(HS_CENSUS_THREADS) hs_census_gather_kernel(const hs_census_dev_t* __restrict__ dp){
+  const hs_census_dev_t& d = *dp;
+  __shared__ int64_t part[HS_CENSUS_THREADS];
+  __shared__ int64_t total_s;
+  const int tid = threadIdx.x;
+  const int n_all = d.cand_off[d.n_loci];
+  const int n = n_all <= d.cap_cand ? n_all : 0;
+  const int per = (n + HS_CENSUS_THREADS - 1)/HS_CENSUS_THREADS;
+  const int k0 = min(n, tid*per), k1 = min(n, k0 + per);
+  int64_t sum = 0;
+  for (int k = k0; k < k1; k++){ const int q = d.cand_req[k]; sum += d.str_seq_off[q+1] - d.str_seq_off[q]; }
+  part[tid] = sum;
+  __syncthreads();
+  if (tid == 0){
+    int64_t run = 0;
+    for (int i = 0; i < HS_CENSUS_THREADS; i++){ const int64_t v = part[i]; part[i] = run; run += v; }
+    total_s = run;
+    *d.cand_chars = run;
+    d.cand_seq_off[n] = (int32_t)run;
+  }
+  __syncthreads();
+  const int64_t total = total_s;
+  int64_t run = part[tid];
+  for (int k = k0; k < k1; k++){ const int q = d.cand_req[k]; d.cand_seq_off[k] = (int32_t)run; run += d.str_seq_off[q+1] - d.str_seq_off[q]; }
+  if (total > d.cap_chars) return;                          // (the whole workgroup: return code 3)
+  __syncthreads();                                          // every candidate's start is written
+  const int lane = tid & 63;
+  for (int k = tid >> 6; k < n; k += HS_CENSUS_THREADS/64){
+    const int q = d.cand_req[k];
+    const int from = d.str_seq_off[q], len = d.str_seq_off[q+1] - from;
+    const int64_t at = d.cand_seq_off[k];
+    for (int i = lane; i < len; i += 64) d.cand_seq[at + i] = d.str_seq[from + i];
+  }
 }

@@ -136,4 +136,18 @@ struct hs_census_dev_t {
   int32_t* req_rank;               // [n_req] position of a candidate in its locus, -1 otherwise
   uint8_t* has_read;               // [n_samp] a read with seed >= 0, zeroed before the launch
   int32_t* ws;                     // route 2
+  // ---- only with the trace fields of a resident traceback result (hipstr_post_census_dev); NULL / 0 otherwise
+  int32_t* check;                  // [2] HS_CENSUS_BAD_* found by hs_census_check_kernel, the lowest read of HS_CENSUS_BAD_NO_STR
+  int32_t  n_reads;                // un-pooled reads of the batch
+  int32_t  check_offsets;          // the handle's offsets are not known to ascend
+  int64_t  str_total;              // elements of str_seq
+  int32_t* cand_seq_off;           // [cap_cand+1] (hs_census_gather_kernel)
+  char*    cand_seq;               // [min(cap_chars, str_total)]
+  int64_t* cand_chars;             // [1] bytes of the candidates' strings
+  int32_t  cap_chars;
 };
+// what hs_census_check_kernel can find in the trace fields
+#define HS_CENSUS_NO_STR_DATA (-100000)   // == HIPSTR_NO_STR_DATA
+#define HS_CENSUS_BAD_NEGATIVE 1       // str_seq_off[0] < 0
+#define HS_CENSUS_BAD_DECREASE 2       // str_seq_off decreases, or ends beyond str_seq
+#define HS_CENSUS_BAD_NO_STR 4         // a spanning request without STR data used by a read with a seed

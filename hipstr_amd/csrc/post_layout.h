@@ -149,3 +149,25 @@ struct hs_assign_dev_t {
   int32_t* locus_base;             // [n_loci] requests in front of the locus
   int32_t* n_req, *req_read, *req_allele;
 };
+
+// ---- read counts from a resident traceback result (assign.hip: hs_trace_stats_kernel; hipstr_assign_trace_stats_dev): the counts of
+// seq_stutter_genotyper.cpp:1124-1127 and the ml_bp of :1150-1154.  The unit is a run of consecutive reads of one (locus, sample) pair — the
+// pair's reads when the labels ascend, as they do in a posterior batch — one wavefront each, four per workgroup, lanes are reads 64 at a
+// time; a sample's counts are integer sums over its runs (zeroed before the launch).  One launch route.
+#define HS_TSTAT_NO_STR_DATA (-100000)     // == HIPSTR_NO_STR_DATA
+#define HS_TSTAT_NO_ML_BP INT32_MIN        // == HIPSTR_NO_ML_BP
+struct hs_tstat_unit_t { int32_t read_begin, n_reads, samp, locus; };       // samp: global sample slot
+struct hs_tstat_locus_t {
+  int64_t hap_begin, var_begin;            // the locus' entries of hap_to_allele / allele_bp_diff
+  int32_t start_bound, stop_bound;         // spans iff aln_start < start_bound && aln_stop > stop_bound (region_start > 4 ? region_start - 4 : 0; region_stop + 4)
+};
+struct hs_tstat_dev_t {
+  const hs_tstat_unit_t*  units;
+  const hs_tstat_locus_t* loci;
+  int32_t n_units;
+  const int32_t* read_req, *best_hap;      // [n_reads]
+  const int32_t* hap_to_allele, *allele_bp_diff;
+  const int32_t* stutter_size, *flank_ins, *flank_del, *aln_start, *aln_stop;     // the resident result's, [n_req]
+  int32_t* n_stutter, *n_flank_indel;      // [n_samp], zeroed before the launch
+  int32_t* ml_bp;                          // [n_reads]
+};

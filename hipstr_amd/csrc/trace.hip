@@ -1193,10 +1193,57 @@ struct ReqOut {                    // one request's results, built by a worker t
   std::vector<std::pair<char,int32_t>> cigar;
 };
 
+// ---- the resident result (api_internal.h: hipstr_trace_dev): where every array lies in the handle's one block.  A chunk's segment has the
+// same layout for the chunk's requests and elements, so the segment of a call of one chunk IS the result.
+const int TD_ARR_POOL[HS_TRACE_DEV_ARRAYS] = {0, 1, 2, 3, 3, 4, 4, 5, 5, 6};
+const int TD_ARR_ESZ[HS_TRACE_DEV_ARRAYS]  = {1, 1, 1, 4, 4, 4, 1, 1, 4, 1};
+static_assert(HS_TRACE_DEV_POOLS == HS_ASM_POOLS, "a resident pool per assembled pool");
+struct TraceDevLayout {
+  size_t ll, mxi, scal[5], off[HS_TRACE_DEV_POOLS], arr[HS_TRACE_DEV_ARRAYS], bytes;
+  TraceDevLayout(size_t n, const int64_t tot[HS_TRACE_DEV_POOLS]){
+    size_t t = 0;
+    auto take = [&](size_t nb){ const size_t at = t; t = (t + (nb ? nb : 1) + 255) & ~(size_t)255; return at; };
+    ll = take(n*8); mxi = take(n*4);
+    for (int i = 0; i < 5; i++) scal[i] = take(n*4);
+    for (int p = 0; p < HS_TRACE_DEV_POOLS; p++) off[p] = take(((size_t)hs_asm_pool_n(p, (int)n) + 1)*4);
+    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) arr[a] = take((size_t)tot[TD_ARR_POOL[a]]*TD_ARR_ESZ[a]);
+    bytes = t;
+  }
+};
+// a handle of n requests and these totals on a fresh block of the context's cache; NULL + last error
+hipstr_trace_dev* trace_dev_new(hipstr::Ctx* ctx, hipStream_t st, int32_t n, const int64_t tot[HS_TRACE_DEV_POOLS]){
+  const TraceDevLayout L((size_t)n, tot);
+  char* blk = (char*)hipstr::dev_alloc(ctx, L.bytes);
+  if (!blk) return NULL;
+  hipstr_trace_dev* td = new hipstr_trace_dev();
+  td->ctx = ctx; td->stream = st; td->n_req = n; td->block = blk;
+  for (int p = 0; p < HS_TRACE_DEV_POOLS; p++){ td->totals[p] = tot[p]; td->off[p] = (int32_t*)(blk + L.off[p]); }
+  td->ll = (double*)(blk + L.ll); td->max_index = (int32_t*)(blk + L.mxi);
+  for (int i = 0; i < 5; i++) td->scal[i] = (int32_t*)(blk + L.scal[i]);
+  for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) td->arr[a] = blk + L.arr[a];
+  return td;
+}
+void trace_dev_drop(hipstr_trace_dev* td){ if (td){ if (td->block) hipstr::dev_free(td->ctx, td->block); delete td; } }
+// the segments of a call's chunks: given back when the call leaves, after everything it queued on them has run
+struct TraceSegs {
+  std::vector<hipstr_trace_dev*> v; std::vector<int> q0; hipStream_t st = NULL;
+  ~TraceSegs(){ if (!v.empty()) hipStreamSynchronize(st); for (hipstr_trace_dev* s : v) trace_dev_drop(s); }
+};
+
+// Device arrays home: one copy per array into its place of a pinned block, one wait, then onto the caller's pages.  What the device-assembled
+// call does with a chunk's pools and hipstr_trace_dev_fetch with the chosen arrays.
+struct HomePiece { const void* dev; size_t bytes; void* dst; size_t pin_off; };
+int copy_home(hipStream_t st, char* pin, const std::vector<HomePiece>& v){
+  for (const HomePiece& h : v) if (h.bytes) TR_HIP(hipMemcpyAsync(pin + h.pin_off, h.dev, h.bytes, hipMemcpyDeviceToHost, st));
+  TR_HIP(hipstr::wait_stream(st));
+  for (const HomePiece& h : v) if (h.bytes) memcpy(h.dst, pin + h.pin_off, h.bytes);
+  return 0;
+}
+
 }  // namespace
 
 static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
-                      const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o);
+                      const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o, hipstr_trace_dev** res);
 
 extern "C" int hipstr_hmm_trace(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                 const char* const* hap_to_ref, hipstr_trace_out_t* o){
@@ -1205,22 +1252,31 @@ extern "C" int hipstr_hmm_trace(const hipstr_batch_t* b, int32_t n_req, const in
 
 extern "C" int hipstr_hmm_trace_seeded(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                        const int32_t* req_seed, const char* const* hap_to_ref, hipstr_trace_out_t* o){
-  return trace_call(b, n_req, req_read, req_allele, req_seed, hap_to_ref, 0u, o);
+  return trace_call(b, n_req, req_read, req_allele, req_seed, hap_to_ref, 0u, o, NULL);
 }
 
 extern "C" int hipstr_hmm_trace_ex(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                    const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o){
   if (flags & ~(uint32_t)HIPSTR_TRACE_ASSEMBLE_DEVICE) return hipstr::api_fail("hipstr_hmm_trace_ex: unknown flag bits");
-  return trace_call(b, n_req, req_read, req_allele, req_seed, hap_to_ref, flags, o);
+  return trace_call(b, n_req, req_read, req_allele, req_seed, hap_to_ref, flags, o, NULL);
 }
 
-// flags 0: the host replays the operation strings; HIPSTR_TRACE_ASSEMBLE_DEVICE: hs_trace_assemble / _scan / _compact build the records
+extern "C" int hipstr_hmm_trace_resident(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                                         const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_dev_t** td){
+  if (td) *td = NULL;
+  if (!td) return hipstr::api_fail("null argument");
+  if (flags) return hipstr::api_fail("hipstr_hmm_trace_resident: unknown flag bits");
+  return trace_call(b, n_req, req_read, req_allele, req_seed, hap_to_ref, HIPSTR_TRACE_ASSEMBLE_DEVICE, NULL, td);
+}
+
+// flags 0: the host replays the operation strings; HIPSTR_TRACE_ASSEMBLE_DEVICE: hs_trace_assemble / _scan / _compact build the records, which
+// go to the caller's buffers (o) or stay on the device (res: a handle, complete when the call returns)
 static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
-                      const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o){
+                      const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o, hipstr_trace_dev** res){
   hipstr::ApiTimer prof_t(hipstr::PB_TRACE);
   const bool on_device = (flags & HIPSTR_TRACE_ASSEMBLE_DEVICE) != 0;
   using hipstr::api_fail;
-  if (!b || !o || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return api_fail("null argument");
+  if (!b || (!o && !res) || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return api_fail("null argument");
   if (b->n_loci < 1) return api_fail("hipstr_hmm_trace needs at least one locus");
   { std::string bad; if (hipstr::validate_tables(b, bad)) return api_fail(bad); }
   const bool timing = getenv("HIPSTR_TRACE_TIMING") != NULL;
@@ -1242,8 +1298,21 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
     }
     opt_base[l+1] = opt_base[l] + cnt;
   }
-  o->hap_aln_off[0] = o->str_seq_off[0] = o->flank_seq_off[0] = o->indel_off[0] = o->snp_off[0] = 0;
-  o->cigar_off[0] = o->aln_str_off[0] = 0;
+  if (o){
+    o->hap_aln_off[0] = o->str_seq_off[0] = o->flank_seq_off[0] = o->indel_off[0] = o->snp_off[0] = 0;
+    o->cigar_off[0] = o->aln_str_off[0] = 0;
+  }
+  if (n_req == 0 && res){                                  // a valid empty handle: the seven leading zeros
+    const int64_t none[HS_TRACE_DEV_POOLS] = {0, 0, 0, 0, 0, 0, 0};
+    hipstr_trace_dev* td = trace_dev_new(T.ctx, T.stream, 0, none);
+    if (!td) return 1;
+    for (int p = 0; p < HS_TRACE_DEV_POOLS; p++)
+      if (hipMemsetAsync(td->off[p], 0, 4, T.stream) != hipSuccess){ hipStreamSynchronize(T.stream); trace_dev_drop(td); return api_fail("hipMemsetAsync failed"); }
+    if (hipstr::wait_stream(T.stream) != hipSuccess){ trace_dev_drop(td); return api_fail("hipstr_hmm_trace_resident: the device failed"); }
+    td->groups = HIPSTR_TRACE_F_ALL; td->checked = true;
+    *res = td;
+    return 0;
+  }
   if (n_req == 0) return 0;
 
   // ---- per request: locus, seed, allele rows (own homopolymer context), sizes
@@ -1451,6 +1520,7 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
     ad.dense_cap[5] = ad.dense_cap[6] = mx_cap[4];
   }
   int64_t pool_total[HS_ASM_POOLS] = {0, 0, 0, 0, 0, 0, 0};       // totals of the chunks done
+  TraceSegs segs; segs.st = T.stream;                            // resident result: a segment per chunk
 
   const auto t_static = now();
   double ms_alloc = 0, ms_kernel = 0, ms_d2h = 0, ms_replay = 0;
@@ -1535,9 +1605,43 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
       if (timing) TR_HIP(hipEventRecord(ev[1], T.stream));
       TR_HIP(hipGetLastError());
       const auto c2 = now();
+      struct PinGuard { hipstr::Ctx* c; void* p; ~PinGuard(){ hipstr::pin_free(c, p); } };
+      if (res){
+        // ---- the records stay: only the totals block comes home; the chunk's dense pieces go device-to-device into a segment of exactly
+        // their size (the next chunk's kernels reuse the staging and result blocks: they queue behind these copies on the same stream)
+        char* tb = (char*)hipstr::pin_alloc(T.ctx, ao_scal);
+        if (!tb) return api_fail("out of pinned host memory");
+        PinGuard tb_guard{T.ctx, tb};
+        TR_HIP(hipMemcpyAsync(tb, d_out, ao_scal, hipMemcpyDeviceToHost, T.stream));
+        TR_HIP(hipstr::wait_stream(T.stream));
+        if (timing){ hipEventDestroy(ev[0]); hipEventDestroy(ev[1]); }
+        const int64_t* tot = (const int64_t*)tb;
+        if (*(const int32_t*)(tb + HS_ASM_POOLS*8) >= 0) return api_fail("internal error: inconsistent traceback operation string");
+        int64_t cnt[HS_ASM_POOLS];
+        for (int p = 0; p < HS_ASM_POOLS; p++){
+          if (tot[p] > 0x7fffffff) return api_fail("too many requests for one call; split the request list");      // (the offsets are 32-bit)
+          cnt[p] = tot[p] - pool_total[p];
+        }
+        hipstr_trace_dev* sg = trace_dev_new(T.ctx, T.stream, nq, cnt);
+        if (!sg) return 1;
+        segs.v.push_back(sg); segs.q0.push_back(q0);
+        auto d2d = [&](void* dst, const void* src, size_t nb){ return nb ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, T.stream) : hipSuccess; };
+        TR_HIP(d2d(sg->ll, hc.ll, (size_t)nq*8)); TR_HIP(d2d(sg->max_index, hc.max_index, (size_t)nq*4));
+        for (int i = 0; i < 5; i++) TR_HIP(d2d(sg->scal[i], ad.stutter_size + (size_t)i*max_nq, (size_t)nq*4));
+        for (int p = 0; p < HS_ASM_POOLS; p++){
+          TR_HIP(hipMemsetAsync(sg->off[p], 0, 4, T.stream));           // (the leading 0: the first chunk's is the result's)
+          TR_HIP(d2d(sg->off[p] + 1, ac.incl + hs_asm_pool_at(p, nq), (size_t)hs_asm_pool_n(p, nq)*4));
+        }
+        const void* const dense[HS_TRACE_DEV_ARRAYS] = { ac.p_hap_aln, ac.p_str_seq, ac.p_flank, ac.p_indel_pos, ac.p_indel_size, ac.p_snp_pos, ac.p_snp_base,
+                                                         ac.p_cig_op, ac.p_cig_len, ac.p_aln };
+        for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) TR_HIP(d2d(sg->arr[a], dense[a], (size_t)cnt[TD_ARR_POOL[a]]*TD_ARR_ESZ[a]));
+        for (int p = 0; p < HS_ASM_POOLS; p++) pool_total[p] = tot[p];
+        q0 = q1;
+        continue;
+      }
       char* hostblk = (char*)hipstr::pin_alloc(T.ctx, o_nops + ao_end);
       if (!hostblk) return api_fail("out of pinned host memory");
-      struct PinGuard { hipstr::Ctx* c; void* p; ~PinGuard(){ hipstr::pin_free(c, p); } } pin_guard{T.ctx, hostblk};
+      PinGuard pin_guard{T.ctx, hostblk};
       char* hout = hostblk + o_nops;
       TR_HIP(hipMemcpyAsync(hostblk, d_res, o_nops, hipMemcpyDeviceToHost, T.stream));                 // ll, max_index
       TR_HIP(hipMemcpyAsync(hout, d_out, ao_i32, hipMemcpyDeviceToHost, T.stream));                    // totals, scalars, offsets
@@ -1567,15 +1671,10 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
         {0, ac.p_hap_aln, 1, o->hap_aln}, {1, ac.p_str_seq, 1, o->str_seq}, {2, ac.p_flank, 1, o->flank_seq},
         {3, ac.p_indel_pos, 4, o->indel_pos}, {3, ac.p_indel_size, 4, o->indel_size}, {4, ac.p_snp_pos, 4, o->snp_pos}, {4, ac.p_snp_base, 1, o->snp_base},
         {5, ac.p_cig_op, 1, o->cigar_op}, {5, ac.p_cig_len, 4, o->cigar_len}, {6, ac.p_aln, 1, o->aln_str} };
-      for (const Pool& pl : pools){
-        const size_t nb = (size_t)(tot[pl.p] - pool_total[pl.p])*pl.esz;
-        if (nb) TR_HIP(hipMemcpyAsync(hout + ((const char*)pl.dev - d_out), pl.dev, nb, hipMemcpyDeviceToHost, T.stream));
-      }
-      TR_HIP(hipstr::wait_stream(T.stream));
-      for (const Pool& pl : pools){
-        const size_t nb = (size_t)(tot[pl.p] - pool_total[pl.p])*pl.esz;
-        if (nb) memcpy((char*)pl.dst + (size_t)pool_total[pl.p]*pl.esz, hout + ((const char*)pl.dev - d_out), nb);
-      }
+      std::vector<HomePiece> home;
+      for (const Pool& pl : pools)
+        home.push_back(HomePiece{pl.dev, (size_t)(tot[pl.p] - pool_total[pl.p])*pl.esz, (char*)pl.dst + (size_t)pool_total[pl.p]*pl.esz, (size_t)((const char*)pl.dev - d_out)});
+      if (copy_home(T.stream, hout, home)) return 1;
       memcpy(o->ll + q0, hostblk + o_ll, (size_t)nq*8); memcpy(o->max_index + q0, hostblk + o_mxi, (size_t)nq*4);
       const int32_t* sc = (const int32_t*)(hout + ao_scal);
       int32_t* const scal_dst[5] = { o->stutter_size, o->flank_ins, o->flank_del, o->aln_start, o->aln_stop };
@@ -1743,13 +1842,140 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
     const auto c4 = now();
     ms_alloc += ms(c0, c1); ms_kernel += ms(c1, c2); ms_d2h += ms(c2, c3); ms_replay += ms(c3, c4);
   }
+  if (res){
+    hipstr_trace_dev* td = NULL;
+    if (segs.v.size() == 1){ td = segs.v[0]; segs.v.clear(); }       // one chunk: its segment is the result, nothing is copied twice
+    else {
+      // several chunks: the segments side by side in flat arrays, then the segments go back
+      td = trace_dev_new(T.ctx, T.stream, n_req, pool_total);
+      if (!td) return 1;
+      struct Drop { hipstr_trace_dev* t; hipStream_t st; ~Drop(){ if (t){ hipStreamSynchronize(st); trace_dev_drop(t); } } } drop{td, T.stream};
+      auto d2d = [&](void* dst, const void* src, size_t nb){ return nb ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, T.stream) : hipSuccess; };
+      int64_t at[HS_ASM_POOLS] = {0, 0, 0, 0, 0, 0, 0};
+      for (int p = 0; p < HS_ASM_POOLS; p++) TR_HIP(hipMemsetAsync(td->off[p], 0, 4, T.stream));
+      for (size_t c = 0; c < segs.v.size(); c++){
+        const hipstr_trace_dev* sg = segs.v[c]; const int q0 = segs.q0[c], nq = sg->n_req;
+        TR_HIP(d2d(td->ll + q0, sg->ll, (size_t)nq*8)); TR_HIP(d2d(td->max_index + q0, sg->max_index, (size_t)nq*4));
+        for (int i = 0; i < 5; i++) TR_HIP(d2d(td->scal[i] + q0, sg->scal[i], (size_t)nq*4));
+        for (int p = 0; p < HS_ASM_POOLS; p++) TR_HIP(d2d(td->off[p] + hs_asm_pool_n(p, q0) + 1, sg->off[p] + 1, (size_t)hs_asm_pool_n(p, nq)*4));
+        for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++){
+          const int p = TD_ARR_POOL[a];
+          TR_HIP(d2d(td->arr[a] + (size_t)at[p]*TD_ARR_ESZ[a], sg->arr[a], (size_t)sg->totals[p]*TD_ARR_ESZ[a]));
+        }
+        for (int p = 0; p < HS_ASM_POOLS; p++) at[p] += sg->totals[p];
+      }
+      TR_HIP(hipstr::wait_stream(T.stream));
+      drop.t = NULL;
+    }
+    if (hipstr::wait_stream(T.stream) != hipSuccess){ trace_dev_drop(td); return api_fail("hipstr_hmm_trace_resident: the device failed"); }
+    td->n_req = n_req; td->groups = HIPSTR_TRACE_F_ALL; td->checked = true;
+    *res = td;
+  }
   if (timing)
     fprintf(stderr, "hipstr_hmm_trace: %d requests; prep %.3f ms, static upload+alloc %.3f, chunk upload %.3f, kernels %.3f, d2h %.3f, replay %.3f, total %.3f\n",
             n_req, ms(t_begin, t_prep), ms(t_prep, t_static), ms_alloc, ms_kernel, ms_d2h, ms_replay, ms(t_begin, now()));
   return 0;
 }
 
+// ---- the resident result's own entry points
+extern "C" int hipstr_trace_dev_sizes(const hipstr_trace_dev_t* td, int32_t* n_req, int64_t totals[7]){
+  if (!td || !n_req || !totals) return hipstr::api_fail("null argument");
+  *n_req = td->n_req;
+  for (int p = 0; p < HS_TRACE_DEV_POOLS; p++) totals[p] = td->totals[p];
+  return 0;
+}
+
+extern "C" int hipstr_trace_dev_fetch(hipstr_trace_dev_t* td, uint32_t fields, hipstr_trace_out_t* o){
+  using hipstr::api_fail;
+  if (fields & ~(uint32_t)HIPSTR_TRACE_F_ALL) return api_fail("hipstr_trace_dev_fetch: unknown field bits");
+  if (!td || !o) return api_fail("null argument");
+  if (fields & ~td->groups) return api_fail("hipstr_trace_dev_fetch: the handle does not hold a chosen group");
+  const size_t n = (size_t)td->n_req;
+  std::vector<HomePiece> home; size_t pin_bytes = 0; bool null_dst = false;
+  auto want = [&](const void* dev, size_t nb, void* dst){
+    if (nb && !dst) null_dst = true;
+    home.push_back(HomePiece{dev, nb, dst, pin_bytes}); pin_bytes = (pin_bytes + nb + 255) & ~(size_t)255;
+  };
+  if (fields & HIPSTR_TRACE_F_SCALARS){
+    want(td->ll, n*8, o->ll); want(td->max_index, n*4, o->max_index);
+    int32_t* const dst[5] = { o->stutter_size, o->flank_ins, o->flank_del, o->aln_start, o->aln_stop };
+    for (int i = 0; i < 5; i++) want(td->scal[i], n*4, dst[i]);
+  }
+  int32_t* const off_dst[HS_TRACE_DEV_POOLS] = { o->hap_aln_off, o->str_seq_off, o->flank_seq_off, o->indel_off, o->snp_off, o->cigar_off, o->aln_str_off };
+  void* const arr_dst[HS_TRACE_DEV_ARRAYS] = { o->hap_aln, o->str_seq, o->flank_seq, o->indel_pos, o->indel_size, o->snp_pos, o->snp_base, o->cigar_op, o->cigar_len, o->aln_str };
+  const uint32_t pool_bit[HS_TRACE_DEV_POOLS] = { HIPSTR_TRACE_F_HAP_ALN, HIPSTR_TRACE_F_STR_SEQ, HIPSTR_TRACE_F_FLANKS, HIPSTR_TRACE_F_INDELS, HIPSTR_TRACE_F_SNPS,
+                                                  HIPSTR_TRACE_F_STITCH, HIPSTR_TRACE_F_STITCH };
+  for (int p = 0; p < HS_TRACE_DEV_POOLS; p++){
+    if (!(fields & pool_bit[p])) continue;
+    if (td->totals[p] > (int64_t)o->cap_chars) return api_fail("hipstr_trace_out_t pools are too small (cap_chars)");
+    want(td->off[p], ((size_t)hs_asm_pool_n(p, (int)n) + 1)*4, off_dst[p]);
+    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) want(td->arr[a], (size_t)td->totals[p]*TD_ARR_ESZ[a], arr_dst[a]);
+  }
+  if (null_dst) return api_fail("null output array");
+  if (pin_bytes == 0) return 0;
+  if (hipstr::api_bind(td->ctx)) return 1;
+  char* pin = (char*)hipstr::pin_alloc(td->ctx, pin_bytes);
+  if (!pin) return api_fail("out of pinned host memory");
+  struct PinGuard { hipstr::Ctx* c; void* p; hipStream_t st; ~PinGuard(){ hipStreamSynchronize(st); hipstr::pin_free(c, p); } } pin_guard{td->ctx, pin, td->stream};
+  return copy_home(td->stream, pin, home);
+}
+
+extern "C" void hipstr_trace_dev_free(hipstr_trace_dev_t* td){
+  if (!td) return;
+  if (td->block && hipstr::api_bind(td->ctx) == 0) hipStreamSynchronize(td->stream);     // a fetch that left early may still be copying
+  trace_dev_drop(td);
+}
+
 #ifndef HIPSTR_NO_DEBUG_ABI
+// Diagnostics: a resident result built from host arrays, for the fabricated cases of the census and the read counts.  An array that is NULL
+// is absent (its group cannot be fetched, a consumer that needs it refuses); nothing is checked here: the consumers do that.
+extern "C" int hipstr_debug_trace_dev_from_host(const hipstr_trace_out_t* tr, int32_t n_req, hipstr_trace_dev_t** out){
+  using hipstr::api_fail;
+  if (out) *out = NULL;
+  if (!tr || !out || n_req < 0) return api_fail("null argument");
+  const size_t n = (size_t)n_req;
+  const int32_t* const off_src[HS_TRACE_DEV_POOLS] = { tr->hap_aln_off, tr->str_seq_off, tr->flank_seq_off, tr->indel_off, tr->snp_off, tr->cigar_off, tr->aln_str_off };
+  const void* const arr_src[HS_TRACE_DEV_ARRAYS] = { tr->hap_aln, tr->str_seq, tr->flank_seq, tr->indel_pos, tr->indel_size, tr->snp_pos, tr->snp_base, tr->cigar_op, tr->cigar_len, tr->aln_str };
+  const int32_t* const scal_src[5] = { tr->stutter_size, tr->flank_ins, tr->flank_del, tr->aln_start, tr->aln_stop };
+  int64_t tot[HS_TRACE_DEV_POOLS]; bool pool_ok[HS_TRACE_DEV_POOLS];
+  for (int p = 0; p < HS_TRACE_DEV_POOLS; p++){
+    tot[p] = off_src[p] ? std::max<int64_t>(0, off_src[p][hs_asm_pool_n(p, n_req)]) : 0;
+    pool_ok[p] = off_src[p] != NULL;
+    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p && tot[p] > 0 && !arr_src[a]) pool_ok[p] = false;
+    if (!pool_ok[p]) tot[p] = 0;
+  }
+  hipstr::ApiTables T;
+  if (hipstr::api_device_tables(&T)) return 1;
+  hipstr_trace_dev* td = trace_dev_new(T.ctx, T.stream, n_req, tot);
+  if (!td) return 1;
+  struct Drop { hipstr_trace_dev* t; hipStream_t st; ~Drop(){ if (t){ hipStreamSynchronize(st); trace_dev_drop(t); } } } drop{td, T.stream};
+  const TraceDevLayout L(n, tot);
+  char* pin = (char*)hipstr::pin_alloc(T.ctx, L.bytes);
+  if (!pin) return api_fail("out of pinned host memory");
+  struct PinGuard { hipstr::Ctx* c; void* p; hipStream_t st; ~PinGuard(){ hipStreamSynchronize(st); hipstr::pin_free(c, p); } } pin_guard{T.ctx, pin, T.stream};
+  auto put = [&](size_t at, const void* src, size_t nb){ if (src && nb) memcpy(pin + at, src, nb); };
+  put(L.ll, tr->ll, n*8); put(L.mxi, tr->max_index, n*4);
+  if (!tr->ll) td->ll = NULL;
+  if (!tr->max_index) td->max_index = NULL;
+  for (int i = 0; i < 5; i++){ put(L.scal[i], scal_src[i], n*4); if (!scal_src[i]) td->scal[i] = NULL; }
+  for (int p = 0; p < HS_TRACE_DEV_POOLS; p++){
+    if (!pool_ok[p]){ td->off[p] = NULL; for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) td->arr[a] = NULL; continue; }
+    put(L.off[p], off_src[p], ((size_t)hs_asm_pool_n(p, n_req) + 1)*4);
+    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) put(L.arr[a], arr_src[a], (size_t)tot[p]*TD_ARR_ESZ[a]);
+  }
+  TR_HIP(hipMemcpyAsync(td->block, pin, L.bytes, hipMemcpyHostToDevice, T.stream));
+  TR_HIP(hipstr::wait_stream(T.stream));
+  td->groups = 0;
+  if (tr->ll && tr->max_index && scal_src[0] && scal_src[1] && scal_src[2] && scal_src[3] && scal_src[4]) td->groups |= HIPSTR_TRACE_F_SCALARS;
+  const uint32_t bit[HS_TRACE_DEV_POOLS] = { HIPSTR_TRACE_F_HAP_ALN, HIPSTR_TRACE_F_STR_SEQ, HIPSTR_TRACE_F_FLANKS, HIPSTR_TRACE_F_INDELS, HIPSTR_TRACE_F_SNPS, 0, 0 };
+  for (int p = 0; p < 5; p++) if (pool_ok[p]) td->groups |= bit[p];
+  if (pool_ok[5] && pool_ok[6]) td->groups |= HIPSTR_TRACE_F_STITCH;
+  td->checked = false;
+  drop.t = NULL;
+  *out = td;
+  return 0;
+}
+
 // Diagnostics (host only): the chunks, fill kernels and walk forms hipstr_hmm_trace_seeded would launch for a request list, from the same
 // decisions (trace_seed_of, trace_compact_reads, trace_side_ws, trace_chunk_end, trace_col_class, trace_mixed_launch, trace_fill_cols,
 // hs_walk_in_lds), as one JSON object.

@@ -491,6 +491,44 @@ int hipstr_hmm_trace_ex(const hipstr_batch_t* batch, int32_t n_req, const int32_
                         uint32_t flags, hipstr_trace_out_t* out);
 
 /*
+ * The resident form of a device-assembled traceback call: the records stay on the device, and the two consumers that need a few of their
+ * fields between the rounds of SeqStutterGenotyper::genotype() — the allele census and the read counts of a record — read them where they
+ * lie (hipstr_post_census_dev, hipstr_assign_trace_stats_dev below).  What a caller still wants on the host it fetches by group.
+ * A handle holds the arrays of hipstr_trace_out_t in ONE block of its context's device cache (no allocation in steady state): ll,
+ * max_index, the five scalars, the seven offset arrays with their leading 0 and the ten pool arrays, dense.  It belongs to the device
+ * (context) of the thread that created it, is read-only once created — several consumer calls may use it, also at once — and must not be
+ * freed while one runs.
+ */
+typedef struct hipstr_trace_dev hipstr_trace_dev_t;
+
+/* hipstr_hmm_trace_ex(..., HIPSTR_TRACE_ASSEMBLE_DEVICE, ...) whose records stay on the device.  flags: 0 (any bit is refused).
+ * On success *td holds n_req records (n_req == 0: a valid empty handle); it is complete when the call returns.  On any failure *td = NULL,
+ * nothing stays allocated, return value and hipstr_last_error() are those hipstr_hmm_trace_ex gives the same request list (cap_chars does
+ * not exist here: the offsets are 32-bit, a pool of more than INT32_MAX elements is "too many requests for one call").  Per chunk of
+ * requests only the 64-byte block of pool totals comes to the host; a call of one chunk keeps that chunk's arrays as they are, a call of
+ * several joins them device-to-device after the last one. */
+int  hipstr_hmm_trace_resident(const hipstr_batch_t* batch, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                               const int32_t* req_seed /* or NULL */, const char* const* hap_to_ref /* or NULL */,
+                               uint32_t flags, hipstr_trace_dev_t** td);
+/* n_req and the elements of the seven pools, in hipstr_trace_out_t's order: hap_aln, str_seq, flank_seq, indel, snp, cigar, aln_str.
+ * Host only once the handle exists: what a caller sizes its buffers with. */
+int  hipstr_trace_dev_sizes(const hipstr_trace_dev_t* td, int32_t* n_req, int64_t totals[7]);
+/* Copies the chosen groups into out (one device-to-host copy per array through a pinned block); arrays of groups not chosen are neither
+ * read nor written and may be NULL.  A chosen pool larger than out->cap_chars: non-zero, "hipstr_trace_out_t pools are too small
+ * (cap_chars)", nothing written.  All groups chosen == the bytes hipstr_hmm_trace_ex writes for the same requests.  Refused: an unknown
+ * bit, a chosen array that is NULL, a group the handle does not hold (hipstr_debug_trace_dev_from_host). */
+#define HIPSTR_TRACE_F_SCALARS 0x01u   /* ll, max_index, stutter_size, flank_ins, flank_del, aln_start, aln_stop */
+#define HIPSTR_TRACE_F_HAP_ALN 0x02u
+#define HIPSTR_TRACE_F_STR_SEQ 0x04u
+#define HIPSTR_TRACE_F_FLANKS  0x08u   /* flank_seq: what assemble_flanks reads */
+#define HIPSTR_TRACE_F_INDELS  0x10u
+#define HIPSTR_TRACE_F_SNPS    0x20u
+#define HIPSTR_TRACE_F_STITCH  0x40u   /* cigar_*, aln_str (+ their offsets) */
+#define HIPSTR_TRACE_F_ALL     0x7fu
+int  hipstr_trace_dev_fetch(hipstr_trace_dev_t* td, uint32_t fields, hipstr_trace_out_t* out);
+void hipstr_trace_dev_free(hipstr_trace_dev_t* td);
+
+/*
  * Reads assigned to the MAP haplotypes and the per-sample read counts of a VCF record: the loop over the reads of
  * SeqStutterGenotyper::write_vcf_record (seq_stutter_genotyper.cpp:1079-1157) with the phase totals of :1355-1356, and the pick of
  * retrace_alignments (:805-841), on a resident hipstr_post_dev_t after hipstr_post_launch — the likelihood matrix is read where it
@@ -618,6 +656,20 @@ typedef struct hipstr_census_out {
   int32_t  cap_cand, cap_chars;
 } hipstr_census_out_t;
 int hipstr_post_census(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, hipstr_census_out_t* out);
+
+/* hipstr_post_census with the five trace fields read from td: rq->trace must be NULL, rq->n_req must equal td's, td must live on pd's
+ * device.  Same outputs, same return codes (3 included), same refusals and messages as hipstr_post_census given
+ * hipstr_trace_dev_fetch(td, ALL).  The checks that need the trace's values run on the device — str_seq_off that is negative or decreases
+ * (before any census kernel runs; skipped for a handle of hipstr_hmm_trace_resident, whose offsets ascend by construction) and the spanning
+ * request without STR data — after every check of the host's tables; a refusal still writes nothing into out.  The candidates' bytes are
+ * gathered on the device (hs_census_gather_kernel) and come home with the counts and the marks. */
+int  hipstr_post_census_dev(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const hipstr_trace_dev_t* td, hipstr_census_out_t* out);
+/* hipstr_assign_trace_stats with the five scalars read from td, on td's device (one kernel: a run of reads of one sample per wavefront).
+ * Same arguments otherwise, same outputs, same refusals; read_req must stay below td's n_req. */
+int  hipstr_assign_trace_stats_dev(const hipstr_post_batch_t* pb, const int32_t* read_req, const hipstr_trace_dev_t* td,
+                                   const int32_t* best_hap, const int32_t* hap_to_allele, const int32_t* allele_bp_diff,
+                                   const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop,
+                                   int32_t* n_stutter, int32_t* n_flank_indel, int32_t* ml_bp);
 
 /*
  * The read x haplotype matrix of a batch of loci, resident on the device between the rounds of SeqStutterGenotyper::genotype

@@ -64,6 +64,11 @@ int hipstr_debug_trace_plan(const hipstr_batch_t* batch, int32_t n_req, const in
  * Used by tests/test_trace_assemble_host.py. */
 int hipstr_debug_trace_assemble_plan(const hipstr_batch_t* batch, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                      const int32_t* req_seed, const char* const* hap_to_ref, char* json, int cap);
+/* Diagnostics: a resident traceback result (hipstr_trace_dev_t) built from host arrays, so that fabricated edge cases run through
+ * hipstr_post_census_dev and hipstr_assign_trace_stats_dev.  tr: arrays for n_req requests; one that is NULL is absent — its group cannot
+ * be fetched, and a consumer that needs it refuses.  Nothing about the values is checked here (the consumers do that, on the device).
+ * *td = NULL on failure.  Freed with hipstr_trace_dev_free.  Used by tests/test_trace_resident_gpu.py. */
+int hipstr_debug_trace_dev_from_host(const hipstr_trace_out_t* tr, int32_t n_req, hipstr_trace_dev_t** td);
 /* Diagnostics (host only): the chunks hipstr_nw_align would cut a batch into under a budget of ws_mib MiB of traceback bytes (<= 0: the
  * call's own default or HIPSTR_NW_WS_MIB) and, per chunk, "p0" / "p1" (pair range), "bytes", "over_budget" (one pair larger than the
  * budget, alone), "rungs" (pairs per rows-per-lane rung of "thresholds"."rows") and "launch" ([kernel, workgroups]).  Refused sizes fail
