@@ -585,6 +585,111 @@ def assign_trace_stats_dev(lib, pb, read_req, td, best_hap, hap_to_allele, allel
     return ns[:n_samp], nf[:n_samp], ml[:n_reads]
 
 
+# ---- the stutter model retrained from the tracebacks (hipstr_em_batch_from_traces, hipstr_em_train_dev)
+class HipstrEmTraceRequest(C.Structure):
+    _fields_ = [("pooled", C.POINTER(HipstrBatch)), ("seed", _i32p), ("read_req", _i32p), ("n_req", C.c_int32), ("req_read", _i32p),
+                ("ref_allele", C.c_int32), ("max_iter", C.c_int32), ("min_ll_abs_change", C.c_double), ("min_ll_frac_change", C.c_double)]
+
+
+class HipstrEmTraceOut(C.Structure):
+    _fields_ = [("trained", _u8p), ("stutter", _f64p), ("n_iter", _i32p), ("final_ll", _f64p), ("em_read_off", _i32p), ("n_sizes", _i32p)]
+
+
+class HipstrDebugEmInput(C.Structure):
+    _fields_ = [("em_read_off", _i32p), ("num_bps", _i32p), ("sample_label", _i32p), ("obs", _i32p), ("log_p1", _f64p), ("log_p2", _f64p),
+                ("size_off", _i32p), ("sizes", _i32p), ("log_freq", _f64p), ("route", _i32p)]
+
+
+def _em_trace_sigs(lib):
+    _sig(lib.hipstr_em_batch_from_traces, C.c_int, [_PBP, C.POINTER(HipstrEmTraceRequest), C.POINTER(HipstrTraceOut), _i32p, _i32p, _i32p, _f64p, _f64p])
+    _sig(lib.hipstr_em_train_dev, C.c_int, [C.c_void_p, C.POINTER(HipstrEmTraceRequest), C.c_void_p, C.POINTER(HipstrEmTraceOut)])
+    _sig(lib.hipstr_debug_em_input_plan, C.c_int, [C.c_int64] * 5 + [C.POINTER(C.c_int64)])
+    _sig(lib.hipstr_debug_em_input_fetch, C.c_int, [C.c_void_p, C.POINTER(HipstrEmTraceRequest), C.c_void_p, C.POINTER(HipstrDebugEmInput)])
+
+
+def _em_trace_request(bptr, seed, read_req, req_read, ref_allele, max_iter, min_ll_abs_change, min_ll_frac_change):
+    """(HipstrEmTraceRequest, what it points into)."""
+    i32 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.int32))
+    keep = [i32(seed), i32(read_req), i32(req_read)]
+    n_req = 0 if keep[2] is None else len(keep[2])
+    pooled = None if bptr is None else (C.cast(bptr, C.POINTER(HipstrBatch)) if not hasattr(bptr, "_obj") else C.pointer(bptr._obj))
+    rq = HipstrEmTraceRequest(pooled, _ptr(keep[0], _i32p), _ptr(keep[1], _i32p), n_req, _ptr(keep[2], _i32p), int(ref_allele), int(max_iter),
+                              float(min_ll_abs_change), float(min_ll_frac_change))
+    return rq, keep
+
+
+def em_batch_from_traces(lib, pb, bptr, seed, read_req, req_read, trace, ref_allele=0, max_iter=100, min_ll_abs_change=0.01, min_ll_frac_change=0.001):
+    """hipstr_em_batch_from_traces (host only) -> dict(read_off, sample_label, num_bps, log_p1, log_p2): the per-read arrays cut to the reads
+    that entered.  pb: a PostBatch; bptr: the pooled batch; trace: dict with aln_start, aln_stop, stutter_size, str_seq_off (what is missing
+    is passed as NULL).  Raises with hipstr_last_error() on a refusal; the exception's `outputs` are the arrays as the call left them
+    (pre-filled with UNTOUCHED / NaN)."""
+    _em_trace_sigs(lib)
+    rq, keep = _em_trace_request(bptr, seed, read_req, req_read, ref_allele, max_iter, min_ll_abs_change, min_ll_frac_change)
+    t = HipstrTraceOut()
+    for nm in ("aln_start", "aln_stop", "stutter_size", "str_seq_off"):
+        if trace is not None and trace.get(nm) is not None:
+            a = np.ascontiguousarray(np.asarray(trace[nm], np.int32)); keep.append(a); setattr(t, nm, a.ctypes.data_as(_i32p))
+    nl = int(pb.struct.n_loci); n = int(pb.a["read_off"][-1]) if nl else 0
+    off = np.full(nl + 1, UNTOUCHED, np.int32); lab = np.full(max(n, 1), UNTOUCHED, np.int32); bps = np.full(max(n, 1), UNTOUCHED, np.int32)
+    p1 = np.full(max(n, 1), np.nan); p2 = np.full(max(n, 1), np.nan)
+    rc = lib.hipstr_em_batch_from_traces(pb.ptr, C.byref(rq), C.byref(t) if trace is not None else None, _ptr(off, _i32p), _ptr(lab, _i32p), _ptr(bps, _i32p),
+                                         _ptr(p1, _f64p), _ptr(p2, _f64p))
+    if rc != 0:
+        e = RuntimeError("hipstr_em_batch_from_traces failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+        e.outputs = dict(read_off=off, sample_label=lab, num_bps=bps, log_p1=p1, log_p2=p2)
+        raise e
+    m = int(off[nl])
+    return dict(read_off=off, sample_label=lab[:m], num_bps=bps[:m], log_p1=p1[:m], log_p2=p2[:m])
+
+
+def em_train_dev(lib, pd, n_loci, bptr, seed, read_req, req_read, td, ref_allele=0, max_iter=100, min_ll_abs_change=0.01, min_ll_frac_change=0.001):
+    """hipstr_em_train_dev -> (trained[n_loci] bool, stutter[n_loci, 6], n_iter, final_ll, em_read_off[n_loci+1], n_sizes[n_loci]) on a
+    hipstr_post_dev_t handle and a TraceDev.  Raises with hipstr_last_error() on a refusal; the exception's `outputs` are the six arrays as
+    the call left them (integers UNTOUCHED, doubles NaN, trained 0xAA)."""
+    _em_trace_sigs(lib)
+    rq, keep = _em_trace_request(bptr, seed, read_req, req_read, ref_allele, max_iter, min_ll_abs_change, min_ll_frac_change)
+    nl = int(n_loci)
+    trained = np.full(max(nl, 1), 0xAA, np.uint8); st = np.full(max(6 * nl, 6), np.nan); it = np.full(max(nl, 1), UNTOUCHED, np.int32)
+    ll = np.full(max(nl, 1), np.nan); off = np.full(nl + 1, UNTOUCHED, np.int32); ns = np.full(max(nl, 1), UNTOUCHED, np.int32)
+    o = HipstrEmTraceOut(_ptr(trained, _u8p), _ptr(st, _f64p), _ptr(it, _i32p), _ptr(ll, _f64p), _ptr(off, _i32p), _ptr(ns, _i32p))
+    rc = lib.hipstr_em_train_dev(pd, C.byref(rq), None if td is None else td.h, C.byref(o))
+    if rc != 0:
+        e = RuntimeError("hipstr_em_train_dev failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+        e.outputs = dict(trained=trained, stutter=st, n_iter=it, final_ll=ll, em_read_off=off, n_sizes=ns)
+        raise e
+    return trained[:nl].astype(bool), st[:6 * nl].reshape(-1, 6), it[:nl], ll[:nl], off, ns[:nl]
+
+
+def em_input_plan(lib, n_runs, run_reads, lo, hi, n_sizes):
+    """hipstr_debug_em_input_plan (host only) as a dict: the decisions of hipstr_amd/csrc/em_input_layout.h and its compiled limits."""
+    _em_trace_sigs(lib)
+    out = np.zeros(12, np.int64)
+    if lib.hipstr_debug_em_input_plan(int(n_runs), int(run_reads), int(lo), int(hi), int(n_sizes), out.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
+        raise RuntimeError("hipstr_debug_em_input_plan failed: " + lib.hipstr_last_error().decode())
+    return dict(run_steps=int(out[0]), last_step=int(out[1]), run_workgroups=int(out[2]), scan_chunks=int(out[3]), scan_last_chunk=int(out[4]),
+                device=bool(out[5]), bitmap_words=int(out[6]), device_priors=bool(out[7]),
+                thresholds=dict(HS_EMI_THREADS=int(out[8]), HS_EMI_WAVE=int(out[9]), HS_EMI_SCAN_CHUNK=int(out[10]), HS_EMI_SPAN_LIMIT=int(out[11])))
+
+
+def em_input_fetch(lib, pd, n_loci, n_reads, bptr, seed, read_req, req_read, td, ref_allele=0):
+    """hipstr_debug_em_input_fetch -> dict(route ("device" / "host"), read_off, num_bps, sample_label, obs, log_p1, log_p2, size_off, sizes,
+    log_freq): what hipstr_em_train_dev prepares before the EM loop."""
+    _em_trace_sigs(lib)
+    rq, keep = _em_trace_request(bptr, seed, read_req, req_read, ref_allele, 100, 0.01, 0.001)
+    nl, n = int(n_loci), int(n_reads)
+    off = np.zeros(nl + 1, np.int32); soff = np.zeros(nl + 1, np.int32); route = np.zeros(1, np.int32)
+    ia = [np.zeros(max(n, 1), np.int32) for _ in range(3)]; fa = [np.zeros(max(n, 1)) for _ in range(2)]
+    sizes = np.zeros(n + nl + 1, np.int32); freq = np.zeros(n + nl + 1)
+    o = HipstrDebugEmInput(_ptr(off, _i32p), _ptr(ia[0], _i32p), _ptr(ia[1], _i32p), _ptr(ia[2], _i32p), _ptr(fa[0], _f64p), _ptr(fa[1], _f64p),
+                           _ptr(soff, _i32p), _ptr(sizes, _i32p), _ptr(freq, _f64p), _ptr(route, _i32p))
+    rc = lib.hipstr_debug_em_input_fetch(pd, C.byref(rq), td.h, C.byref(o))
+    if rc != 0:
+        raise RuntimeError("hipstr_debug_em_input_fetch failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    m = int(off[nl]); k = int(soff[nl])
+    return dict(route="host" if route[0] else "device", read_off=off, num_bps=ia[0][:m], sample_label=ia[1][:m], obs=ia[2][:m], log_p1=fa[0][:m],
+                log_p2=fa[1][:m], size_off=soff, sizes=sizes[:k], log_freq=freq[:k])
+
+
 def census_plan(lib, n_req, n_reads):
     """hipstr_debug_census_plan (host only) as a dict: the route of a locus of n_req requests and n_reads un-pooled reads and the compiled
     limits of hipstr_amd/csrc/census_layout.h."""
@@ -1005,6 +1110,7 @@ def load_hmm():
     _sig(lib.hipstr_debug_rm_plan, C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)])
     _trace_dev_sigs(lib)
     _sig(lib.hipstr_post_census_dev, C.c_int, [C.c_void_p, C.POINTER(HipstrCensusRequest), C.c_void_p, C.POINTER(HipstrCensusOut)])
+    _em_trace_sigs(lib)
     return lib
 
 

@@ -1728,6 +1728,22 @@ int hipstr_post_fetch(hipstr_post_dev_t* pd, double* log_post, double* sample_to
 
 void hipstr_post_free(hipstr_post_dev_t* pd){ delete pd; }
 
+// what hipstr_em_train_dev (em_input.hip) reads of a run
+extern "C++" {
+void hipstr::post_view(const hipstr_post_dev* pd, PostView* v){
+  const PostRun& R = pd->R;
+  v->ctx = R.ctx; v->stream = R.stream; v->ev_up = R.ev_up; v->d_units = R.h.units; v->units = R.units.data(); v->n_units = R.units.size();
+  v->n_loci = pd->n_samples.size(); v->log_p1 = R.h.log_p1; v->log_p2 = R.h.log_p2; v->n_reads = R.n_reads; v->n_samp = R.n_samp;
+  v->n_samples = pd->n_samples.data(); v->haploid = pd->haploid.data();
+}
+int hipstr::api_tables_of(Ctx* c, ApiTables* t){
+  if (!c || bind(c)) return 1;
+  t->int_log = c->int_log; t->qual_correct = c->qc; t->qual_error = c->qe; t->m2m = c->m2m; t->m2i = c->m2i;
+  t->stream = thread_stream(c); t->ctx = c;
+  return 0;
+}
+}  // extern "C++"
+
 int hipstr_gt_offsets(const hipstr_post_batch_t* pb, const hipstr_gt_request_t* rq, int64_t* gl_off, int64_t* pgl_off){
   if (!pb || !rq || !gl_off || !pgl_off) return fail("null argument");
   int64_t g = 0, pg = 0, so = 0;

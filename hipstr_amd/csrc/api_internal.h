@@ -114,3 +114,30 @@ struct hipstr_trace_dev {
   int32_t* off[HS_TRACE_DEV_POOLS] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL};
   char* arr[HS_TRACE_DEV_ARRAYS] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
 };
+
+// ---- what hipstr_em_train_dev (em_input.hip) needs of a posterior run (api.hip) and of the stutter EM (em.hip)
+struct hs_post_unit_t; struct hipstr_post_dev; struct hipstr_em_batch;
+namespace hipstr {
+struct PostView {                    // a posterior run after hipstr_post_upload: what lies where (read-only)
+  Ctx* ctx; hipStream_t stream;
+  hipEvent_t ev_up;                  // recorded behind an asynchronous upload of the inputs, or NULL (they were waited for)
+  const hs_post_unit_t* d_units;     // device: the (locus, sample) runs of reads, locus-major
+  const hs_post_unit_t* units;       // the host's copy
+  size_t n_units, n_loci;
+  const double* log_p1, *log_p2;     // device, [n_reads]
+  int n_reads; int64_t n_samp;
+  const int32_t* n_samples;          // [n_loci]
+  const uint8_t* haploid;            // [n_loci]
+};
+void post_view(const hipstr_post_dev* pd, PostView* v);
+int  api_tables_of(Ctx* c, ApiTables* t);     // api_device_tables for a given context (binds it)
+
+int em_train_batch_on(const ApiTables& T, const hipstr_em_batch* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll);
+// em_prepare's results for a batch (host only; its refusals): per locus the allele sizes (size_off), per read the allele index, per allele the initial log frequency
+int em_prepare_host(const hipstr_em_batch* eb, std::vector<int32_t>& size_off, std::vector<int32_t>& sizes, std::vector<int32_t>& obs, std::vector<double>& log_freq);
+struct EmLocusFacts { int32_t A, S, R, period, haploid, read_begin, bps_off; };
+struct EmDeviceArrays { int32_t *bps, *obs, *sample_label, *weight; double *log_p1, *log_p2, *gtp; };      // the EM's seven per-read and per-allele arrays, device
+// the EM loop on arrays prepared on the device: loci as em_prepare lays them out (reads_of_sample: [sum S], locus-major)
+int em_train_prepared(const ApiTables& T, int n_loci, const EmLocusFacts* facts, const int32_t* reads_of_sample, const EmDeviceArrays& arr,
+                      int max_iter, double min_abs_change, double min_frac_change, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll);
+}  // namespace hipstr

@@ -768,6 +768,25 @@ struct EmPrep {
   std::vector<double> gtp;
   int64_t post_off = 0, ll_off = 0, prior_off = 0, sa_off = 0; int samp_off = 0;
 };
+// One locus' record and its (locus, sample) posterior units, behind those of the loci before it (P's running offsets): the layout of every
+// device array of the loop.  bps_off: where the locus' A allele sizes and log frequencies start in bps / gtp.
+void em_push_locus(EmPrep& P, int l, int A, int S, int r0, int R, int period, int haploid, int32_t bps_off, const int32_t* reads_of_sample){
+  hs_em_locus_t& L = P.loci[l];
+  memset(&L, 0, sizeof L);
+  L.A = A; L.S = S; L.R = R; L.period = period; L.haploid = haploid;
+  L.read_begin = r0; L.samp_begin = P.samp_off; L.bps_off = bps_off;
+  L.post_off = P.post_off; L.ll_off = P.ll_off; L.prior_off = P.prior_off; L.sa_off = P.sa_off;
+  int r = r0;
+  for (int s = 0; s < S; s++){                                       // posterior-kernel units: (locus, sample)
+    hs_post_unit_t u; memset(&u, 0, sizeof u);
+    u.post_off = P.post_off + (int64_t)s*A*A; u.prior_off = P.prior_off; u.n_alleles = A; u.samp_index = P.samp_off + s;
+    u.read_begin = r; u.ll_off = P.ll_off + (int64_t)(r - r0)*A;
+    r += reads_of_sample[s];
+    u.n_reads = r - u.read_begin;
+    P.units.push_back(u); P.unit_locus.push_back(l);
+  }
+  P.post_off += (int64_t)S*A*A; P.ll_off += (int64_t)R*A; P.prior_off += (int64_t)A*A; P.samp_off += S; P.sa_off += (int64_t)S*A;
+}
 int em_prepare(const hipstr_em_batch_t* eb, bool host_loop, EmPrep& P){
   using hipstr::api_fail;
   const int nl = eb->n_loci;
@@ -822,49 +841,25 @@ int em_prepare(const hipstr_em_batch_t* eb, bool host_loop, EmPrep& P){
     Q.gtp.resize(A);
     for (int a = 0; a < A; a++) Q.gtp[a] = (host_loop ? log(g[a]) : cr_log(g[a])) - lt;
   });
-  int64_t post_off = 0, ll_off = 0, prior_off = 0, sa_off = 0; int samp_off = 0;
   for (int l = 0; l < nl; l++){
     const LocusPrep& Q = lp[l];
     if (Q.err) return api_fail(Q.err);
-    const int S = eb->n_samples[l], r0 = eb->read_off[l], r1 = eb->read_off[l+1], R = r1 - r0;
-    const int A = (int)Q.sizes.size();
-    hs_em_locus_t& L = loci[l];
-    memset(&L, 0, sizeof L);
-    L.A = A; L.S = S; L.R = R; L.period = eb->period[l]; L.haploid = (eb->haploid && eb->haploid[l]) ? 1 : 0;
-    L.read_begin = r0; L.samp_begin = samp_off; L.bps_off = (int32_t)bps.size();
-    L.post_off = post_off; L.ll_off = ll_off; L.prior_off = prior_off; L.sa_off = sa_off;
+    const int r0 = eb->read_off[l], r1 = eb->read_off[l+1];
+    em_push_locus(P, l, (int)Q.sizes.size(), eb->n_samples[l], r0, r1 - r0, eb->period[l], (eb->haploid && eb->haploid[l]) ? 1 : 0, (int32_t)bps.size(), Q.reads_of_sample.data());
     gtp.insert(gtp.end(), Q.gtp.begin(), Q.gtp.end());
     bps.insert(bps.end(), Q.sizes.begin(), Q.sizes.end());
-    int r = r0;
-    for (int s = 0; s < S; s++){                                       // posterior-kernel units: (locus, sample)
-      hs_post_unit_t u; memset(&u, 0, sizeof u);
-      u.post_off = post_off + (int64_t)s*A*A; u.prior_off = prior_off; u.n_alleles = A; u.samp_index = samp_off + s;
-      u.read_begin = r; u.ll_off = ll_off + (int64_t)(r - r0)*A;
-      r += Q.reads_of_sample[s];
-      u.n_reads = r - u.read_begin;
-      units.push_back(u); unit_locus.push_back(l);
-    }
-    post_off += (int64_t)S*A*A; ll_off += (int64_t)R*A; prior_off += (int64_t)A*A; samp_off += S; sa_off += (int64_t)S*A;
   }
-  P.post_off = post_off; P.ll_off = ll_off; P.prior_off = prior_off; P.sa_off = sa_off; P.samp_off = samp_off;
   return 0;
 }
 
-}  // namespace
-
-extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
-  hipstr::ApiTimer prof_t(hipstr::PB_EM_TRAIN);
-  using hipstr::api_fail;
-  if (!eb || !trained || !stutter || !n_iter || !final_ll) return api_fail("null argument");
-  const int nl = eb->n_loci;
-  if (nl < 0) return api_fail("negative locus count");
-  if (nl == 0) return 0;
-  hipstr::ApiTables T;
-  if (hipstr::api_device_tables(&T)) return 1;
+// The loop of train() (:171-226) for a prepared batch: P's locus records and posterior units, and the seven per-read and per-allele arrays
+// they index, already on the device — uploaded from em_prepare's host arrays (hipstr_em_train) or built there (em_input.hip:
+// hipstr_em_train_dev).  Everything else the loop needs is allocated here, through `dev` (whose blocks outlive the loop's kernels).
+struct EmArrays { int32_t *bps, *obs, *lab, *w; double *p1, *p2, *gtp; };
+int em_loop(const hipstr::ApiTables& T, EmBufs& dev, EmPrep& P, const EmArrays& in, int max_iter, double min_abs_change, double min_frac_change,
+            bool host_loop, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
   const hipstr::HostTables& HT = hipstr::host_tables();
-  const int n_reads = eb->read_off[nl];
   const bool timing = getenv("HIPSTR_TIMING") != NULL;
-  const bool host_loop = getenv("HIPSTR_EM_HOST_LOOP") && atoi(getenv("HIPSTR_EM_HOST_LOOP")) != 0;       // the round-4 loop: host libm, every locus in every round
   auto t_prev = std::chrono::steady_clock::now();
   double t_gpu = 0.0, t_host = 0.0;
   auto lap = [&](const char* what, double* into){
@@ -873,28 +868,20 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
     t_prev = now;
     if (into) *into += dt; else if (timing) fprintf(stderr, "hipstr_em_train: %s %.3f ms\n", what, 1e3*dt);
   };
-
-  // ---- alleles, read -> allele index, initial allele frequencies, (locus, sample) units; the refusals
-  EmPrep P;
-  if (em_prepare(eb, host_loop, P)) return 1;
   std::vector<hs_em_locus_t>& loci = P.loci; std::vector<hs_post_unit_t>& units = P.units;
-  std::vector<int32_t>& bps = P.bps; std::vector<int32_t>& obs = P.obs; std::vector<int32_t>& unit_locus = P.unit_locus;
-  std::vector<double>& gtp = P.gtp;
+  std::vector<int32_t>& unit_locus = P.unit_locus;
+  const int nl = (int)loci.size();
   const int64_t post_off = P.post_off, ll_off = P.ll_off, prior_off = P.prior_off, sa_off = P.sa_off; const int samp_off = P.samp_off;
-  lap("alleles and units", NULL);
   // ---- device state
-  EmBufs dev;
-  dev.stream = T.stream;
   hs_em_dev_t h; memset(&h, 0, sizeof h);
   hs_post_dev_t ph; memset(&ph, 0, sizeof ph);
-  hs_em_locus_t* d_loci; hs_post_unit_t* d_units; int32_t *d_active, *d_unit_active, *d_bps, *d_obs, *d_lab, *d_w, *d_mapgt;
-  double *d_logp, *d_p1, *d_p2, *d_gtp, *d_ll, *d_prior, *d_post, *d_tot, *d_newll, *d_sums, *d_rowlse, *d_leff, *d_part, *d_keep, *d_gmax; int32_t* d_cat;
-  std::vector<int32_t> ones(n_reads, 1);
+  hs_em_locus_t* d_loci; hs_post_unit_t* d_units; int32_t *d_active, *d_unit_active, *d_mapgt;
+  int32_t* const d_bps = in.bps, * const d_obs = in.obs, * const d_lab = in.lab, * const d_w = in.w;
+  double* const d_p1 = in.p1, * const d_p2 = in.p2, * const d_gtp = in.gtp;
+  double *d_logp, *d_ll, *d_prior, *d_post, *d_tot, *d_newll, *d_sums, *d_rowlse, *d_leff, *d_part, *d_keep, *d_gmax; int32_t* d_cat;
   if (dev.put(&d_loci, loci.data(), loci.size()) || dev.put(&d_units, units.data(), units.size()) || dev.alloc(&d_active, nl) ||
-      dev.alloc(&d_unit_active, units.size()) || dev.put(&d_bps, bps.data(), bps.size()) || dev.put(&d_obs, obs.data(), obs.size()) ||
-      dev.put(&d_lab, eb->sample_label, n_reads) || dev.put(&d_w, ones.data(), ones.size()) || dev.alloc(&d_mapgt, 2*(size_t)samp_off) ||
-      dev.alloc(&d_logp, 9*(size_t)nl) || dev.put(&d_p1, eb->log_p1, n_reads) || dev.put(&d_p2, eb->log_p2, n_reads) ||
-      dev.put(&d_gtp, gtp.data(), gtp.size()) || dev.alloc(&d_ll, ll_off) || dev.alloc(&d_prior, prior_off) || dev.alloc(&d_post, post_off) ||
+      dev.alloc(&d_unit_active, units.size()) || dev.alloc(&d_mapgt, 2*(size_t)samp_off) ||
+      dev.alloc(&d_logp, 9*(size_t)nl) || dev.alloc(&d_ll, ll_off) || dev.alloc(&d_prior, prior_off) || dev.alloc(&d_post, post_off) ||
       dev.alloc(&d_tot, samp_off) || dev.alloc(&d_newll, nl) || dev.alloc(&d_sums, 7*(size_t)nl) || dev.alloc(&d_rowlse, post_off) ||
       dev.alloc(&d_cat, ll_off) || dev.alloc(&d_leff, ll_off) || dev.alloc(&d_part, 7*(size_t)HS_EM_PARTS*nl) || dev.alloc(&d_keep, 7*(size_t)nl) || dev.alloc(&d_gmax, sa_off)) return 1;
   h.loci = d_loci; h.active = d_active; h.logp = d_logp; h.bps = d_bps; h.obs = d_obs; h.sample_label = d_lab; h.log_p1 = d_p1; h.log_p2 = d_p2;
@@ -932,8 +919,8 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
       hb[k] = h; hb[k].active = NULL;
       hb[k].list = d_list[k]; hb[k].counts = d_counts[k]; hb[k].next_list = d_list[k ^ 1]; hb[k].next_counts = d_counts[k ^ 1]; hb[k].next_units = d_ulist[k ^ 1];
       hb[k].next_unit_begin = d_ubegin; hb[k].unit_first = d_ufirst; hb[k].logp_rw = d_logp; hb[k].sp = d_sp; hb[k].cur_ll = d_curll; hb[k].iter = d_iter;
-      hb[k].state = d_state; hb[k].n_iter = d_niter; hb[k].final_ll = d_fll; hb[k].max_iter = eb->max_iter; hb[k].n_loci = nl;
-      hb[k].min_abs = eb->min_ll_abs_change; hb[k].min_frac = eb->min_ll_frac_change;
+      hb[k].state = d_state; hb[k].n_iter = d_niter; hb[k].final_ll = d_fll; hb[k].max_iter = max_iter; hb[k].n_loci = nl;
+      hb[k].min_abs = min_abs_change; hb[k].min_frac = min_frac_change;
       pb2[k] = ph; pb2[k].unit_active = NULL; pb2[k].unit_list = d_ulist[k]; pb2[k].n_list = d_counts[k] + 1;
     }
     hs_em_dev_t* d_hb; hs_post_dev_t* d_pb;
@@ -960,7 +947,7 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
     hipLaunchKernelGGL(hs_em_units, dim3(nl), dim3(HS_EM_UNITS_THREADS), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
     unsigned bound_l = (unsigned)nl, bound_u = (unsigned)n_units;
     int rounds = 0;
-    for (int r = 0; r <= hs_em_last_round(eb->max_iter); r++){
+    for (int r = 0; r <= hs_em_last_round(max_iter); r++){
       const hs_em_dev_t* H = d_hb + (r & 1); const hs_post_dev_t* PH = d_pb + (r & 1);
       if (bound_l > 0){
         hipLaunchKernelGGL(hs_em_fill, dim3(bound_l), dim3(256), 0, T.stream, H);
@@ -1020,7 +1007,7 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
     int n_active = 0;
     for (int l = 0; l < nl; l++){
       State& s = st[l];
-      if (!s.done && s.it > eb->max_iter){ s.done = true; s.ok = false; }      // ran out of iterations: train() returns false
+      if (!s.done && s.it > max_iter){ s.done = true; s.ok = false; }      // ran out of iterations: train() returns false
       active[l] = s.done ? 0 : 1; n_active += active[l];
       const double* sp = s.sp;                                                 // StutterModel constructor (stutter_model.h:44-58)
       double* q = &logp[9*(size_t)l];
@@ -1067,7 +1054,7 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
       const double nw[6] = { in_pgeom, exp(t[0] - log_total), exp(t[1] - log_total), out_pgeom, exp(t[4] - log_total), exp(t[5] - log_total) };
       const double abs_change = new_LL - s.LL, frac_change = -(new_LL - s.LL)/s.LL;
       bool conv = false;
-      if (abs_change < eb->min_ll_abs_change && frac_change < eb->min_ll_frac_change) conv = true;
+      if (abs_change < min_abs_change && frac_change < min_frac_change) conv = true;
       else {
         conv = true;
         for (int k = 0; k < 6; k++) if (!(fabs(s.sp[k] - nw[k]) < 0.0001)) conv = false;      // parameters_within_threshold (stutter_model.h:62-65)
@@ -1083,6 +1070,69 @@ extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, do
     memcpy(stutter + 6*(size_t)l, st[l].sp, 6*sizeof(double));
   }
   return 0;
+}
+
+// hipstr_em_train on the device of T: em_prepare on the host, its arrays uploaded, the loop.
+int em_train_on(const hipstr::ApiTables& T, const hipstr_em_batch_t* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
+  const int nl = eb->n_loci;
+  const int n_reads = eb->read_off[nl];
+  const bool host_loop = getenv("HIPSTR_EM_HOST_LOOP") && atoi(getenv("HIPSTR_EM_HOST_LOOP")) != 0;       // the round-4 loop: host libm, every locus in every round
+  const auto t0 = std::chrono::steady_clock::now();
+  // ---- alleles, read -> allele index, initial allele frequencies, (locus, sample) units; the refusals
+  EmPrep P;
+  if (em_prepare(eb, host_loop, P)) return 1;
+  if (getenv("HIPSTR_TIMING")) fprintf(stderr, "hipstr_em_train: %s %.3f ms\n", "alleles and units", 1e3*std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  EmBufs dev;
+  dev.ctx = T.ctx; dev.stream = T.stream;
+  EmArrays in;
+  std::vector<int32_t> ones(n_reads, 1);
+  if (dev.put(&in.bps, P.bps.data(), P.bps.size()) || dev.put(&in.obs, P.obs.data(), P.obs.size()) || dev.put(&in.lab, eb->sample_label, n_reads) ||
+      dev.put(&in.w, ones.data(), ones.size()) || dev.put(&in.p1, eb->log_p1, n_reads) || dev.put(&in.p2, eb->log_p2, n_reads) ||
+      dev.put(&in.gtp, P.gtp.data(), P.gtp.size())) return 1;
+  return em_loop(T, dev, P, in, eb->max_iter, eb->min_ll_abs_change, eb->min_ll_frac_change, host_loop, trained, stutter, n_iter, final_ll);
+}
+
+}  // namespace
+
+extern "C" int hipstr_em_train(const hipstr_em_batch_t* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
+  hipstr::ApiTimer prof_t(hipstr::PB_EM_TRAIN);
+  using hipstr::api_fail;
+  if (!eb || !trained || !stutter || !n_iter || !final_ll) return api_fail("null argument");
+  const int nl = eb->n_loci;
+  if (nl < 0) return api_fail("negative locus count");
+  if (nl == 0) return 0;
+  hipstr::ApiTables T;
+  if (hipstr::api_device_tables(&T)) return 1;
+  return em_train_on(T, eb, trained, stutter, n_iter, final_ll);
+}
+
+// ---- what em_input.hip (hipstr_em_train_dev) calls: api_internal.h
+int hipstr::em_train_batch_on(const ApiTables& T, const hipstr_em_batch_t* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
+  return em_train_on(T, eb, trained, stutter, n_iter, final_ll);
+}
+int hipstr::em_prepare_host(const hipstr_em_batch_t* eb, std::vector<int32_t>& size_off, std::vector<int32_t>& sizes, std::vector<int32_t>& obs, std::vector<double>& log_freq){
+  EmPrep P;
+  if (eb->n_loci > 0 && em_prepare(eb, false, P)) return 1;
+  size_off.assign(1, 0);
+  for (const hs_em_locus_t& L : P.loci) size_off.push_back(L.bps_off + L.A);
+  sizes = P.bps; obs = P.obs; log_freq = P.gtp;
+  return 0;
+}
+int hipstr::em_train_prepared(const ApiTables& T, int n_loci, const EmLocusFacts* facts, const int32_t* reads_of_sample, const EmDeviceArrays& arr,
+                              int max_iter, double min_abs_change, double min_frac_change, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
+  hipstr::ApiTimer prof_t(hipstr::PB_EM_TRAIN);
+  EmPrep P;
+  P.loci.assign((size_t)n_loci, hs_em_locus_t());
+  int64_t so = 0;
+  for (int l = 0; l < n_loci; l++){
+    const EmLocusFacts& F = facts[l];
+    em_push_locus(P, l, F.A, F.S, F.read_begin, F.R, F.period, F.haploid, F.bps_off, reads_of_sample + so);
+    so += F.S;
+  }
+  EmBufs dev;
+  dev.ctx = T.ctx; dev.stream = T.stream;
+  const EmArrays in = { arr.bps, arr.obs, arr.sample_label, arr.weight, arr.log_p1, arr.log_p2, arr.gtp };
+  return em_loop(T, dev, P, in, max_iter, min_abs_change, min_frac_change, false, trained, stutter, n_iter, final_ll);
 }
 
 #ifndef HIPSTR_NO_DEBUG_ABI

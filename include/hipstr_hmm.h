@@ -672,6 +672,57 @@ int  hipstr_assign_trace_stats_dev(const hipstr_post_batch_t* pb, const int32_t*
                                    int32_t* n_stutter, int32_t* n_flank_indel, int32_t* ml_bp);
 
 /*
+ * The stutter model retrained from the round's tracebacks: SeqStutterGenotyper::recompute_stutter_models (seq_stutter_genotyper.cpp:1542-1581,
+ * reached from genotyper_bam_processor.cpp:237-239) — the traced alignments are walked, every read whose trace spans the STR block hands
+ * its observed size, log_p1 and log_p2 to its sample (:1555-1566), and EMStutterGenotyper::train runs on them (hipstr_em_train above).
+ * Read r of locus l ENTERS the EM iff seed[r] >= 0, q = read_req[r] >= 0, and aln_start[q] < blk_start[3l+1] and aln_stop[q] > blk_end[3l+1],
+ * both strict (:1558-1559).  An entering read has num_bps = (str_seq_off[q+1] - str_seq_off[q]) + stutter_size[q], the read's log_p1 and
+ * log_p2 and its sample label; reads keep their order (grouped by ascending sample), samples and loci without an entering read stay in the
+ * batch (the reference constructs str_num_bps(num_samples_)).  period comes from pooled->period, haploid and n_samples from the posterior
+ * batch or run.
+ * Refused (non-zero, hipstr_last_error(), no output written): null arguments, pooled->n_loci that differs from the posterior batch's,
+ * req_read outside the pooled reads or not grouped by locus in locus order, read_req outside [-1, n_req), a read whose request belongs to
+ * another locus, an entering read whose request has stutter_size == HIPSTR_NO_STR_DATA (AlignmentTrace::stutter_size asserts,
+ * AlignmentTraceback.h:95-98; the message names the lowest such read).
+ */
+typedef struct hipstr_em_trace_request {
+  const hipstr_batch_t* pooled;   /* the round's pooled batch: only n_loci, blk_start, blk_end, period and read_off (the locus of a request) are read */
+  const int32_t* seed;            /* [n_reads] seed_positions_ of the un-pooled reads; < 0 = traced_alns[r] == NULL */
+  const int32_t* read_req;        /* [n_reads] hipstr_post_assign(HIPSTR_ASSIGN_RETRACE)'s read_req; -1 = no trace */
+  int32_t        n_req;
+  const int32_t* req_read;        /* [n_req] as given to the traceback call: fixes every request's locus */
+  int32_t        ref_allele, max_iter;              /* as hipstr_em_batch_t (0 and 100 at the reference's call site) */
+  double         min_ll_abs_change, min_ll_frac_change;
+} hipstr_em_trace_request_t;
+
+typedef struct hipstr_em_trace_out {
+  uint8_t* trained; double* stutter; int32_t* n_iter; double* final_ll;   /* as hipstr_em_train, [n_loci] / [6*n_loci] */
+  int32_t* em_read_off;   /* [n_loci+1] reads that entered the EM, or NULL */
+  int32_t* n_sizes;       /* [n_loci] allele sizes of the EM (reference size included), or NULL */
+} hipstr_em_trace_out_t;
+
+/* Host only (no device needed; works on a library that never opened one): the batch recompute_stutter_models builds, from host traces —
+ * only aln_start, aln_stop, stutter_size and str_seq_off of `tr` and n_loci, n_samples, read_off, sample_label, log_p1, log_p2 of `pb` are
+ * read.  em_read_off: [n_loci+1]; the four per-read arrays have room for every read of pb.  With period = pooled->period, haploid and
+ * n_samples = pb's and read_off = em_read_off they are a hipstr_em_batch_t. */
+int hipstr_em_batch_from_traces(const hipstr_post_batch_t* pb, const hipstr_em_trace_request_t* rq, const hipstr_trace_out_t* tr,
+                                int32_t* em_read_off /*[n_loci+1]*/, int32_t* sample_label, int32_t* num_bps,
+                                double* log_p1, double* log_p2 /* each [n_reads] capacity */);
+
+/* The same reads selected, compacted and prepared where the records lie, and hipstr_em_train's loop on them: stutter_size, aln_start,
+ * aln_stop and str_seq_off are read from td, log_p1, log_p2 and the (locus, sample) runs of reads from what hipstr_post_upload left on the
+ * device (the run need not have been launched); only seed, read_req and per-locus tables are uploaded, and per locus and per (locus, sample)
+ * a few counts come home.  Outputs, return codes and hipstr_last_error() are those of hipstr_em_train on the batch
+ * hipstr_em_batch_from_traces builds from hipstr_trace_dev_fetch(td, SCALARS | STR_SEQ), bit for bit; em_read_off and n_sizes (either may
+ * be NULL) are that batch's read offsets and the EM's allele counts.  Refused as hipstr_em_batch_from_traces refuses, and: rq->n_req that
+ * differs from td's, td on another device than pd, a handle without the scalars or the str_seq offsets.  Every refusal but the read without
+ * STR data is decided before any kernel runs; none writes into out.  A locus whose sizes span the table of integer logarithms (10 000
+ * values) or more, and every batch hipstr_em_train refuses, takes the host's preparation on the fetched compact arrays.  Device and pinned
+ * blocks come from the context's caches: no allocation in steady state. */
+int hipstr_em_train_dev(hipstr_post_dev_t* pd, const hipstr_em_trace_request_t* rq, const hipstr_trace_dev_t* td,
+                        hipstr_em_trace_out_t* out);
+
+/*
  * The read x haplotype matrix of a batch of loci, resident on the device between the rounds of SeqStutterGenotyper::genotype
  * (seq_stutter_genotyper.cpp:603-671): log_aln_probs_ (R x A per locus, un-pooled reads; genotyper.h:33) and seed_positions_, in the layout
  * of hipstr_post_batch_t::log_aln_probs.  The forward pass writes one row per POOLED read (hipstr_hmm_align, P x A); the posteriors, the

@@ -110,6 +110,24 @@ int hipstr_debug_rm_plan(int32_t n_alleles, int64_t n_items, int64_t out[5]);
  * HS_CENSUS_REQ_INTS.  Used by tests/test_census_plan.py. */
 int hipstr_debug_census_plan(int64_t n_req, int64_t n_reads, int64_t out[10]);
 
+/* Diagnostics (host only): the decisions hipstr_em_train_dev takes (hipstr_amd/csrc/em_input_layout.h) for a batch of n_runs (locus, sample)
+ * runs whose run in question has run_reads reads, and for a locus whose sizes (ref_allele included) lie in [lo, hi] and are n_sizes many:
+ * out[0] steps of a wavefront over the run, out[1] reads of its last step, out[2] workgroups of the select / scatter launches, out[3] chunks
+ * of the scan, out[4] runs of its last chunk, out[5] 1 = the locus is prepared on the device (presence bitmap), 0 = the call takes the host's
+ * preparation, out[6] words of the bitmap (0 on the host path), out[7] 1 = the initial allele frequencies are evaluated on the device (0:
+ * "too many distinct allele sizes" awaits on the host); then the compiled limits: out[8] HS_EMI_THREADS, out[9] HS_EMI_WAVE, out[10]
+ * HS_EMI_SCAN_CHUNK, out[11] HS_EMI_SPAN_LIMIT.  Used by tests/test_em_input_plan.py. */
+int hipstr_debug_em_input_plan(int64_t n_runs, int64_t run_reads, int64_t lo, int64_t hi, int64_t n_sizes, int64_t out[12]);
+/* Diagnostics: what hipstr_em_train_dev prepares before the EM loop, for the same arguments (the same refusals): the compact arrays, the
+ * alleles' sizes per locus (size_off: [n_loci+1]), the reads' allele indices and the initial log allele frequencies; *route = 0 when the
+ * device prepared them, 1 when the call took the host's preparation.  Per-read arrays: room for every read of the run; sizes / log_freq:
+ * room for reads + loci.  Used by tests/test_em_from_traces_gpu.py. */
+typedef struct hipstr_debug_em_input {
+  int32_t* em_read_off; int32_t* num_bps; int32_t* sample_label; int32_t* obs; double* log_p1; double* log_p2;
+  int32_t* size_off; int32_t* sizes; double* log_freq; int32_t* route;
+} hipstr_debug_em_input_t;
+int hipstr_debug_em_input_fetch(hipstr_post_dev_t* pd, const hipstr_em_trace_request_t* rq, const hipstr_trace_dev_t* td, hipstr_debug_em_input_t* out);
+
 /* Diagnostics (host only): one entry {A, G, Bnd} of the tabulated closed form the STR kernel uses for a "simple" visiting
  * list (StutterAlignerClass.cpp:59-150 for a periodic block): with `bound` columns of the block in reach, a run of U0 equal
  * configurations at the block's right end and `tail` configurations in total, fast_log_sum_exp over the pushed values is
