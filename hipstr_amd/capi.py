@@ -690,6 +690,114 @@ def em_input_fetch(lib, pd, n_loci, n_reads, bptr, seed, read_req, req_read, td,
                 log_p2=fa[1][:m], size_off=soff, sizes=sizes[:k], log_freq=freq[:k])
 
 
+class HipstrPoolOut(C.Structure):
+    _fields_ = [("pool_index", _i32p), ("n_pools", _i32p), ("pool_off", _i32p), ("pool_rep", _i32p), ("pool_size", _i32p),
+                ("pool_qual_off", _i32p), ("pool_quals", C.POINTER(C.c_char))]
+
+
+POOL_ON_HOST = 1        # HIPSTR_POOL_ON_HOST
+POOL_ROUTES = ("device", "host", "copy", "net", "radix")
+POOL_LAST = ("device_loci", "host_loci", "collision_loci", "pools_copy", "pools_net", "pools_radix", "chunks", "reads_uploaded")
+POOL_FILL = -7          # what run_pool fills the integer outputs with before the call (qualities: 0x5A)
+POOL_FIELDS = ("pool_index", "n_pools", "pool_off", "pool_rep", "pool_size", "pool_qual_off", "pool_quals")
+
+
+def _pool_sigs(lib):
+    _sig(lib.hipstr_pool_reads, C.c_int, [_BP, C.POINTER(HipstrPoolOut)])
+    _sig(lib.hipstr_pool_reads_host, C.c_int, [_BP, C.POINTER(HipstrPoolOut)])
+    _sig(lib.hipstr_pool_batch, C.c_void_p, [_BP, C.c_uint32])
+    _sig(lib.hipstr_pooled_batch_batch, _BP, [C.c_void_p])
+    _sig(lib.hipstr_pooled_batch_pool_index, _i32p, [C.c_void_p])
+    _sig(lib.hipstr_pooled_batch_free, None, [C.c_void_p])
+    _sig(lib.hipstr_debug_pool_plan, C.c_int, [_BP, C.c_double, C.c_char_p, C.c_int])
+    _sig(lib.hipstr_debug_pool_last, C.c_int, [C.POINTER(C.c_int64)])
+    _sig(lib.hipstr_debug_pool_last_timing, C.c_int, [_f64p])
+
+
+def _batch_struct(bptr):
+    return bptr.contents if hasattr(bptr, "contents") else (bptr._obj if hasattr(bptr, "_obj") else bptr)
+
+
+def run_pool(lib, bptr, host=False):
+    """hipstr_pool_reads (host=True: hipstr_pool_reads_host) on a batch of un-pooled reads: a dict of the seven output arrays at their full
+    size — what the call leaves untouched still holds POOL_FILL / 0x5A."""
+    b = _batch_struct(bptr)
+    nl = b.n_loci
+    n = int(b.read_off[nl]) if nl else 0
+    nb = int(b.base_off[n]) if n else 0
+    a = dict(pool_index=np.full(n, POOL_FILL, np.int32), n_pools=np.full(nl, POOL_FILL, np.int32), pool_off=np.full(nl + 1, POOL_FILL, np.int32),
+             pool_rep=np.full(n, POOL_FILL, np.int32), pool_size=np.full(n, POOL_FILL, np.int32), pool_qual_off=np.full(n + 1, POOL_FILL, np.int32),
+             pool_quals=np.full(nb + 1, 0x5A, np.uint8))
+    o = HipstrPoolOut(*[a[k].ctypes.data_as(_i32p) for k in POOL_FIELDS[:6]], a["pool_quals"].ctypes.data_as(C.POINTER(C.c_char)))
+    rc = (lib.hipstr_pool_reads_host if host else lib.hipstr_pool_reads)(bptr, C.byref(o))
+    if rc != 0:
+        raise RuntimeError("hipstr_pool_reads%s failed: %s" % ("_host" if host else "", lib.hipstr_last_error().decode()))
+    return a
+
+
+def pool_plan(lib, bptr, ws_mib=0.0):
+    """What hipstr_pool_reads would do with a batch (host only: hipstr_debug_pool_plan) as a dict."""
+    return _plan_json(lib, "hipstr_debug_pool_plan", lambda buf, cap: lib.hipstr_debug_pool_plan(bptr, ws_mib, buf, cap))
+
+
+def pool_last(lib):
+    """hipstr_debug_pool_last as a dict keyed by POOL_LAST."""
+    out = (C.c_int64 * 8)()
+    assert lib.hipstr_debug_pool_last(out) == 0
+    return dict(zip(POOL_LAST, [int(x) for x in out]))
+
+
+def pool_last_timing(lib):
+    out = (C.c_double * 4)()
+    assert lib.hipstr_debug_pool_last_timing(out) == 0
+    return dict(kernel_ms=out[0], bytes_up=out[1], bytes_down=out[2], stage_s=out[3])
+
+
+class PooledBatch:
+    """hipstr_pool_batch: the pooled batch (ptr: a hipstr_batch_t for hipstr_hmm_upload) and the un-pooled reads' pool indices."""
+
+    def __init__(self, lib, bptr, flags=0):
+        self.lib = lib
+        self.h = lib.hipstr_pool_batch(bptr, flags)
+        if not self.h:
+            raise RuntimeError("hipstr_pool_batch failed: " + lib.hipstr_last_error().decode())
+        b = _batch_struct(bptr)
+        self.n_unpooled = int(b.read_off[b.n_loci]) if b.n_loci else 0
+        self.ptr = lib.hipstr_pooled_batch_batch(self.h)
+        pi = lib.hipstr_pooled_batch_pool_index(self.h)
+        self.pool_index = np.ctypeslib.as_array(pi, shape=(self.n_unpooled,)).copy() if self.n_unpooled else np.zeros(0, np.int32)
+
+    def arrays(self):
+        """The pooled batch's arrays as numpy copies (bytes arrays without their closing NUL)."""
+        p = self.ptr.contents; nl = p.n_loci
+        raw = lambda name, cnt: C.string_at(C.c_void_p.from_buffer(p, getattr(HipstrBatch, name).offset).value, cnt) if cnt else b""      # (a c_char_p field read as such stops at a NUL)
+        i32 = lambda ptr, cnt: np.ctypeslib.as_array(ptr, shape=(cnt,)).copy() if cnt else np.zeros(0, np.int32)
+        d = dict(blk_start=i32(p.blk_start, 3 * nl), blk_end=i32(p.blk_end, 3 * nl), blk_nopts=i32(p.blk_nopts, 3 * nl), period=i32(p.period, nl),
+                 stutter=np.ctypeslib.as_array(p.stutter, shape=(6 * nl,)).copy() if nl else np.zeros(0))
+        nopt = int(d["blk_nopts"].sum())
+        d["opt_off"] = i32(p.opt_off, nopt + 1); d["hap_off"] = i32(p.hap_off, nl + 1); d["read_off"] = i32(p.read_off, nl + 1)
+        d["seq"] = np.frombuffer(raw("seq", int(d["opt_off"][-1])), np.uint8).copy()
+        P = int(d["read_off"][-1])
+        d["base_off"] = i32(p.base_off, P + 1); d["cigar_off"] = i32(p.cigar_off, P + 1); d["read_start"] = i32(p.read_start, P)
+        nb, nc = int(d["base_off"][-1]), int(d["cigar_off"][-1])
+        d["bases"] = np.frombuffer(raw("bases", nb), np.uint8).copy(); d["quals"] = np.frombuffer(raw("quals", nb), np.uint8).copy()
+        d["cigar_op"] = np.frombuffer(raw("cigar_op", nc), np.uint8).copy(); d["cigar_len"] = i32(p.cigar_len, nc)
+        A = int(d["hap_off"][-1])
+        d["realign_hap"] = np.ctypeslib.as_array(p.realign_hap, shape=(A,)).copy() if p.realign_hap else np.zeros(0, np.uint8)
+        d["realign_read"] = np.ctypeslib.as_array(p.realign_read, shape=(P,)).copy() if p.realign_read else np.zeros(0, np.uint8)
+        return d
+
+    def close(self):
+        if self.h:
+            self.lib.hipstr_pooled_batch_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def census_plan(lib, n_req, n_reads):
     """hipstr_debug_census_plan (host only) as a dict: the route of a locus of n_req requests and n_reads un-pooled reads and the compiled
     limits of hipstr_amd/csrc/census_layout.h."""
@@ -1111,6 +1219,7 @@ def load_hmm():
     _trace_dev_sigs(lib)
     _sig(lib.hipstr_post_census_dev, C.c_int, [C.c_void_p, C.POINTER(HipstrCensusRequest), C.c_void_p, C.POINTER(HipstrCensusOut)])
     _em_trace_sigs(lib)
+    _pool_sigs(lib)
     return lib
 
 

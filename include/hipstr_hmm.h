@@ -773,6 +773,49 @@ int  hipstr_rm_fetch(hipstr_read_matrix_t* rm, double* ll /* [sum R_l*A_l] */, i
 /* Every hipstr_post_dev_t built on the matrix' pointer must have been freed. */
 void hipstr_rm_free(hipstr_read_matrix_t* rm);
 
+/*
+ * ReadPooler (read_pooler.h:13-53, read_pooler.cpp:3-20) and BaseQuality::median_base_qualities (base_quality.cpp:11-28) for a batch of
+ * UN-POOLED reads: what stands in front of hipstr_hmm_upload.  Only n_loci, read_off, base_off, bases and quals of the batch are read.
+ * Two reads of a locus share a pool iff their sequences are equal byte for byte (length included, case not folded; reads of length 0 form
+ * one pool with empty qualities); pools are numbered in order of first appearance by read index; pool_rep is that first read; the quality
+ * at position i of a pool is sorted(member bytes at i)[n / 2] with bytes ordered as signed char (the upper median: n = 2 gives the larger).
+ * Loci are independent; a locus without reads has 0 pools.  The arrays are sized by the input, so they always suffice; entries past
+ * pool_off[n_loci] of the per-pool arrays and past pool_qual_off[pool_off[n_loci]] are left untouched.
+ * hipstr_pool_reads works on the device, in chunks of whole loci under a workspace budget (HIPSTR_POOL_WS_MIB, default 512): reads are
+ * grouped by a 64-bit hash and every member is then compared with its pool's first read byte for byte — a locus in which two different
+ * reads share a hash, and a locus of more reads than the grouping kernel holds in LDS (4096), is pooled by the host code inside the same
+ * call.  hipstr_pool_reads_host is that host code for the whole batch; it needs no device.  Both give identical bytes in every output.
+ * Refused (non-zero + hipstr_last_error(), nothing written, nothing launched): NULL arguments, a NULL output array, offset tables the other
+ * entry points refuse.  hipstr_pool_reads without a device fails as every device entry point does; it does not fall back to the host.
+ * A HIP error while the call runs (an allocation, a copy, a launch) is non-zero + hipstr_last_error() as well, but "nothing written" holds
+ * for the first chunk only: the outputs of the loci of the chunks before the failing one are written already (discard them).
+ * read_off[0] is normally 0.  Where it is not, reads 0 .. read_off[0] belong to no locus: their pool_index entries are left untouched,
+ * and pool_rep counts from the batch's read 0 all the same.
+ */
+typedef struct hipstr_pool_out {
+  int32_t* pool_index;     /* [n_reads]   pool of the read within its locus: ReadPooler::add_alignment's return value            */
+  int32_t* n_pools;        /* [n_loci]                                                                                           */
+  int32_t* pool_off;       /* [n_loci+1]  prefix sums of n_pools                                                                  */
+  int32_t* pool_rep;       /* [n_reads]   per pool (pool_off order): the read that opened it, as an index into the batch's reads  */
+  int32_t* pool_size;      /* [n_reads]   per pool: members                                                                       */
+  int32_t* pool_qual_off;  /* [n_reads+1] per pool: start of its qualities                                                        */
+  char*    pool_quals;     /* [base_off[n_reads]] median qualities, pools back to back                                            */
+} hipstr_pool_out_t;
+int hipstr_pool_reads(const hipstr_batch_t* unpooled, hipstr_pool_out_t* out);        /* on the device */
+int hipstr_pool_reads_host(const hipstr_batch_t* unpooled, hipstr_pool_out_t* out);   /* host only, no device needed */
+
+/* The batch ReadPooler leaves behind, in one allocation: the haplotype arrays copied, per pool its first read's bases, start and CIGAR and
+ * the pool's median qualities, realign_read = NULL — ready for hipstr_hmm_upload — and the reads' pool indices for
+ * hipstr_read_layout_t::pool_index.  flags: HIPSTR_POOL_ON_HOST pools with hipstr_pool_reads_host, 0 on the device.  NULL +
+ * hipstr_last_error() on a refusal or a failure.  hipstr_pooled_batch_pool_index is indexed by the un-pooled batch's read number, read 0
+ * first: with read_off[0] > 0 the entries of the reads in front of the first locus are 0 and mean nothing. */
+#define HIPSTR_POOL_ON_HOST 1u
+typedef struct hipstr_pooled_batch hipstr_pooled_batch_t;
+hipstr_pooled_batch_t* hipstr_pool_batch(const hipstr_batch_t* unpooled, uint32_t flags);
+const hipstr_batch_t*  hipstr_pooled_batch_batch(const hipstr_pooled_batch_t* p);
+const int32_t*         hipstr_pooled_batch_pool_index(const hipstr_pooled_batch_t* p);      /* [n_reads of the un-pooled batch] */
+void hipstr_pooled_batch_free(hipstr_pooled_batch_t* p);
+
 /* The diagnostics entry points (hipstr_debug_*: what the tests, the fuzzers and bench.py look inside the library with) are declared in
  * hipstr_hmm_debug.h — not part of the drop-in ABI; a build with -DHIPSTR_NO_DEBUG_ABI leaves them out of the library. */
 

@@ -110,6 +110,23 @@ int hipstr_debug_rm_plan(int32_t n_alleles, int64_t n_items, int64_t out[5]);
  * HS_CENSUS_REQ_INTS.  Used by tests/test_census_plan.py. */
 int hipstr_debug_census_plan(int64_t n_req, int64_t n_reads, int64_t out[10]);
 
+/* Diagnostics (host only): what hipstr_pool_reads would do with a batch under a budget of ws_mib MiB of workspace per chunk (<= 0: the
+ * call's own default or HIPSTR_POOL_WS_MIB), from the functions of hipstr_amd/csrc/pool_layout.h the call and its kernels use, as one JSON
+ * object: "thresholds" (the compiled limits), "routes" (every route name: a locus is pooled on the "device" or, for its size, on the
+ * "host"; a pool's medians are a "copy", come from the "net" or from the "radix" select), per chunk "l0" / "l1" (locus range), "reads" and
+ * "bytes" (uploaded reads and the workspace they take), "device_loci", "host_loci", "lds_bytes" (of the grouping launch), "hash_steps"
+ * (most steps of a hash wavefront), "pools" ([copy, net, radix]: pools by median route, from the host's pooling) and "routes_hit".  Same
+ * conventions as hipstr_debug_trace_plan.  Used by tests/test_pool_host.py. */
+int hipstr_debug_pool_plan(const hipstr_batch_t* unpooled, double ws_mib, char* json, int cap);
+/* Diagnostics: the calling thread's last hipstr_pool_reads (or hipstr_pool_batch on the device): out[0] loci pooled on the device, out[1]
+ * loci the host pooled for their size, out[2] loci the host redid after a hash collision, out[3..5] pools of the device's loci by median
+ * route (copy, net, radix), out[6] chunks, out[7] reads uploaded.  hipstr_debug_pool_last_timing: out[0] milliseconds between HIP events
+ * around the call's kernels (0 unless HIPSTR_POOL_TIMING is set), out[1] bytes sent to the device, out[2] bytes copied back, out[3] seconds
+ * the host spent staging the reads.  A call that was refused leaves the numbers of the call before it; one that failed on the way leaves
+ * zeros.  Used by tests/test_pool_gpu.py and tools/pool_timing.py. */
+int hipstr_debug_pool_last(int64_t out[8]);
+int hipstr_debug_pool_last_timing(double out[4]);
+
 /* Diagnostics (host only): the decisions hipstr_em_train_dev takes (hipstr_amd/csrc/em_input_layout.h) for a batch of n_runs (locus, sample)
  * runs whose run in question has run_reads reads, and for a locus whose sizes (ref_allele included) lie in [lo, hi] and are n_sizes many:
  * out[0] steps of a wavefront over the run, out[1] reads of its last step, out[2] workgroups of the select / scatter launches, out[3] chunks
