@@ -1067,6 +1067,50 @@ _scalar_probes = {
 }
 
 
+_u32p = C.POINTER(C.c_uint32)
+_i64p = C.POINTER(C.c_int64)
+# the float log-sum-exp primitives in bulk (hipstr_amd/csrc/float_lse.h): the same three signatures in the product (hipstr_debug_*, device
+# and _host), the oracle (oracle_*) and the compiled reference (ref_*), bound by the helpers below on first use
+_float_lse_probes = {
+    "float_fn": [C.c_int, C.c_uint32, C.c_int64, _u32p],
+    "fast_lse2": [_f64p, _f64p, _f64p, C.c_int64],
+    "fast_lse_vec": [_f64p, _i64p, _f64p, C.c_int64],
+}
+FLOAT_FN = {"fasterexp": 0, "fasterlog": 1, "fastexp": 2, "fastlog": 3, "lse2_term": 4, "div_pow2": 5, "div_log": 6, "rcp_pow2": 7, "rcp_log": 8}
+
+
+def _float_lse_fn(lib, name):
+    """Entry point `name` of `lib` with its signature set — bound where it is used, not by the loaders: load_oracle() / load_ref() / load_hmm()
+    go on working with a library that was built before these entries existed."""
+    fn = getattr(lib, name)
+    kind = next(k for k in _float_lse_probes if k in name)
+    _sig(fn, C.c_int, _float_lse_probes[kind])
+    return fn
+
+
+def float_fn(lib, name, which, bits_lo, count):
+    """The result bits (uint32 array) of function `which` (a FLOAT_FN name or number) at the `count` float bit patterns from bits_lo, from
+    entry point `name` of `lib` (hipstr_debug_float_fn[_host], oracle_float_fn, ref_float_fn)."""
+    out = np.empty(int(count), np.uint32)
+    rc = _float_lse_fn(lib, name)(FLOAT_FN.get(which, which), int(bits_lo), int(count), out.ctypes.data_as(_u32p))
+    assert rc == 0, (name, which, hex(bits_lo), count, lib.hipstr_last_error() if name.startswith("hipstr_") else rc)
+    return out
+
+
+def fast_lse2(lib, name, a, b):
+    a = np.ascontiguousarray(a, np.float64); b = np.ascontiguousarray(b, np.float64); out = np.empty_like(a)
+    assert a.shape == b.shape and _float_lse_fn(lib, name)(a.ctypes.data_as(_f64p), b.ctypes.data_as(_f64p), out.ctypes.data_as(_f64p), a.size) == 0, name
+    return out
+
+
+def fast_lse_vec(lib, name, rows):
+    """fast_log_sum_exp(vector) of every row of `rows` (a list of 1-d arrays) from entry point `name` of `lib`."""
+    off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    v = np.ascontiguousarray(np.concatenate(rows), np.float64); out = np.empty(len(rows), np.float64)
+    assert _float_lse_fn(lib, name)(v.ctypes.data_as(_f64p), off.ctypes.data_as(_i64p), out.ctypes.data_as(_f64p), len(rows)) == 0, name
+    return out
+
+
 def load_oracle():
     """oracle/libhipstr_oracle.so — the C restatement.  TEST INFRASTRUCTURE: callers must be
     tests/, __graft_entry__.smoke() or bench.py's cpu_baseline leg."""

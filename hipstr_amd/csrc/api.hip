@@ -29,6 +29,7 @@
 #include "census_layout.h"
 #include "prep.h"
 #include "api_internal.h"
+#include "float_lse.h"
 
 extern "C" __global__ void hs_str_kernel(const hs_dev_t* dp, int active_begin, int only_long);
 extern "C" __global__ void hs_str_kernel_generic(const hs_dev_t* dp, int active_begin, int pw_grouped);
@@ -39,6 +40,9 @@ extern "C" __global__ void hs_posterior_accumulate_kernel(const hs_post_dev_t* d
 extern "C" __global__ void hs_posterior_finish_kernel(const hs_post_dev_t* dp);
 extern "C" __global__ void hs_genotype_kernel(const hs_gt_dev_t* dp);
 extern "C" __global__ void hs_cr_math_kernel(int which, const double* x, double* y, int64_t n);
+extern "C" __global__ void hs_float_fn_kernel(int which, uint32_t bits_lo, int64_t count, uint32_t* out);
+extern "C" __global__ void hs_fast_lse2_kernel(const double* a, const double* b, double* out, int64_t n, double thr);
+extern "C" __global__ void hs_fast_lse_vec_kernel(const double* v, const int64_t* row_off, double* out, int64_t n_rows, double thr);
 extern "C" __global__ void hs_assign_kernel(const hs_assign_dev_t* dp);
 extern "C" __global__ void hs_assign_kernel_wg(const hs_assign_dev_t* dp);
 extern "C" __global__ void hs_assign_scan_kernel(const hs_assign_dev_t* dp);
@@ -1132,6 +1136,103 @@ int hipstr_debug_cr_math(int which, const double* x, double* y, int64_t n){
   }
   c->dev_cache.put(dx); c->dev_cache.put(dy);
   return rc ? fail("hipstr_debug_cr_math: device call failed") : 0;
+}
+// float_lse.h on the device and, the _host forms, on the host (tests/test_float_lse_gpu.py, tests/test_float_lse.py)
+namespace {
+const int64_t FLOAT_FN_MAX = (int64_t)1 << 28;       // results of one call: 1 GiB
+int float_fn_args(int which, uint32_t bits_lo, int64_t count, const uint32_t* out, int n_modes){
+  if (!out || count < 0) return fail("null argument");
+  if (which < 0 || which >= n_modes) return fail("hipstr_debug_float_fn: no such function");
+  if (count > FLOAT_FN_MAX || (uint64_t)bits_lo + (uint64_t)count > ((uint64_t)1 << 32)) return fail("hipstr_debug_float_fn: range too long");
+  return 0;
+}
+// rows of at least one value each, offsets ascending from 0
+int lse_vec_args(const double* v, const int64_t* row_off, const double* out, int64_t n_rows){
+  if (!v || !row_off || !out || n_rows < 0) return fail("null argument");
+  if (n_rows && row_off[0] != 0) return fail("hipstr_debug_fast_lse_vec: row_off[0] != 0");
+  for (int64_t r = 0; r < n_rows; r++) if (row_off[r+1] <= row_off[r]) return fail("hipstr_debug_fast_lse_vec: empty row");
+  return 0;
+}
+}
+int hipstr_debug_float_fn(int which, uint32_t bits_lo, int64_t count, uint32_t* out_bits){
+  if (float_fn_args(which, bits_lo, count, out_bits, 9)) return 1;
+  if (count == 0) return 0;
+  Ctx* c = current_ctx();
+  if (!c || bind(c)) return 1;
+  uint32_t* d = (uint32_t*)c->dev_cache.get((size_t)count*4);
+  int rc = 1;
+  if (d){
+    hipLaunchKernelGGL(hs_float_fn_kernel, dim3((unsigned)((count + 255)/256)), dim3(256), 0, c->stream, which, bits_lo, count, d);
+    if (hipstr::wait_stream(c->stream) == hipSuccess && hipMemcpy(out_bits, d, (size_t)count*4, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+  }
+  c->dev_cache.put(d);
+  return rc ? fail("hipstr_debug_float_fn: device call failed") : 0;
+}
+int hipstr_debug_float_fn_host(int which, uint32_t bits_lo, int64_t count, uint32_t* out_bits){
+  if (float_fn_args(which, bits_lo, count, out_bits, 7)) return 1;        // the controls are the device's reciprocal: no host form
+  for (int64_t i = 0; i < count; i++){
+    const float x = f_from_bits(bits_lo + (uint32_t)i);
+    float r;
+    switch (which){
+      case 0: r = f_fasterexp(x); break;
+      case 1: r = f_fasterlog(x); break;
+      case 2: r = f_fastexp(x); break;
+      case 3: r = f_fastlog(x); break;
+      case 4: r = f_lse2_term(x); break;
+      case 5: r = f_div_tab(27.7280233f, x); break;
+      default: r = f_div_tab(1.72587999f, x); break;
+    }
+    out_bits[i] = f_to_bits(r);
+  }
+  return 0;
+}
+int hipstr_debug_fast_lse2(const double* a, const double* b, double* out, int64_t n){
+  if (!a || !b || !out || n < 0) return fail("null argument");
+  if (n == 0) return 0;
+  Ctx* c = current_ctx();
+  if (!c || bind(c)) return 1;
+  double* da = (double*)c->dev_cache.get((size_t)n*8); double* db = (double*)c->dev_cache.get((size_t)n*8); double* dy = (double*)c->dev_cache.get((size_t)n*8);
+  int rc = 1;
+  if (da && db && dy && hipMemcpy(da, a, (size_t)n*8, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(db, b, (size_t)n*8, hipMemcpyHostToDevice) == hipSuccess){
+    hipLaunchKernelGGL(hs_fast_lse2_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, c->stream, (const double*)da, (const double*)db, dy, n, hipstr::host_tables().log_thresh);
+    if (hipstr::wait_stream(c->stream) == hipSuccess && hipMemcpy(out, dy, (size_t)n*8, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+  }
+  c->dev_cache.put(da); c->dev_cache.put(db); c->dev_cache.put(dy);
+  return rc ? fail("hipstr_debug_fast_lse2: device call failed") : 0;
+}
+int hipstr_debug_fast_lse2_host(const double* a, const double* b, double* out, int64_t n){
+  if (!a || !b || !out || n < 0) return fail("null argument");
+  const double thr = hipstr::host_tables().log_thresh;
+  for (int64_t i = 0; i < n; i++) out[i] = fast_lse2(a[i], b[i], thr);
+  return 0;
+}
+int hipstr_debug_fast_lse_vec(const double* v, const int64_t* row_off, double* out, int64_t n_rows){
+  if (lse_vec_args(v, row_off, out, n_rows)) return 1;
+  if (n_rows == 0) return 0;
+  Ctx* c = current_ctx();
+  if (!c || bind(c)) return 1;
+  const size_t nv = (size_t)row_off[n_rows];
+  double* dv = (double*)c->dev_cache.get(nv*8); int64_t* dr = (int64_t*)c->dev_cache.get((size_t)(n_rows + 1)*8); double* dy = (double*)c->dev_cache.get((size_t)n_rows*8);
+  int rc = 1;
+  if (dv && dr && dy && hipMemcpy(dv, v, nv*8, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dr, row_off, (size_t)(n_rows + 1)*8, hipMemcpyHostToDevice) == hipSuccess){
+    hipLaunchKernelGGL(hs_fast_lse_vec_kernel, dim3((unsigned)((n_rows + 63)/64)), dim3(64), 0, c->stream, (const double*)dv, (const int64_t*)dr, dy, n_rows, hipstr::host_tables().log_thresh);
+    if (hipstr::wait_stream(c->stream) == hipSuccess && hipMemcpy(out, dy, (size_t)n_rows*8, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+  }
+  c->dev_cache.put(dv); c->dev_cache.put(dr); c->dev_cache.put(dy);
+  return rc ? fail("hipstr_debug_fast_lse_vec: device call failed") : 0;
+}
+int hipstr_debug_fast_lse_vec_host(const double* v, const int64_t* row_off, double* out, int64_t n_rows){
+  if (lse_vec_args(v, row_off, out, n_rows)) return 1;
+  const double thr = hipstr::host_tables().log_thresh;
+  for (int64_t r = 0; r < n_rows; r++){
+    Lse lse;
+    for (int pass = 0; pass < 2; pass++){
+      lse.start(pass, v[row_off[r]]);
+      for (int64_t i = row_off[r]; i < row_off[r+1]; i++) lse.push(pass, v[i], thr);
+    }
+    out[r] = lse.finish();
+  }
+  return 0;
 }
 void* hipstr_debug_cache_get(int64_t bytes){ Ctx* c = current_ctx(); if (!c || bind(c) || bytes < 0) return NULL; return c->dev_cache.get((size_t)bytes); }
 void hipstr_debug_cache_put(void* p){ Ctx* c = current_ctx(); if (c && p) c->dev_cache.put(p); }

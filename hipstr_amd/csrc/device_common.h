@@ -1,9 +1,10 @@
-// device_common.h — wave primitives and the bit-exact float log-sum-exp helpers shared by the HIP kernels.
+// device_common.h — wave primitives shared by the HIP kernels (and, through float_lse.h, the bit-exact float log-sum-exp helpers).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "layout.h"
+#include "float_lse.h"
 
 namespace {
 
@@ -72,29 +73,7 @@ __device__ __forceinline__ double wave_sum_d(double v){
   return rdlane(v, 63);
 }
 
-// ------------------------------------------------------------------ float approximations (bit-exact)
-__device__ __forceinline__ float f_fasterexp(float p){           // fastonebigheader.h:206-218
-  const float y = __fmul_rn(1.442695040f, p);
-  const float c = (y < -126.0f) ? -126.0f : y;
-  return __uint_as_float((uint32_t)__fmul_rn(8388608.0f, __fadd_rn(c, 126.94269504f)));
-}
-__device__ __forceinline__ float f_fasterlog(float x){           // fastonebigheader.h:348-358
-  float y = (float)__float_as_uint(x);
-  y = __fmul_rn(y, 8.2629582881927490e-8f);
-  return __fsub_rn(y, 87.989971088f);
-}
-
-// streaming form of fast_log_sum_exp(vector) (mathops.cpp:97-106): pass 0 finds the max,
-// pass 1 accumulates.  The float terms are summed in double, which is exact for any order.
-struct Lse {
-  double mx, tot;
-  __device__ __forceinline__ void start(int pass, double first){ if (pass == 0) mx = first; else tot = 0.0; }
-  __device__ __forceinline__ void push(int pass, double v, double thr){
-    if (pass == 0) mx = fmax(mx, v);
-    else { const double d = v - mx; if (d > thr) tot += (double)f_fasterexp((float)d); }
-  }
-  __device__ __forceinline__ double finish() const { return mx + (double)f_fasterlog((float)tot); }
-};
+// (the bit-exact float approximations f_fasterexp / f_fasterlog and the streaming Lse: float_lse.h)
 
 __device__ __forceinline__ double emit(uint8_t r, uint8_t c, double2 q){ return r == c ? q.x : q.y; }
 

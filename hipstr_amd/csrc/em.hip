@@ -37,6 +37,7 @@
 #include "prep.h"
 #include "api_internal.h"
 #include "cr_math.h"
+#include "float_lse.h"
 
 extern "C" __global__ void hs_posterior_kernel(const hs_post_dev_t* dp);
 
@@ -103,48 +104,7 @@ __device__ __forceinline__ int em_locus(const hs_em_dev_t& d){
 
 namespace {
 
-// The two float divisions of the reference's bit-trick exp2 / log (fastonebigheader.h:188-198: 27.7280233f / (4.84252568f - z), z in [0, 1];
-// :320-338: 1.72587999f / (0.3520887068f + mx), mx in [0.5, 1)) as v_rcp_f32 + one Newton step + a residual correction: six instructions
-// instead of the compiler's IEEE sequence (scale, reciprocal, three refinements, fmas, fixup: twice that), and the IEEE quotient for EVERY
-// float denominator of both ranges — tools/div_probe.hip checks all 8.4 M of them on the device.  Operands outside those ranges: never here.
-__device__ __forceinline__ float e_div_tab(float n, float d){
-  float r = __builtin_amdgcn_rcpf(d);
-  r = __fmaf_rn(__fmaf_rn(-d, r, 1.0f), r, r);
-  const float q = __fmul_rn(n, r);
-  return __fmaf_rn(__fmaf_rn(-d, q, n), r, q);
-}
-__device__ __forceinline__ float e_fasterexp(float p){           // fastonebigheader.h:206-218
-  const float y = __fmul_rn(1.442695040f, p);
-  const float c = (y < -126.0f) ? -126.0f : y;
-  return __uint_as_float((uint32_t)__fmul_rn(8388608.0f, __fadd_rn(c, 126.94269504f)));
-}
-__device__ __forceinline__ float e_fasterlog(float x){           // fastonebigheader.h:348-358
-  float y = (float)__float_as_uint(x);
-  y = __fmul_rn(y, 8.2629582881927490e-8f);
-  return __fsub_rn(y, 87.989971088f);
-}
-__device__ __forceinline__ float e_fastpow2(float p){            // fastonebigheader.h:188-198
-  const float offset = (p < 0.0f) ? 1.0f : 0.0f;
-  const float clipp = (p < -126.0f) ? -126.0f : p;
-  const int w = (int)clipp;
-  const float z = __fadd_rn(__fsub_rn(clipp, (float)w), offset);
-  const float t = __fsub_rn(__fadd_rn(__fadd_rn(clipp, 121.2740575f), e_div_tab(27.7280233f, __fsub_rn(4.84252568f, z))), __fmul_rn(1.49012907f, z));
-  return __uint_as_float((uint32_t)__fmul_rn(8388608.0f, t));
-}
-__device__ __forceinline__ float e_fastlog(float x){             // fastonebigheader.h:320-338
-  const uint32_t vi = __float_as_uint(x);
-  const float mx = __uint_as_float((vi & 0x007FFFFFu) | 0x3f000000u);
-  float y = (float)vi;
-  y = __fmul_rn(y, 1.1920928955078125e-7f);
-  const float l2 = __fsub_rn(__fsub_rn(__fsub_rn(y, 124.22551499f), __fmul_rn(1.498030302f, mx)),
-                             e_div_tab(1.72587999f, __fadd_rn(0.3520887068f, mx)));
-  return __fmul_rn(0.69314718f, l2);
-}
-__device__ __forceinline__ double e_fast_lse2(double a, double b, double thr){    // mathops.cpp:86-95
-  const double hi = a > b ? a : b, lo = a > b ? b : a;
-  const double diff = lo - hi;
-  return diff < thr ? hi : hi + (double)e_fastlog(__fadd_rn(1.0f, e_fastpow2(__fmul_rn(1.442695040f, (float)diff))));
-}
+// (the float log-sum-exp primitives — f_fasterexp / f_fasterlog, fast_lse2 — for device and host: float_lse.h)
 
 // StutterModel::log_stutter_pmf (stutter_model.cpp:29-53) from the nine logs the constructor keeps (stutter_model.h:44-58)
 __device__ __forceinline__ double em_pmf(const double* lp, int period, int sample_bps, int read_bps){
@@ -506,8 +466,8 @@ __global__ void __launch_bounds__(256) hs_em_mstep_part(const hs_em_dev_t* __res
       double m = -DBL_MAX;
       for (int j = 0; j < A; j++){
         const double lj = llr[j];
-        const double both0 = e_fast_lse2(one_a, b2 + lj, d.log_thresh);                       // diplotype (a, j)
-        const double both1 = same ? both0 : e_fast_lse2(b1 + lj, two_a, d.log_thresh);        // diplotype (j, a)
+        const double both0 = fast_lse2(one_a, b2 + lj, d.log_thresh);                         // diplotype (a, j)
+        const double both1 = same ? both0 : fast_lse2(b1 + lj, two_a, d.log_thresh);          // diplotype (j, a)
         m = fmax(m, fmax(gp[a*A + j] + (one_a - both0), gp[j*A + a] + (two_a - both1)));
       }
       const double md = m + le;                           // adding one number keeps the order: max(f) + le == max(f + le)
@@ -524,14 +484,14 @@ __global__ void __launch_bounds__(256) hs_em_mstep_part(const hs_em_dev_t* __res
       double sc = 0.0, sd = 0.0;
       for (int j = 0; j < A; j++){
         const double lj = llr[j];
-        const double both0 = e_fast_lse2(one_a, b2 + lj, d.log_thresh);
-        const double both1 = same ? both0 : e_fast_lse2(b1 + lj, two_a, d.log_thresh);
+        const double both0 = fast_lse2(one_a, b2 + lj, d.log_thresh);
+        const double both1 = same ? both0 : fast_lse2(b1 + lj, two_a, d.log_thresh);
         const double f0 = gp[a*A + j] + (one_a - both0), f1 = gp[j*A + a] + (two_a - both1);
-        { const double df = f0 - mc; if (df > d.log_thresh) sc += (double)e_fasterexp((float)df); }
-        { const double df = f1 - mc; if (df > d.log_thresh) sc += (double)e_fasterexp((float)df); }
+        { const double df = f0 - mc; if (df > d.log_thresh) sc += (double)f_fasterexp((float)df); }
+        { const double df = f1 - mc; if (df > d.log_thresh) sc += (double)f_fasterexp((float)df); }
         if (has_d){
-          { const double df = (f0 + le) - md; if (df > d.log_thresh) sd += (double)e_fasterexp((float)df); }
-          { const double df = (f1 + le) - md; if (df > d.log_thresh) sd += (double)e_fasterexp((float)df); }
+          { const double df = (f0 + le) - md; if (df > d.log_thresh) sd += (double)f_fasterexp((float)df); }
+          { const double df = (f1 + le) - md; if (df > d.log_thresh) sd += (double)f_fasterexp((float)df); }
         }
       }
 #pragma unroll
@@ -588,9 +548,9 @@ __global__ void __launch_bounds__(256) hs_em_mstep(const hs_em_dev_t* __restrict
       double t = 0.0;
       for (int q = 0; q < HS_EM_PARTS; q++) t += part[q*7 + k];
       // the pseudocount entries: 0.0 in every vector, ln 1.1 in the two diffs vectors
-      { const double df = 0.0 - mxk; if (df > d.log_thresh) t += (double)e_fasterexp((float)df); }
-      if (k == 3 || k == 6){ const double df = d.log_1p1 - mxk; if (df > d.log_thresh) t += (double)e_fasterexp((float)df); }
-      d.sums[7*l + k] = mxk + (double)e_fasterlog((float)t);
+      { const double df = 0.0 - mxk; if (df > d.log_thresh) t += (double)f_fasterexp((float)df); }
+      if (k == 3 || k == 6){ const double df = d.log_1p1 - mxk; if (df > d.log_thresh) t += (double)f_fasterexp((float)df); }
+      d.sums[7*l + k] = mxk + (double)f_fasterlog((float)t);
     }
   }
 }
@@ -633,15 +593,15 @@ __global__ void __launch_bounds__(64) hs_em_finish(const hs_em_dev_t* __restrict
     const double mxk = keep[7*l + k];
     double tt = 0.0;
     for (int q = 0; q < HS_EM_PARTS; q++) tt += part[q*7 + k];
-    { const double df = 0.0 - mxk; if (df > d.log_thresh) tt += (double)e_fasterexp((float)df); }
-    if (k == 3 || k == 6){ const double df = d.log_1p1 - mxk; if (df > d.log_thresh) tt += (double)e_fasterexp((float)df); }
-    t[k] = mxk + (double)e_fasterlog((float)tt);
+    { const double df = 0.0 - mxk; if (df > d.log_thresh) tt += (double)f_fasterexp((float)df); }
+    if (k == 3 || k == 6){ const double df = d.log_1p1 - mxk; if (df > d.log_thresh) tt += (double)f_fasterexp((float)df); }
+    t[k] = mxk + (double)f_fasterlog((float)tt);
   }
   const int it = d.iter[l];
   d.n_iter[l] = it; d.final_ll[l] = new_LL;
   const double LL = d.cur_ll[l];
   if (new_LL < LL + 1e-10){ d.state[l] = 1; return; }                           // :190-194 (TOLERANCE = 1e-10)
-  const double out_total = e_fast_lse2(t[4], t[5], d.log_thresh);
+  const double out_total = fast_lse2(t[4], t[5], d.log_thresh);
   const double in_pgeom  = fmin(0.999, cr_exp(em_lse2_exact(t[0], t[1]) - t[3]));
   const double out_pgeom = fmin(0.999, cr_exp(out_total - t[6]));
   const double m3 = fmax(fmax(t[0], t[1]), t[2]);
@@ -726,28 +686,6 @@ struct EmBufs {
   }
 };
 
-// host copies of the reference's float approximations (mathops.cpp:86-95, fastonebigheader.h:188-204, 320-338)
-inline float h_bits(uint32_t u){ float f; memcpy(&f, &u, 4); return f; }
-inline uint32_t h_ubits(float f){ uint32_t u; memcpy(&u, &f, 4); return u; }
-float h_fastpow2(float p){
-  const float offset = (p < 0) ? 1.0f : 0.0f;
-  const float clipp = (p < -126) ? -126.0f : p;
-  const int w = (int)clipp;
-  const float z = clipp - w + offset;
-  return h_bits((uint32_t)((1 << 23) * (clipp + 121.2740575f + 27.7280233f / (4.84252568f - z) - 1.49012907f * z)));
-}
-float h_fastlog(float x){
-  const uint32_t vi = h_ubits(x);
-  const float mx = h_bits((vi & 0x007FFFFF) | 0x3f000000);
-  float y = (float)vi;
-  y *= 1.1920928955078125e-7f;
-  return 0.69314718f * (y - 124.22551499f - 1.498030302f * mx - 1.72587999f / (0.3520887068f + mx));
-}
-double h_fast_lse2(double a, double b, double thr){
-  const double hi = a > b ? a : b, lo = a > b ? b : a;
-  const double diff = lo - hi;
-  return diff < thr ? hi : hi + h_fastlog(1 + h_fastpow2(1.442695040f * (float)diff));
-}
 double h_lse2(double a, double b){ return a > b ? a + log(1 + exp(b - a)) : b + log(1 + exp(a - b)); }       // mathops.cpp:52-57
 
 // |effective difference| of an observed size against an allele size, as hs_em_fill forms it (the index into the table of integer
@@ -1045,7 +983,7 @@ int em_loop(const hipstr::ApiTables& T, EmBufs& dev, EmPrep& P, const EmArrays& 
       n_iter[l] = s.it; final_ll[l] = new_LL;
       if (new_LL < s.LL + 1e-10){ s.done = true; s.ok = true; continue; }      // :190-194 (TOLERANCE = 1e-10)
       const double* t = &sums[7*(size_t)l];                                    // in_up, in_down, in_eq, in_diffs, out_up, out_down, out_diffs
-      const double out_total = h_fast_lse2(t[4], t[5], HT.log_thresh);
+      const double out_total = fast_lse2(t[4], t[5], HT.log_thresh);
       const double in_pgeom  = std::min(0.999, exp(h_lse2(t[0], t[1]) - t[3]));
       const double out_pgeom = std::min(0.999, exp(out_total - t[6]));
       const double m3 = std::max(std::max(t[0], t[1]), t[2]);

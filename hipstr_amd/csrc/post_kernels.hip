@@ -14,46 +14,11 @@
 
 #include "post_layout.h"
 #include "cr_math.h"
+#include "float_lse.h"
 
 // (HS_POST_ECHUNK, HS_POST_REGS and the path / tile decisions: post_layout.h)
 
-namespace {
-
-// The two float divisions of the reference's bit-trick exp2 / log (fastonebigheader.h:188-198: 27.7280233f / (4.84252568f - z), z in [0, 1];
-// :320-338: 1.72587999f / (0.3520887068f + mx), mx in [0.5, 1)) as v_rcp_f32 + one Newton step + a residual correction: six instructions
-// instead of the compiler's IEEE sequence (scale, reciprocal, three refinements, fmas, fixup: twice that), and the IEEE quotient for EVERY
-// float denominator of both ranges — tools/div_probe.hip checks all 8.4 M of them on the device.  Operands outside those ranges: never here.
-__device__ __forceinline__ float f_div_tab(float n, float d){
-  float r = __builtin_amdgcn_rcpf(d);
-  r = __fmaf_rn(__fmaf_rn(-d, r, 1.0f), r, r);
-  const float q = __fmul_rn(n, r);
-  return __fmaf_rn(__fmaf_rn(-d, q, n), r, q);
-}
-__device__ __forceinline__ float f_fastpow2(float p){             // fastonebigheader.h:188-198
-  const float offset = (p < 0.0f) ? 1.0f : 0.0f;
-  const float clipp = (p < -126.0f) ? -126.0f : p;
-  const int w = (int)clipp;
-  const float z = __fadd_rn(__fsub_rn(clipp, (float)w), offset);
-  const float t = __fsub_rn(__fadd_rn(__fadd_rn(clipp, 121.2740575f), f_div_tab(27.7280233f, __fsub_rn(4.84252568f, z))), __fmul_rn(1.49012907f, z));
-  return __uint_as_float((uint32_t)__fmul_rn(8388608.0f, t));
-}
-__device__ __forceinline__ float f_fastexp(float p){ return f_fastpow2(__fmul_rn(1.442695040f, p)); }
-__device__ __forceinline__ float f_fastlog(float x){              // fastonebigheader.h:320-338
-  const uint32_t vi = __float_as_uint(x);
-  const float mx = __uint_as_float((vi & 0x007FFFFFu) | 0x3f000000u);
-  float y = (float)vi;
-  y = __fmul_rn(y, 1.1920928955078125e-7f);
-  const float l2 = __fsub_rn(__fsub_rn(__fsub_rn(y, 124.22551499f), __fmul_rn(1.498030302f, mx)),
-                             f_div_tab(1.72587999f, __fadd_rn(0.3520887068f, mx)));
-  return __fmul_rn(0.69314718f, l2);
-}
-__device__ __forceinline__ double fast_lse2(double a, double b, double thr){    // mathops.cpp:86-95
-  const double hi = a > b ? a : b, lo = a > b ? b : a;
-  const double diff = lo - hi;
-  return diff < thr ? hi : hi + (double)f_fastlog(__fadd_rn(1.0f, f_fastexp((float)diff)));
-}
-
-}  // namespace
+// (the float pair log-sum-exp fast_lse2 and its bit-trick fastexp / fastlog with their hand-made division: float_lse.h)
 
 // phase 0: the whole of it, one workgroup per (locus, sample).  With few units and many diplotypes (configs[4]: 256 loci x ONE sample x
 // 128^2 diplotypes x 200 reads: 256 workgroups of 64 sequential diplotypes per thread on 256 CUs) the accumulation is split over
@@ -420,4 +385,44 @@ hs_genotype_kernel(const hs_gt_dev_t* __restrict__ dp){
 extern "C" __global__ void __launch_bounds__(256) hs_cr_math_kernel(int which, const double* __restrict__ x, double* __restrict__ y, int64_t n){
   const int64_t i = (int64_t)blockIdx.x*256 + threadIdx.x;
   if (i < n) y[i] = which ? cr_log(x[i]) : cr_exp(x[i]);
+}
+
+// tests: float_lse.h on the device (tests/test_float_lse_gpu.py compares with the oracle's restatement, bit for bit).  hs_float_fn_kernel
+// evaluates one function at the `count` consecutive float bit patterns from bits_lo: the arguments are made here, only result bits leave.
+// which: 0 fasterexp, 1 fasterlog, 2 fastexp, 3 fastlog, 4 the pair term fastlog(1 + fastexp(p)), 5 f_div_tab(27.7280233f, d),
+// 6 f_div_tab(1.72587999f, d); 7 and 8 are the CONTROL of 5 and 6: n * rcp(d) without Newton step or correction, which is not the IEEE quotient.
+extern "C" __global__ void __launch_bounds__(256) hs_float_fn_kernel(int which, uint32_t bits_lo, int64_t count, uint32_t* __restrict__ out){
+  const int64_t i = (int64_t)blockIdx.x*256 + threadIdx.x;
+  if (i >= count) return;
+  const float x = __uint_as_float(bits_lo + (uint32_t)i);
+  float r;
+  switch (which){
+    case 0: r = f_fasterexp(x); break;
+    case 1: r = f_fasterlog(x); break;
+    case 2: r = f_fastexp(x); break;
+    case 3: r = f_fastlog(x); break;
+    case 4: r = f_lse2_term(x); break;
+    case 5: r = f_div_tab(27.7280233f, x); break;
+    case 6: r = f_div_tab(1.72587999f, x); break;
+    case 7: r = __fmul_rn(27.7280233f, __builtin_amdgcn_rcpf(x)); break;
+    default: r = __fmul_rn(1.72587999f, __builtin_amdgcn_rcpf(x)); break;
+  }
+  out[i] = __float_as_uint(r);
+}
+// the double wrapper of the pair form: threshold test, ordering, double-to-float cast, final double addition
+extern "C" __global__ void __launch_bounds__(256) hs_fast_lse2_kernel(const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out, int64_t n, double thr){
+  const int64_t i = (int64_t)blockIdx.x*256 + threadIdx.x;
+  if (i < n) out[i] = fast_lse2(a[i], b[i], thr);
+}
+// the streaming Lse over rows v[row_off[r] .. row_off[r+1]), a thread per row, pushed the way the kernels push (pass 0: maximum, pass 1: sum)
+extern "C" __global__ void __launch_bounds__(64) hs_fast_lse_vec_kernel(const double* __restrict__ v, const int64_t* __restrict__ row_off, double* __restrict__ out, int64_t n_rows, double thr){
+  const int64_t r = (int64_t)blockIdx.x*64 + threadIdx.x;
+  if (r >= n_rows) return;
+  const int64_t b = row_off[r], e = row_off[r+1];
+  Lse lse;
+  for (int pass = 0; pass < 2; pass++){
+    lse.start(pass, v[b]);
+    for (int64_t i = b; i < e; i++) lse.push(pass, v[i], thr);
+  }
+  out[r] = lse.finish();
 }

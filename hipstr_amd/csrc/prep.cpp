@@ -8,6 +8,7 @@
 // stream, instead of objects the CPU loop walks.  O(A·H) work per locus; the
 // O(P·A·H·L) dynamic programme runs on the device.
 #include "prep.h"
+#include "float_lse.h"
 
 #include <algorithm>
 #include <atomic>
@@ -308,20 +309,7 @@ static const int* upstream_runs(const char* s, int n, int shift){
 static std::atomic<bool> g_host_tables(false);     // HIPSTR_HOST_TABLES=1 (tests, comparison runs; re-read at the start of every prepare_batch): constants and tables written by the host, as up to round 3
 static std::atomic<double> g_bnd_scale(1.0);      // tests only (HIPSTR_DEBUG_BND_SCALE): re-read from the environment at the start of every prepare_batch; concurrent calls store the same value
 
-// ---- host copies of the float bit tricks (fastonebigheader.h:206-218, 348-358), used to tabulate the closed form below
-static float h_fasterexp(float p){
-  const float y = 1.442695040f * p;
-  const float c = (y < -126.0f) ? -126.0f : y;
-  const float z = c + 126.94269504f;
-  const uint32_t u = (uint32_t)(8388608.0f * z);
-  float r; memcpy(&r, &u, 4); return r;
-}
-static float h_fasterlog(float x){
-  uint32_t u; memcpy(&u, &x, 4);
-  float y = (float)u;
-  y = y * 8.2629582881927490e-8f;
-  return y - 87.989971088f;
-}
+// (the float bit tricks f_fasterexp / f_fasterlog used to tabulate the closed form below: float_lse.h, host side)
 
 // One entry {A, G, Bnd} of the tabulated closed form of a simple visiting list (hmm_kernels.hip simple_eval is the long form):
 // the pushed values are lp0 (1 + nplain times), ln(U0) + lp0 and ln(tail - stop) + lp0, so with A = the largest of the added
@@ -343,16 +331,16 @@ static void simple_table_entry_compute(int lim, int U0, int tail, double ent[3])
   double tot = 0.0, delta = 1e300;
   for (int i = 0; i < 3; i++){
     if (!on[i]) continue;
-    if (a[i] == amax){ tot += w[i] * (double)h_fasterexp(0.0f); continue; }        // the device difference is exactly zero
+    if (a[i] == amax){ tot += w[i] * (double)f_fasterexp(0.0f); continue; }        // the device difference is exactly zero
     const double x = a[i] - amax;
     const float f = (float)x;
     const double m_lo = 0.5*((double)f + (double)nextafterf(f, -INFINITY)), m_hi = 0.5*((double)f + (double)nextafterf(f, INFINITY));
     delta = std::min(delta, std::min(x - m_lo, m_hi - x));
     delta = std::min(delta, fabs(x - T.log_thresh));
-    if (x > T.log_thresh) tot += w[i] * (double)h_fasterexp(f);
+    if (x > T.log_thresh) tot += w[i] * (double)f_fasterexp(f);
   }
   ent[0] = amax;
-  ent[1] = (double)h_fasterlog((float)tot);
+  ent[1] = (double)f_fasterlog((float)tot);
   ent[2] = (delta >= 1e300) ? 1e300 : std::max(0.0, delta * 1125899906842624.0 /* 2^50 */ - amax - 1.0);
   if (ent[2] < 1e300) ent[2] *= g_bnd_scale.load();      // tests: shrink the guarantee (HIPSTR_DEBUG_BND_SCALE)
 }

@@ -178,6 +178,22 @@ int64_t hipstr_debug_cache_poison(int byte);
  * element — the functions the posterior, genotype and EM kernels use in place of the device's own exp / log so that they reproduce
  * the host libm's bits. */
 int hipstr_debug_cr_math(int which, const double* x, double* y, int64_t n);
+/* Diagnostics (tests): the float log-sum-exp primitives of hipstr_amd/csrc/float_lse.h — the reference's bit-trick fasterexp / fasterlog
+ * (vector log-sum-exp) and fastexp / fastlog (pair log-sum-exp) — evaluated ON THE DEVICE at the `count` consecutive float bit patterns
+ * from bits_lo (bits_lo + count <= 2^32, count <= 2^28): the arguments are generated on the device and only the results' bits come back.
+ * which: 0 fasterexp, 1 fasterlog, 2 fastexp, 3 fastlog, 4 the pair term fastlog(1 + fastexp(p)), 5 the hand-made division
+ * 27.7280233f / d (fastpow2's), 6 1.72587999f / d (fastlog's); 7 and 8 are the CONTROLS of 5 and 6: n * rcp(d) without Newton step or
+ * correction, which differs from the IEEE quotient at some denominators (a sweep that never sees a difference there proves nothing).
+ * hipstr_debug_fast_lse2: the double wrapper fast_log_sum_exp(a[i], b[i]) (threshold test, ordering, cast, final addition);
+ * hipstr_debug_fast_lse_vec: the streaming Lse over the rows v[row_off[r] .. row_off[r+1]) (row_off[0] = 0, no empty row), both with
+ * the library's LOG_THRESH.  The _host forms run the same header's host side without a device — what em.hip's host path and prep.cpp
+ * run (which = 0..6).  Used by tests/test_float_lse.py and tests/test_float_lse_gpu.py. */
+int hipstr_debug_float_fn(int which, uint32_t bits_lo, int64_t count, uint32_t* out_bits);
+int hipstr_debug_fast_lse2(const double* a, const double* b, double* out, int64_t n);
+int hipstr_debug_fast_lse_vec(const double* v, const int64_t* row_off, double* out, int64_t n_rows);
+int hipstr_debug_float_fn_host(int which, uint32_t bits_lo, int64_t count, uint32_t* out_bits);
+int hipstr_debug_fast_lse2_host(const double* a, const double* b, double* out, int64_t n);
+int hipstr_debug_fast_lse_vec_host(const double* v, const int64_t* row_off, double* out, int64_t n_rows);
 /* Diagnostics: (realigned allele, side) pairs of a batch by the STR kernel that takes them: counts[1] periodic blocks (tabulated closed form),
  * counts[2] blocks with one or two interruptions (piecewise closed form), counts[3] more interruptions (lists replayed in the grouped layout),
  * counts[0] the rest (per-read kernel). */

@@ -139,6 +139,36 @@ double oracle_fast_lse2(double a, double b){         /* mathops.cpp:86-95 */
   }
 }
 
+/* Batch forms for the exhaustive sweeps of tests/test_float_lse.py and tests/test_float_lse_gpu.py (the scalar entries are too slow to
+ * call 10^8 times): one function at the `count` consecutive float bit patterns from bits_lo, result bits out.  which: 0 fasterexp,
+ * 1 fasterlog, 2 fastexp, 3 fastlog, 4 the pair term fastlog(1 + fastexp(p)) as mathops.cpp:89 writes it, 5 / 6 the IEEE quotients
+ * 27.7280233f / d and 1.72587999f / d of fastpow2 and fastlog2.  The signatures of hipstr_debug_float_fn, _fast_lse2, _fast_lse_vec. */
+int oracle_float_fn(int which, uint32_t bits_lo, int64_t count, uint32_t* out_bits){
+  if (which < 0 || which > 6 || count < 0 || !out_bits) return 1;
+  for (int64_t i = 0; i < count; i++){
+    float x = bits_to_float(bits_lo + (uint32_t)i), r;
+    switch (which){
+      case 0: r = o_fasterexp(x); break;
+      case 1: r = o_fasterlog(x); break;
+      case 2: r = o_fastexp(x); break;
+      case 3: r = o_fastlog(x); break;
+      case 4: r = o_fastlog(1 + o_fastexp(x)); break;
+      case 5: r = 27.7280233f / x; break;
+      default: r = 1.72587999f / x; break;
+    }
+    out_bits[i] = float_to_bits(r);
+  }
+  return 0;
+}
+int oracle_fast_lse2_batch(const double* a, const double* b, double* out, int64_t n){
+  for (int64_t i = 0; i < n; i++) out[i] = oracle_fast_lse2(a[i], b[i]);
+  return 0;
+}
+int oracle_fast_lse_vec_batch(const double* v, const int64_t* row_off, double* out, int64_t n_rows){
+  for (int64_t r = 0; r < n_rows; r++) out[r] = oracle_fast_lse_vec(v + row_off[r], (int)(row_off[r+1] - row_off[r]));
+  return 0;
+}
+
 double oracle_log_sum_exp(const double* v, int n){   /* mathops.cpp:44-50 (exact) */
   double m = v[0];
   for (int i = 1; i < n; i++) if (v[i] > m) m = v[i];

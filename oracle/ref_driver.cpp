@@ -209,6 +209,38 @@ double ref_fast_lse_vec(const double* v, int n){
 }
 double ref_fast_lse2(double a, double b){ return fast_log_sum_exp(a, b); }
 double ref_log_sum_exp(const double* v, int n){ return log_sum_exp(v, v+n); }
+// Batch forms (tests/test_float_lse.py sweeps every float argument; the scalar entries are too slow for that): the reference's own
+// fastonebigheader.h functions at `count` consecutive float bit patterns from bits_lo.  which: 0 fasterexp, 1 fasterlog, 2 fastexp,
+// 3 fastlog, 4 fastlog(1 + fastexp(p)) (mathops.cpp:89), 5 / 6 the float quotients inside fastpow2 and fastlog2.
+int ref_float_fn(int which, uint32_t bits_lo, int64_t count, uint32_t* out_bits){
+  if (which < 0 || which > 6 || count < 0 || !out_bits) return 1;
+  for (int64_t i = 0; i < count; i++){
+    const uint32_t u = bits_lo + (uint32_t)i;
+    float x, r; memcpy(&x, &u, 4);
+    switch (which){
+      case 0: r = fasterexp(x); break;
+      case 1: r = fasterlog(x); break;
+      case 2: r = fastexp(x); break;
+      case 3: r = fastlog(x); break;
+      case 4: r = fastlog(1 + fastexp(x)); break;
+      case 5: r = 27.7280233f / x; break;
+      default: r = 1.72587999f / x; break;
+    }
+    memcpy(&out_bits[i], &r, 4);
+  }
+  return 0;
+}
+int ref_fast_lse2_batch(const double* a, const double* b, double* out, int64_t n){
+  for (int64_t i = 0; i < n; i++) out[i] = fast_log_sum_exp(a[i], b[i]);
+  return 0;
+}
+int ref_fast_lse_vec_batch(const double* v, const int64_t* row_off, double* out, int64_t n_rows){
+  for (int64_t r = 0; r < n_rows; r++){
+    std::vector<double> vals(v + row_off[r], v + row_off[r+1]);
+    out[r] = fast_log_sum_exp(vals);
+  }
+  return 0;
+}
 
 } // extern "C"
 
