@@ -120,7 +120,41 @@ void dump_doubles(FILE* f, const char* key, const double* v, size_t n, bool hex)
 }  // namespace
 
 // one locus: seeded reads -> SeqStutterGenotyper -> genotype() [-> recompute_stutter_models()] -> dump to `f`
-struct LocusParams { uint64_t seed; int n_samples, reads_per_sample, period; bool recompute, reassemble, nw; };
+struct LocusParams { uint64_t seed; int n_samples, reads_per_sample, period; bool recompute, reassemble, nw; const char* dump_inputs; };
+// [--dump-inputs] what a caller of the C-ABI needs to run the rounds of genotype() itself, as the constructor left it (before genotype()):
+// region, initial blocks, the repeat block and its period, the stutter model, and per UN-pooled read the fields HapAlignerMI355X flattens
+// into a hipstr_batch_t (start, CIGAR, bases, qualities; strand) with its sample, second_mate_, log_p1_ and log_p2_.  Data only; doubles as bits.
+static int dump_inputs(const char* path, SeqStutterGenotyper& g, const Region& region){
+  FILE* f = fopen(path, "w");
+  if (!f){ perror(path); return 2; }
+  fprintf(f, "region %s %d %d %d %s\n", region.chrom().c_str(), (int)region.start(), (int)region.stop(), region.period(), region.name().c_str());
+  fprintf(f, "initialized %d\nnum_samples %d\nnum_reads %u\n", g.initialized_ ? 1 : 0, g.num_samples_, g.num_reads_);
+  if (g.initialized_){
+    for (int b = 0; b < g.haplotype_->num_blocks(); b++){
+      HapBlock* blk = g.haplotype_->get_block(b);
+      fprintf(f, "block %d %d %d %d", b, blk->start(), blk->end(), blk->num_options());
+      for (int o = 0; o < blk->num_options(); o++) fprintf(f, " %s", blk->get_seq(o).c_str());
+      fprintf(f, "\n");
+      RepeatStutterInfo* info = blk->get_repeat_info();
+      if (info != NULL){
+        StutterModel* m = info->get_stutter_model();
+        double sp[6] = { m->get_parameter(true, 'P'), m->get_parameter(true, 'U'), m->get_parameter(true, 'D'), m->get_parameter(false, 'P'), m->get_parameter(false, 'U'), m->get_parameter(false, 'D') };
+        fprintf(f, "repeat_block %d %d\n", b, info->get_period());
+        dump_doubles(f, "stutter_model", sp, 6, true);
+      }
+    }
+  }
+  for (unsigned i = 0; i < g.num_reads_; i++){
+    const Alignment& a = g.alns_[i];
+    uint64_t u1, u2; memcpy(&u1, &g.log_p1_[i], 8); memcpy(&u2, &g.log_p2_[i], 8);
+    fprintf(f, "read %u %d %d %d %d ", i, g.sample_label_[i], g.second_mate_[i] ? 1 : 0, a.is_from_reverse_strand() ? 1 : 0, a.get_start());
+    const std::vector<CigarElement>& cig = a.get_cigar_list();
+    for (size_t c = 0; c < cig.size(); c++) fprintf(f, "%d%c", cig[c].get_num(), cig[c].get_type());
+    fprintf(f, " %s %s %016llx %016llx\n", a.get_sequence().c_str(), a.get_base_qualities().c_str(), (unsigned long long)u1, (unsigned long long)u2);
+  }
+  fclose(f);
+  return 0;
+}
 #include <atomic>
 #include <chrono>
 // where a locus' wall time goes inside this driver, summed over threads (nanoseconds): simulating the reads | the reference's constructor +
@@ -215,6 +249,7 @@ static int run_locus(const LocusParams& lp, FILE* f){
   std::vector<StutterModel*> models(1, &model);
   std::stringstream log;
   SeqStutterGenotyper g(group, false, reassemble, alns, log_p1, log_p2, sample_names, chrom, models, NULL, log);
+  if (lp.dump_inputs != NULL && dump_inputs(lp.dump_inputs, g, region) != 0) return 2;
   const bool ok = g.genotype(1000, 4, 0.15, log);
   bool ok2 = true;
   if (ok && recompute) ok2 = g.recompute_stutter_models(log, 1000, 4, 0.15, 100, 0.01, 0.001);
@@ -278,7 +313,7 @@ static int run_locus(const LocusParams& lp, FILE* f){
 #include <thread>
 
 extern "C" int flow_main(int argc, char** argv){
-  LocusParams lp; lp.seed = 1; lp.n_samples = 10; lp.reads_per_sample = 9; lp.period = 4; lp.recompute = false; lp.reassemble = true; lp.nw = false;
+  LocusParams lp; lp.seed = 1; lp.n_samples = 10; lp.reads_per_sample = 9; lp.period = 4; lp.recompute = false; lp.reassemble = true; lp.nw = false; lp.dump_inputs = NULL;
   const char* out_path = NULL; int n_loci = 0, n_threads = 1; bool use_stream = false, profile = false;
   for (int i = 1; i < argc; i++){
     if (!strcmp(argv[i], "--seed")) lp.seed = strtoull(argv[++i], NULL, 10);
@@ -289,6 +324,7 @@ extern "C" int flow_main(int argc, char** argv){
     else if (!strcmp(argv[i], "--no-flanks")) lp.reassemble = false;
     else if (!strcmp(argv[i], "--nw")) lp.nw = true;                        // also dump the Needleman-Wunsch results of the locus (realign()'s call, aln_haps_to_ref)
     else if (!strcmp(argv[i], "--out")) out_path = argv[++i];
+    else if (!strcmp(argv[i], "--dump-inputs")) lp.dump_inputs = argv[++i];  // one-locus form: the inputs of genotype() as the constructor left them (tests/flow_chain.py)
     else if (!strcmp(argv[i], "--loci")) n_loci = atoi(argv[++i]);          // many loci (seeds seed, seed+1, ...; periods cycling 2..5) ...
     else if (!strcmp(argv[i], "--threads")) n_threads = atoi(argv[++i]);    // ... one SeqStutterGenotyper per host thread at a time
     else if (!strcmp(argv[i], "--profile")) profile = true;                 // many-loci form: where the host threads' time went (MI355X build: library and adapter buckets)

@@ -1,7 +1,7 @@
 """GPU: hipstr_post_assign — reads assigned to their sample's MAP haplotypes, the per-sample read counts of a VCF record and the
 traceback request list, on the resident posteriors (include/hipstr_hmm.h).
 
-The yardstick is `restate` below: a line-by-line Python restatement of the loop over the reads in SeqStutterGenotyper::write_vcf_record
+The yardstick is `restate` (tests/flow_chain.py, shared with the end-to-end chain): a line-by-line Python restatement of the loop over the reads in SeqStutterGenotyper::write_vcf_record
 (reference src/seq_stutter_genotyper.cpp:1079-1157), of the phase totals (:1355-1356) and of retrace_alignments' pick (:823-825), with
 mathops.cpp:52-57 and :64-70 for the two log-sum-exps.  LIMITATION: the compiled reference cannot provide goldens for this stage
 (write_vcf_record needs htslib, which the oracle build does not have), so the expected values come from this restatement and not from
@@ -30,86 +30,8 @@ INT_KEYS = ("best_hap", "read_strand") + capi.ASSIGN_COUNTERS
 REQ_KEYS = ("req_read", "req_allele", "read_req")
 
 
-def _lse2(a, b, exp, log):            # mathops.cpp:52-57
-    if a > b:
-        return a + log(1 + exp(b - a))
-    return b + log(1 + exp(a - b))
-
-
-def _lse_vec(v, exp, log, pairwise=False):      # mathops.cpp:64-70
-    mx = max(v)
-    if pairwise:                      # NOT the reference: a tree sum, to show that the order of the additions matters
-        t = [exp(x - mx) for x in v]
-        while len(t) > 1:
-            t = [t[i] + t[i + 1] if i + 1 < len(t) else t[i] for i in range(0, len(t), 2)]
-        return mx + log(t[0])
-    total = 0.0
-    for x in v:
-        total += exp(x - mx)
-    return mx + log(total)
-
-
-def restate(pb, LL, map_gt, seed, reverse=None, pool_index=None, pool_off=None, rule=capi.ASSIGN_VCF, tol=0.0, exp=math.exp, log=math.log,
-            pairwise=False):
-    """seq_stutter_genotyper.cpp:1079-1157 + :1355-1356 (+ :823-825 for rule == ASSIGN_RETRACE) over a PostBatch; the shape of capi.run_assign."""
-    a = pb.a
-    nl = len(a["n_alleles"]); n = int(a["read_off"][-1]); ns = int(pb.samp_off[-1])
-    tol = tol if tol != 0 else 0.1                                     # STRAND_TOLERANCE, seq_stutter_genotyper.h:157
-    p1 = [float(x) for x in a["log_p1"]]; p2 = [float(x) for x in a["log_p2"]]
-    LL = [float(x) for x in LL]
-    o = dict(best_hap=np.full(n, -1, np.int32), read_strand=np.full(n, -1, np.int32), log_phase_one=np.full(n, np.nan), read_req=np.full(n, -1, np.int32),
-             phase1_reads=np.zeros(ns), phase2_reads=np.zeros(ns))
-    for k in capi.ASSIGN_COUNTERS:
-        o[k] = np.zeros(ns, np.int32)
-    phases = [[] for _ in range(ns)]
-    cache = {}; req_read = []; req_allele = []
-    ptr = 0
-    for l in range(nl):
-        A = int(a["n_alleles"][l]); haploid = a["haploid"] is not None and bool(a["haploid"][l])
-        for r in range(int(a["read_off"][l]), int(a["read_off"][l + 1])):
-            row = LL[ptr:ptr + A]; ptr += A
-            if seed[r] < 0:                                            # :1080
-                continue
-            s = int(pb.samp_off[l]) + int(a["sample_label"][r])        # :1085
-            ha, hb = int(map_gt[s][0]), int(map_gt[s][1])              # :1088-1089
-            if ha < 0 or hb < 0:                                       # no MAP pair (every diplotype -inf): the reference would index haplotype -1
-                continue                                               # here (in Python: silently the LAST allele); the library skips the sample's reads
-            x1 = LOG_ONE_HALF + p1[r] + row[ha]; x2 = LOG_ONE_HALF + p2[r] + row[hb]
-            total = _lse2(x1, x2, exp, log)                            # :1090
-            lpo = LOG_ONE_HALF + p1[r] + row[ha] - total               # :1091
-            phases[s].append(lpo); o["log_phase_one"][r] = lpo
-            strand = 0                                                 # :1095
-            if (not haploid) and ((ha != hb) or (abs(p1[r] - p2[r]) > TOLERANCE)):      # :1096
-                v1 = p1[r] + row[ha]; v2 = p2[r] + row[hb]             # :1097
-                if abs(v1 - v2) > tol:                                 # :1098
-                    strand = 0 if v1 > v2 else 1                       # :1099
-                    rv = reverse is not None and bool(reverse[r])
-                    if strand == 0:                                    # :1100-1107
-                        o["uniq_one"][s] += 1; o["rv_uniq_one"][s] += 1 if rv else 0
-                    else:
-                        o["uniq_two"][s] += 1; o["rv_uniq_two"][s] += 1 if rv else 0
-            if rule == capi.ASSIGN_RETRACE:
-                best = ha if x1 > x2 else hb                           # :825
-            else:
-                best = ha if strand == 0 else hb                       # :1113
-            o["best_hap"][r] = best; o["read_strand"][r] = strand
-            if pool_index is not None:                                 # :1115-1122 / :828-835: the cache fills in order of first occurrence
-                key = (l, int(pool_index[r]), best)
-                if key not in cache:
-                    cache[key] = len(req_read); req_read.append(int(pool_off[l]) + int(pool_index[r])); req_allele.append(best)
-                o["read_req"][r] = cache[key]
-            o["n_aligned"][s] += 1                                     # :1135
-            if abs(p1[r] - p2[r]) > TOLERANCE:                         # :1138-1144
-                o["n_snp"][s] += 1
-                if p1[r] > p2[r]:
-                    o["n_strand_one"][s] += 1
-                else:
-                    o["n_strand_two"][s] += 1
-    for s in range(ns):                                                # :1355-1356
-        ph1 = 0 if o["n_aligned"][s] == 0 else exp(_lse_vec(phases[s], exp, log, pairwise))
-        o["phase1_reads"][s] = ph1; o["phase2_reads"][s] = int(o["n_aligned"][s]) - ph1
-    o["n_req"] = len(req_read); o["req_read"] = np.array(req_read, np.int32); o["req_allele"] = np.array(req_allele, np.int32)
-    return o
+# the restatement itself (and the two log-sum-exps it uses): tests/flow_chain.py, shared with the end-to-end chain
+from flow_chain import _lse2, _lse_vec, assign_restate as restate  # noqa: E402,F401
 
 
 _CR = []

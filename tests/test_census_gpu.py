@@ -1,7 +1,7 @@
 """GPU: hipstr_post_census — the stutter-candidate alleles of a round and the called / spanned marks of its options, on the resident
 posteriors (include/hipstr_hmm.h).
 
-The yardstick is `restate` below: a line-by-line Python restatement of SeqStutterGenotyper::get_stutter_candidate_alleles (reference
+The yardstick is `restate` (tests/flow_chain.py, shared with the end-to-end chain): a line-by-line Python restatement of SeqStutterGenotyper::get_stutter_candidate_alleles (reference
 src/seq_stutter_genotyper.cpp:843-879, with :582-584 for the order and the new haplotype count) and of get_unused_alleles (:229-315) — dicts,
 sets, sorted(key=lambda s: (len(s), s)), and Python floats for the one division of :869 and the one fabs of :282.  LIMITATION: the compiled
 reference cannot provide goldens for this stage — both functions are private members reached only from inside genotype() — so the expected
@@ -31,31 +31,8 @@ STR2 = (100, 120, ["ACAC", "ACACAC"])
 SPAN, SHORT_L, SHORT_R = (50, 200), (100, 200), (50, 120)           # (aln_start, aln_stop) against a block of [100, 120)
 
 
-def gray_h2a(nopts):
-    """A haps_to_alleles-shaped map per block for a reflected mixed-radix Gray code with block 0 fastest."""
-    A = nopts[0] * nopts[1] * nopts[2]; out = [[], [], []]
-    for i in range(A):
-        q = i
-        for k in range(3):
-            d = q % nopts[k]; q //= nopts[k]
-            out[k].append(nopts[k] - 1 - d if q % 2 else d)
-    return out
-
-
-class Locus:
-    """blocks: 3 x (start, end, [options]); samples: per sample the list of reads (log_p1, log_p2, LL row, seed, request within the locus or -1);
-    reqs: list of (pool within the locus, aln_start, aln_stop, stutter_size, str_seq bytes)."""
-
-    def __init__(self, blocks, samples, reqs, n_pooled=None, haploid=0, h2a=None):
-        self.blocks, self.samples, self.reqs, self.haploid = blocks, samples, reqs, haploid
-        self.nopts = [len(b[2]) for b in blocks]
-        self.A = self.nopts[0] * self.nopts[1] * self.nopts[2]
-        self.n_pooled = n_pooled if n_pooled is not None else (max([r[0] for r in reqs]) + 1 if reqs else 0)
-        self.h2a = h2a if h2a is not None else gray_h2a(self.nopts)
-
-
-class Case:
-    pass
+# gray_h2a, Locus, Case (shared with the end-to-end chain): tests/flow_chain.py
+from flow_chain import gray_h2a, Locus, Case, census_restate as restate  # noqa: E402,F401
 
 
 def batch_of(loci):
@@ -78,91 +55,6 @@ def build(loci):
     c.h2a = [np.array([v for L in loci for v in L.h2a[k]], np.int32) for k in range(3)]
     c.pool_off = pool_off
     return c
-
-
-def restate(c, map_gt, h2a=None, uncallable=None, min_reads=2, min_frac=0.15, LL=None, trace=None, read_req=None, req_read=None, seed=None):
-    """seq_stutter_genotyper.cpp:843-879 (+ :582-584) and :229-315 over a Case; the shape of capi.run_census."""
-    a = c.pb.a; nl = len(c.loci)
-    h2a = c.h2a if h2a is None else h2a
-    LL = [float(x) for x in (c.LL if LL is None else LL)]
-    tr = c.trace if trace is None else trace
-    read_req = c.read_req if read_req is None else read_req; req_read = c.req_read if req_read is None else req_read; seed = c.seed if seed is None else seed
-    raw = bytes(tr["str_seq"]) if isinstance(tr["str_seq"], bytes) else tr["str_seq"].raw
-    soff = [int(x) for x in tr["str_seq_off"]]
-    strs = [raw[soff[q]:soff[q + 1]] for q in range(len(req_read))]
-    start, stop, stut = [list(map(int, tr[k][:len(req_read)])) for k in ("aln_start", "aln_stop", "stutter_size")]
-    req_locus = [int(np.searchsorted(c.pool_off, r, side="right")) - 1 for r in req_read]
-    p1 = [float(x) for x in a["log_p1"]]; p2 = [float(x) for x in a["log_p2"]]
-    ns = int(c.pb.samp_off[-1]); n_opts = sum(sum(L.nopts) for L in c.loci)
-    o = dict(cand=[], cand_req=[], new_n_haps=[], n_spanning=np.zeros(ns, np.int32), n_span_stutter=np.zeros(ns, np.int32),
-             called=np.full(n_opts, FILL, np.uint8), spanned=np.full(n_opts, FILL, np.uint8))
-    ptr = 0; hap0 = 0; opt0 = 0
-    for l, L in enumerate(c.loci):
-        A = L.A; S = len(L.samples); s0 = int(c.pb.samp_off[l]); haploid = bool(L.haploid)
-        bs, be = L.blocks[1][0], L.blocks[1][1]
-        r0, r1 = int(a["read_off"][l]), int(a["read_off"][l + 1])
-        lab = [int(x) for x in a["sample_label"][r0:r1]]
-        # ---- get_stutter_candidate_alleles
-        counts = [0] * S; sc = [dict() for _ in range(S)]
-        for r in range(r0, r1):
-            q = int(read_req[r])
-            if seed[r] < 0 or q < 0:                                   # traced_alns[read_index] == NULL, :853
-                continue
-            if start[q] < bs:                                          # :856
-                if stop[q] > be:                                       # :857
-                    if stut[q] != 0:                                   # :858
-                        sc[lab[r - r0]][strs[q]] = sc[lab[r - r0]].get(strs[q], 0) + 1
-                        o["n_span_stutter"][s0 + lab[r - r0]] += 1
-                    counts[lab[r - r0]] += 1                           # :860
-        cand = set()
-        for s in range(S):
-            for k, v in sc[s].items():
-                if v >= min_reads and 1.0 * v / counts[s] >= min_frac:         # :869
-                    if k not in [x.encode() for x in L.blocks[1][2]]:          # :870
-                        cand.add(k)
-        cand = sorted(cand, key=lambda s: (len(s), s))                 # :582 orderByLengthAndSequence
-        o["cand"].append(cand)
-        mine = [q for q in range(len(req_read)) if req_locus[q] == l]
-        o["cand_req"] += [min(q for q in mine if strs[q] == k) for k in cand]
-        o["new_n_haps"].append(A // L.nopts[1] * (L.nopts[1] + len(cand)))     # :583-584
-        o["n_spanning"][s0:s0 + S] = counts
-        # ---- get_unused_alleles
-        aligned = [False] * S                                          # :244-247
-        for r in range(r0, r1):
-            if seed[r] >= 0:
-                aligned[lab[r - r0]] = True
-        for k in range(3):
-            ob = opt0 + sum(L.nopts[:k])
-            if h2a[k] is None:
-                continue
-            m = [int(x) for x in h2a[k][hap0:hap0 + A]]
-            called = [0] * L.nopts[k]; spanned = [0] * L.nopts[k]
-            if k == 1:                                                 # :266-291
-                for r in range(r0, r1):
-                    row = LL[ptr + (r - r0) * A:ptr + (r - r0 + 1) * A]
-                    q = int(read_req[r])
-                    if seed[r] < 0 or q < 0:
-                        continue
-                    if start[q] < bs and stop[q] > be and stut[q] == 0:
-                        ha, hb = int(map_gt[s0 + lab[r - r0]][0]), int(map_gt[s0 + lab[r - r0]][1])
-                        if ha < 0 or hb < 0:
-                            continue
-                        best = ha
-                        if (not haploid) and ha != hb:
-                            v1 = p1[r] + row[ha]; v2 = p2[r] + row[hb]
-                            if abs(v1 - v2) > TOLERANCE:
-                                best = ha if v1 > v2 else hb
-                        spanned[m[best]] = 1
-                o["spanned"][ob:ob + L.nopts[k]] = spanned
-            for s in range(S):                                         # :294-301
-                ha, hb = int(map_gt[s0 + s][0]), int(map_gt[s0 + s][1])
-                if aligned[s] and not (uncallable is not None and uncallable[s0 + s]) and ha >= 0 and hb >= 0:
-                    called[m[ha]] = 1; called[m[hb]] = 1
-            o["called"][ob:ob + L.nopts[k]] = called
-        ptr += (r1 - r0) * A; hap0 += A; opt0 += sum(L.nopts)
-    o["cand_off"] = np.concatenate([[0], np.cumsum([len(x) for x in o["cand"]])]).astype(np.int32)
-    o["cand_req"] = np.array(o["cand_req"], np.int32); o["new_n_haps"] = np.array(o["new_n_haps"], np.int64)
-    return o
 
 
 KEYS = ("cand_off", "cand_req", "new_n_haps", "n_spanning", "n_span_stutter", "called", "spanned")

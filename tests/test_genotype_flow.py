@@ -191,6 +191,9 @@ if __name__ == "__main__" and "--regen" in sys.argv:
     for n, a in CASES.items():
         with tempfile.TemporaryDirectory() as t:
             txt = _run("libflow_ref.so", a, t)
+        if os.path.exists(os.path.join(GOLD, "flow_%s.txt.gz" % n)) and _gold(n) == txt:
+            print(n, "unchanged")          # a dump that did not change keeps its committed bytes (three were written with a time stamp in the gzip header)
+            continue
         with gzip.GzipFile(os.path.join(GOLD, "flow_%s.txt.gz" % n), "wb", mtime=0) as f:
             f.write(txt.encode())
         print(n, len(txt), "bytes")

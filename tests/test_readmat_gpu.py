@@ -5,7 +5,7 @@ re-layout of add_and_remove_alleles (:371-386).
 
 Every comparison is on the bit patterns (view(np.uint64)): the only arithmetic is one IEEE double addition per mate pair and column, so
 nothing rounds differently and there is no tolerance.  The yardsticks: the compiled reference's own matrices (tests/golden/pool_scatter_*.npz,
-written by its classes) and, for the shapes the fixtures do not reach, `host_scatter` / `host_remap` below — :530-564 and :371-386 restated
+written by its classes) and, for the shapes the fixtures do not reach, `host_scatter` / `host_remap` (tests/flow_chain.py) — :530-564 and :371-386 restated
 in numpy on the rows hipstr_hmm_process_reads returns for the same pooled batch."""
 import ctypes as C
 import glob
@@ -34,39 +34,8 @@ def same(got, want, what):
     assert np.array_equal(g, w), "%s: %d of %d entries differ, first at %s" % (what, int((g != w).sum()), g.size, np.argwhere(g != w)[:1].tolist())
 
 
-# ------------------------------------------------------------------------------------------------------------------ the host path, restated
-def host_scatter(M, seeds, A, read_off, pool_index, mates, copy, pool_ll, pool_seeds, pool_read_off, realign_hap):
-    """seq_stutter_genotyper.cpp:530-564 on flat arrays, locus by locus (M and seeds are changed in place).  pool_ll / pool_seeds: what
-    process_reads wrote for the pooled batch (P x A per locus); realign_hap: per locus a boolean array or None = all."""
-    mo = po = 0
-    for l in range(len(A)):
-        a = int(A[l]); r0, r1 = int(read_off[l]), int(read_off[l + 1]); P = int(pool_read_off[l + 1] - pool_read_off[l])
-        Ml = M[mo:mo + (r1 - r0) * a].reshape(r1 - r0, a); Pl = pool_ll[po:po + P * a].reshape(P, a)
-        re = np.ones(a, bool) if realign_hap[l] is None else np.asarray(realign_hap[l], bool)
-        for i in range(r0, r1):                                   # :532-543
-            if not copy[i]:
-                continue
-            seeds[i] = pool_seeds[pool_read_off[l] + pool_index[i]]
-            Ml[i - r0, re] = Pl[pool_index[i], re]
-        for i in range(r0, r1):                                   # :551-564
-            if not mates[i] or not copy[i]:
-                continue
-            total = Ml[i - r0 - 1, re] + Ml[i - r0, re]
-            Ml[i - r0 - 1, re] = total; Ml[i - r0, re] = total
-        mo += (r1 - r0) * a; po += P * a
-
-
-def host_remap(M, A, read_off, new_A, mapping):
-    """seq_stutter_genotyper.cpp:371-386 per locus -> the new flat matrix."""
-    out = []; mo = jo = 0
-    for l in range(len(A)):
-        a, na, R = int(A[l]), int(new_A[l]), int(read_off[l + 1] - read_off[l])
-        old = M[mo:mo + R * a].reshape(R, a); new = np.full((R, na), UNALIGNED)
-        for j in range(a):
-            if mapping[jo + j] != -1:
-                new[:, mapping[jo + j]] = old[:, j]
-        out.append(new.ravel()); mo += R * a; jo += a
-    return np.concatenate(out) if out else np.zeros(0)
+# the host path, restated (seq_stutter_genotyper.cpp:530-564 and :371-386): tests/flow_chain.py, shared with the end-to-end chain
+from flow_chain import host_scatter, host_remap  # noqa: E402
 
 
 def upload_and_align(hmm, b, seed_in=None):
