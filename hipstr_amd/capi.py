@@ -690,6 +690,163 @@ def em_input_fetch(lib, pd, n_loci, n_reads, bptr, seed, read_req, req_read, td,
                 log_p2=fa[1][:m], size_off=soff, sizes=sizes[:k], log_freq=freq[:k])
 
 
+# ---- the flank reassembly (hipstr_flank_kmer_lengths, hipstr_flank_assemble, hipstr_flank_assemble_dev)
+class HipstrFlankRequest(C.Structure):
+    _fields_ = [("pooled", C.POINTER(HipstrBatch)), ("seed", _i32p), ("read_req", _i32p), ("n_req", C.c_int32), ("req_read", _i32p),
+                ("pool_index", _i32p), ("sample_masked", _u8p), ("min_kmer", C.c_int32), ("max_kmer", C.c_int32), ("min_path_weight", C.c_int32),
+                ("max_paths", C.c_int32), ("max_total_haplotypes", C.c_int32), ("max_flank_haplotypes", C.c_int32), ("min_flank_freq", C.c_double)]
+
+
+class HipstrFlankOut(C.Structure):
+    _fields_ = [("status", _i32p), ("new_n_haps", C.POINTER(C.c_int64)), ("opt_off", _i32p), ("opt_seq_off", _i32p), ("opt_seq", C.c_char_p),
+                ("opt_n_samples", _i32p), ("sample_status", _u8p), ("realign_sample", _u8p), ("realign_pool", _u8p), ("copy_read", _u8p),
+                ("task_k", _i32p), ("task_n_paths", _i32p), ("path_weight", _i32p), ("path_seq_off", _i32p), ("path_seq", C.c_char_p),
+                ("cap_opts", C.c_int32), ("cap_opt_chars", C.c_int32), ("cap_paths", C.c_int32), ("cap_path_chars", C.c_int32)]
+
+
+FLANK_FILL = 0xAA            # what run_flank fills the byte outputs with before the call
+FLANK_FLAGS = dict(edges=0x01, nodes=0x02, recs=0x04, reads=0x08, len=0x10, byte=0x20, k=0x40, pool=0x80, peel=0x100, param=0x200, range=0x400)      # HS_FLK_F_*
+
+
+def _flank_sigs(lib):
+    _sig(lib.hipstr_flank_kmer_lengths, C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p])
+    _sig(lib.hipstr_flank_assemble, C.c_int, [_PBP, C.POINTER(HipstrFlankRequest), C.POINTER(HipstrTraceOut), C.POINTER(HipstrFlankOut)])
+    _sig(lib.hipstr_flank_assemble_dev, C.c_int, [C.c_void_p, C.POINTER(HipstrFlankRequest), C.c_void_p, C.POINTER(HipstrFlankOut)])
+    _sig(lib.hipstr_debug_flank_plan, C.c_int, [_PBP, C.POINTER(HipstrFlankRequest), C.POINTER(HipstrTraceOut), C.c_char_p, C.c_int])
+    _sig(lib.hipstr_debug_flank_last, C.c_int, [C.POINTER(C.c_int64), _i32p, _i32p, C.c_int64])
+
+
+def flank_kmer_lengths(lib, bptr, min_kmer=0, max_kmer=0):
+    """hipstr_flank_kmer_lengths -> int32 [n_loci, 2] (-1 = too repetitive)."""
+    _flank_sigs(lib)
+    b = _batch_struct(bptr)
+    out = np.full(max(2 * int(b.n_loci), 1), UNTOUCHED, np.int32)
+    if lib.hipstr_flank_kmer_lengths(C.byref(b), int(min_kmer), int(max_kmer), _ptr(out, _i32p)) != 0:
+        raise RuntimeError("hipstr_flank_kmer_lengths failed: " + lib.hipstr_last_error().decode())
+    return out[:2 * int(b.n_loci)].reshape(-1, 2)
+
+
+def _flank_request(bptr, seed, read_req, req_read, pool_index, sample_masked, kw):
+    i32 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.int32))
+    keep = [i32(seed), i32(read_req), i32(req_read), i32(pool_index), None if sample_masked is None else np.ascontiguousarray(np.asarray(sample_masked, np.uint8))]
+    n_req = 0 if keep[2] is None else len(keep[2])
+    pooled = None if bptr is None else (C.cast(bptr, C.POINTER(HipstrBatch)) if not hasattr(bptr, "_obj") else C.pointer(bptr._obj))
+    rq = HipstrFlankRequest(pooled, _ptr(keep[0], _i32p), _ptr(keep[1], _i32p), kw.pop("n_req", n_req), _ptr(keep[2], _i32p), _ptr(keep[3], _i32p), _ptr(keep[4], _u8p),
+                            int(kw.pop("min_kmer", 0)), int(kw.pop("max_kmer", 0)), int(kw.pop("min_path_weight", 0)), int(kw.pop("max_paths", 0)),
+                            int(kw.pop("max_total_haplotypes", 1000)), int(kw.pop("max_flank_haplotypes", 4)), float(kw.pop("min_flank_freq", 0.15)))
+    assert not kw, kw
+    return rq, keep
+
+
+def _flank_trace(trace, keep):
+    if trace is None:
+        return None
+    t = HipstrTraceOut()
+    if trace.get("flank_seq_off") is not None:
+        a = np.ascontiguousarray(np.asarray(trace["flank_seq_off"], np.int32)); keep.append(a); t.flank_seq_off = a.ctypes.data_as(_i32p)
+    if trace.get("flank_seq") is not None:
+        v = trace["flank_seq"]; keep.append(v)
+        t.flank_seq = v if isinstance(v, bytes) else C.cast(v, C.c_char_p)
+    return t
+
+
+def run_flank(lib, pb, bptr, seed, read_req, req_read, pool_index, trace=None, td=None, pd=None, sample_masked=None, caps=None, want_paths=True,
+              null_out=None, **kw):
+    """hipstr_flank_assemble (trace: dict with flank_seq_off / flank_seq) or hipstr_flank_assemble_dev (td: a TraceDev; pd: a hipstr_post_dev_t
+    handle, or None = pb is uploaded and freed here) -> dict: "rc" (0 or 3), "status", "new_n_haps", "opts" (per locus, per flank: list of
+    (bytes, supporting samples)), "sample_status", "realign_sample", "realign_pool", "copy_read", "task_k", "task_n_paths", "paths" (per task:
+    list of (weight, bytes)), "raw" (every output array as the call left it: integers UNTOUCHED, bytes FLANK_FILL before the call) and, after
+    rc 3, "need" (the four cap_* fields).  pb: the PostBatch (its sizes are read on both routes); bptr: the pooled batch.  caps: dict of the
+    four capacities (default: sized by a first call).  null_out: name of an output array to pass as NULL.  Other keywords: the request's
+    parameters.  Raises with hipstr_last_error() on any other failure; the exception's `raw` holds the arrays."""
+    _flank_sigs(lib)
+    rq, keep = _flank_request(bptr, seed, read_req, req_read, pool_index, sample_masked, dict(kw))
+    t = _flank_trace(trace, keep)
+    nl = int(pb.struct.n_loci)
+    n_reads = int(pb.a["read_off"][-1]) if nl else 0
+    n_samp = int(pb.samp_off[-1])
+    b = _batch_struct(bptr) if bptr is not None else None
+    n_pooled = int(np.ctypeslib.as_array(b.read_off, shape=(int(b.n_loci) + 1,))[-1]) if (b is not None and int(b.n_loci) > 0 and b.read_off) else 0
+    own = td is not None and pd is None
+    if own:
+        pd = lib.hipstr_post_upload(pb.ptr, None)
+        if not pd:
+            raise RuntimeError("hipstr_post_upload failed: " + lib.hipstr_last_error().decode())
+
+    def call(c):
+        k = dict(status=np.full(max(nl, 1), UNTOUCHED, np.int32), new_n_haps=np.full(max(nl, 1), UNTOUCHED, np.int64), opt_off=np.full(2 * nl + 1, UNTOUCHED, np.int32),
+                 opt_seq_off=np.full(c["opts"] + 1, UNTOUCHED, np.int32), opt_n_samples=np.full(max(c["opts"], 1), UNTOUCHED, np.int32),
+                 sample_status=np.full(max(n_samp, 1), FLANK_FILL, np.uint8), realign_sample=np.full(max(n_samp, 1), FLANK_FILL, np.uint8),
+                 realign_pool=np.full(max(n_pooled, 1), FLANK_FILL, np.uint8), copy_read=np.full(max(n_reads, 1), FLANK_FILL, np.uint8),
+                 task_k=np.full(max(2 * n_samp, 1), UNTOUCHED, np.int32), task_n_paths=np.full(max(2 * n_samp, 1), UNTOUCHED, np.int32),
+                 path_weight=np.full(max(c["paths"], 1), UNTOUCHED, np.int32), path_seq_off=np.full(c["paths"] + 1, UNTOUCHED, np.int32))
+        oseq = C.create_string_buffer(max(c["opt_chars"], 1)); pseq = C.create_string_buffer(max(c["path_chars"], 1))
+        o = HipstrFlankOut()
+        for nm, a in k.items():
+            if nm == null_out or (not want_paths and nm in ("task_k", "task_n_paths", "path_weight", "path_seq_off")):
+                continue
+            setattr(o, nm, a.ctypes.data_as(dict(new_n_haps=C.POINTER(C.c_int64)).get(nm, _u8p if a.dtype == np.uint8 else _i32p)))
+        if null_out != "opt_seq":
+            o.opt_seq = C.cast(oseq, C.c_char_p)
+        if want_paths:
+            o.path_seq = C.cast(pseq, C.c_char_p)
+        o.cap_opts, o.cap_opt_chars, o.cap_paths, o.cap_path_chars = c["opts"], c["opt_chars"], c["paths"], c["path_chars"]
+        rc = (lib.hipstr_flank_assemble(pb.ptr, C.byref(rq), None if t is None else C.byref(t), C.byref(o)) if td is None else
+              lib.hipstr_flank_assemble_dev(pd, C.byref(rq), td.h if hasattr(td, "h") else td, C.byref(o)))
+        k["opt_seq"] = oseq.raw; k["path_seq"] = pseq.raw
+        return rc, k, dict(opts=int(o.cap_opts), opt_chars=int(o.cap_opt_chars), paths=int(o.cap_paths), path_chars=int(o.cap_path_chars))
+
+    try:
+        if caps is None:
+            rc, k, need = call(dict(opts=0, opt_chars=0, paths=0, path_chars=0))
+            if rc == 3:
+                rc, k, need = call(need)
+        else:
+            rc, k, need = call(dict(caps))
+    finally:
+        if own:
+            lib.hipstr_post_free(pd)
+    if rc not in (0, 3):
+        e = RuntimeError("%s failed rc=%d: %s" % ("hipstr_flank_assemble" if td is None else "hipstr_flank_assemble_dev", rc, lib.hipstr_last_error().decode()))
+        e.raw = k
+        raise e
+    out = dict(rc=rc, raw=k, need=need, opt_off=k["opt_off"])
+    if rc != 0:
+        return out
+    out.update(status=k["status"][:nl], new_n_haps=k["new_n_haps"][:nl], sample_status=k["sample_status"][:n_samp], realign_sample=k["realign_sample"][:n_samp],
+               realign_pool=k["realign_pool"][:n_pooled], copy_read=k["copy_read"][:n_reads])
+    oo, so = k["opt_off"], k["opt_seq_off"]
+    flat = [(k["opt_seq"][so[i]:so[i + 1]], int(k["opt_n_samples"][i])) for i in range(int(oo[2 * nl]))]
+    out["opts"] = [[flat[oo[2 * l + f]:oo[2 * l + f + 1]] for f in range(2)] for l in range(nl)]
+    if want_paths:
+        out["task_k"] = k["task_k"][:2 * n_samp]; out["task_n_paths"] = k["task_n_paths"][:2 * n_samp]
+        po = k["path_seq_off"]; paths = []; at = 0
+        for tsk in range(2 * n_samp):
+            m = int(k["task_n_paths"][tsk])
+            paths.append([(int(k["path_weight"][i]), k["path_seq"][po[i]:po[i + 1]]) for i in range(at, at + m)])
+            at += m
+        out["paths"] = paths
+    return out
+
+
+def flank_plan(lib, pb, bptr, seed, read_req, req_read, pool_index, trace, sample_masked=None, **kw):
+    """hipstr_debug_flank_plan (host only) as a dict; "tasks" rows are lists in the order of "fields"."""
+    _flank_sigs(lib)
+    rq, keep = _flank_request(bptr, seed, read_req, req_read, pool_index, sample_masked, dict(kw))
+    t = _flank_trace(trace, keep)
+    return _plan_json(lib, "hipstr_debug_flank_plan", lambda buf, cap: lib.hipstr_debug_flank_plan(pb.ptr, C.byref(rq), C.byref(t), buf, cap))
+
+
+def flank_last(lib, n_tasks=0):
+    """hipstr_debug_flank_last -> dict(tasks, skipped, host_tasks, fetched_strings, bytes_up, bytes_down, flags[n_tasks], sizes[n_tasks, 4])."""
+    _flank_sigs(lib)
+    out = np.zeros(8, np.int64); fl = np.zeros(max(n_tasks, 1), np.int32); sz = np.zeros(max(4 * n_tasks, 4), np.int32)
+    if lib.hipstr_debug_flank_last(out.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(fl, _i32p), _ptr(sz, _i32p), int(n_tasks)) != 0:
+        raise RuntimeError("hipstr_debug_flank_last failed: " + lib.hipstr_last_error().decode())
+    return dict(tasks=int(out[0]), skipped=int(out[1]), host_tasks=int(out[2]), fetched_strings=bool(out[3]), bytes_up=int(out[4]), bytes_down=int(out[5]),
+                flags=fl[:n_tasks], sizes=sz[:4 * n_tasks].reshape(-1, 4))
+
+
 class HipstrPoolOut(C.Structure):
     _fields_ = [("pool_index", _i32p), ("n_pools", _i32p), ("pool_off", _i32p), ("pool_rep", _i32p), ("pool_size", _i32p),
                 ("pool_qual_off", _i32p), ("pool_quals", C.POINTER(C.c_char))]

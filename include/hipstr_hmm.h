@@ -816,6 +816,84 @@ const hipstr_batch_t*  hipstr_pooled_batch_batch(const hipstr_pooled_batch_t* p)
 const int32_t*         hipstr_pooled_batch_pool_index(const hipstr_pooled_batch_t* p);      /* [n_reads of the un-pooled batch] */
 void hipstr_pooled_batch_free(hipstr_pooled_batch_t* p);
 
+/*
+ * The flank reassembly that closes SeqStutterGenotyper::genotype(): assemble_flanks (seq_stutter_genotyper.cpp:40-217, reached from :666-668)
+ * with DebruijnGraph (debruijn_graph.cpp) and the pre-check of :618-629, batched over loci.  Per flank (0 = block 0, 1 = block 2; ref_seq =
+ * option 0 of the block) and per sample, one TASK: for k from calc_kmer_length(ref_seq, min_kmer, max_k) to max_k = min(max_kmer, len - 1) the
+ * graph of ref_seq (weight 2, its edges never pruned) takes the flank_seq(block) of every read of the sample that has a trace (seed >= 0 and
+ * read_req >= 0, as in the census) and a non-empty string (strings of length <= k do not count), is pruned with
+ * max(2, ceil(0.02 * strings)), and the first k whose graph is acyclic with a proper source and sink gives at most max_paths sink paths
+ * (weight >= min_path_weight), in the reference's pop order (libstdc++'s heap order among equal weights).  The aggregation (:99-201) runs as
+ * written on those records: the 0.25 depth share, FLANK_ASSEMBLY_INDEL for an alternative of another length (a later path of the same sample
+ * may still set realign_sample), FLANK_ASSEMBLY_CYCLIC, the LOW_FREQUENCY_ALT_FLANK pruning, flank 1 skipping what flank 0 masked, the three
+ * ways a locus fails, new options in bytewise order, and the two masks add_and_remove_alleles takes.
+ *
+ * Tasks are numbered 2*samp_off[l] + flank*S_l + s (samp_off: hipstr_post_offsets).  A sample with sample_masked set is skipped (its status
+ * stays 0); so is every task of a flank without a k-mer length.
+ * Per locus: status 0 = ok, 1 = no k-mer length for a flank (:58-59), 2 = more than max_flank_haplotypes alternatives (:158-162), 3 = more than
+ * max_total_haplotypes haplotypes (:176-180); new_n_haps as :48-55, :169 compute it (integer division as written).  For a locus with
+ * status != 0 only status is promised (both entry points still write the same bytes).
+ * Capacities: hipstr_post_census' convention — when cap_opts, cap_opt_chars, cap_paths or cap_path_chars is too small the call returns 3,
+ * opt_off is filled (opt_off[2*n_loci] = options needed) and the four cap_* fields of `out` are overwritten with what is needed; nothing else
+ * is promised.  The path arrays are optional: all of task_k, task_n_paths, path_weight, path_seq_off, path_seq may be NULL (each on its own).
+ * Refused (non-zero, hipstr_last_error(), decided before any launch, nothing written): null arguments, pooled->n_loci that differs from the
+ * posterior batch's, read_req outside [-1, n_req), a read whose request belongs to another locus, requests not grouped by locus in locus
+ * order, a pool_index outside the locus' pooled reads, a block without options, a handle without the FLANKS group, td on another device
+ * than pd, rq->n_req that differs from td's.
+ */
+typedef struct hipstr_flank_request {
+  const hipstr_batch_t* pooled;     /* the round's pooled batch: only n_loci, blk_nopts, opt_off, seq, hap_off, read_off are read */
+  const int32_t* seed;              /* [n_reads] seed_positions_ of the un-pooled reads; < 0 = traced_alns[r] == NULL */
+  const int32_t* read_req;          /* [n_reads] hipstr_post_assign(HIPSTR_ASSIGN_RETRACE)'s read_req; -1 = no trace */
+  int32_t        n_req;
+  const int32_t* req_read;          /* [n_req] as given to the traceback call: fixes every request's locus */
+  const int32_t* pool_index;        /* [n_reads] pool of the read within its locus (pool_index_) */
+  const uint8_t* sample_masked;     /* [n_samp] !call_sample_[s].empty() before the stage, or NULL = none */
+  int32_t  min_kmer, max_kmer, min_path_weight, max_paths;       /* 0 = the reference's 10 / 15 / 2 / 10 */
+  int32_t  max_total_haplotypes, max_flank_haplotypes;           /* as given (no default) */
+  double   min_flank_freq;
+} hipstr_flank_request_t;
+
+#define HIPSTR_FLANK_OK 0
+#define HIPSTR_FLANK_ASSEMBLY_INDEL 1
+#define HIPSTR_FLANK_ASSEMBLY_CYCLIC 2
+#define HIPSTR_FLANK_LOW_FREQUENCY_ALT 3
+#define HIPSTR_FLANK_TASK_CYCLIC (-1)
+#define HIPSTR_FLANK_TASK_SKIPPED (-2)
+typedef struct hipstr_flank_out {
+  int32_t* status;          /* [n_loci] */
+  int64_t* new_n_haps;      /* [n_loci] */
+  int32_t* opt_off;         /* [2*n_loci+1] the new options of (locus, flank), std::map order */
+  int32_t* opt_seq_off;     /* [cap_opts+1] */
+  char*    opt_seq;         /* [cap_opt_chars] */
+  int32_t* opt_n_samples;   /* [cap_opts] samples supporting the option (haplotype_to_sample[..].size()) */
+  uint8_t* sample_status;   /* [n_samp] HIPSTR_FLANK_* the stage set, 0 = unchanged */
+  uint8_t* realign_sample;  /* [n_samp] */
+  uint8_t* realign_pool;    /* [pooled reads] realign_pools (:185-191), pooled->read_off's numbering */
+  uint8_t* copy_read;       /* [n_reads] copy_reads */
+  int32_t* task_k;          /* [2*n_samp] accepted k, HIPSTR_FLANK_TASK_CYCLIC or _SKIPPED; or NULL */
+  int32_t* task_n_paths;    /* [2*n_samp] or NULL */
+  int32_t* path_weight;     /* [cap_paths] min_weight of every path, task after task, pop order; or NULL */
+  int32_t* path_seq_off;    /* [cap_paths+1] or NULL */
+  char*    path_seq;        /* [cap_path_chars] or NULL */
+  int32_t  cap_opts, cap_opt_chars, cap_paths, cap_path_chars;
+} hipstr_flank_out_t;
+
+/* calc_kmer_length for both flanks of every locus (host only): kmer[2*l + flank], -1 = too repetitive (:623) — a ref_seq of length <=
+ * min_kmer included.  Only n_loci, blk_nopts, opt_off and seq of the batch are read.  0 = 10 / 15. */
+int hipstr_flank_kmer_lengths(const hipstr_batch_t* batch, int32_t min_kmer, int32_t max_kmer, int32_t* kmer /* [2*n_loci] */);
+/* Host only (works on a library that never opened a device).  Only flank_seq_off / flank_seq of `tr` and n_loci, n_samples, read_off,
+ * sample_label of `pb` are read. */
+int hipstr_flank_assemble(const hipstr_post_batch_t* pb, const hipstr_flank_request_t* rq, const hipstr_trace_out_t* tr, hipstr_flank_out_t* out);
+/* The same stage where the records lie: the strings are read from td, the (locus, sample) runs of reads from what hipstr_post_upload left on
+ * the device (the run need not have been launched); of the per-read arrays only seed and read_req are uploaded.  One wavefront assembles one
+ * task (hipstr_amd/csrc/flank_task.h); only the per-task records and the paths' bytes come home, and the aggregation is the host entry
+ * point's own function on them.  A task beyond a limit of hipstr_amd/csrc/flank_layout.h (distinct edges, nodes, path records, reads, string
+ * length, a byte other than ACGTN, k above 15) is assembled by the host code inside the same call, on flank strings fetched once.  Outputs,
+ * return codes and hipstr_last_error() equal hipstr_flank_assemble on hipstr_trace_dev_fetch(td, HIPSTR_TRACE_F_FLANKS), byte for byte.
+ * Device and pinned blocks come from the context's caches. */
+int hipstr_flank_assemble_dev(hipstr_post_dev_t* pd, const hipstr_flank_request_t* rq, const hipstr_trace_dev_t* td, hipstr_flank_out_t* out);
+
 /* The diagnostics entry points (hipstr_debug_*: what the tests, the fuzzers and bench.py look inside the library with) are declared in
  * hipstr_hmm_debug.h — not part of the drop-in ABI; a build with -DHIPSTR_NO_DEBUG_ABI leaves them out of the library. */
 

@@ -118,6 +118,20 @@ int hipstr_debug_census_plan(int64_t n_req, int64_t n_reads, int64_t out[10]);
  * (most steps of a hash wavefront), "pools" ([copy, net, radix]: pools by median route, from the host's pooling) and "routes_hit".  Same
  * conventions as hipstr_debug_trace_plan.  Used by tests/test_pool_host.py. */
 int hipstr_debug_pool_plan(const hipstr_batch_t* unpooled, double ws_mib, char* json, int cap);
+/* Diagnostics (host only): what hipstr_flank_assemble_dev would do with a request on the strings of `tr` (flank_seq_off / flank_seq), from the
+ * functions of hipstr_amd/csrc/flank_layout.h the call and its kernel use, as one JSON object: "thresholds" (the compiled limits, "lds_bytes"
+ * of a workgroup), "caps" (the limits of this call: the compiled ones, or smaller ones from HIPSTR_DEBUG_FLANK_CAPS =
+ * "edges,nodes,recs,reads,len,path_len", read per call; 0 or missing = the compiled limit), "peel_rounds", "routes" (every route name), "fields"
+ * (the columns of "tasks"), per task, in task order, [accepted k, most distinct edges, most nodes, path records, reads of the run, longest
+ * string that entered (the reference flank included), longest path, strings that entered at the last k, HS_FLK_F_* flags, route index],
+ * "routes_hit", "pool_bytes" and "workgroups".  The sizes come from the host twin.  Refusals as in hipstr_flank_assemble.  Same conventions as
+ * hipstr_debug_trace_plan.  Used by tests/test_flank_plan.py. */
+int hipstr_debug_flank_plan(const hipstr_post_batch_t* pb, const hipstr_flank_request_t* rq, const hipstr_trace_out_t* tr, char* json, int cap);
+/* Diagnostics: the calling thread's last hipstr_flank_assemble_dev: out[0] tasks, out[1] tasks skipped, out[2] tasks the host twin assembled
+ * for a limit, out[3] 1 when the flank strings were fetched, out[4] bytes sent to the device, out[5] bytes copied back; flags (HS_FLK_F_* per
+ * task as the kernel set them) and sizes (per task: most edges, most nodes, path records, strings that entered, as the kernel counted
+ * them up to where it stopped) are filled for up to cap_tasks tasks and may be NULL.  A refused call leaves the numbers of the call before. */
+int hipstr_debug_flank_last(int64_t out[8], int32_t* flags, int32_t* sizes, int64_t cap_tasks);
 /* Diagnostics: the calling thread's last hipstr_pool_reads (or hipstr_pool_batch on the device): out[0] loci pooled on the device, out[1]
  * loci the host pooled for their size, out[2] loci the host redid after a hash collision, out[3..5] pools of the device's loci by median
  * route (copy, net, radix), out[6] chunks, out[7] reads uploaded.  hipstr_debug_pool_last_timing: out[0] milliseconds between HIP events

@@ -42,6 +42,7 @@
 #include "seq_stutter_genotyper.h"
 #undef private
 #undef protected
+#include "debruijn_graph.h"
 #include "SeqAlignment/AlignmentModel.h"
 #include "SeqAlignment/NeedlemanWunsch.h"
 #include "mathops.h"
@@ -312,9 +313,60 @@ static int run_locus(const LocusParams& lp, FILE* f){
 #include <chrono>
 #include <thread>
 
+// [--debruijn-cases IN --out OUT] the reference's own DebruijnGraph driven through the call sequence of assemble_flanks
+// (seq_stutter_genotyper.cpp:54-96) on cases read from a text file — per case one flank's ref_seq and, per sample, the strings its traced
+// reads would hand over (tests/golden/make_golden_flank.py writes the file and stores the records as tests/golden/flank_*.npz):
+//   case NAME MIN_KMER MAX_KMER MIN_PATH_WEIGHT MAX_PATHS N_SAMPLES / ref SEQ / per sample: sample N, then N lines of one string ("-" = empty)
+// Written: "case NAME kmer K" (calc_kmer_length's result, -1 = false) and, unless K is -1, per sample "task S k K n PATHS" (k -1 = no
+// acyclic k) followed by "path WEIGHT SEQ" in the order enumerate_paths returns them.
+static int run_debruijn_cases(const char* in_path, FILE* out){
+  std::ifstream in(in_path);
+  if (!in){ perror(in_path); return 2; }
+  auto seq = [](const std::string& s){ return s == "-" ? std::string() : s; };
+  std::string line;
+  while (std::getline(in, line)){
+    if (line.empty()) continue;
+    std::istringstream hd(line);
+    std::string word, name; int min_kmer = 0, max_kmer = 0, min_path_weight = 0, max_paths = 0, n_samples = 0;
+    hd >> word >> name >> min_kmer >> max_kmer >> min_path_weight >> max_paths >> n_samples;
+    if (word != "case" || !hd){ fprintf(stderr, "bad case line: %s\n", line.c_str()); return 2; }
+    std::string ref_seq;
+    std::getline(in, line); { std::istringstream ls(line); ls >> word >> ref_seq; ref_seq = seq(ref_seq); }
+    const int max_k = std::min(max_kmer, ref_seq.size() == 0 ? -1 : (int)ref_seq.size()-1);                          // :54
+    int kmer_length;
+    const bool have_k = DebruijnGraph::calc_kmer_length(ref_seq, min_kmer, max_k, kmer_length);                      // :58
+    fprintf(out, "case %s kmer %d\n", name.c_str(), have_k ? kmer_length : -1);
+    for (int s = 0; s < n_samples; s++){
+      int n = 0;
+      std::getline(in, line); { std::istringstream ls(line); ls >> word >> n; }
+      std::vector<std::string> strings((size_t)n);
+      for (int i = 0; i < n; i++){ std::getline(in, line); strings[i] = seq(line); }
+      if (!have_k) continue;
+      std::vector< std::pair<std::string,int> > assembly_data;
+      bool acyclic = false; int k_used = -1;
+      for (int k = kmer_length; k <= max_k; k++){                                                                    // :77-96
+        DebruijnGraph assembler(k, ref_seq);
+        for (const std::string& str : strings)
+          if (!str.empty())
+            assembler.add_string(str);
+        assembler.prune_edges(0.02, 2);
+        if (!assembler.has_cycles() && assembler.is_source_ok() && assembler.is_sink_ok()){
+          acyclic = true; k_used = k;
+          assembler.enumerate_paths(min_path_weight, max_paths, assembly_data);
+          break;
+        }
+      }
+      fprintf(out, "task %d k %d n %zu\n", s, acyclic ? k_used : -1, assembly_data.size());
+      for (size_t i = 0; i < assembly_data.size(); i++) fprintf(out, "path %d %s\n", assembly_data[i].second, assembly_data[i].first.c_str());
+    }
+  }
+  return 0;
+}
+
 extern "C" int flow_main(int argc, char** argv){
   LocusParams lp; lp.seed = 1; lp.n_samples = 10; lp.reads_per_sample = 9; lp.period = 4; lp.recompute = false; lp.reassemble = true; lp.nw = false; lp.dump_inputs = NULL;
   const char* out_path = NULL; int n_loci = 0, n_threads = 1; bool use_stream = false, profile = false;
+  const char* debruijn_cases = NULL;
   for (int i = 1; i < argc; i++){
     if (!strcmp(argv[i], "--seed")) lp.seed = strtoull(argv[++i], NULL, 10);
     else if (!strcmp(argv[i], "--samples")) lp.n_samples = atoi(argv[++i]);
@@ -328,8 +380,16 @@ extern "C" int flow_main(int argc, char** argv){
     else if (!strcmp(argv[i], "--loci")) n_loci = atoi(argv[++i]);          // many loci (seeds seed, seed+1, ...; periods cycling 2..5) ...
     else if (!strcmp(argv[i], "--threads")) n_threads = atoi(argv[++i]);    // ... one SeqStutterGenotyper per host thread at a time
     else if (!strcmp(argv[i], "--profile")) profile = true;                 // many-loci form: where the host threads' time went (MI355X build: library and adapter buckets)
+    else if (!strcmp(argv[i], "--debruijn-cases")) debruijn_cases = argv[++i];  // the reference's DebruijnGraph on cases of a text file (see run_debruijn_cases)
     else if (!strcmp(argv[i], "--stream")) use_stream = true;               // MI355X build: alignment rounds of the loci in flight share batches
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+  }
+  if (debruijn_cases){
+    FILE* f = out_path ? fopen(out_path, "w") : stdout;
+    if (!f){ perror(out_path); return 2; }
+    const int rc = run_debruijn_cases(debruijn_cases, f);
+    if (out_path) fclose(f);
+    return rc;
   }
   precompute_integer_logs();                 // hipstr_main.cpp:352
   init_alignment_model();
