@@ -910,6 +910,27 @@ def pool_last_timing(lib):
     return dict(kernel_ms=out[0], bytes_up=out[1], bytes_down=out[2], stage_s=out[3])
 
 
+def batch_arrays(ptr):
+    """The arrays of a hipstr_batch_t the library returned (a pointer) as numpy copies (bytes arrays without their closing NUL)."""
+    p = ptr.contents; nl = p.n_loci
+    raw = lambda name, cnt: C.string_at(C.c_void_p.from_buffer(p, getattr(HipstrBatch, name).offset).value, cnt) if cnt else b""      # (a c_char_p field read as such stops at a NUL)
+    i32 = lambda ptr, cnt: np.ctypeslib.as_array(ptr, shape=(cnt,)).copy() if cnt else np.zeros(0, np.int32)
+    d = dict(blk_start=i32(p.blk_start, 3 * nl), blk_end=i32(p.blk_end, 3 * nl), blk_nopts=i32(p.blk_nopts, 3 * nl), period=i32(p.period, nl),
+             stutter=np.ctypeslib.as_array(p.stutter, shape=(6 * nl,)).copy() if nl else np.zeros(0))
+    nopt = int(d["blk_nopts"].sum())
+    d["opt_off"] = i32(p.opt_off, nopt + 1); d["hap_off"] = i32(p.hap_off, nl + 1); d["read_off"] = i32(p.read_off, nl + 1)
+    d["seq"] = np.frombuffer(raw("seq", int(d["opt_off"][-1])), np.uint8).copy()
+    P = int(d["read_off"][-1])
+    d["base_off"] = i32(p.base_off, P + 1); d["cigar_off"] = i32(p.cigar_off, P + 1); d["read_start"] = i32(p.read_start, P)
+    nb, nc = int(d["base_off"][-1]), int(d["cigar_off"][-1])
+    d["bases"] = np.frombuffer(raw("bases", nb), np.uint8).copy(); d["quals"] = np.frombuffer(raw("quals", nb), np.uint8).copy()
+    d["cigar_op"] = np.frombuffer(raw("cigar_op", nc), np.uint8).copy(); d["cigar_len"] = i32(p.cigar_len, nc)
+    A = int(d["hap_off"][-1])
+    d["realign_hap"] = np.ctypeslib.as_array(p.realign_hap, shape=(A,)).copy() if p.realign_hap else np.zeros(0, np.uint8)
+    d["realign_read"] = np.ctypeslib.as_array(p.realign_read, shape=(P,)).copy() if p.realign_read else np.zeros(0, np.uint8)
+    return d
+
+
 class PooledBatch:
     """hipstr_pool_batch: the pooled batch (ptr: a hipstr_batch_t for hipstr_hmm_upload) and the un-pooled reads' pool indices."""
 
@@ -926,27 +947,172 @@ class PooledBatch:
 
     def arrays(self):
         """The pooled batch's arrays as numpy copies (bytes arrays without their closing NUL)."""
-        p = self.ptr.contents; nl = p.n_loci
-        raw = lambda name, cnt: C.string_at(C.c_void_p.from_buffer(p, getattr(HipstrBatch, name).offset).value, cnt) if cnt else b""      # (a c_char_p field read as such stops at a NUL)
-        i32 = lambda ptr, cnt: np.ctypeslib.as_array(ptr, shape=(cnt,)).copy() if cnt else np.zeros(0, np.int32)
-        d = dict(blk_start=i32(p.blk_start, 3 * nl), blk_end=i32(p.blk_end, 3 * nl), blk_nopts=i32(p.blk_nopts, 3 * nl), period=i32(p.period, nl),
-                 stutter=np.ctypeslib.as_array(p.stutter, shape=(6 * nl,)).copy() if nl else np.zeros(0))
-        nopt = int(d["blk_nopts"].sum())
-        d["opt_off"] = i32(p.opt_off, nopt + 1); d["hap_off"] = i32(p.hap_off, nl + 1); d["read_off"] = i32(p.read_off, nl + 1)
-        d["seq"] = np.frombuffer(raw("seq", int(d["opt_off"][-1])), np.uint8).copy()
-        P = int(d["read_off"][-1])
-        d["base_off"] = i32(p.base_off, P + 1); d["cigar_off"] = i32(p.cigar_off, P + 1); d["read_start"] = i32(p.read_start, P)
-        nb, nc = int(d["base_off"][-1]), int(d["cigar_off"][-1])
-        d["bases"] = np.frombuffer(raw("bases", nb), np.uint8).copy(); d["quals"] = np.frombuffer(raw("quals", nb), np.uint8).copy()
-        d["cigar_op"] = np.frombuffer(raw("cigar_op", nc), np.uint8).copy(); d["cigar_len"] = i32(p.cigar_len, nc)
-        A = int(d["hap_off"][-1])
-        d["realign_hap"] = np.ctypeslib.as_array(p.realign_hap, shape=(A,)).copy() if p.realign_hap else np.zeros(0, np.uint8)
-        d["realign_read"] = np.ctypeslib.as_array(p.realign_read, shape=(P,)).copy() if p.realign_read else np.zeros(0, np.uint8)
-        return d
+        return batch_arrays(self.ptr)
 
     def close(self):
         if self.h:
             self.lib.hipstr_pooled_batch_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipstrHapgenRequest(C.Structure):
+    _fields_ = [("region_start", _i32p), ("region_stop", _i32p), ("period", _i32p), ("chrom_len", C.POINTER(C.c_int64)), ("win_off", _i32p),
+                ("window", C.POINTER(C.c_char)), ("n_samples", _i32p), ("sample_label", _i32p), ("read_stop", _i32p), ("use_read", _u8p), ("stutter", _f64p)]
+
+
+class HipstrHapgenOut(C.Structure):
+    _fields_ = [("status", _i32p), ("blk_start", _i32p), ("blk_end", _i32p), ("blk_nopts", _i32p), ("opt_off", _i32p), ("seq", C.POINTER(C.c_char)),
+                ("n_spanning", _i32p), ("n_samples_spanning", _i32p), ("n_distinct", _i32p), ("left_trim", _i32p), ("right_trim", _i32p),
+                ("min_aln_start", _i32p), ("max_aln_stop", _i32p), ("ext_off", _i32p), ("ext_len", _i32p), ("dist_len", _i32p), ("dist_rep", _i32p),
+                ("dist_reads", _i32p), ("dist_strong", _i32p), ("dist_frac", _f64p)]
+
+
+HAPGEN_ON_HOST = 1      # HIPSTR_HAPGEN_ON_HOST
+HAPGEN_ROUTES = ("device", "host")
+HAPGEN_LAST = ("device_loci", "host_loci", "collision_loci", "chunks", "reads_uploaded", "unused5", "unused6", "unused7")
+HAPGEN_FILL = -7        # what run_hapgen fills the integer outputs with before the call (sequence bytes: 0x5A, dist_frac: -7.0)
+HAPGEN_FIELDS = tuple(f for f, _ in HipstrHapgenOut._fields_)
+HAPGEN_OPTIONAL = ("ext_off", "ext_len", "dist_len", "dist_rep", "dist_reads", "dist_strong", "dist_frac")
+HAPGEN_STATUS = ("", "Haplotype blocks are too near to the chromosome ends", "No spanning alignments")
+
+
+def _hapgen_sigs(lib):
+    RQ, OUT = C.POINTER(HipstrHapgenRequest), C.POINTER(HipstrHapgenOut)
+    _sig(lib.hipstr_hapgen, C.c_int, [_BP, RQ, OUT])
+    _sig(lib.hipstr_hapgen_host, C.c_int, [_BP, RQ, OUT])
+    _sig(lib.hipstr_hapgen_status_message, C.c_char_p, [C.c_int32])
+    _sig(lib.hipstr_hapgen_batch, C.c_void_p, [_BP, RQ, C.c_uint32])
+    _sig(lib.hipstr_hapgen_batch_batch, _BP, [C.c_void_p])
+    _sig(lib.hipstr_hapgen_batch_locus, _i32p, [C.c_void_p])
+    _sig(lib.hipstr_hapgen_batch_status, _i32p, [C.c_void_p])
+    _sig(lib.hipstr_hapgen_batch_free, None, [C.c_void_p])
+    _sig(lib.hipstr_debug_hapgen_plan, C.c_int, [_BP, RQ, C.c_double, C.c_char_p, C.c_int])
+    _sig(lib.hipstr_debug_hapgen_last, C.c_int, [C.POINTER(C.c_int64)])
+    _sig(lib.hipstr_debug_hapgen_last_timing, C.c_int, [_f64p])
+
+
+class HapgenRequest:
+    """A hipstr_hapgen_request_t over numpy arrays it keeps alive.  windows: one bytes object per locus; read_stop / use_read / stutter may be None."""
+
+    def __init__(self, region_start, region_stop, period, chrom_len, windows, n_samples, sample_label, read_stop=None, use_read=None, stutter=None):
+        i32 = lambda x: np.ascontiguousarray(np.asarray(x, np.int32))
+        win_off = np.concatenate([[0], np.cumsum([len(w) for w in windows])]).astype(np.int32)
+        self.a = dict(region_start=i32(region_start), region_stop=i32(region_stop), period=i32(period),
+                      chrom_len=np.ascontiguousarray(np.asarray(chrom_len, np.int64)), win_off=win_off,
+                      window=np.frombuffer(b"".join(windows) + b"\0", np.uint8).copy(), n_samples=i32(n_samples),
+                      sample_label=i32(sample_label if len(sample_label) else [0]), read_stop=None if read_stop is None else i32(read_stop),
+                      use_read=None if use_read is None else np.ascontiguousarray(np.asarray(use_read, np.uint8)),
+                      stutter=None if stutter is None else np.ascontiguousarray(np.asarray(stutter, np.float64)))
+        a = self.a
+        self.struct = HipstrHapgenRequest(_ptr(a["region_start"], _i32p), _ptr(a["region_stop"], _i32p), _ptr(a["period"], _i32p),
+                                          a["chrom_len"].ctypes.data_as(C.POINTER(C.c_int64)), _ptr(a["win_off"], _i32p),
+                                          a["window"].ctypes.data_as(C.POINTER(C.c_char)), _ptr(a["n_samples"], _i32p), _ptr(a["sample_label"], _i32p),
+                                          _ptr(a["read_stop"], _i32p), _ptr(a["use_read"], _u8p), _ptr(a["stutter"], _f64p))
+
+    @property
+    def ptr(self):
+        return C.byref(self.struct)
+
+
+def hapgen_arrays(bptr, rq):
+    """Room for every output of hipstr_hapgen on (bptr, rq), filled with HAPGEN_FILL / 0x5A / -7.0, and the struct that points into it."""
+    b = _batch_struct(bptr)
+    nl = b.n_loci
+    n = int(b.read_off[nl]) if nl else 0
+    nb = int(b.base_off[n]) if n else 0
+    nw = int(rq.a["win_off"][-1]) if nl else 0
+    size = dict(status=nl, blk_start=3 * nl, blk_end=3 * nl, blk_nopts=3 * nl, opt_off=3 * nl + n + 1, seq=nw + nb + 1)
+    a = {}
+    for k in HAPGEN_FIELDS:
+        if k == "seq":
+            a[k] = np.full(size[k], 0x5A, np.uint8)
+        elif k == "dist_frac":
+            a[k] = np.full(n + 1, float(HAPGEN_FILL), np.float64)
+        else:
+            a[k] = np.full(size.get(k, nl if k not in HAPGEN_OPTIONAL else n) + 1, HAPGEN_FILL, np.int32)
+    return a
+
+
+def hapgen_out_struct(a, skip=()):
+    typ = dict(seq=C.POINTER(C.c_char), dist_frac=_f64p)
+    return HipstrHapgenOut(*[None if k in skip else a[k].ctypes.data_as(typ.get(k, _i32p)) for k in HAPGEN_FIELDS])
+
+
+def run_hapgen(lib, bptr, rq, host=False, skip=(), raw=False):
+    """hipstr_hapgen (host=True: hipstr_hapgen_host): a dict of the outputs cut to what the call wrote (options: a list of lists of bytes per
+    block).  skip: optional outputs passed as NULL.  raw=True: the arrays at their full size, what the call left untouched still HAPGEN_FILL."""
+    a = hapgen_arrays(bptr, rq)
+    o = hapgen_out_struct(a, skip)
+    rc = (lib.hipstr_hapgen_host if host else lib.hipstr_hapgen)(bptr, rq.ptr, C.byref(o))
+    if rc != 0:
+        raise RuntimeError("hipstr_hapgen%s failed: %s" % ("_host" if host else "", lib.hipstr_last_error().decode()))
+    if raw:
+        return a
+    b = _batch_struct(bptr)
+    nl = b.n_loci
+    n0 = int(b.read_off[0]) if nl else 0
+    n = int(b.read_off[nl]) if nl else 0
+    g = {k: a[k][:nl].copy() for k in ("status", "n_spanning", "n_samples_spanning", "n_distinct", "left_trim", "right_trim", "min_aln_start", "max_aln_stop")}
+    for k in ("blk_start", "blk_end", "blk_nopts"):
+        g[k] = a[k][:3 * nl].copy()
+    nopt = int(g["blk_nopts"].sum())
+    g["opt_off"] = a["opt_off"][:nopt + 1].copy()
+    g["seq"] = a["seq"][:int(g["opt_off"][-1])].tobytes()
+    nd = int(g["n_distinct"].sum())
+    for k in HAPGEN_OPTIONAL:
+        if k not in skip:
+            g[k] = a[k][n0:n].copy() if k.startswith("ext") else a[k][:nd].copy()
+    oo = g["opt_off"]
+    g["options"] = [g["seq"][oo[i]:oo[i + 1]] for i in range(nopt)]
+    g["untouched"] = all(np.all(a[k][m:] == HAPGEN_FILL) for k, m in (("status", nl), ("blk_nopts", 3 * nl), ("opt_off", nopt + 1))) and \
+        bool(np.all(a["seq"][len(g["seq"]):] == 0x5A)) and all(k in skip or np.all(a[k][nd:] == HAPGEN_FILL) for k in HAPGEN_OPTIONAL if k.startswith("dist"))
+    return g
+
+
+def hapgen_plan(lib, bptr, rq, ws_mib=0.0):
+    """What hipstr_hapgen would do with a request (host only: hipstr_debug_hapgen_plan) as a dict."""
+    return _plan_json(lib, "hipstr_debug_hapgen_plan", lambda buf, cap: lib.hipstr_debug_hapgen_plan(bptr, rq.ptr, ws_mib, buf, cap))
+
+
+def hapgen_last(lib):
+    """hipstr_debug_hapgen_last as a dict keyed by HAPGEN_LAST."""
+    out = (C.c_int64 * 8)()
+    assert lib.hipstr_debug_hapgen_last(out) == 0
+    return dict(zip(HAPGEN_LAST, [int(x) for x in out]))
+
+
+def hapgen_last_timing(lib):
+    out = (C.c_double * 4)()
+    assert lib.hipstr_debug_hapgen_last_timing(out) == 0
+    return dict(kernel_ms=out[0], bytes_up=out[1], bytes_down=out[2], stage_s=out[3])
+
+
+class HapgenBatch:
+    """hipstr_hapgen_batch: the un-pooled batch of the loci with status 0 (ptr: a hipstr_batch_t for hipstr_pool_batch), their original
+    indices (locus) and the status of all loci."""
+
+    def __init__(self, lib, bptr, rq, flags=0):
+        self.lib = lib
+        self.h = lib.hipstr_hapgen_batch(bptr, rq.ptr, flags)
+        if not self.h:
+            raise RuntimeError("hipstr_hapgen_batch failed: " + lib.hipstr_last_error().decode())
+        nl = _batch_struct(bptr).n_loci
+        self.ptr = lib.hipstr_hapgen_batch_batch(self.h)
+        nk = self.ptr.contents.n_loci
+        self.locus = np.ctypeslib.as_array(lib.hipstr_hapgen_batch_locus(self.h), shape=(nk,)).copy() if nk else np.zeros(0, np.int32)
+        self.status = np.ctypeslib.as_array(lib.hipstr_hapgen_batch_status(self.h), shape=(nl,)).copy() if nl else np.zeros(0, np.int32)
+
+    def arrays(self):
+        return batch_arrays(self.ptr)
+
+    def close(self):
+        if self.h:
+            self.lib.hipstr_hapgen_batch_free(self.h); self.h = None
 
     def __del__(self):
         try:
@@ -1421,6 +1587,7 @@ def load_hmm():
     _sig(lib.hipstr_post_census_dev, C.c_int, [C.c_void_p, C.POINTER(HipstrCensusRequest), C.c_void_p, C.POINTER(HipstrCensusOut)])
     _em_trace_sigs(lib)
     _pool_sigs(lib)
+    _hapgen_sigs(lib)
     return lib
 
 

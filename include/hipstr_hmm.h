@@ -894,6 +894,99 @@ int hipstr_flank_assemble(const hipstr_post_batch_t* pb, const hipstr_flank_requ
  * Device and pinned blocks come from the context's caches. */
 int hipstr_flank_assemble_dev(hipstr_post_dev_t* pd, const hipstr_flank_request_t* rq, const hipstr_trace_dev_t* td, hipstr_flank_out_t* out);
 
+/*
+ * HaplotypeGenerator for a batch of single-region loci: what SeqStutterGenotyper::init -> build_haplotype (seq_stutter_genotyper.cpp:422-488)
+ * leaves behind, from UN-POOLED reads, a region and a reference window — add_haplotype_block (HaplotypeGenerator.cpp:286-337) with
+ * gen_candidate_seqs (:157-241), extract_sequence (:82-155), trim (:12-80), get_aln_bounds (:243-254), fuse_haplotype_blocks (:339-366) and
+ * the bounds loop of build_haplotype (:428-432).  The reference-VCF path (add_vcf_haplotype_block) and loci of several regions are not here.
+ * The reads come as a hipstr_batch_t of which only n_loci, read_off, base_off, bases, read_start and cigar_* are read.
+ *
+ * Per locus: status 1 when region_start < 40 or region_stop + 40 > chrom_len (:292); else, with the padded region [region_start - 5,
+ * region_stop + 5] and the smallest start / largest stop of the FLAGGED reads (use_read), status 2 when min + 5 >= region_start - 5 or
+ * max - 5 <= region_stop + 5 (:305); else status 0 and the three blocks.  A flagged read is COUNTED when start < region_start - 5 and
+ * stop > region_stop + 5 (stop as given: the reference only compares it, so either end convention of the caller works); its extracted
+ * string is the run of its bases the walk of :86-152 collects — an insertion is kept when the walk stands in [region_start - 5, region_stop
+ * + 5], either edge included, skipped before it; deleted bases are skipped; an empty extraction is the allele "" — folded to upper case
+ * (a-z only).  Per sample s (ascending), with n_s counted reads, a string with c of them is strong when c >= 2 and c >= 0.2 * n_s, and adds
+ * c * 1.0 / n_s to the string's sample fraction (IEEE double, summed in ascending sample index); a sample without counted reads adds nothing
+ * and is not among the spanning samples.  A string is selected when it is strong in a sample, or its fraction > 0.05 * spanning samples, or
+ * its reads > 0.05 * counted reads.  The options of block 1 are the padded region's reference string first, then the other selected strings
+ * by (length, bytes as unsigned char); trim (ideal_min_length = 3 * period) then takes a common prefix / suffix of at most 5 bases off all of
+ * them and moves the block's bounds.  Blocks 0 and 2 are the reference from max(blk1_start - 35, min start of ALL the locus' reads) — at most
+ * blk1_start - 10 — to block 1, and from block 1 to min(blk1_end + 35, max stop of ALL reads), at least blk1_end + 10.
+ * Deviation from the reference: a locus without a flagged read makes :305 compute INT_MAX + 5 and INT_MIN - 5, signed overflow; here that
+ * arithmetic is done in 64 bits, so such a locus has status 2.
+ *
+ * Sizes: every output array is sized by the input.  Options (entries of opt_off, less one) <= 3*n_loci + n_reads; sequence bytes <=
+ * win_off[n_loci] + base_off[n_reads]; the dist_* arrays hold at most n_reads entries.  A locus with status != 0 has 0 options in every
+ * block, blk_start = blk_end = 0, its counts and trims are 0 and its reads' ext_off / ext_len are -1; min_aln_start / max_aln_stop are
+ * written for every locus (INT32_MAX / INT32_MIN for one without reads).
+ * hipstr_hapgen works on the device, in chunks of whole loci under a workspace budget (HIPSTR_HAPGEN_WS_MIB, default 256): counted reads are
+ * grouped by a 64-bit hash of their extracted bytes and every member is then compared with its group's first read byte for byte — a locus in
+ * which two different strings share a hash, and a locus beyond a cap of hipstr_amd/csrc/hapgen_layout.h (reads, samples, distinct strings),
+ * is done by the host code inside the same call.  hipstr_hapgen_host is that host code for the whole batch; it needs no device.  Both give
+ * identical bytes in every output, dist_frac included.
+ * Refused (non-zero + hipstr_last_error(), nothing written, nothing launched): NULL arguments, a NULL required array, offset tables the
+ * other entry points refuse, a CIGAR op other than = X I D, a period < 1, region_stop < region_start, n_samples < 0, a sample_label outside
+ * [0, n_samples), a window shorter than region_stop - region_start + 80 for a locus that passes the chromosome-end check, a read whose
+ * given read_stop exceeds start + the sum of its =, X and D runs (the one input on which the reference's walk runs off the CIGAR, :153).
+ * hipstr_hapgen without a device fails as every device entry point does; it does not fall back to the host.  A HIP error in a later chunk
+ * leaves the loci of the chunks before it written, as with hipstr_pool_reads.  Reads in front of read_off[0] belong to no locus: their
+ * ext_off / ext_len are left untouched.
+ */
+typedef struct hipstr_hapgen_request {
+  const int32_t* region_start;  /* [n_loci] Region::start()                                              */
+  const int32_t* region_stop;   /* [n_loci] Region::stop(), exclusive                                    */
+  const int32_t* period;        /* [n_loci]                                                              */
+  const int64_t* chrom_len;     /* [n_loci] chrom_seq.size(): the end checks of :292                     */
+  const int32_t* win_off;       /* [n_loci+1] offsets into window                                        */
+  const char*    window;        /* per locus chrom_seq[region_start-40, region_stop+40), any case        */
+  const int32_t* n_samples;     /* [n_loci]                                                              */
+  const int32_t* sample_label;  /* [n_reads] sample within the locus; NO order of the reads is assumed   */
+  const int32_t* read_stop;     /* [n_reads] Alignment::get_stop(), or NULL = start + sum of =,X,D runs  */
+  const uint8_t* use_read;      /* [n_reads] use_for_hap_generation(0), or NULL = all                    */
+  const double*  stutter;       /* [6*n_loci] only copied into the batch hipstr_hapgen_batch returns     */
+} hipstr_hapgen_request_t;
+typedef struct hipstr_hapgen_out {
+  int32_t* status;              /* [n_loci]   0 ok, 1 too near to the chromosome ends, 2 no spanning alignments */
+  int32_t* blk_start;           /* [3*n_loci] as in hipstr_batch_t                                              */
+  int32_t* blk_end;             /* [3*n_loci]                                                                   */
+  int32_t* blk_nopts;           /* [3*n_loci] 0 for every block of a failed locus                               */
+  int32_t* opt_off;             /* [n_opts+1] locus-major, block-major, option-minor                            */
+  char*    seq;                 /* upper case                                                                   */
+  int32_t* n_spanning;          /* [n_loci] tot_reads: counted reads                                            */
+  int32_t* n_samples_spanning;  /* [n_loci] tot_samples                                                         */
+  int32_t* n_distinct;          /* [n_loci] distinct extracted strings                                          */
+  int32_t* left_trim;           /* [n_loci] what trim took off                                                  */
+  int32_t* right_trim;          /* [n_loci]                                                                     */
+  int32_t* min_aln_start;       /* [n_loci] over ALL reads of the locus (:428-432)                              */
+  int32_t* max_aln_stop;        /* [n_loci]                                                                     */
+  int32_t* ext_off;             /* [n_reads] or NULL: first base of the read's extracted run, within the read; -1 = not counted */
+  int32_t* ext_len;             /* [n_reads] or NULL: its length; -1 = not counted                              */
+  int32_t* dist_len;            /* [n_reads] or NULL: per distinct string, locus after locus (n_distinct each), in (length, bytes) order */
+  int32_t* dist_rep;            /* [n_reads] or NULL: the first read (batch index) that carries it              */
+  int32_t* dist_reads;          /* [n_reads] or NULL: read_counts                                               */
+  int32_t* dist_strong;         /* [n_reads] or NULL: must_inc — samples in which it is strong                  */
+  double*  dist_frac;           /* [n_reads] or NULL: sample_counts                                             */
+} hipstr_hapgen_out_t;
+int hipstr_hapgen(const hipstr_batch_t* reads, const hipstr_hapgen_request_t* rq, hipstr_hapgen_out_t* out);        /* on the device */
+int hipstr_hapgen_host(const hipstr_batch_t* reads, const hipstr_hapgen_request_t* rq, hipstr_hapgen_out_t* out);   /* host only, no device needed */
+/* failure_msg_ of the reference for a status: "" for 0, NULL for a code that is none */
+const char* hipstr_hapgen_status_message(int32_t status);
+
+/* The un-pooled batch build_haplotype leaves behind, in one allocation, over the loci whose status is 0 (in locus order): the haplotype
+ * arrays from the stage, hap_off from the option counts, period and stutter from the request, the kept loci's reads copied (quals too:
+ * reads->quals must be given), realign_hap = realign_read = NULL — ready for hipstr_pool_batch and hipstr_post_*.  flags:
+ * HIPSTR_HAPGEN_ON_HOST uses hipstr_hapgen_host, 0 the device.  NULL + hipstr_last_error() on a refusal or a failure.  _locus: the original
+ * index of every kept locus ([_batch()->n_loci]); _status: the status of all loci ([reads->n_loci]). */
+#define HIPSTR_HAPGEN_ON_HOST 1u
+typedef struct hipstr_hapgen_batch hipstr_hapgen_batch_t;
+hipstr_hapgen_batch_t* hipstr_hapgen_batch(const hipstr_batch_t* reads, const hipstr_hapgen_request_t* rq, uint32_t flags);
+const hipstr_batch_t*  hipstr_hapgen_batch_batch(const hipstr_hapgen_batch_t* h);
+const int32_t*         hipstr_hapgen_batch_locus(const hipstr_hapgen_batch_t* h);
+const int32_t*         hipstr_hapgen_batch_status(const hipstr_hapgen_batch_t* h);
+void hipstr_hapgen_batch_free(hipstr_hapgen_batch_t* h);
+
 /* The diagnostics entry points (hipstr_debug_*: what the tests, the fuzzers and bench.py look inside the library with) are declared in
  * hipstr_hmm_debug.h — not part of the drop-in ABI; a build with -DHIPSTR_NO_DEBUG_ABI leaves them out of the library. */
 

@@ -140,6 +140,23 @@ int hipstr_debug_flank_last(int64_t out[8], int32_t* flags, int32_t* sizes, int6
  * zeros.  Used by tests/test_pool_gpu.py and tools/pool_timing.py. */
 int hipstr_debug_pool_last(int64_t out[8]);
 int hipstr_debug_pool_last_timing(double out[4]);
+/* Diagnostics (host only): what hipstr_hapgen would do with a request under a budget of ws_mib MiB of workspace per chunk (<= 0: the
+ * call's own default or HIPSTR_HAPGEN_WS_MIB), from the functions of hipstr_amd/csrc/hapgen_layout.h the call and its kernels use, as one
+ * JSON object: "thresholds" (the compiled limits), "budget_bytes", "max_lds_bytes" (the grouping workgroup's LDS at the caps), "routes"
+ * (a locus is done on the "device" or, for its reads or samples, on the "host"), per chunk "l0" / "l1", "reads" and "bytes" (uploaded reads
+ * and the workspace they take), "device_loci", "host_loci", "lds_bytes", and "routes_hit".  A locus with more distinct strings than
+ * HS_HAPGEN_MAX_DISTINCT is found on the device only and is not in the plan.  Refusals as hipstr_hapgen (-1).  Same conventions as
+ * hipstr_debug_trace_plan.  Used by tests/test_hapgen_host.py. */
+int hipstr_debug_hapgen_plan(const hipstr_batch_t* reads, const hipstr_hapgen_request_t* rq, double ws_mib, char* json, int cap);
+/* Diagnostics: the calling thread's last hipstr_hapgen (or hipstr_hapgen_batch on the device): out[0] loci done on the device, out[1] loci
+ * the host did for their size (reads, samples, or distinct strings found on the device), out[2] loci the host redid after a hash
+ * collision, out[3] chunks, out[4] reads uploaded, out[5..7] 0.  hipstr_debug_hapgen_last_timing: out[0] milliseconds between HIP events
+ * around the call's kernels (0 unless HIPSTR_HAPGEN_TIMING is set), out[1] bytes sent to the device, out[2] bytes copied back, out[3]
+ * seconds the host spent staging.  HIPSTR_DEBUG_HAPGEN_HASH_BITS (read by every call) keeps that many low bits of the hash: collisions at
+ * test sizes.  A refused call leaves the numbers of the call before it; one that failed on the way leaves zeros.  Used by
+ * tests/test_hapgen_gpu.py and tools/hapgen_timing.py. */
+int hipstr_debug_hapgen_last(int64_t out[8]);
+int hipstr_debug_hapgen_last_timing(double out[4]);
 
 /* Diagnostics (host only): the decisions hipstr_em_train_dev takes (hipstr_amd/csrc/em_input_layout.h) for a batch of n_runs (locus, sample)
  * runs whose run in question has run_reads reads, and for a locus whose sizes (ref_allele included) lie in [lo, hi] and are n_sizes many:

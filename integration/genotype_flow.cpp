@@ -44,6 +44,7 @@
 #undef protected
 #include "debruijn_graph.h"
 #include "SeqAlignment/AlignmentModel.h"
+#include "SeqAlignment/HaplotypeGenerator.h"
 #include "SeqAlignment/NeedlemanWunsch.h"
 #include "mathops.h"
 #include "null_ostream.h"
@@ -363,10 +364,88 @@ static int run_debruijn_cases(const char* in_path, FILE* out){
   return 0;
 }
 
+// [--hapgen-cases IN --out OUT [--time REPS]] the reference's own HaplotypeGenerator driven as build_haplotype drives it
+// (seq_stutter_genotyper.cpp:428-488, one region, no reference VCF) on cases read from a text file (tests/golden/make_golden_hapgen.py
+// writes the file from tests/hapgen_cases.py and stores the records as tests/golden/hapgen_*.npz):
+//   case NAME REGION_START REGION_STOP PERIOD N_SAMPLES N_READS / chrom SEQ / per read: read SAMPLE START STOP USE CIGAR SEQ
+// Written: "case NAME status CODE MESSAGE" (0 = built; 1, 2 = the two failure_msg() strings of add_haplotype_block, 9 = another) and, for a
+// built haplotype, per block "block B START END N_OPTIONS SEQ..." ("-" = the empty option).  With --time REPS every case is built REPS
+// times more and a last line "time SECONDS CASES REPS" gives the seconds spent inside HaplotypeGenerator alone.  Data only.
+static int run_hapgen_cases(const char* in_path, FILE* out, int time_reps){
+  std::ifstream in(in_path);
+  if (!in){ perror(in_path); return 2; }
+  std::string line;
+  double seconds = 0; int n_cases = 0;
+  while (std::getline(in, line)){
+    if (line.empty()) continue;
+    std::istringstream hd(line);
+    std::string word, name; int region_start = 0, region_stop = 0, period = 0, n_samples = 0, n_reads = 0;
+    hd >> word >> name >> region_start >> region_stop >> period >> n_samples >> n_reads;
+    if (word != "case" || !hd){ fprintf(stderr, "bad case line: %s\n", line.c_str()); return 2; }
+    std::string chrom;
+    std::getline(in, line); { std::istringstream ls(line); ls >> word >> chrom; }
+    std::vector<Alignment> alns; std::vector<int> sample_label;
+    for (int i = 0; i < n_reads; i++){
+      std::getline(in, line);
+      std::istringstream ls(line);
+      int sample = 0, start = 0, stop = 0, use = 0; std::string cig, seq;
+      ls >> word >> sample >> start >> stop >> use >> cig >> seq;
+      if (word != "read" || !ls){ fprintf(stderr, "bad read line: %s\n", line.c_str()); return 2; }
+      std::vector<CigarElement> cigar; std::string aln; size_t k = 0;
+      for (size_t c = 0; c < cig.size(); ){
+        int num = 0;
+        while (c < cig.size() && cig[c] >= '0' && cig[c] <= '9') num = 10*num + (cig[c++] - '0');
+        const char op = cig[c++];
+        cigar.push_back(CigarElement(op, num));
+        if (op == 'D') aln += std::string(num, '-'); else { aln += seq.substr(k, num); k += num; }
+      }
+      std::stringstream rn; rn << "r" << i;
+      Alignment a(start, stop, false, rn.str(), std::string(seq.size(), 'F'), seq, aln);
+      a.set_cigar_list(cigar);
+      a.set_hap_gen_info(std::vector<bool>(1, use != 0));
+      alns.push_back(a); sample_label.push_back(sample);
+    }
+    Region region("chr1", region_start, region_stop, period, name);
+    StutterModel model(0.9, 0.05, 0.05, 0.7, 0.005, 0.005, period);
+    std::vector<std::string> vcf_alleles;
+    n_cases++;
+    for (int rep = 0; rep <= time_reps; rep++){
+      const auto t0 = std::chrono::steady_clock::now();
+      int32_t min_aln_start = INT_MAX, max_aln_stop = INT_MIN;                                                       // :428-432
+      for (size_t i = 0; i < alns.size(); i++){
+        min_aln_start = std::min(min_aln_start, alns[i].get_start());
+        max_aln_stop  = std::max(max_aln_stop,  alns[i].get_stop());
+      }
+      HaplotypeGenerator hap_generator(min_aln_start, max_aln_stop);
+      std::vector< std::vector<Alignment> > gen_hap_alns(n_samples);                                                                 // :439-442
+      for (size_t i = 0; i < alns.size(); i++)
+        if (alns[i].use_for_hap_generation(0))
+          gen_hap_alns[sample_label[i]].push_back(alns[i]);
+      bool success = hap_generator.add_haplotype_block(region, chrom, gen_hap_alns, vcf_alleles, &model);           // :462
+      if (success) success = hap_generator.fuse_haplotype_blocks(chrom);                                            // :471
+      const auto t1 = std::chrono::steady_clock::now();
+      if (rep > 0){ seconds += std::chrono::duration<double>(t1 - t0).count(); continue; }
+      const std::string& msg = hap_generator.failure_msg();
+      const int code = success ? 0 : msg == "Haplotype blocks are too near to the chromosome ends" ? 1 : msg == "No spanning alignments" ? 2 : 9;
+      fprintf(out, "case %s status %d %s\n", name.c_str(), code, msg.c_str());
+      if (success){
+        const std::vector<HapBlock*> blocks = hap_generator.get_haplotype_blocks();
+        for (size_t b = 0; b < blocks.size(); b++){
+          fprintf(out, "block %zu %d %d %d", b, blocks[b]->start(), blocks[b]->end(), blocks[b]->num_options());
+          for (int o = 0; o < blocks[b]->num_options(); o++) fprintf(out, " %s", blocks[b]->get_seq(o).empty() ? "-" : blocks[b]->get_seq(o).c_str());
+          fprintf(out, "\n");
+        }
+      }
+    }
+  }
+  if (time_reps > 0) fprintf(out, "time %.6f %d %d\n", seconds, n_cases, time_reps);
+  return 0;
+}
+
 extern "C" int flow_main(int argc, char** argv){
   LocusParams lp; lp.seed = 1; lp.n_samples = 10; lp.reads_per_sample = 9; lp.period = 4; lp.recompute = false; lp.reassemble = true; lp.nw = false; lp.dump_inputs = NULL;
   const char* out_path = NULL; int n_loci = 0, n_threads = 1; bool use_stream = false, profile = false;
-  const char* debruijn_cases = NULL;
+  const char* debruijn_cases = NULL, *hapgen_cases = NULL; int time_reps = 0;
   for (int i = 1; i < argc; i++){
     if (!strcmp(argv[i], "--seed")) lp.seed = strtoull(argv[++i], NULL, 10);
     else if (!strcmp(argv[i], "--samples")) lp.n_samples = atoi(argv[++i]);
@@ -381,6 +460,8 @@ extern "C" int flow_main(int argc, char** argv){
     else if (!strcmp(argv[i], "--threads")) n_threads = atoi(argv[++i]);    // ... one SeqStutterGenotyper per host thread at a time
     else if (!strcmp(argv[i], "--profile")) profile = true;                 // many-loci form: where the host threads' time went (MI355X build: library and adapter buckets)
     else if (!strcmp(argv[i], "--debruijn-cases")) debruijn_cases = argv[++i];  // the reference's DebruijnGraph on cases of a text file (see run_debruijn_cases)
+    else if (!strcmp(argv[i], "--hapgen-cases")) hapgen_cases = argv[++i];      // the reference's HaplotypeGenerator on cases of a text file (see run_hapgen_cases)
+    else if (!strcmp(argv[i], "--time")) time_reps = atoi(argv[++i]);           // with --hapgen-cases: build every case that many times more and report the seconds
     else if (!strcmp(argv[i], "--stream")) use_stream = true;               // MI355X build: alignment rounds of the loci in flight share batches
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
@@ -388,6 +469,13 @@ extern "C" int flow_main(int argc, char** argv){
     FILE* f = out_path ? fopen(out_path, "w") : stdout;
     if (!f){ perror(out_path); return 2; }
     const int rc = run_debruijn_cases(debruijn_cases, f);
+    if (out_path) fclose(f);
+    return rc;
+  }
+  if (hapgen_cases){
+    FILE* f = out_path ? fopen(out_path, "w") : stdout;
+    if (!f){ perror(out_path); return 2; }
+    const int rc = run_hapgen_cases(hapgen_cases, f, time_reps);
     if (out_path) fclose(f);
     return rc;
   }
