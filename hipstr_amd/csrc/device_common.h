@@ -5,12 +5,11 @@
 
 #include "layout.h"
 #include "float_lse.h"
+#include "flank_sweep_step.h"      // T_I2I, T_I2M, T_D2D, T_D2M and the flank sweeps' row step
 
 namespace {
 
 constexpr double IMP = HS_IMPOSSIBLE;
-constexpr double T_I2I = -1.0, T_I2M = -0.4586751453870818910216436;   // AlignmentModel.h:7-10
-constexpr double T_D2D = -1.0, T_D2M = -0.4586751453870818910216436;
 
 // ------------------------------------------------------------------ wave primitives
 __device__ __forceinline__ int shr1(int old, int src){

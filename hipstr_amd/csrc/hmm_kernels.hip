@@ -94,9 +94,10 @@ __global__ void __launch_bounds__(64) hs_col_kernel(const hs_dev_t* __restrict__
 // The banded sweep above runs the bands of an item one after the other and hands the boundary row of every column from band to band
 // through an HBM scratch row (1 KB per column per hand-over: ~150 KB per item at the north-star shape, the largest traffic of the
 // whole pass).  Here the HS_COOP_WAVES wavefronts of a workgroup take one band each and run them as a pipeline, wavefront w working
-// on column t - w at step t: the boundary of a column travels through a two-slot LDS ring (16 B x 64 lanes), a workgroup barrier
-// per step keeps the wavefronts one column apart, and an item takes nmax + nb - 1 steps instead of nb * nmax.  Fewer rows per
-// wavefront also means the row constants fit the SGPR file and the state fits 3 wavefronts per SIMD.  Same cells, same operation
+// on column t - w at step t: the boundary of a column travels through an LDS ring (16 B x 64 lanes per column), a workgroup barrier
+// per step keeps the wavefronts one column apart (leading flanks; the trailing flanks' bands wait on counters instead: below), and an
+// item takes nmax + nb - 1 steps instead of nb * nmax.  Fewer rows per wavefront also means the state — (M, I) per row — fits 4
+// wavefronts per SIMD (HS_COOP_OCC; the leading flanks keep 3, HS_LEAD_OCC).  Same cells, same operation
 // order per cell: bit-identical to the serial sweep.  Blocks with more rows than HS_COOP_WAVES x HS_COOP_ROWS run in rounds of
 // HS_COOP_WAVES bands, the boundary between rounds going through the scratch row as before.
 #ifndef HS_COOP_WAVES
@@ -106,7 +107,7 @@ __global__ void __launch_bounds__(64) hs_col_kernel(const hs_dev_t* __restrict__
 #define HS_COOP_ROWS 15
 #endif
 #ifndef HS_COOP_OCC
-#define HS_COOP_OCC 3         // wavefronts per SIMD the register allocation aims at
+#define HS_COOP_OCC 4         // wavefronts per SIMD the register allocation aims at: 15 rows x (M, I) + operands fit 128 registers
 #endif
 
 // LDS operations of this wavefront are complete (and its global stores, when it hands a boundary over through memory), then the
@@ -127,6 +128,9 @@ typedef __attribute__((address_space(3))) double* hs_lds_d2;
 // ds_read_b128, issued two rows ahead of its use: the LDS pipe is idle in this kernel, the VALU is what binds.  The loads are inline
 // assembly (volatile: not hoisted back out of the column loop into registers) with their own s_waitcnt; LDS operations of a wavefront
 // complete in order, so the compiler's own counts for the ring accesses only ever wait longer, never less.
+#ifndef HS_LEAD_OCC
+#define HS_LEAD_OCC 3         // the leading flanks' own: a chain of few items per workgroup, a barrier per column — a fourth workgroup per CU only slows the hand-overs (3.75 against 4.0 ms per NS pass)
+#endif
 #ifndef HS_COOP_LDS_CONSTS
 #define HS_COOP_LDS_CONSTS 1
 #endif
@@ -135,6 +139,9 @@ typedef __attribute__((address_space(3))) double* hs_lds_d2;
 #endif
 #ifndef HS_COOP_LDS_DEPTH
 #define HS_COOP_LDS_DEPTH 3       // rows between a pair's request and its use (<= 6)
+#endif
+#ifndef HS_COOP_LDS_DEPTH_TALL
+#define HS_COOP_LDS_DEPTH_TALL 2  // the same for bands of 14 and 15 rows: a third pair in flight does not fit 128 registers without scratch in the column loop
 #endif
 typedef double hs_d2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ hs_d2v kload(uint32_t addr, int off){      // off: a constant once the row loop is unrolled
@@ -179,7 +186,7 @@ __device__ unsigned long long g_ft[1024][8][6];
 #define HS_FT_NOW() 0ull
 #endif
 // (the counters' addresses and values are wave-uniform: they stay in scalar registers and pass through short-lived vector registers inside
-// the statement — the sweep has none to spare: 15 rows x (M, I, D) + constants fill the 168 a wavefront may have at three per SIMD)
+// the statement — the sweep has none to spare: 15 rows x (M, I) + operands fill the 128 a wavefront may have at four per SIMD)
 __device__ __forceinline__ int prog_read(uint32_t addr_uniform){
   int v;
   asm volatile("v_mov_b32 %0, %1\n\tds_read_b32 %0, %0\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "s"(addr_uniform) : "memory");
@@ -189,6 +196,19 @@ __device__ __forceinline__ void prog_write(uint32_t addr_uniform, int v_uniform)
   int t0, t1;
   asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3\n\tds_write_b32 %0, %1" : "=&v"(t0), "=&v"(t1) : "s"(addr_uniform), "s"(v_uniform) : "memory");
 }
+// The sweep of one band (NR rows from row0) over the nmax columns of an item: ONE top-down pass per column, two values per row.
+//   state      Mp[r], Ip[r] = M[r][j], I[r][j] going into pass j (column 0: M = e[r][0], I = blc[0], HapAligner.cpp:123-126)
+//   pass j     takes the boundary (M, D)[row0-1][j] — the band above's through the ring or the HBM scratch, the block's first row for the
+//              first band — and walks the rows once (hs_fused_row_step, flank_sweep_step.h): D[r][j], max(I[r][j], D[r-1][j]), I[r][j+1] and
+//              M[r][j+1], the 11 operations per cell of the reference's recurrence on the same operands; (M, D)[last row][j] is what it
+//              hands to the band below.  It consumes column j + 1's operands (emissions: written to the LDS table before the rows; blc[j+1];
+//              the first row's M[0][j+1]), so the column prefetch runs two columns ahead.
+//   stores     M of a read's last column n - 1 is complete after pass n - 2: there lt[row0 + r] (and LEAD: rowp[n-1]) are stored — for a side
+//              of one column right after the initialisation; lt[0] and side_prob where the first row's M of column n - 1 is formed.
+//   last pass  j == nmax - 1 has no column to produce: it keeps its hand-over and its counter / barrier step (every wavefront of the
+//              workgroup counts nmax columns per sweep, a wavefront without a band included: coop_rounds) and skips its rows.
+// (Until this form a column was walked twice — M bottom-up in place, then D, Q = max(I, D above) and the next I top-down — with Q kept per
+// row between the walks: three values per row, 168 registers, three wavefronts per SIMD.)  Same operations on the same operands: bit-identical.
 template <int NR, bool FIRST, bool LAST, bool LEAD, bool EL>
 __device__ __forceinline__ void band_sweep_coop(const hs_dev_t& d, int lane, bool live, int n, int nmax, const double* __restrict__ col,
                                                 const hs_row_t* __restrict__ rows, int row0, int c0, const double* __restrict__ mr,
@@ -212,9 +232,14 @@ __device__ __forceinline__ void band_sweep_coop(const hs_dev_t& d, int lane, boo
     hc[r] = meta & 0xff;                                               // (EL: not used — the table's writers compare)
     if (!KL){ m2m[KL ? 0 : r] = uni(d.m2m[(meta >> 8) & 15]); m2i[KL ? 0 : r] = uni(d.m2i[(meta >> 8) & 15]); }
   }
-  double Mp[NR], Qp[NR], Ip[NR];          // per row: M[r][j], Q[r] = max(I[r][j], D[r-1][j]) and — ahead by a column — I[r][j+1]
-  double nx_blc = col[0], nx_blw = col[1], nx_rd = col[2];
+  double Mp[NR], Ip[NR];                  // per row: M[r][j] and I[r][j] going into pass j, M[r][j+1] and I[r][j+1] coming out of it
+  // Column operands: pass j consumes column j + 1's (c1_*: the emissions M[.][j+1] takes, blc[j+1] for I[.][j+1], row 0's M[0][j+1]) and has
+  // column j + 2's in flight (nx_*).  A lane past its own read end keeps re-reading its last column: what it computes is never stored.
+  const int jc1 = max(min(1, n - 1), 0);
+  const double blc0 = col[0], blw0 = col[1]; const int rd0 = (int)col[2];
+  double nx_blc = col[3*jc1], nx_blw = col[3*jc1+1], nx_rd = col[3*jc1+2];
   double nx_mr = 0.0;
+  if (FIRST && !LEAD) nx_mr = mr[jc1 - 1 >= 0 ? jc1 - 1 : 0];
   // EL: table of two column parities x (64 / npad reads) x HS_ETAB_ROWS entries; lane `slot` of a read writes the entry of row `slot`
   // (npad == 8: and of row slot + 8), comparing the column's read base with that row's base
   static_assert(!EL || NR <= 16, "rows of a band in the emission table");
@@ -228,9 +253,29 @@ __device__ __forceinline__ void band_sweep_coop(const hs_dev_t& d, int lane, boo
     if (e_slot < NR) etab[par*HS_ETAB_PAR + e_wr] = (rdb == (e_char & 0xff)) ? blc : blw;
     if (NR > 8 && npad == 8 && e_slot + 8 < NR) etab[par*HS_ETAB_PAR + e_wr + 8] = (rdb == (e_char >> 8)) ? blc : blw;
   };
-  if (EL){ e_write(0, nx_rd, nx_blc, nx_blw); wave_lds_sync(); }
-  double diagM = 0;
+  if (EL){ e_write(0, (double)rd0, blc0, blw0); wave_lds_sync(); }
+  // Column 0 (HapAligner.cpp:123-126): M = e, I = blc; its D is formed by pass 0 like every other column's.
+#pragma unroll
+  for (int r = 0; r < NR; r++){
+    double e;
+    if (EL){ e = eload(e_rd, 8*r); ewait1<0>(e); }      // column 0: parity 0
+    else e = (rd0 == hc[r]) ? blc0 : blw0;
+    Mp[r] = e; Ip[r] = blc0;
+  }
   double pre = 0.0;                              // LEAD: left_prob, a strictly sequential sum in the reference
+  double topM = 0.0;                             // FIRST: M of the block's first row in the column the next pass starts from
+  if (FIRST){
+    const double e0 = (rd0 == c0) ? blc0 : blw0;
+    if (LEAD){ topM = e0 + pre; pre += blc0; if (n == 1 && live) *side_out = pre; }      // side_prob: the whole side hangs off the haplotype
+    else topM = e0;
+    if (n == 1 && live) lt[0] = topM;
+  }
+  // M of a read's last column, n - 1, is complete after pass n - 2 — for a side of one column, here
+  if (n == 1 && live){
+#pragma unroll
+    for (int r = 0; r < NR; r++) lt[row0 + r] = Mp[r];
+    if (LAST && LEAD) rowp[0] = Mp[NR - 1];
+  }
   const uint32_t a_me = (uint32_t)uni((int)(uintptr_t)(prog + w)), a_top = (uint32_t)uni((int)(uintptr_t)(prog + (w > 0 ? w - 1 : 0))), a_bot = (uint32_t)uni((int)(uintptr_t)(prog + w + 1));
   // base: the columns this workgroup's bands had finished before this sweep — the counters are never reset where sweeps follow each other
   // without a barrier (hs_trail_kernel_coop); a column's number, its ring slot and the values waited for are base + j
@@ -240,12 +285,15 @@ __device__ __forceinline__ void band_sweep_coop(const hs_dev_t& d, int lane, boo
   // barrier wakes its waiters faster than a polled counter: 3.8 against 4.8 ms per NS pass): the bands meet at a barrier after every
   // column, band w one column behind band w - 1, as until round 5; the counters are not used.
   constexpr bool BAR = LEAD;
-#pragma unroll 1       // (left to itself the compiler peels and unrolls the column loop: 2000 scratch operations in a kernel that has 168 registers and needs them all)
+  // nmax passes, every one with its hand-over: the counters and the barrier steps count columns, the same totals in every wavefront of
+  // the workgroup.  The last pass (j == nmax - 1, wave-uniform) skips the row loop — column nmax does not exist, and nothing reads the
+  // D of column nmax - 1 — and hands the boundary it received straight on: the band below skips its rows in that pass too.
+#pragma unroll 1       // (left to itself the compiler peels and unrolls the column loop)
   for (int t = 0; t < (BAR ? nsteps : nmax); t++){
     const int j = BAR ? t - w : t;
     if (!BAR || (j >= 0 && j < nmax)){
-      const double blcj = nx_blc, blwj = nx_blw; const int rdj = (int)nx_rd;
-      const double cur_mr = nx_mr;
+      const double c1_blc = nx_blc, c1_blw = nx_blw; const int c1_rd = (int)nx_rd;
+      const double c1_mr = nx_mr;
       double2 cur_b = make_double2(0.0, 0.0);
       if (!FIRST){
         if (topg){
@@ -254,6 +302,9 @@ __device__ __forceinline__ void band_sweep_coop(const hs_dev_t& d, int lane, boo
           if (!BAR && wlast >= 0 && top_seen <= base - nmax + j)
             while ((top_seen = prog_read((uint32_t)uni((int)(uintptr_t)(prog + wlast)))) <= base - nmax + j) __builtin_amdgcn_s_sleep(1);
           cur_b = *(const double2*)(bnd + ((size_t)j*64 + lane)*2);
+          // (consumed here, in front of the column prefetch below: left pending, the pair's first use after the prefetch makes every
+          //  column of every band wait for its own prefetch — the wait is placed where the two boundary paths have joined)
+          asm volatile("" : "+v"(cur_b.x), "+v"(cur_b.y));
         } else {
           if (!BAR && top_seen <= base + j){
             const unsigned long long t0_ = HS_FT_NOW(); int spins_ = 0;
@@ -263,91 +314,78 @@ __device__ __forceinline__ void band_sweep_coop(const hs_dev_t& d, int lane, boo
           const int e = 2*(((base + j) & (HS_RING - 1))*64 + lane); cur_b = make_double2(lds_top[e], lds_top[e + 1]);
         }
       }
+      const bool rows_pass = j + 1 < nmax;          // wave-uniform
       {
-        const int jn = min(j + 1, n - 1);           // a lane past its own read end keeps re-reading its last column
+        const int jn = max(min(j + 2, n - 1), 0);      // (also in the last pass, where nothing takes it: no second copy of the operands for a pass without a prefetch)
         nx_blc = col[3*jn]; nx_blw = col[3*jn+1]; nx_rd = col[3*jn+2];
         if (FIRST && !LEAD) nx_mr = mr[jn - 1 >= 0 ? jn - 1 : 0];
       }
       double upM, upD;
       if (FIRST){
-        const double e0 = (rdj == c0) ? blcj : blwj;
-        if (LEAD){
-          upM = e0 + pre;
-          pre += blcj;
-          if (j == n-1 && live) *side_out = pre;                     // side_prob: the whole side hangs off the haplotype
-        } else upM = (j == 0) ? e0 : e0 + cur_mr;
-        upD = IMP;
-        if (j == n-1 && live) lt[0] = upM;
+        upM = topM; upD = IMP;
+        if (rows_pass){      // M of the block's first row in column j + 1 (HapAligner.cpp:33-42 / :130-139)
+          const double e0 = (c1_rd == c0) ? c1_blc : c1_blw;
+          if (LEAD){
+            topM = e0 + pre;
+            pre += c1_blc;
+            if (j + 2 == n && live) *side_out = pre;
+          } else topM = e0 + c1_mr;
+          if (j + 2 == n && live) lt[0] = topM;
+        }
       } else { upM = cur_b.x; upD = cur_b.y; }
-      const double topM = upM;
-      // Round 6: 11 instead of 12 FP64 operations per cell.  I[r][j+1] = blc[j+1] + max(M[r-1][j] + T_I2M, I[r][j] + T_I2I) and
-      // D[r][j] = max(M[r-1][j] + T_D2M, D[r-1][j] + T_D2D) start from the SAME sum — T_I2M and T_D2M are one constant
-      // (AlignmentModel.h:7-10) — which the sweep used to form twice, once per column.  So the D pass of column j also forms row r's I of
-      // column j + 1 (the next column's blc is already here: it is prefetched at the top of the column) and, before I[r][j] is
-      // overwritten, Q[r] = max(I[r][j], D[r-1][j]) — what M[r][j+1] takes its second addend from.  D itself is not kept across columns any
-      // more (only Q needs it): the state stays three values per row.  Same operations on the same operands, one of them shared:
-      // bit-identical.
-      auto dstep = [&](int r, double Icur){      // row r of the top-down pass; Icur = I[r][j]; upM / upD = M / D of the row above in this column
-        const double X = upM + T_D2M;
-        const double nD = fmax(X, upD + T_D2D);
-        Qp[r] = fmax(Icur, upD);
-        Ip[r] = nx_blc + fmax(X, Icur + T_I2I);
-        upM = Mp[r]; upD = nD;
-      };
-      if (j == 0){
-#pragma unroll
-        for (int r = 0; r < NR; r++){           // first read column (HapAligner.cpp:123-126): M = e, I = blc, D from the row above
-          double e;
-          if (EL){ e = eload(e_rd, 8*r); ewait1<0>(e); }      // column 0: parity 0
-          else e = (rdj == hc[r]) ? blcj : blwj;
-          Mp[r] = e;
-          dstep(r, blcj);
-        }
-      } else {
-        // M bottom-up in place (row r takes M[r-1] of the previous column), then D, Q and the next column's I top-down through the new M
+      if (rows_pass){
+        const int par = (j + 1) & 1;
+        if (EL) e_write(par, (double)c1_rd, c1_blc, c1_blw);       // column j + 1's emissions, which this pass's rows read back (a wavefront's LDS operations execute in order)
         if (KL){
-          // rows NR-1 .. 0; the pair of row r (and, EL, its emission) is requested while row r + KD is computed
-          constexpr int KD = HS_COOP_LDS_DEPTH, KM = KD + 1, PER = EL ? 2 : 1;       // PER: requests per row
+          // rows 0 .. NR-1; the pair of row r (and, EL, its emission) is requested while row r - KD is computed, and has arrived when
+          // row r - 1 is: that row forms this row's sum of its own M and this row's m2m (flank_sweep_step.h)
+          constexpr int KD = NR >= 14 ? HS_COOP_LDS_DEPTH_TALL : HS_COOP_LDS_DEPTH, KM = KD + 1, PER = EL ? 2 : 1;       // PER: requests per row
+          static_assert(KD >= 2, "a row reads the pair of the row below");
           hs_d2v kq[KM]; double eq[EL ? KM : 1];
-          const uint32_t e_col = EL ? e_rd + (uint32_t)(8*HS_ETAB_PAR)*(uint32_t)(j & 1) : 0;
+          const uint32_t e_col = EL ? e_rd + (uint32_t)(8*HS_ETAB_PAR)*(uint32_t)par : 0;
 #pragma unroll
-          for (int a = 0; a < KD; a++) if (NR - 1 - a >= 0){
-            const int r = NR - 1 - a >= 0 ? NR - 1 - a : 0;
-            kq[r % KM] = kload(kaddr, 16*r);
-            if (EL) eq[EL ? r % KM : 0] = eload(e_col, 8*r);
+          for (int a = 0; a < KD; a++) if (a < NR){
+            kq[a % KM] = kload(kaddr, 16*a);
+            if (EL) eq[EL ? a % KM : 0] = eload(e_col, 8*a);
           }
+          {   // row 0's pair
+            constexpr int young0 = ((KD < NR ? KD : NR) - 1) * PER;
+            if (EL) ewait<young0>(eq[0], kq[0]); else kwait<young0>(kq[0]);
+          }
+          const double lastM = Mp[NR - 1];
+          double X = upM + T_D2M, A = upM + kq[0].x;
 #pragma unroll
-          for (int r = NR - 1; r >= 0; r--){
-            if (r >= KD){
-              kq[(r - KD) % KM] = kload(kaddr, 16*(r - KD));
-              if (EL) eq[EL ? (r - KD) % KM : 0] = eload(e_col, 8*(r - KD));
+          for (int r = 0; r < NR; r++){
+            if (r + KD < NR){
+              kq[(r + KD) % KM] = kload(kaddr, 16*(r + KD));
+              if (EL) eq[EL ? (r + KD) % KM : 0] = eload(e_col, 8*(r + KD));
             }
-            const int young = (r >= KD ? KD : r) * PER;             // requests issued after this row's
+            const int rb = r + 1 < NR ? r + 1 : r;                                  // the row whose requests this row waits for
+            const int young = ((r + KD < NR ? r + KD : NR - 1) - rb) * PER;         // requests issued after that row's
             if (EL) switch (young){
-              case 0: ewait<0>(eq[EL ? r % KM : 0], kq[r % KM]); break; case 2: ewait<2>(eq[EL ? r % KM : 0], kq[r % KM]); break;
-              case 4: ewait<4>(eq[EL ? r % KM : 0], kq[r % KM]); break; case 6: ewait<6>(eq[EL ? r % KM : 0], kq[r % KM]); break;
-              case 8: ewait<8>(eq[EL ? r % KM : 0], kq[r % KM]); break; case 10: ewait<10>(eq[EL ? r % KM : 0], kq[r % KM]); break;
-              default: ewait<12>(eq[EL ? r % KM : 0], kq[r % KM]); break;
+              case 0: ewait<0>(eq[EL ? rb % KM : 0], kq[rb % KM]); break; case 2: ewait<2>(eq[EL ? rb % KM : 0], kq[rb % KM]); break;
+              case 4: ewait<4>(eq[EL ? rb % KM : 0], kq[rb % KM]); break; case 6: ewait<6>(eq[EL ? rb % KM : 0], kq[rb % KM]); break;
+              case 8: ewait<8>(eq[EL ? rb % KM : 0], kq[rb % KM]); break; default: ewait<10>(eq[EL ? rb % KM : 0], kq[rb % KM]); break;
             } else switch (young){
-              case 0: kwait<0>(kq[r % KM]); break; case 1: kwait<1>(kq[r % KM]); break; case 2: kwait<2>(kq[r % KM]); break;
-              case 3: kwait<3>(kq[r % KM]); break; case 4: kwait<4>(kq[r % KM]); break; case 5: kwait<5>(kq[r % KM]); break;
-              default: kwait<6>(kq[r % KM]); break;
+              case 0: kwait<0>(kq[rb % KM]); break; case 1: kwait<1>(kq[rb % KM]); break; case 2: kwait<2>(kq[rb % KM]); break;
+              case 3: kwait<3>(kq[rb % KM]); break; case 4: kwait<4>(kq[rb % KM]); break; default: kwait<5>(kq[rb % KM]); break;
             }
-            const double e = EL ? eq[EL ? r % KM : 0] : ((rdj == hc[r]) ? blcj : blwj);
-            const double dM = (r == 0) ? diagM : Mp[r > 0 ? r-1 : 0];
-            Mp[r] = e + fmax(dM + kq[r % KM].x, Qp[r] + kq[r % KM].y);
+            const double e = EL ? eq[EL ? r % KM : 0] : ((c1_rd == hc[r]) ? c1_blc : c1_blw);
+            hs_fused_row_step(X, A, upD, Mp[r], Ip[r], e, c1_blc, kq[r % KM].y, r + 1 < NR, kq[rb % KM].x);
           }
+          upM = lastM;
         } else {
+          const double lastM = Mp[NR - 1];
+          double X = upM + T_D2M, A = upM + m2m[0];
 #pragma unroll
-        for (int r = NR - 1; r >= 0; r--){
-          const double e = (rdj == hc[r]) ? blcj : blwj;
-          const double dM = (r == 0) ? diagM : Mp[r > 0 ? r-1 : 0];
-          Mp[r] = e + fmax(dM + m2m[KL ? 0 : r], Qp[r] + m2i[KL ? 0 : r]);
+          for (int r = 0; r < NR; r++){
+            const double e = (c1_rd == hc[r]) ? c1_blc : c1_blw;
+            hs_fused_row_step(X, A, upD, Mp[r], Ip[r], e, c1_blc, m2i[KL ? 0 : r], r + 1 < NR, m2m[KL || r + 1 >= NR ? 0 : r + 1]);
+          }
+          upM = lastM;
         }
-        }
-#pragma unroll
-        for (int r = 0; r < NR; r++) dstep(r, Ip[r]);
       }
+      // (upM, upD) = (M, D) of the band's last row in column j
       if (!LAST){
         if (botg) *(double2*)(bnd + ((size_t)j*64 + lane)*2) = make_double2(upM, upD);
         else {
@@ -358,7 +396,7 @@ __device__ __forceinline__ void band_sweep_coop(const hs_dev_t& d, int lane, boo
           }
           const int e = 2*(((base + j) & (HS_RING - 1))*64 + lane); lds_bot[e] = upM; lds_bot[e + 1] = upD;
         }
-      } else if (LEAD){ if (j < n && live) rowp[j] = upM; }
+      } else if (LEAD){ if (j + 1 < n && live) rowp[j] = upM; }
       // this column is done: its boundary (if a band below reads it from the ring) is stored, and the ring slot the band above filled for it
       // has been read — both in front of the counter's store, and a wavefront's LDS operations execute in order
       if (!BAR && !(FIRST && LAST)){
@@ -366,11 +404,10 @@ __device__ __forceinline__ void band_sweep_coop(const hs_dev_t& d, int lane, boo
         else asm volatile("" ::: "memory");
         prog_write(a_me, base + j + 1);
       }
-      if (EL) e_write((j + 1) & 1, nx_rd, nx_blc, nx_blw);       // the next column's emissions (its values were requested at the top of this one)
-      diagM = topM;                              // top boundary of this column = diagonal of the band's first row next column
-      if (j == n-1 && live){
+      if (j + 2 == n && live){                   // this pass completed the last read column of this lane's read
 #pragma unroll
-        for (int r = 0; r < NR; r++) lt[row0 + r] = Mp[r];           // last read column of this lane's read
+        for (int r = 0; r < NR; r++) lt[row0 + r] = Mp[r];
+        if (LAST && LEAD) rowp[n - 1] = Mp[NR - 1];
       }
     }
     if (BAR) coop_barrier(botg);
@@ -424,7 +461,8 @@ __device__ __forceinline__ void coop_rounds(const hs_dev_t& d, int w, int lane, 
       const int row0 = 1 + b*nr_base + min(b, nr_rem);
       const bool first = (b == 0), last = (b + 1 == nbands);
       const bool topg = (w == 0) && (g > 0), botg = (w + 1 == nb_round) && !last;
-      hs_lds_cd2 lds_top = (hs_lds_cd2)ring[w > 0 ? w - 1 : 0]; hs_lds_d2 lds_bot = (hs_lds_d2)ring[w];
+      // ring[w]: band w -> band w + 1.  The round's last band hands over through the HBM scratch or not at all: W - 1 slot arrays
+      hs_lds_cd2 lds_top = (hs_lds_cd2)ring[w > 0 ? w - 1 : 0]; hs_lds_d2 lds_bot = (hs_lds_d2)ring[w < W - 1 ? w : W - 2];
       hs_lds_d2 ktab = (hs_lds_d2)ktabs[w];
       hs_lds_d2 etab = EL ? (hs_lds_d2)etabs[w] : (hs_lds_d2)ktabs[w];
       switch (nr){
@@ -454,6 +492,8 @@ __device__ __forceinline__ void coop_rounds(const hs_dev_t& d, int w, int lane, 
 //   * every wavefront reads the record of item k when it gets there, sweeps, and goes on to item k + 1 without a barrier: the bands' column
 //     counters count through the items (coop_rounds, gcol), so the first band starts the next item while the last is still three columns
 //     behind in this one — the pipeline never drains.
+// LDS: ring[W-1] (band w -> band w + 1; the round's last band hands over through HBM or not at all) + tables + records = 38 536 B for
+// <15,4>: four workgroups per CU, as the 128 registers allow.
 // No barrier is left, not even between the rounds of a flank deeper than one round: the last band of a round stores its boundary in the
 // workgroup's HBM scratch, drains the store and only then publishes the column in its counter (prog[W-1]); the next round's first band
 // waits for that counter column by column and reads the boundary from the scratch (coop_rounds with gcol, band_sweep_coop topg / wlast).
@@ -469,7 +509,8 @@ template <int R, int W, int OCC>
 __global__ void __launch_bounds__(64*W, OCC) hs_trail_kernel_coop(const hs_dev_t* __restrict__ dp, int item_begin, int item_end, int chunk){
   const hs_dev_t& d = *dp;
   const int lane = threadIdx.x & 63, w = uni((int)(threadIdx.x >> 6));
-  __shared__ double2 ring[W][HS_RING*64];
+  static_assert(W >= 2, "bands per round");
+  __shared__ double2 ring[W - 1][HS_RING*64];      // band w -> band w + 1
   __shared__ int s_prog[W + 1];             // columns finished per band wavefront (band_sweep_coop); [W]: never written, the last band's lower neighbour
   __shared__ int s_q[2 + W];                // [0] records published; [2 + w] items whose record wavefront w has read
   __shared__ double2 ktabs[W][24];          // per wavefront: (m2m, m2i) of its band's rows (HS_COOP_LDS_CONSTS)
@@ -580,7 +621,8 @@ template <int R, int W, int OCC>
 __global__ void __launch_bounds__(64*W, OCC) hs_lead_kernel_coop(const hs_dev_t* __restrict__ dp, int item_begin, int item_end, int chunk){
   const hs_dev_t& d = *dp;
   const int lane = threadIdx.x & 63, w = uni((int)(threadIdx.x >> 6));
-  __shared__ double2 ring[W][HS_RING*64];
+  static_assert(W >= 2, "bands per round");
+  __shared__ double2 ring[W - 1][HS_RING*64];      // band w -> band w + 1
   __shared__ int s_prog[W + 1];                 // columns finished per band wavefront (band_sweep_coop); [W]: never written, the last band's lower neighbour
   __shared__ double2 ktabs[W][24];          // per wavefront: (m2m, m2i) of its band's rows (HS_COOP_LDS_CONSTS)
   __shared__ int s_item;
@@ -3009,7 +3051,7 @@ extern "C" void hs_launch_lead2(unsigned n_active, unsigned n_wavefronts, hipStr
     case HS_FLANK_LATENCY:
       hipLaunchKernelGGL((hs_lead_kernel_coop<HS_LAT_ROWS, HS_LAT_WAVES, 2>), dim3(std::max(1u, std::min(n_wavefronts, 256u))), dim3(64*HS_LAT_WAVES), 0, st, dp, item_begin, item_end, chunk); break;
     default:
-      hipLaunchKernelGGL((hs_lead_kernel_coop<HS_COOP_ROWS, HS_COOP_WAVES, HS_COOP_OCC>), dim3(std::max(1u, std::min(n_wavefronts, 256u*HS_COOP_OCC*4/HS_COOP_WAVES))), dim3(64*HS_COOP_WAVES), 0, st, dp, item_begin, item_end, chunk); break;
+      hipLaunchKernelGGL((hs_lead_kernel_coop<HS_COOP_ROWS, HS_COOP_WAVES, HS_LEAD_OCC>), dim3(std::max(1u, std::min(n_wavefronts, 256u*HS_LEAD_OCC*4/HS_COOP_WAVES))), dim3(64*HS_COOP_WAVES), 0, st, dp, item_begin, item_end, chunk); break;
   }
 }
 extern "C" void hs_launch_trail(unsigned n_wavefronts, hipStream_t st, const hs_dev_t* dp, int item_begin, int item_end, int chunk, int max_cols, int max_rows){

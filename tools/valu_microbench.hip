@@ -1,6 +1,7 @@
 // valu_microbench.hip — issue cost of the instruction classes the HMM kernels are made of, measured on the device (gfx950):
 // a wavefront runs long straight-line runs of ONE instruction over 8 independent register chains (no dependent-issue stalls) and
-// times them with s_memtime; 1, 2 and 4 wavefronts per SIMD show whether the cost is issue (scales) or latency (hides).
+// times them with s_memtime; 1, 2, 3 and 4 wavefronts per SIMD show whether the cost is issue (scales) or latency (hides) — 3 and 4 are
+// what a kernel of 168 or of 128 registers runs at: the ratio is what the flank sweeps' fourth wavefront can win.
 //   hipcc --offload-arch=gfx950 -O2 tools/valu_microbench.hip -o tools/valu_microbench && tools/valu_microbench > profiles/rNN_valu_microbench.json
 // The numbers feed tools/sq_counters.py (pipe occupancy from the ISA mix) instead of an assumed 4 cycles for everything.
 #include <hip/hip_runtime.h>
@@ -123,12 +124,13 @@ int main(){
   }
   const double ratio = (double)sclk_khz * 1e3 / memtime_hz;     // shader cycles (at the nominal clock) per s_memtime tick
   printf("{\n \"device_clock_khz\": %d, \"wall_clock_attr_khz\": %d, \"memtime_hz_measured\": %.4g, \"cycles_per_tick\": %.4f, \"note\": \"cycles of ONE SIMD per wave64 instruction = slowest wavefront's s_memtime window x (shader clock / memtime clock) / instructions issued on that SIMD in the window; 8 independent register chains, 2000 x 64 instructions per wavefront\",\n \"cycles_per_wave64_instruction\": {\n", sclk_khz, wall_khz, memtime_hz, ratio);
-  double r[N_OPS][3];
-#define RUN(OP) for (int w = 0; w < 3; w++) r[OP][w] = run<OP>(1 << w, d_out, ratio);
+  double r[N_OPS][4];
+  static const int kWaves[4] = {1, 2, 3, 4};
+#define RUN(OP) for (int w = 0; w < 4; w++) r[OP][w] = run<OP>(kWaves[w], d_out, ratio);
   RUN(OP_ADD_F64) RUN(OP_MAX_F64) RUN(OP_FMA_F64) RUN(OP_ADD_F32) RUN(OP_ADD_U32) RUN(OP_MOV_B32) RUN(OP_CNDMASK) RUN(OP_CMP_F64) RUN(OP_CMP_U32)
   RUN(OP_READLANE) RUN(OP_DPP_MOV) RUN(OP_MIX_F64_B32) RUN(OP_DS_READ_B64) RUN(OP_CVT_F32_F64) RUN(OP_AND_B32) RUN(OP_LSHL_ADD) RUN(OP_CMP_CND_VCC) RUN(OP_CND_E64) RUN(OP_ADD_F64_SGPR) RUN(OP_CMP_CND_E64)
   for (int o = 0; o < N_OPS; o++)
-    printf("  \"%s\": {\"1_wave_per_simd\": %.3f, \"2_waves_per_simd\": %.3f, \"4_waves_per_simd\": %.3f}%s\n", kNames[o], r[o][0], r[o][1], r[o][2], o + 1 < N_OPS ? "," : "");
+    printf("  \"%s\": {\"1_wave_per_simd\": %.3f, \"2_waves_per_simd\": %.3f, \"3_waves_per_simd\": %.3f, \"4_waves_per_simd\": %.3f}%s\n", kNames[o], r[o][0], r[o][1], r[o][2], r[o][3], o + 1 < N_OPS ? "," : "");
   printf(" }\n}\n");
   return 0;
 }
