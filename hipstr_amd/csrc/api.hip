@@ -79,8 +79,6 @@ namespace {
 thread_local std::string g_err;
 int fail(const std::string& m){ g_err = m; return 1; }
 
-#define HS_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
-  g_err = std::string(#call) + ": " + hipGetErrorString(e_); return 1; } } while (0)
 #define HS_HIP_NULL(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
   g_err = std::string(#call) + ": " + hipGetErrorString(e_); return NULL; } } while (0)
 
@@ -1837,6 +1835,18 @@ void hipstr::post_view(const hipstr_post_dev* pd, PostView* v){
   v->n_loci = pd->n_samples.size(); v->log_p1 = R.h.log_p1; v->log_p2 = R.h.log_p2; v->n_reads = R.n_reads; v->n_samp = R.n_samp;
   v->n_samples = pd->n_samples.data(); v->haploid = pd->haploid.data();
 }
+void hipstr::PostView::locus_tables(std::vector<int32_t>& read_off, std::vector<int32_t>& unit_off) const {
+  read_off.assign(n_loci + 1, 0); unit_off.assign(n_loci + 1, 0);
+  size_t ui = 0; int rend = 0;
+  for (size_t l = 0; l < n_loci; l++){
+    read_off[l] = rend;
+    for (int s = 0; s < n_samples[l]; s++, ui++){
+      if (s == 0) read_off[l] = units[ui].read_begin;
+      rend = units[ui].read_begin + units[ui].n_reads;
+    }
+    read_off[l+1] = rend; unit_off[l+1] = (int32_t)ui;
+  }
+}
 int hipstr::api_tables_of(Ctx* c, ApiTables* t){
   if (!c || bind(c)) return 1;
   t->int_log = c->int_log; t->qual_correct = c->qc; t->qual_error = c->qe; t->m2m = c->m2m; t->m2i = c->m2i;
@@ -2047,36 +2057,30 @@ int hipstr_post_assign(hipstr_post_dev_t* pd, const hipstr_assign_request_t* rq,
   const size_t o_args = ar.add(&h, sizeof h);
   if (ar.reserve(ctx)) return 1;
   // results, back to back (one copy home), then what stays on the device: counts and bases per locus, the first-occurrence tables
-  size_t tot = 0;
-  auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
-  const size_t r_nreq = take(4), r_best = take(n*4), r_strand = take(n*4), r_rreq = take(n*4), r_lpo = take(n*8), r_cnt = take(8*ns*4),
-               r_ph1 = take(ns*8), r_ph2 = take(ns*8), r_rr = take(cap*4), r_ra = take(cap*4);
-  const size_t res_bytes = tot;
-  const size_t d_count = take(nl*4), d_base = take(nl*4), d_tab = take((size_t)P.tab_ints*4);
-  struct Blocks { Ctx* c; hipStream_t st; char* dev = NULL; char* pin = NULL;
-                  ~Blocks(){ if (dev || pin) hipStreamSynchronize(st); if (dev) c->dev_cache.put(dev); if (pin) c->pin_cache.put(pin); } } B{ctx, R.stream};
-  B.dev = (char*)ctx->dev_cache.get(tot);
-  if (!B.dev) return 1;
-  B.pin = (char*)ctx->pin_cache.get(res_bytes);
-  if (!B.pin) return 1;
+  hipstr::ResultBlocks B;
+  const size_t r_nreq = B.take(4), r_best = B.take(n*4), r_strand = B.take(n*4), r_rreq = B.take(n*4), r_lpo = B.take(n*8), r_cnt = B.take(8*ns*4),
+               r_ph1 = B.take(ns*8), r_ph2 = B.take(ns*8), r_rr = B.take(cap*4), r_ra = B.take(cap*4);
+  B.end_results();
+  const size_t d_count = B.take(nl*4), d_base = B.take(nl*4), d_tab = B.take((size_t)P.tab_ints*4);
+  if (B.reserve(ctx, R.stream)) return 1;
   h.units = R.h.units; h.log_aln_probs = R.h.log_aln_probs; h.log_p1 = R.h.log_p1; h.log_p2 = R.h.log_p2; h.map_gt = R.h.map_gt;
   h.unit_locus = ar.at<int32_t>(o_ul); h.loci = ar.at<hs_assign_locus_t>(o_loci); h.seed = ar.at<int32_t>(o_seed);
   h.reverse = rq->reverse ? ar.at<uint8_t>(o_rev) : NULL; h.pool_index = req ? ar.at<int32_t>(o_pool) : NULL;
   h.n_units = (int32_t)R.units.size(); h.n_loci = (int32_t)nl; h.rule = rq->rule; h.cap_req = (int32_t)cap;
   h.log_half = T.log_half; h.strand_tolerance = rq->strand_tolerance == 0 ? 0.1 : rq->strand_tolerance;       // seq_stutter_genotyper.h:157
-  h.best_hap = (int32_t*)(B.dev + r_best); h.read_strand = (int32_t*)(B.dev + r_strand); h.read_req = (int32_t*)(B.dev + r_rreq);
-  h.log_phase_one = (double*)(B.dev + r_lpo); h.counters = (int32_t*)(B.dev + r_cnt); h.n_samp = (int32_t)ns;
-  h.phase1 = (double*)(B.dev + r_ph1); h.phase2 = (double*)(B.dev + r_ph2);
-  h.tab = (int32_t*)(B.dev + d_tab); h.locus_count = (int32_t*)(B.dev + d_count); h.locus_base = (int32_t*)(B.dev + d_base);
-  h.n_req = (int32_t*)(B.dev + r_nreq); h.req_read = (int32_t*)(B.dev + r_rr); h.req_allele = (int32_t*)(B.dev + r_ra);
+  h.best_hap = B.dev<int32_t>(r_best); h.read_strand = B.dev<int32_t>(r_strand); h.read_req = B.dev<int32_t>(r_rreq);
+  h.log_phase_one = B.dev<double>(r_lpo); h.counters = B.dev<int32_t>(r_cnt); h.n_samp = (int32_t)ns;
+  h.phase1 = B.dev<double>(r_ph1); h.phase2 = B.dev<double>(r_ph2);
+  h.tab = B.dev<int32_t>(d_tab); h.locus_count = B.dev<int32_t>(d_count); h.locus_base = B.dev<int32_t>(d_base);
+  h.n_req = B.dev<int32_t>(r_nreq); h.req_read = B.dev<int32_t>(r_rr); h.req_allele = B.dev<int32_t>(r_ra);
   if (pd->foreign_stream) HS_HIP(hipDeviceSynchronize());          // the posterior kernel may still be running on a stream of the caller's
   hipStream_t st = R.stream;
   if (rm_order_behind(R.h.log_aln_probs, st)) return 1;
   if (ar.send(st)) return 1;
   const hs_assign_dev_t* d_args = ar.at<hs_assign_dev_t>(o_args);
   if (req){
-    HS_HIP(hipMemsetAsync(B.dev + d_count, 0, nl*4, st));
-    if (P.tab_ints) HS_HIP(hipMemsetAsync(B.dev + d_tab, 0x7f, (size_t)P.tab_ints*4, st));
+    HS_HIP(hipMemsetAsync(B.dev<char>(d_count), 0, nl*4, st));
+    if (P.tab_ints) HS_HIP(hipMemsetAsync(B.dev<char>(d_tab), 0x7f, (size_t)P.tab_ints*4, st));
   }
   const unsigned wgs = (unsigned)hs_assign_workgroups((int64_t)R.units.size(), P.waves);
   if (P.waves == 1) hipLaunchKernelGGL(hs_assign_kernel, dim3(wgs), dim3(HS_ASSIGN_THREADS), 0, st, d_args);
@@ -2086,22 +2090,21 @@ int hipstr_post_assign(hipstr_post_dev_t* pd, const hipstr_assign_request_t* rq,
     hipLaunchKernelGGL(hs_assign_requests_kernel, dim3((unsigned)nl), dim3(HS_ASSIGN_THREADS), 0, st, d_args);
   }
   HS_HIP(hipGetLastError());
-  HS_HIP(hipMemcpyAsync(B.pin, B.dev, res_bytes, hipMemcpyDeviceToHost, st));
-  HS_HIP(hipstr::wait_stream(st));
-  const int32_t* bh = (const int32_t*)(B.pin + r_best);
+  if (B.fetch()) return 1;
+  const int32_t* bh = B.host<int32_t>(r_best);
   if (req){
-    const int32_t n_req = *(const int32_t*)(B.pin + r_nreq);
+    const int32_t n_req = *B.host<int32_t>(r_nreq);
     *out->n_req = n_req;
     if (n_req > out->cap_req){ fail("request arrays too small: *n_req holds the number needed"); return 3; }
-    memcpy(out->req_read, B.pin + r_rr, (size_t)n_req*4); memcpy(out->req_allele, B.pin + r_ra, (size_t)n_req*4);
-    memcpy(out->read_req, B.pin + r_rreq, n*4);
+    memcpy(out->req_read, B.host<char>(r_rr), (size_t)n_req*4); memcpy(out->req_allele, B.host<char>(r_ra), (size_t)n_req*4);
+    memcpy(out->read_req, B.host<char>(r_rreq), n*4);
   }
-  memcpy(out->best_hap, bh, n*4); memcpy(out->read_strand, B.pin + r_strand, n*4);
-  const double* lpo = (const double*)(B.pin + r_lpo);
+  memcpy(out->best_hap, bh, n*4); memcpy(out->read_strand, B.host<char>(r_strand), n*4);
+  const double* lpo = B.host<double>(r_lpo);
   for (size_t r = 0; r < n; r++) if (bh[r] >= 0) out->log_phase_one[r] = lpo[r];        // (skipped reads: untouched)
   int32_t* const cnt[8] = { out->n_aligned, out->n_snp, out->n_strand_one, out->n_strand_two, out->uniq_one, out->uniq_two, out->rv_uniq_one, out->rv_uniq_two };
-  for (int k = 0; k < 8; k++) memcpy(cnt[k], B.pin + r_cnt + (size_t)k*ns*4, ns*4);
-  memcpy(out->phase1_reads, B.pin + r_ph1, ns*8); memcpy(out->phase2_reads, B.pin + r_ph2, ns*8);
+  for (int k = 0; k < 8; k++) memcpy(cnt[k], B.host<char>(r_cnt) + (size_t)k*ns*4, ns*4);
+  memcpy(out->phase1_reads, B.host<char>(r_ph1), ns*8); memcpy(out->phase2_reads, B.host<char>(r_ph2), ns*8);
   return 0;
 }
 
@@ -2252,21 +2255,15 @@ int census_call(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const 
   const size_t o_args = ar.add(&h, sizeof h);
   if (ar.reserve(ctx)) return 1;
   // results, back to back (one copy home), then what stays on the device
-  size_t tot = 0;
-  auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
-  const size_t r_coff = take((nl + 1)*4), r_creq = take(cap*4), r_nsp = take(ns*4), r_nss = take(ns*4), r_called = take(no), r_spanned = take(no);
+  hipstr::ResultBlocks B;
+  const size_t r_coff = B.take((nl + 1)*4), r_creq = B.take(cap*4), r_nsp = B.take(ns*4), r_nss = B.take(ns*4), r_called = B.take(no), r_spanned = B.take(no);
   // (resident trace fields: what the check found, the candidates' offsets and byte count; their bytes last: only those in use come home)
   const size_t dev_chars = dev ? (size_t)std::min<int64_t>(out->cap_chars, td->totals[1]) : 0;
-  const size_t r_check = dev ? take(8) : 0, r_cchars = dev ? take(8) : 0, r_csoff = dev ? take((cap + 1)*4) : 0;
-  const size_t res_bytes = tot;
-  const size_t r_cseq = dev ? take(dev_chars) : 0;
-  const size_t d_count = take(nl*4), d_has = take(ns), d_rank = take(nq*4), d_ws = take((size_t)P.ws_ints*4);
-  struct Blocks { Ctx* c; hipStream_t st; char* dev = NULL; char* pin = NULL;
-                  ~Blocks(){ if (dev || pin) hipStreamSynchronize(st); if (dev) c->dev_cache.put(dev); if (pin) c->pin_cache.put(pin); } } B{ctx, R.stream};
-  B.dev = (char*)ctx->dev_cache.get(tot);
-  if (!B.dev) return 1;
-  B.pin = (char*)ctx->pin_cache.get(res_bytes);
-  if (!B.pin) return 1;
+  const size_t r_check = dev ? B.take(8) : 0, r_cchars = dev ? B.take(8) : 0, r_csoff = dev ? B.take((cap + 1)*4) : 0;
+  B.end_results();
+  const size_t r_cseq = dev ? B.take(dev_chars) : 0;
+  const size_t d_count = B.take(nl*4), d_has = B.take(ns), d_rank = B.take(nq*4), d_ws = B.take((size_t)P.ws_ints*4);
+  if (B.reserve(ctx, R.stream)) return 1;
   h.loci = ar.at<hs_census_locus_t>(o_loci);
   for (int k = 0; k < 3; k++){
     h.list[k] = ar.at<int32_t>(o_list[k]); h.n_list[k] = (int32_t)P.list[k].size();
@@ -2277,8 +2274,8 @@ int census_call(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const 
   h.seed = ar.at<int32_t>(o_seed); h.read_req = ar.at<int32_t>(o_rreq); h.read_samp = ar.at<int32_t>(o_rsamp);
   if (dev){
     h.aln_start = td->scal[3]; h.aln_stop = td->scal[4]; h.stutter_size = td->scal[0]; h.str_seq_off = td->off[1]; h.str_seq = td->arr[1];
-    h.check = (int32_t*)(B.dev + r_check); h.n_reads = (int32_t)n; h.check_offsets = td->checked ? 0 : 1; h.str_total = td->totals[1];
-    h.cand_seq_off = (int32_t*)(B.dev + r_csoff); h.cand_seq = B.dev + r_cseq; h.cand_chars = (int64_t*)(B.dev + r_cchars); h.cap_chars = out->cap_chars;
+    h.check = B.dev<int32_t>(r_check); h.n_reads = (int32_t)n; h.check_offsets = td->checked ? 0 : 1; h.str_total = td->totals[1];
+    h.cand_seq_off = B.dev<int32_t>(r_csoff); h.cand_seq = B.dev<char>(r_cseq); h.cand_chars = B.dev<int64_t>(r_cchars); h.cap_chars = out->cap_chars;
   } else {
     h.aln_start = ar.at<int32_t>(o_start); h.aln_stop = ar.at<int32_t>(o_stop); h.stutter_size = ar.at<int32_t>(o_stut);
     h.str_seq_off = ar.at<int32_t>(o_soff); h.str_seq = ar.at<char>(o_sseq);
@@ -2287,10 +2284,10 @@ int census_call(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const 
   h.o1_off = ar.at<int32_t>(o_o1off); h.o1_seq = ar.at<char>(o_o1seq);
   h.uncallable = rq->sample_uncallable ? ar.at<uint8_t>(o_unc) : NULL;
   h.min_reads = rq->min_reads == 0 ? 2 : rq->min_reads; h.min_frac = rq->min_frac == 0 ? 0.15 : rq->min_frac;      // seq_stutter_genotyper.cpp:869
-  h.cand_off = (int32_t*)(B.dev + r_coff); h.cand_req = (int32_t*)(B.dev + r_creq);
-  h.n_spanning = (int32_t*)(B.dev + r_nsp); h.n_span_stutter = (int32_t*)(B.dev + r_nss);
-  h.called = (uint8_t*)(B.dev + r_called); h.spanned = (uint8_t*)(B.dev + r_spanned);
-  h.cand_count = (int32_t*)(B.dev + d_count); h.has_read = (uint8_t*)(B.dev + d_has); h.req_rank = (int32_t*)(B.dev + d_rank); h.ws = (int32_t*)(B.dev + d_ws);
+  h.cand_off = B.dev<int32_t>(r_coff); h.cand_req = B.dev<int32_t>(r_creq);
+  h.n_spanning = B.dev<int32_t>(r_nsp); h.n_span_stutter = B.dev<int32_t>(r_nss);
+  h.called = B.dev<uint8_t>(r_called); h.spanned = B.dev<uint8_t>(r_spanned);
+  h.cand_count = B.dev<int32_t>(d_count); h.has_read = B.dev<uint8_t>(d_has); h.req_rank = B.dev<int32_t>(d_rank); h.ws = B.dev<int32_t>(d_ws);
   if (pd->foreign_stream) HS_HIP(hipDeviceSynchronize());          // the posterior kernel may still be running on a stream of the caller's
   hipStream_t st = R.stream;
   if (rm_order_behind(R.h.log_aln_probs, st)) return 1;
@@ -2301,15 +2298,14 @@ int census_call(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const 
     hipLaunchKernelGGL(hs_census_check_kernel, dim3(1), dim3(HS_CENSUS_THREADS), 0, st, d_args);
     if (h.check_offsets){
       HS_HIP(hipGetLastError());
-      HS_HIP(hipMemcpyAsync(B.pin + r_check, B.dev + r_check, 8, hipMemcpyDeviceToHost, st));
-      HS_HIP(hipstr::wait_stream(st));
-      const int bad = *(const int32_t*)(B.pin + r_check);
+      if (B.fetch(r_check, 8)) return 1;             // the check word alone, ahead of the results
+      const int bad = *B.host<int32_t>(r_check);
       if (bad & HS_CENSUS_BAD_NEGATIVE) return fail("hipstr_post_census: str_seq_off must not be negative");
       if (bad & HS_CENSUS_BAD_DECREASE) return fail("hipstr_post_census: str_seq_off must not decrease");
     }
   }
-  HS_HIP(hipMemsetAsync(B.dev + r_nsp, 0, (dev ? r_check : res_bytes) - r_nsp, st));          // the counts and the marks
-  HS_HIP(hipMemsetAsync(B.dev + d_count, 0, d_rank - d_count, st));                // candidates per locus, the samples' flags
+  HS_HIP(hipMemsetAsync(B.dev<char>(r_nsp), 0, (dev ? r_check : B.res) - r_nsp, st));          // the counts and the marks
+  HS_HIP(hipMemsetAsync(B.dev<char>(d_count), 0, d_rank - d_count, st));            // candidates per locus, the samples' flags
   if (!P.list[0].empty()) hipLaunchKernelGGL(hs_census_wave_kernel, dim3((unsigned)hs_census_workgroups(0, (int64_t)P.list[0].size())), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   if (!P.list[1].empty()) hipLaunchKernelGGL(hs_census_lds_kernel, dim3((unsigned)P.list[1].size()), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   if (!P.list[2].empty()) hipLaunchKernelGGL(hs_census_global_kernel, dim3((unsigned)P.list[2].size()), dim3(HS_CENSUS_THREADS), 0, st, d_args);
@@ -2317,34 +2313,25 @@ int census_call(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const 
   if (nq) hipLaunchKernelGGL(hs_census_emit_kernel, dim3((unsigned)((nq + HS_CENSUS_THREADS - 1)/HS_CENSUS_THREADS)), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   if (dev && nq) hipLaunchKernelGGL(hs_census_gather_kernel, dim3(1), dim3(HS_CENSUS_THREADS), 0, st, d_args);
   HS_HIP(hipGetLastError());
-  HS_HIP(hipMemcpyAsync(B.pin, B.dev, res_bytes, hipMemcpyDeviceToHost, st));
-  HS_HIP(hipstr::wait_stream(st));
-  const int32_t* coff = (const int32_t*)(B.pin + r_coff);
-  const int32_t* creq = (const int32_t*)(B.pin + r_creq);
-  if (dev && nq && (*(const int32_t*)(B.pin + r_check) & HS_CENSUS_BAD_NO_STR))
+  if (B.fetch()) return 1;
+  const int32_t* coff = B.host<int32_t>(r_coff);
+  const int32_t* creq = B.host<int32_t>(r_creq);
+  if (dev && nq && (*B.host<int32_t>(r_check) & HS_CENSUS_BAD_NO_STR))
     return fail("hipstr_post_census: a spanning request without STR data (AlignmentTrace::stutter_size asserts)");
   memcpy(out->cand_off, coff, (nl + 1)*4);
   const int32_t n_cand = coff[nl];
   if (n_cand > out->cap_cand){ fail("candidate arrays too small: cand_off[n_loci] holds the number needed"); return 3; }
   int64_t chars = 0;
-  if (dev) chars = nq ? *(const int64_t*)(B.pin + r_cchars) : 0;
+  if (dev) chars = nq ? *B.host<int64_t>(r_cchars) : 0;
   else for (int32_t k = 0; k < n_cand; k++) chars += tr->str_seq_off[creq[k] + 1] - tr->str_seq_off[creq[k]];
   if (chars > out->cap_chars){ fail("candidate string pool too small: cap_chars of str_seq_off[n_req] always holds it"); return 3; }
   // the candidates' strings are the caller's own bytes: copied here from trace->str_seq in the order the device fixed
   if (dev){
     // ... or gathered on the device in that order: the bytes in use come home in a copy of their own
     out->cand_seq_off[0] = 0;
-    if (nq) memcpy(out->cand_seq_off, B.pin + r_csoff, ((size_t)n_cand + 1)*4);
+    if (nq) memcpy(out->cand_seq_off, B.host<char>(r_csoff), ((size_t)n_cand + 1)*4);
     if (n_cand) memcpy(out->cand_req, creq, (size_t)n_cand*4);
-    if (chars){
-      char* pin_seq = (char*)ctx->pin_cache.get((size_t)chars);
-      if (!pin_seq) return 1;
-      const bool ok = hipMemcpyAsync(pin_seq, B.dev + r_cseq, (size_t)chars, hipMemcpyDeviceToHost, st) == hipSuccess && hipstr::wait_stream(st) == hipSuccess;
-      if (ok) memcpy(out->cand_seq, pin_seq, (size_t)chars);
-      else hipStreamSynchronize(st);
-      ctx->pin_cache.put(pin_seq);
-      if (!ok) return fail("device-to-host copy failed");
-    }
+    if (hipstr::fetch_to_host(ctx, st, out->cand_seq, B.dev<char>(r_cseq), (size_t)chars)) return 1;
   } else {
   out->cand_seq_off[0] = 0;
   for (int32_t k = 0; k < n_cand; k++){
@@ -2358,13 +2345,13 @@ int census_call(hipstr_post_dev_t* pd, const hipstr_census_request_t* rq, const 
     const int64_t n1 = P.loci[l].n_opts[1];
     out->new_n_haps[l] = (int64_t)P.loci[l].n_alleles / n1 * (n1 + (coff[l+1] - coff[l]));
   }
-  memcpy(out->n_spanning, B.pin + r_nsp, ns*4); memcpy(out->n_span_stutter, B.pin + r_nss, ns*4);
+  memcpy(out->n_spanning, B.host<char>(r_nsp), ns*4); memcpy(out->n_span_stutter, B.host<char>(r_nss), ns*4);
   for (size_t l = 0; l < nl; l++)
     for (int k = 0; k < 3; k++)
       if (rq->hap_to_allele[k]){
         const hs_census_locus_t& L = P.loci[l];
-        memcpy(out->called + L.opt_begin[k], B.pin + r_called + L.opt_begin[k], (size_t)L.n_opts[k]);
-        if (k == 1) memcpy(out->spanned + L.opt_begin[k], B.pin + r_spanned + L.opt_begin[k], (size_t)L.n_opts[k]);
+        memcpy(out->called + L.opt_begin[k], B.host<char>(r_called) + L.opt_begin[k], (size_t)L.n_opts[k]);
+        if (k == 1) memcpy(out->spanned + L.opt_begin[k], B.host<char>(r_spanned) + L.opt_begin[k], (size_t)L.n_opts[k]);
       }
   return 0;
 }
@@ -2390,26 +2377,44 @@ int hipstr_debug_census_plan(int64_t n_req, int64_t n_reads, int64_t out[10]){
 }
 #endif
 
-// Host only: the read counts that need the tracebacks (seq_stutter_genotyper.cpp:1124-1127, 1150-1154).
-int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read_req, const hipstr_trace_out_t* tr,
-                              const int32_t* best_hap, const int32_t* hap_to_allele, const int32_t* allele_bp_diff,
-                              const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop,
-                              int32_t* n_stutter, int32_t* n_flank_indel, int32_t* ml_bp){
-  if (!pb || !read_req || !tr || !best_hap || !hap_to_allele || !allele_bp_diff || !n_variants || !region_start || !region_stop ||
+extern "C++" {
+namespace {
+// What both forms of hipstr_assign_trace_stats check, before anything is written or launched.  trace: the host's or the resident result;
+// scalars: its five arrays are there.  each_read(l, r, so): what a form adds for a read that passed (nonzero: refused); so, ao, vo: the
+// samples, haplotypes and variants in front of locus l, and of all loci on return.
+template <typename F>
+int trace_stats_check(const hipstr_post_batch_t* pb, const int32_t* read_req, const void* trace, bool scalars, const int32_t* best_hap, const int32_t* hap_to_allele,
+                      const int32_t* allele_bp_diff, const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop,
+                      const int32_t* n_stutter, const int32_t* n_flank_indel, const int32_t* ml_bp, int64_t& so, int64_t& ao, int64_t& vo, F each_read){
+  if (!pb || !read_req || !trace || !best_hap || !hap_to_allele || !allele_bp_diff || !n_variants || !region_start || !region_stop ||
       !n_stutter || !n_flank_indel || !ml_bp) return fail("null argument");
-  if (!tr->stutter_size || !tr->flank_ins || !tr->flank_del || !tr->aln_start || !tr->aln_stop) return fail("trace output without stutter_size / flank_ins / flank_del / aln_start / aln_stop");
+  if (!scalars) return fail("trace output without stutter_size / flank_ins / flank_del / aln_start / aln_stop");
   if (pb->n_loci < 0 || (pb->n_loci && (!pb->n_alleles || !pb->n_samples || !pb->read_off || !pb->sample_label))) return fail("null argument");
-  int64_t so = 0, ao = 0, vo = 0;
-  for (int l = 0; l < pb->n_loci; l++){                    // everything checked before anything is written
+  so = ao = vo = 0;
+  for (int l = 0; l < pb->n_loci; l++){
     const int A = pb->n_alleles[l], S = pb->n_samples[l], V = n_variants[l];
     if (A < 1 || S < 0 || V < 1 || pb->read_off[l+1] < pb->read_off[l]) return fail("inconsistent locus tables");
     for (int a = 0; a < A; a++) if (hap_to_allele[ao + a] < 0 || hap_to_allele[ao + a] >= V) return fail("hap_to_allele entry out of range");
     for (int r = pb->read_off[l]; r < pb->read_off[l+1]; r++){
       if (pb->sample_label[r] < 0 || pb->sample_label[r] >= S) return fail("sample_label out of range");
       if (read_req[r] >= 0 && (best_hap[r] < 0 || best_hap[r] >= A)) return fail("best_hap out of range for a read with a request");
+      if (each_read(l, r, so)) return 1;
     }
     so += S; ao += A; vo += V;
   }
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+// Host only: the read counts that need the tracebacks (seq_stutter_genotyper.cpp:1124-1127, 1150-1154).
+int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read_req, const hipstr_trace_out_t* tr,
+                              const int32_t* best_hap, const int32_t* hap_to_allele, const int32_t* allele_bp_diff,
+                              const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop,
+                              int32_t* n_stutter, int32_t* n_flank_indel, int32_t* ml_bp){
+  int64_t so = 0, ao = 0, vo = 0;
+  if (trace_stats_check(pb, read_req, tr, tr && tr->stutter_size && tr->flank_ins && tr->flank_del && tr->aln_start && tr->aln_stop, best_hap, hap_to_allele,
+                        allele_bp_diff, n_variants, region_start, region_stop, n_stutter, n_flank_indel, ml_bp, so, ao, vo, [](int, int, int64_t){ return 0; })) return 1;
   const int n_reads = pb->n_loci ? pb->read_off[pb->n_loci] : 0;
   for (int64_t s = 0; s < so; s++){ n_stutter[s] = 0; n_flank_indel[s] = 0; }
   for (int r = 0; r < n_reads; r++) ml_bp[r] = HIPSTR_NO_ML_BP;
@@ -2434,32 +2439,25 @@ int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read
 static_assert(HS_TSTAT_NO_STR_DATA == HIPSTR_NO_STR_DATA && HS_CENSUS_NO_STR_DATA == HIPSTR_NO_STR_DATA && HS_TSTAT_NO_ML_BP == HIPSTR_NO_ML_BP,
               "the kernels' copies of the public constants");
 // The same counts with the five scalars read from a resident traceback result, on its device (assign.hip: hs_trace_stats_kernel).  The
-// host's table checks are those above, before any launch; the units are the runs of reads of one sample.
+// host's table checks are the same function's, before any launch; the units are the runs of reads of one sample.
 int hipstr_assign_trace_stats_dev(const hipstr_post_batch_t* pb, const int32_t* read_req, const hipstr_trace_dev_t* td,
                                   const int32_t* best_hap, const int32_t* hap_to_allele, const int32_t* allele_bp_diff,
                                   const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop,
                                   int32_t* n_stutter, int32_t* n_flank_indel, int32_t* ml_bp){
-  if (!pb || !read_req || !td || !best_hap || !hap_to_allele || !allele_bp_diff || !n_variants || !region_start || !region_stop ||
-      !n_stutter || !n_flank_indel || !ml_bp) return fail("null argument");
-  if (!td->scal[0] || !td->scal[1] || !td->scal[2] || !td->scal[3] || !td->scal[4]) return fail("trace output without stutter_size / flank_ins / flank_del / aln_start / aln_stop");
-  if (pb->n_loci < 0 || (pb->n_loci && (!pb->n_alleles || !pb->n_samples || !pb->read_off || !pb->sample_label))) return fail("null argument");
-  std::vector<hs_tstat_unit_t> units; std::vector<hs_tstat_locus_t> loci((size_t)pb->n_loci);
+  std::vector<hs_tstat_unit_t> units;
   int64_t so = 0, ao = 0, vo = 0;
-  for (int l = 0; l < pb->n_loci; l++){                    // everything checked before anything is written or launched
-    const int A = pb->n_alleles[l], S = pb->n_samples[l], V = n_variants[l];
-    if (A < 1 || S < 0 || V < 1 || pb->read_off[l+1] < pb->read_off[l]) return fail("inconsistent locus tables");
-    for (int a = 0; a < A; a++) if (hap_to_allele[ao + a] < 0 || hap_to_allele[ao + a] >= V) return fail("hap_to_allele entry out of range");
-    for (int r = pb->read_off[l]; r < pb->read_off[l+1]; r++){
-      if (pb->sample_label[r] < 0 || pb->sample_label[r] >= S) return fail("sample_label out of range");
-      if (read_req[r] >= 0 && (best_hap[r] < 0 || best_hap[r] >= A)) return fail("best_hap out of range for a read with a request");
-      if (read_req[r] >= td->n_req) return fail("read_req outside the trace handle's requests");
-      if (r > pb->read_off[l] && pb->sample_label[r] == pb->sample_label[r-1]) units.back().n_reads++;
-      else units.push_back(hs_tstat_unit_t{r, 1, (int32_t)(so + pb->sample_label[r]), l});
-    }
+  if (trace_stats_check(pb, read_req, td, td && td->scal[0] && td->scal[1] && td->scal[2] && td->scal[3] && td->scal[4], best_hap, hap_to_allele,
+                        allele_bp_diff, n_variants, region_start, region_stop, n_stutter, n_flank_indel, ml_bp, so, ao, vo, [&](int l, int r, int64_t so_l){
+        if (read_req[r] >= td->n_req) return fail("read_req outside the trace handle's requests");
+        if (r > pb->read_off[l] && pb->sample_label[r] == pb->sample_label[r-1]) units.back().n_reads++;
+        else units.push_back(hs_tstat_unit_t{r, 1, (int32_t)(so_l + pb->sample_label[r]), l});
+        return 0;
+      })) return 1;
+  std::vector<hs_tstat_locus_t> loci((size_t)pb->n_loci);
+  for (int64_t l = 0, a = 0, v = 0; l < pb->n_loci; a += pb->n_alleles[l], v += n_variants[l], l++){
     hs_tstat_locus_t& L = loci[l];
-    L.hap_begin = ao; L.var_begin = vo;
+    L.hap_begin = a; L.var_begin = v;
     L.start_bound = region_start[l] > 4 ? region_start[l] - 4 : 0; L.stop_bound = region_stop[l] + 4;
-    so += S; ao += A; vo += V;
   }
   const size_t n = pb->n_loci ? (size_t)pb->read_off[pb->n_loci] : 0, ns = (size_t)so;
   if (units.empty()){                                      // no read: nothing for the device to do
@@ -2475,27 +2473,21 @@ int hipstr_assign_trace_stats_dev(const hipstr_post_batch_t* pb, const int32_t* 
   hs_tstat_dev_t h; memset(&h, 0, sizeof h);
   const size_t o_args = ar.add(&h, sizeof h);
   if (ar.reserve(ctx)) return 1;
-  size_t tot = 0;
-  auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
-  const size_t r_st = take(ns*4), r_fi = take(ns*4), r_ml = take(n*4);
-  struct Blocks { Ctx* c; hipStream_t st; char* dev = NULL; char* pin = NULL;
-                  ~Blocks(){ if (dev || pin) hipStreamSynchronize(st); if (dev) c->dev_cache.put(dev); if (pin) c->pin_cache.put(pin); } } B{ctx, st};
-  B.dev = (char*)ctx->dev_cache.get(tot);
-  if (!B.dev) return 1;
-  B.pin = (char*)ctx->pin_cache.get(tot);
-  if (!B.pin) return 1;
+  hipstr::ResultBlocks B;
+  const size_t r_st = B.take(ns*4), r_fi = B.take(ns*4), r_ml = B.take(n*4);
+  B.end_results();                                         // all of it comes home
+  if (B.reserve(ctx, st)) return 1;
   h.units = ar.at<hs_tstat_unit_t>(o_units); h.loci = ar.at<hs_tstat_locus_t>(o_loci); h.n_units = (int32_t)units.size();
   h.read_req = ar.at<int32_t>(o_rreq); h.best_hap = ar.at<int32_t>(o_best); h.hap_to_allele = ar.at<int32_t>(o_h2a); h.allele_bp_diff = ar.at<int32_t>(o_bp);
   h.stutter_size = td->scal[0]; h.flank_ins = td->scal[1]; h.flank_del = td->scal[2]; h.aln_start = td->scal[3]; h.aln_stop = td->scal[4];
-  h.n_stutter = (int32_t*)(B.dev + r_st); h.n_flank_indel = (int32_t*)(B.dev + r_fi); h.ml_bp = (int32_t*)(B.dev + r_ml);
+  h.n_stutter = B.dev<int32_t>(r_st); h.n_flank_indel = B.dev<int32_t>(r_fi); h.ml_bp = B.dev<int32_t>(r_ml);
   if (ar.send(st)) return 1;
   const hs_tstat_dev_t* d_args = ar.at<hs_tstat_dev_t>(o_args);
-  HS_HIP(hipMemsetAsync(B.dev + r_st, 0, r_ml - r_st, st));                        // the samples' counts
+  HS_HIP(hipMemsetAsync(B.dev<char>(r_st), 0, r_ml - r_st, st));                       // the samples' counts
   hipLaunchKernelGGL(hs_trace_stats_kernel, dim3((unsigned)hs_assign_workgroups((int64_t)units.size(), 1)), dim3(HS_ASSIGN_THREADS), 0, st, d_args);
   HS_HIP(hipGetLastError());
-  HS_HIP(hipMemcpyAsync(B.pin, B.dev, tot, hipMemcpyDeviceToHost, st));
-  HS_HIP(hipstr::wait_stream(st));
-  memcpy(n_stutter, B.pin + r_st, ns*4); memcpy(n_flank_indel, B.pin + r_fi, ns*4); memcpy(ml_bp, B.pin + r_ml, n*4);
+  if (B.fetch()) return 1;
+  memcpy(n_stutter, B.host<char>(r_st), ns*4); memcpy(n_flank_indel, B.host<char>(r_fi), ns*4); memcpy(ml_bp, B.host<char>(r_ml), n*4);
   return 0;
 }
 

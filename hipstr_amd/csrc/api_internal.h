@@ -5,6 +5,9 @@
 #include <string>
 #include <vector>
 #include <string.h>
+#include <stdlib.h>
+#include <algorithm>
+#include "block_pieces.h"
 
 namespace hipstr {
 
@@ -22,6 +25,8 @@ struct ApiTables {                 // device copies of HostTables, owned by the 
 };
 int api_device_tables(ApiTables* t);          // tables of the calling thread's current context; 1 + hipstr_last_error() on failure
 int api_fail(const std::string& message);     // records hipstr_last_error(); returns 1
+// a HIP call of an entry point: on failure "<the call as written>: <the driver's words>" is the last error and the function returns 1
+#define HS_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return ::hipstr::api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 
 // Cached blocks: a freed block goes back to its context's free list instead of hipFree / hipHostFree (both synchronise the
 // device and cost 0.1-10 ms); a request is served from the list when a block of at most 1.25x the size is there.
@@ -64,6 +69,130 @@ struct HostArena {
   }
   template <typename T> T* at(size_t off) const { return (T*)(dev + off); }
 };
+
+// ---- blocks of the caches on the result side.  One rule, stated in the destructors below and nowhere else: the caches serve other host
+// threads, so a block goes back only after the stream that may still be working on it has been waited for, whichever way the call leaves.
+// On the normal path the results were fetched through wait_stream already and that wait costs a few microseconds; hipStreamSynchronize
+// is the backstop of the error paths.
+
+// Device scratch arrays of a chunked call (traceback, Needleman-Wunsch, the stutter EM): one cache block each, all of them back when the
+// call leaves, behind every stream it was told about.
+struct ScratchBufs {
+  std::vector<void*> p;
+  Ctx* ctx = NULL;                  // taken on first use: blocks come from (and return to) the context's cache, no hipMalloc / hipFree per call
+  hipStream_t streams[3] = {NULL, NULL, NULL}; int n_streams = 0;
+  void runs_on(hipStream_t st){ for (int i = 0; i < n_streams; i++) if (streams[i] == st) return; if (n_streams < 3) streams[n_streams++] = st; }
+  ScratchBufs(){}
+  ScratchBufs(const ScratchBufs&) = delete;
+  ~ScratchBufs(){ if (ctx){ for (int i = 0; i < n_streams; i++) hipStreamSynchronize(streams[i]); for (void* x : p) dev_free(ctx, x); } }
+  template <typename T> int alloc(T** out, size_t count){
+    *out = NULL;
+    if (!ctx) ctx = api_current_ctx();
+    if (!ctx) return 1;
+    *out = (T*)dev_alloc(ctx, (count ? count : 1)*sizeof(T));
+    if (!*out) return 1;
+    p.push_back(*out);
+    return 0;
+  }
+  template <typename T> int put(T** out, const T* src, size_t count){
+    if (alloc(out, count)) return 1;
+    if (count) HS_HIP(hipMemcpy(*out, src, count*sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+  }
+};
+
+// The results of a one-shot call: the pieces that come home first, back to back (take, then end_results), then what stays on the device;
+// one device block of the whole size and one pinned block of the results' size; one copy home.  Lives as long as the host reads the
+// pinned pieces.
+struct ResultBlocks : BlockPieces {
+  Ctx* ctx = NULL; hipStream_t st = NULL; char* d = NULL; char* h = NULL;
+  ResultBlocks(){}
+  ResultBlocks(const ResultBlocks&) = delete;
+  ~ResultBlocks(){ if (d || h) hipStreamSynchronize(st); if (d) dev_free(ctx, d); if (h) pin_free(ctx, h); }
+  int reserve(Ctx* c, hipStream_t s){        // after the last take(): the blocks; everything the call queues on them goes to s
+    ctx = c; st = s;
+    d = (char*)dev_alloc(ctx, tot);
+    if (!d) return 1;
+    h = (char*)pin_alloc(ctx, res);
+    return h ? 0 : 1;
+  }
+  template <typename T> T* dev(size_t off) const { return (T*)(d + off); }
+  template <typename T> const T* host(size_t off) const { return (const T*)(h + off); }      // (a results' piece, after fetch)
+  int fetch(size_t off, size_t bytes){       // part of the results home, at the same offset
+    HS_HIP(hipMemcpyAsync(h + off, d + off, bytes, hipMemcpyDeviceToHost, st));
+    HS_HIP(wait_stream(st));
+    return 0;
+  }
+  int fetch(){ return fetch(0, res); }
+};
+
+// One chunk of a call that walks its loci in chunks (read pooling, allele generation): uploaded | workspace | results in one device block,
+// the uploaded pieces packed in a pinned block, the results fetched into another.  `busy` from the first copy queued until the results are
+// home: only then has the destructor a stream to wait for.  e0, e1: around the kernels, when the call is timed.
+struct ChunkBlocks : BlockPieces {
+  Ctx* ctx; hipStream_t st; char* dev = NULL; char* pin_up = NULL; char* pin_res = NULL; bool busy = false;
+  hipEvent_t e0 = NULL, e1 = NULL;
+  size_t up_bytes = 0, res0 = 0;             // where the uploaded pieces end and the results begin
+  ChunkBlocks(Ctx* c, hipStream_t s) : ctx(c), st(s) {}
+  ChunkBlocks(const ChunkBlocks&) = delete;
+  ~ChunkBlocks(){
+    if (busy) hipStreamSynchronize(st);
+    if (dev) dev_free(ctx, dev);
+    if (pin_up) pin_free(ctx, pin_up);
+    if (pin_res) pin_free(ctx, pin_res);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+  }
+  void end_upload(){ up_bytes = tot; }
+  void begin_results(){ res0 = tot; }
+  size_t res_bytes() const { return tot - res0; }
+  int reserve(){
+    dev = (char*)dev_alloc(ctx, tot);
+    if (!dev) return 1;
+    pin_up = (char*)pin_alloc(ctx, up_bytes);
+    if (!pin_up) return 1;
+    pin_res = (char*)pin_alloc(ctx, res_bytes());
+    return pin_res ? 0 : 1;
+  }
+  template <typename T> T* up(size_t off) const { return (T*)(pin_up + off); }               // an uploaded piece, to be filled
+  template <typename T> const T* host(size_t off) const { return (const T*)(pin_res + (off - res0)); }      // a results' piece, after fetch
+  int upload(bool timing){                   // the uploaded pieces on their way, e0 behind them
+    if (timing){ HS_HIP(hipEventCreate(&e0)); HS_HIP(hipEventCreate(&e1)); }
+    busy = true;
+    HS_HIP(hipMemcpyAsync(dev, pin_up, up_bytes, hipMemcpyHostToDevice, st));
+    if (timing) HS_HIP(hipEventRecord(e0, st));
+    return 0;
+  }
+  int fetch(bool timing, double* kernel_ms){ // e1 behind the kernels, the results home; the kernels' milliseconds are added when timed
+    if (timing) HS_HIP(hipEventRecord(e1, st));
+    HS_HIP(hipMemcpyAsync(pin_res, dev + res0, res_bytes(), hipMemcpyDeviceToHost, st));
+    HS_HIP(wait_stream(st));
+    busy = false;
+    if (timing){ float ms = 0; HS_HIP(hipEventElapsedTime(&ms, e0, e1)); *kernel_ms += ms; }
+    return 0;
+  }
+};
+// the per-thread record of such a call (hipstr_debug_pool_last, hipstr_debug_hapgen_last): counts, and kernel ms | bytes up | bytes home | packing s
+struct ChunkLast { int64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double t[4] = {0, 0, 0, 0}; };
+// a chunk's workspace in bytes: ws_mib when positive, else the variable `env` when it holds a positive number, else default_mib; at least
+// 4 KiB, at most cap_bytes
+inline int64_t chunk_budget(double ws_mib, const char* env, double default_mib, double cap_bytes){
+  double mib = ws_mib > 0 ? ws_mib : default_mib;
+  if (!(ws_mib > 0)) if (const char* e = getenv(env)){ const double v = atof(e); if (v > 0) mib = v; }
+  return (int64_t)std::min(std::max(mib*1048576.0, 4096.0), cap_bytes);
+}
+
+// One device array into a (pageable) host array through a pinned block of the cache; returns when it has landed.  (The forward pass'
+// large results: fetch_array, api.hip.)
+inline int fetch_to_host(Ctx* ctx, hipStream_t st, void* dst, const void* src, size_t bytes){
+  if (!bytes) return 0;
+  char* p = (char*)pin_alloc(ctx, bytes);
+  if (!p) return 1;
+  const bool ok = hipMemcpyAsync(p, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess && wait_stream(st) == hipSuccess;
+  if (ok) memcpy(dst, p, bytes); else hipStreamSynchronize(st);
+  pin_free(ctx, p);
+  return ok ? 0 : api_fail("device-to-host copy failed");
+}
 
 // ---- where the host time of the entry points goes (hipstr_debug_api_profile, include/hipstr_hmm.h): wall-clock seconds and calls per
 // bucket, summed over all threads while enabled.  Buckets nest: the indented ones are parts of the entry point above them.
@@ -128,6 +257,8 @@ struct PostView {                    // a posterior run after hipstr_post_upload
   int n_reads; int64_t n_samp;
   const int32_t* n_samples;          // [n_loci]
   const uint8_t* haploid;            // [n_loci]
+  // per locus its reads [read_off[l], read_off[l+1]) and its units [unit_off[l], unit_off[l+1]), from the units (locus-major, one per sample)
+  void locus_tables(std::vector<int32_t>& read_off, std::vector<int32_t>& unit_off) const;
 };
 void post_view(const hipstr_post_dev* pd, PostView* v);
 int  api_tables_of(Ctx* c, ApiTables* t);     // api_device_tables for a given context (binds it)

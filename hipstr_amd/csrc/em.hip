@@ -661,30 +661,6 @@ __global__ void __launch_bounds__(HS_EM_UNITS_THREADS) hs_em_units(const hs_em_d
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
-#define EM_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
-  hipstr::api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
-
-struct EmBufs {
-  std::vector<void*> p;
-  hipstr::Ctx* ctx = NULL;          // blocks come from (and return to) the context's cache: no hipMalloc / hipFree per call
-  // the blocks go back to a cache other host threads draw from: nothing launched by this call may still be running (error paths leave early)
-  hipStream_t stream = NULL;        // the stream the call's kernels run on
-  ~EmBufs(){ if (ctx){ if (stream) hipStreamSynchronize(stream); for (void* x : p) hipstr::dev_free(ctx, x); } }
-  template <typename T> int alloc(T** out, size_t count){
-    *out = NULL;
-    if (!ctx) ctx = hipstr::api_current_ctx();
-    if (!ctx) return 1;
-    *out = (T*)hipstr::dev_alloc(ctx, (count ? count : 1)*sizeof(T));
-    if (!*out) return 1;
-    p.push_back(*out);
-    return 0;
-  }
-  template <typename T> int put(T** out, const T* src, size_t count){
-    if (alloc(out, count)) return 1;
-    if (count) EM_HIP(hipMemcpy(*out, src, count*sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-  }
-};
 
 double h_lse2(double a, double b){ return a > b ? a + log(1 + exp(b - a)) : b + log(1 + exp(a - b)); }       // mathops.cpp:52-57
 
@@ -794,7 +770,7 @@ int em_prepare(const hipstr_em_batch_t* eb, bool host_loop, EmPrep& P){
 // they index, already on the device — uploaded from em_prepare's host arrays (hipstr_em_train) or built there (em_input.hip:
 // hipstr_em_train_dev).  Everything else the loop needs is allocated here, through `dev` (whose blocks outlive the loop's kernels).
 struct EmArrays { int32_t *bps, *obs, *lab, *w; double *p1, *p2, *gtp; };
-int em_loop(const hipstr::ApiTables& T, EmBufs& dev, EmPrep& P, const EmArrays& in, int max_iter, double min_abs_change, double min_frac_change,
+int em_loop(const hipstr::ApiTables& T, hipstr::ScratchBufs& dev, EmPrep& P, const EmArrays& in, int max_iter, double min_abs_change, double min_frac_change,
             bool host_loop, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
   const hipstr::HostTables& HT = hipstr::host_tables();
   const bool timing = getenv("HIPSTR_TIMING") != NULL;
@@ -825,7 +801,7 @@ int em_loop(const hipstr::ApiTables& T, EmBufs& dev, EmPrep& P, const EmArrays& 
   h.loci = d_loci; h.active = d_active; h.logp = d_logp; h.bps = d_bps; h.obs = d_obs; h.sample_label = d_lab; h.log_p1 = d_p1; h.log_p2 = d_p2;
   h.gtp = d_gtp; h.ll = d_ll; h.prior = d_prior; h.post = d_post; h.sample_total = d_tot; h.int_log = T.int_log; h.new_ll = d_newll; h.sums = d_sums; h.row_lse = d_rowlse; h.cat = d_cat; h.leff = d_leff; h.part = d_part; h.gmax = d_gmax;
   unsigned long long* d_dbg = NULL;
-  if (timing){ if (dev.alloc(&d_dbg, 4)) return 1; EM_HIP(hipMemset(d_dbg, 0, 4*sizeof(unsigned long long))); }
+  if (timing){ if (dev.alloc(&d_dbg, 4)) return 1; HS_HIP(hipMemset(d_dbg, 0, 4*sizeof(unsigned long long))); }
   h.dbg = d_dbg;
   h.log_thresh = HT.log_thresh; h.log_half = HT.log_half; h.log_1p1 = host_loop ? log(1.1) : cr_log(1.1);
   ph.units = d_units; ph.log_aln_probs = d_ll; ph.log_p1 = d_p1; ph.log_p2 = d_p2; ph.read_weight = d_w; ph.log_prior = d_prior;
@@ -839,9 +815,9 @@ int em_loop(const hipstr::ApiTables& T, EmBufs& dev, EmPrep& P, const EmArrays& 
     hipStream_t stream = NULL; hipEvent_t ev_fork = NULL, ev_join = NULL;
     ~SideStream(){ if (stream) hipStreamSynchronize(stream); if (ev_fork) hipEventDestroy(ev_fork); if (ev_join) hipEventDestroy(ev_join); if (stream) hipStreamDestroy(stream); }
   } side;
-  EM_HIP(hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking));
-  EM_HIP(hipEventCreateWithFlags(&side.ev_fork, hipEventDisableTiming));
-  EM_HIP(hipEventCreateWithFlags(&side.ev_join, hipEventDisableTiming));
+  HS_HIP(hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking));
+  HS_HIP(hipEventCreateWithFlags(&side.ev_fork, hipEventDisableTiming));
+  HS_HIP(hipEventCreateWithFlags(&side.ev_join, hipEventDisableTiming));
   if (!host_loop){
     // ---- the device-resident loop: state, the two sets of lists (a round reads one and writes the other), two argument blocks each for
     // the EM kernels and the posterior kernel that differ only in which set is which
@@ -869,7 +845,7 @@ int em_loop(const hipstr::ApiTables& T, EmBufs& dev, EmPrep& P, const EmArrays& 
     if (!pin.p) return 1;
     hipEvent_t ev_cnt[NBUF] = {NULL, NULL, NULL, NULL};
     struct EvGuard { hipEvent_t* e; int n; ~EvGuard(){ for (int i = 0; i < n; i++) if (e[i]) hipEventDestroy(e[i]); } } evg{ev_cnt, NBUF};
-    for (int i = 0; i < NBUF; i++) EM_HIP(hipEventCreateWithFlags(&ev_cnt[i], hipEventDisableTiming));
+    for (int i = 0; i < NBUF; i++) HS_HIP(hipEventCreateWithFlags(&ev_cnt[i], hipEventDisableTiming));
     auto wait_event = [&](hipEvent_t e) -> hipError_t {           // without burning a core (hipEventSynchronize spins: tools/wait_probe.hip)
       for (unsigned n = 0;; n++){
         const hipError_t q = hipEventQuery(e);
@@ -890,38 +866,38 @@ int em_loop(const hipstr::ApiTables& T, EmBufs& dev, EmPrep& P, const EmArrays& 
       if (bound_l > 0){
         hipLaunchKernelGGL(hs_em_fill, dim3(bound_l), dim3(256), 0, T.stream, H);
         hipLaunchKernelGGL(hs_posterior_kernel, dim3(std::max(1u, bound_u)), dim3(256), 0, T.stream, PH);
-        EM_HIP(hipEventRecord(side.ev_fork, T.stream));                  // posteriors are in place: the allele-frequency scans branch off
-        EM_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));        // (beside the M-step on the side stream: 0.51 against 0.57 s per 10 000 loci in series, profiles/r05_notes.md)
+        HS_HIP(hipEventRecord(side.ev_fork, T.stream));                  // posteriors are in place: the allele-frequency scans branch off
+        HS_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));        // (beside the M-step on the side stream: 0.51 against 0.57 s per 10 000 loci in series, profiles/r05_notes.md)
         hipLaunchKernelGGL(hs_em_gt_priors, dim3(bound_l), dim3(HS_EM_THREADS), hs_em_lds_doubles()*sizeof(double), side.stream, H);
-        EM_HIP(hipEventRecord(side.ev_join, side.stream));
+        HS_HIP(hipEventRecord(side.ev_join, side.stream));
         hipLaunchKernelGGL(hs_em_gmax, dim3(bound_l), dim3(256), 0, T.stream, H);
         hipLaunchKernelGGL(hs_em_mstep_part<0>, dim3(bound_l, HS_EM_PARTS), dim3(256), 0, T.stream, H, (const double*)NULL);
         hipLaunchKernelGGL(hs_em_mstep_keepmax, dim3(bound_l), dim3(64), 0, T.stream, H, d_keep);
         hipLaunchKernelGGL(hs_em_mstep_part<1>, dim3(bound_l, HS_EM_PARTS), dim3(256), 0, T.stream, H, (const double*)d_keep);
         hipLaunchKernelGGL(hs_em_finish, dim3(bound_l), dim3(64), 0, T.stream, H, (const double*)d_keep);
-        EM_HIP(hipStreamWaitEvent(T.stream, side.ev_join, 0));            // the next round's hs_em_fill reads the new allele frequencies
+        HS_HIP(hipStreamWaitEvent(T.stream, side.ev_join, 0));            // the next round's hs_em_fill reads the new allele frequencies
         hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(HS_EM_COMPACT_THREADS), 0, T.stream, H);
         hipLaunchKernelGGL(hs_em_units, dim3(bound_l), dim3(HS_EM_UNITS_THREADS), 0, T.stream, H);
         rounds++;
       }
-      EM_HIP(hipMemcpyAsync(pin.p + 2*(r % NBUF), d_counts[(r & 1) ^ 1], 2*sizeof(int32_t), hipMemcpyDeviceToHost, T.stream));
-      EM_HIP(hipEventRecord(ev_cnt[r % NBUF], T.stream));
-      EM_HIP(hipGetLastError());
+      HS_HIP(hipMemcpyAsync(pin.p + 2*(r % NBUF), d_counts[(r & 1) ^ 1], 2*sizeof(int32_t), hipMemcpyDeviceToHost, T.stream));
+      HS_HIP(hipEventRecord(ev_cnt[r % NBUF], T.stream));
+      HS_HIP(hipGetLastError());
       if (r >= 1){
         // what round r - 1 left: the loci (and units) of round r — a bound for the grids of round r + 1, and the stop signal — while
         // round r is already queued
-        EM_HIP(wait_event(ev_cnt[(r - 1) % NBUF]));
+        HS_HIP(wait_event(ev_cnt[(r - 1) % NBUF]));
         bound_l = (unsigned)pin.p[2*((r - 1) % NBUF)]; bound_u = (unsigned)pin.p[2*((r - 1) % NBUF) + 1];
         if (bound_l == 0) break;
       }
     }
-    EM_HIP(hipstr::wait_stream(T.stream));
+    HS_HIP(hipstr::wait_stream(T.stream));
     lap("device loop", &t_gpu);
     std::vector<int32_t> state(nl), niter(nl);
-    EM_HIP(hipMemcpy(state.data(), d_state, nl*sizeof(int32_t), hipMemcpyDeviceToHost));
-    EM_HIP(hipMemcpy(niter.data(), d_niter, nl*sizeof(int32_t), hipMemcpyDeviceToHost));
-    EM_HIP(hipMemcpy(final_ll, d_fll, nl*sizeof(double), hipMemcpyDeviceToHost));
-    EM_HIP(hipMemcpy(stutter, d_sp, 6*(size_t)nl*sizeof(double), hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(state.data(), d_state, nl*sizeof(int32_t), hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(niter.data(), d_niter, nl*sizeof(int32_t), hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(final_ll, d_fll, nl*sizeof(double), hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(stutter, d_sp, 6*(size_t)nl*sizeof(double), hipMemcpyDeviceToHost));
     for (int l = 0; l < nl; l++){ trained[l] = state[l] == 1 ? 1 : 0; n_iter[l] = niter[l]; }
     if (timing){
       unsigned long long c[4] = {0, 0, 0, 0};
@@ -956,25 +932,25 @@ int em_loop(const hipstr::ApiTables& T, EmBufs& dev, EmPrep& P, const EmArrays& 
     if (n_active == 0) break;
     for (size_t u = 0; u < units.size(); u++) unit_active[u] = active[unit_locus[u]];
     lap("", &t_host);
-    EM_HIP(hipMemcpy(d_active, active.data(), nl*sizeof(int32_t), hipMemcpyHostToDevice));
-    EM_HIP(hipMemcpy(d_unit_active, unit_active.data(), units.size()*sizeof(int32_t), hipMemcpyHostToDevice));
-    EM_HIP(hipMemcpy(d_logp, logp.data(), logp.size()*sizeof(double), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(d_active, active.data(), nl*sizeof(int32_t), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(d_unit_active, unit_active.data(), units.size()*sizeof(int32_t), hipMemcpyHostToDevice));
+    HS_HIP(hipMemcpy(d_logp, logp.data(), logp.size()*sizeof(double), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(hs_em_fill, dim3(nl), dim3(256), 0, T.stream, d_h);
     hipLaunchKernelGGL(hs_posterior_kernel, dim3((unsigned)units.size()), dim3(256), 0, T.stream, (const hs_post_dev_t*)d_ph);
-    EM_HIP(hipEventRecord(side.ev_fork, T.stream));                      // posteriors are in place: the allele-frequency scans branch off
-    EM_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));
+    HS_HIP(hipEventRecord(side.ev_fork, T.stream));                      // posteriors are in place: the allele-frequency scans branch off
+    HS_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));
     hipLaunchKernelGGL(hs_em_gt_priors, dim3(nl), dim3(HS_EM_THREADS), hs_em_lds_doubles()*sizeof(double), side.stream, d_h);
-    EM_HIP(hipEventRecord(side.ev_join, side.stream));
+    HS_HIP(hipEventRecord(side.ev_join, side.stream));
     hipLaunchKernelGGL(hs_em_gmax, dim3(nl), dim3(256), 0, T.stream, d_h);
     hipLaunchKernelGGL(hs_em_mstep_part<0>, dim3(nl, HS_EM_PARTS), dim3(256), 0, T.stream, d_h, (const double*)NULL);
     hipLaunchKernelGGL(hs_em_mstep_keepmax, dim3(nl), dim3(64), 0, T.stream, d_h, d_keep);
     hipLaunchKernelGGL(hs_em_mstep_part<1>, dim3(nl, HS_EM_PARTS), dim3(256), 0, T.stream, d_h, (const double*)d_keep);
     hipLaunchKernelGGL(hs_em_mstep, dim3(nl), dim3(256), 0, T.stream, d_h, (const double*)d_keep);
-    EM_HIP(hipStreamWaitEvent(T.stream, side.ev_join, 0));                // ... and join before the host reads this iteration's results
-    EM_HIP(hipGetLastError());
-    EM_HIP(hipstr::wait_stream(T.stream));
-    EM_HIP(hipMemcpy(newll.data(), d_newll, nl*sizeof(double), hipMemcpyDeviceToHost));
-    EM_HIP(hipMemcpy(sums.data(), d_sums, sums.size()*sizeof(double), hipMemcpyDeviceToHost));
+    HS_HIP(hipStreamWaitEvent(T.stream, side.ev_join, 0));                // ... and join before the host reads this iteration's results
+    HS_HIP(hipGetLastError());
+    HS_HIP(hipstr::wait_stream(T.stream));
+    HS_HIP(hipMemcpy(newll.data(), d_newll, nl*sizeof(double), hipMemcpyDeviceToHost));
+    HS_HIP(hipMemcpy(sums.data(), d_sums, sums.size()*sizeof(double), hipMemcpyDeviceToHost));
     lap("", &t_gpu);
     for (int l = 0; l < nl; l++){
       State& s = st[l];
@@ -1020,8 +996,8 @@ int em_train_on(const hipstr::ApiTables& T, const hipstr_em_batch_t* eb, uint8_t
   EmPrep P;
   if (em_prepare(eb, host_loop, P)) return 1;
   if (getenv("HIPSTR_TIMING")) fprintf(stderr, "hipstr_em_train: %s %.3f ms\n", "alleles and units", 1e3*std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-  EmBufs dev;
-  dev.ctx = T.ctx; dev.stream = T.stream;
+  hipstr::ScratchBufs dev;
+  dev.ctx = T.ctx; dev.runs_on(T.stream);
   EmArrays in;
   std::vector<int32_t> ones(n_reads, 1);
   if (dev.put(&in.bps, P.bps.data(), P.bps.size()) || dev.put(&in.obs, P.obs.data(), P.obs.size()) || dev.put(&in.lab, eb->sample_label, n_reads) ||
@@ -1067,8 +1043,8 @@ int hipstr::em_train_prepared(const ApiTables& T, int n_loci, const EmLocusFacts
     em_push_locus(P, l, F.A, F.S, F.read_begin, F.R, F.period, F.haploid, F.bps_off, reads_of_sample + so);
     so += F.S;
   }
-  EmBufs dev;
-  dev.ctx = T.ctx; dev.stream = T.stream;
+  hipstr::ScratchBufs dev;
+  dev.ctx = T.ctx; dev.runs_on(T.stream);
   const EmArrays in = { arr.bps, arr.obs, arr.sample_label, arr.weight, arr.log_p1, arr.log_p2, arr.gtp };
   return em_loop(T, dev, P, in, max_iter, min_abs_change, min_frac_change, false, trained, stutter, n_iter, final_ll);
 }

@@ -203,9 +203,6 @@ extern "C" __global__ void __launch_bounds__(HS_EMI_THREADS) hs_emi_alleles_kern
 namespace {
 using hipstr::api_fail;
 
-#define EMI_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
-  hipstr::api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
-
 // The checks of the host's tables both forms share, worded as hipstr_post_census words its own: the locus of every request, every read's
 // request.  read_off: [n_loci+1] the un-pooled reads of every locus.
 int emi_check_tables(int nl, const int32_t* read_off, const hipstr_em_trace_request_t* rq, std::vector<int32_t>& req_locus){
@@ -283,26 +280,12 @@ struct EmiRun {
   hipstr::PostView V;
   hipstr::ApiTables T;
   hipstr::HostArena ar;
-  char* dev = NULL; char* pin = NULL;
+  hipstr::ResultBlocks B;
   hs_emi_dev_t h;
   int nl = 0; size_t n = 0, nu = 0;
   const int32_t *run_count = NULL, *lo = NULL, *hi = NULL, *em_read_off = NULL, *n_sizes = NULL;      // pinned: what came home
   bool host_path = false;            // the whole call takes em_prepare on the fetched compact arrays
-  ~EmiRun(){
-    if (dev || pin) hipStreamSynchronize(T.stream);
-    if (dev) hipstr::dev_free(V.ctx, dev);
-    if (pin) hipstr::pin_free(V.ctx, pin);
-  }
-  // a device array to the host through a pinned block of the cache
-  int fetch(void* dst, const void* src, size_t bytes){
-    if (!bytes) return 0;
-    char* p = (char*)hipstr::pin_alloc(V.ctx, bytes);
-    if (!p) return 1;
-    const bool ok = hipMemcpyAsync(p, src, bytes, hipMemcpyDeviceToHost, T.stream) == hipSuccess && hipstr::wait_stream(T.stream) == hipSuccess;
-    if (ok) memcpy(dst, p, bytes); else hipStreamSynchronize(T.stream);
-    hipstr::pin_free(V.ctx, p);
-    return ok ? 0 : api_fail("device-to-host copy failed");
-  }
+  int fetch(void* dst, const void* src, size_t bytes){ return hipstr::fetch_to_host(V.ctx, T.stream, dst, src, bytes); }
 };
 
 // Everything up to the EM loop: the refusals, the five kernels, the counts home.  nl == 0: nothing is done (X.nl == 0).
@@ -318,23 +301,16 @@ int emi_prepare(hipstr_post_dev_t* pd, const hipstr_em_trace_request_t* rq, cons
   const size_t n = (size_t)V.n_reads, nu = V.n_units;
   // the loci's runs and reads, from the run's units (locus-major, a unit per sample)
   std::vector<hs_emi_locus_t> loci((size_t)nl);
-  std::vector<int32_t> unit_locus(nu), read_off((size_t)nl + 1, 0);
+  std::vector<int32_t> unit_locus(nu), read_off, unit_off;
+  V.locus_tables(read_off, unit_off);
   const hipstr_batch_t* b = rq->pooled;
-  {
-    size_t ui = 0; int rend = 0;
-    for (int l = 0; l < nl; l++){
-      hs_emi_locus_t& L = loci[l]; memset(&L, 0, sizeof L);
-      L.unit_first = (int32_t)ui; L.n_units = V.n_samples[l];
-      L.samp_begin = ui < nu ? V.units[ui].samp_index : (int32_t)V.n_samp;
-      read_off[l] = rend;
-      for (int s = 0; s < V.n_samples[l]; s++, ui++){
-        if (s == 0) read_off[l] = V.units[ui].read_begin;
-        rend = V.units[ui].read_begin + V.units[ui].n_reads;
-        unit_locus[ui] = l;
-      }
-      read_off[l+1] = rend;
-      if (b->n_loci == nl){ L.blk_start = b->blk_start[3*l + 1]; L.blk_end = b->blk_end[3*l + 1]; }
-    }
+  for (int l = 0; l < nl; l++){
+    hs_emi_locus_t& L = loci[l]; memset(&L, 0, sizeof L);
+    const size_t ui = (size_t)unit_off[l];
+    L.unit_first = unit_off[l]; L.n_units = V.n_samples[l];
+    L.samp_begin = ui < nu ? V.units[ui].samp_index : (int32_t)V.n_samp;
+    std::fill(unit_locus.begin() + unit_off[l], unit_locus.begin() + unit_off[l+1], l);
+    if (b->n_loci == nl){ L.blk_start = b->blk_start[3*l + 1]; L.blk_end = b->blk_end[3*l + 1]; }
   }
   std::vector<int32_t> req_locus;
   if (emi_check_tables(nl, read_off.data(), rq, req_locus)) return 1;
@@ -350,27 +326,24 @@ int emi_prepare(hipstr_post_dev_t* pd, const hipstr_em_trace_request_t* rq, cons
   const size_t o_args = ar.add(&h, sizeof h);
   if (ar.reserve(V.ctx)) return 1;
   // what comes home, back to back (one copy), then what stays on the device
-  size_t tot = 0;
-  auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
-  const size_t r_count = take(nu*4), r_lo = take((size_t)nl*4), r_hi = take((size_t)nl*4), r_check = take(4), r_eoff = take(((size_t)nl + 1)*4), r_nsz = take((size_t)nl*4);
-  const size_t res_bytes = tot;
-  const size_t d_rbps = take(n*4), d_rin = take(n), d_base = take((nu + 1)*4), d_nb = take(n*4), d_lab = take(n*4), d_w = take(n*4), d_obs = take(n*4),
-               d_p1 = take(n*8), d_p2 = take(n*8), d_bps = take((n + (size_t)nl)*4), d_gtp = take((n + (size_t)nl)*8);
-  X.dev = (char*)hipstr::dev_alloc(V.ctx, tot);
-  if (!X.dev) return 1;
-  X.pin = (char*)hipstr::pin_alloc(V.ctx, res_bytes);
-  if (!X.pin) return 1;
+  hipstr::ResultBlocks& B = X.B;
+  const size_t r_count = B.take(nu*4), r_lo = B.take((size_t)nl*4), r_hi = B.take((size_t)nl*4), r_check = B.take(4), r_eoff = B.take(((size_t)nl + 1)*4),
+               r_nsz = B.take((size_t)nl*4);
+  B.end_results();
+  const size_t d_rbps = B.take(n*4), d_rin = B.take(n), d_base = B.take((nu + 1)*4), d_nb = B.take(n*4), d_lab = B.take(n*4), d_w = B.take(n*4), d_obs = B.take(n*4),
+               d_p1 = B.take(n*8), d_p2 = B.take(n*8), d_bps = B.take((n + (size_t)nl)*4), d_gtp = B.take((n + (size_t)nl)*8);
+  if (B.reserve(V.ctx, st)) return 1;
   h.units = V.d_units; h.loci = ar.at<hs_emi_locus_t>(o_loci); h.unit_locus = ar.at<int32_t>(o_uloc);
   h.n_units = (int32_t)nu; h.n_loci = nl; h.ref_allele = rq->ref_allele; h.n_reads = (int32_t)n;
   h.log_p1 = V.log_p1; h.log_p2 = V.log_p2; h.seed = ar.at<int32_t>(o_seed); h.read_req = ar.at<int32_t>(o_rreq);
   h.stutter_size = td->scal[0]; h.aln_start = td->scal[3]; h.aln_stop = td->scal[4]; h.str_seq_off = td->off[1];
-  h.read_bps = (int32_t*)(X.dev + d_rbps); h.read_in = (uint8_t*)(X.dev + d_rin); h.run_base = (int32_t*)(X.dev + d_base);
-  h.run_count = (int32_t*)(X.dev + r_count); h.lo = (int32_t*)(X.dev + r_lo); h.hi = (int32_t*)(X.dev + r_hi); h.check = (int32_t*)(X.dev + r_check);
-  h.em_read_off = (int32_t*)(X.dev + r_eoff); h.n_sizes = (int32_t*)(X.dev + r_nsz);
-  h.num_bps = (int32_t*)(X.dev + d_nb); h.sample_label = (int32_t*)(X.dev + d_lab); h.weight = (int32_t*)(X.dev + d_w); h.obs = (int32_t*)(X.dev + d_obs);
-  h.c_log_p1 = (double*)(X.dev + d_p1); h.c_log_p2 = (double*)(X.dev + d_p2); h.bps = (int32_t*)(X.dev + d_bps); h.gtp = (double*)(X.dev + d_gtp);
+  h.read_bps = B.dev<int32_t>(d_rbps); h.read_in = B.dev<uint8_t>(d_rin); h.run_base = B.dev<int32_t>(d_base);
+  h.run_count = B.dev<int32_t>(r_count); h.lo = B.dev<int32_t>(r_lo); h.hi = B.dev<int32_t>(r_hi); h.check = B.dev<int32_t>(r_check);
+  h.em_read_off = B.dev<int32_t>(r_eoff); h.n_sizes = B.dev<int32_t>(r_nsz);
+  h.num_bps = B.dev<int32_t>(d_nb); h.sample_label = B.dev<int32_t>(d_lab); h.weight = B.dev<int32_t>(d_w); h.obs = B.dev<int32_t>(d_obs);
+  h.c_log_p1 = B.dev<double>(d_p1); h.c_log_p2 = B.dev<double>(d_p2); h.bps = B.dev<int32_t>(d_bps); h.gtp = B.dev<double>(d_gtp);
   // the run's inputs may still be on their way (a small run sends them asynchronously on its own stream)
-  if (V.ev_up && st != V.stream) EMI_HIP(hipStreamWaitEvent(st, V.ev_up, 0));
+  if (V.ev_up && st != V.stream) HS_HIP(hipStreamWaitEvent(st, V.ev_up, 0));
   if (ar.send(st)) return 1;
   const hs_emi_dev_t* d_args = ar.at<hs_emi_dev_t>(o_args);
   const unsigned g_runs = (unsigned)hs_emi_run_workgroups((int64_t)nu);
@@ -379,12 +352,11 @@ int emi_prepare(hipstr_post_dev_t* pd, const hipstr_em_trace_request_t* rq, cons
   hipLaunchKernelGGL(hs_emi_scan_kernel, dim3(1), dim3(HS_EMI_THREADS), 0, st, d_args);
   if (nu) hipLaunchKernelGGL(hs_emi_scatter_kernel, dim3(g_runs), dim3(HS_EMI_THREADS), 0, st, d_args);
   hipLaunchKernelGGL(hs_emi_alleles_kernel, dim3((unsigned)nl), dim3(HS_EMI_THREADS), 0, st, d_args);
-  EMI_HIP(hipGetLastError());
-  EMI_HIP(hipMemcpyAsync(X.pin, X.dev, res_bytes, hipMemcpyDeviceToHost, st));
-  EMI_HIP(hipstr::wait_stream(st));
-  X.run_count = (const int32_t*)(X.pin + r_count); X.lo = (const int32_t*)(X.pin + r_lo); X.hi = (const int32_t*)(X.pin + r_hi);
-  X.em_read_off = (const int32_t*)(X.pin + r_eoff); X.n_sizes = (const int32_t*)(X.pin + r_nsz);
-  const int32_t bad = *(const int32_t*)(X.pin + r_check);
+  HS_HIP(hipGetLastError());
+  if (B.fetch()) return 1;
+  X.run_count = B.host<int32_t>(r_count); X.lo = B.host<int32_t>(r_lo); X.hi = B.host<int32_t>(r_hi);
+  X.em_read_off = B.host<int32_t>(r_eoff); X.n_sizes = B.host<int32_t>(r_nsz);
+  const int32_t bad = *B.host<int32_t>(r_check);
   if (bad != HS_EMI_NO_READ) return emi_fail_no_str(bad);
   // what the device does not prepare: the batches hipstr_em_train refuses (its verdict and message: em_prepare's, on the compact arrays)
   // and a legal locus whose sizes span the table of integer logarithms or more

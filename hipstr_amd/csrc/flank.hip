@@ -33,9 +33,6 @@ namespace {
 using hipstr::api_fail;
 namespace hf = hipstr_flank;
 
-#define FLK_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
-  hipstr::api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
-
 // the caps of this call: HIPSTR_DEBUG_FLANK_CAPS = "edges,nodes,recs,reads,len,path_len" (missing or 0 = the compiled limit), read per call
 hs_flk_caps_t flank_caps(){
   hs_flk_caps_t c = hs_flk_default_caps();
@@ -145,19 +142,8 @@ extern "C" int hipstr_flank_assemble_dev(hipstr_post_dev_t* pd, const hipstr_fla
   hf::Tables T;
   const int nl = (int)V.n_loci;
   T.n_loci = nl; T.n_samples = V.n_samples;
-  T.read_off.assign((size_t)nl + 1, 0); T.samp_off.assign((size_t)nl + 1, 0);
-  {
-    size_t ui = 0; int rend = 0;
-    for (int l = 0; l < nl; l++){
-      T.read_off[l] = rend;
-      for (int s = 0; s < V.n_samples[l]; s++, ui++){
-        if (s == 0) T.read_off[l] = V.units[ui].read_begin;
-        rend = V.units[ui].read_begin + V.units[ui].n_reads;
-        T.run_begin.push_back(V.units[ui].read_begin); T.run_len.push_back(V.units[ui].n_reads);
-      }
-      T.read_off[l+1] = rend; T.samp_off[l+1] = T.samp_off[l] + V.n_samples[l];
-    }
-  }
+  V.locus_tables(T.read_off, T.samp_off);
+  for (size_t ui = 0; ui < (size_t)T.n_samp(); ui++){ T.run_begin.push_back(V.units[ui].read_begin); T.run_len.push_back(V.units[ui].n_reads); }
   const std::string why = hf::check_tables(rq, T);
   if (!why.empty()) return api_fail(why);
   const int64_t n_tasks = T.n_tasks();
@@ -197,50 +183,35 @@ extern "C" int hipstr_flank_assemble_dev(hipstr_post_dev_t* pd, const hipstr_fla
                o_seed = ar.add(rq->seed, n*4), o_rreq = ar.add(rq->read_req, n*4), o_args = ar.add(&h, sizeof h);
   if (ar.reserve(V.ctx)) return 1;
   // what comes home (one copy), then the pool
-  size_t tot = 0;
-  auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
-  const size_t r_used = take(8), r_k = take(nt*4), r_flag = take(nt*4), r_np = take(nt*4), r_size = take(nt*4*HS_FLK_SIZES), r_at = take(nt*4);
-  const size_t res_bytes = tot;
-  const size_t d_pool = take((size_t)pool_cap);
-  struct Blocks {                      // back to the caches behind the stream, whichever way the call leaves
-    hipstr::Ctx* ctx; hipStream_t st; char* dev = NULL; char* pin = NULL; char* pin2 = NULL;
-    ~Blocks(){ if (dev || pin || pin2) hipStreamSynchronize(st); if (dev) hipstr::dev_free(ctx, dev); if (pin) hipstr::pin_free(ctx, pin); if (pin2) hipstr::pin_free(ctx, pin2); }
-  } B{V.ctx, st};
-  B.dev = (char*)hipstr::dev_alloc(V.ctx, tot);
-  if (!B.dev) return 1;
-  B.pin = (char*)hipstr::pin_alloc(V.ctx, res_bytes);
-  if (!B.pin) return 1;
+  hipstr::ResultBlocks B;
+  const size_t r_used = B.take(8), r_k = B.take(nt*4), r_flag = B.take(nt*4), r_np = B.take(nt*4), r_size = B.take(nt*4*HS_FLK_SIZES), r_at = B.take(nt*4);
+  B.end_results();
+  const size_t d_pool = B.take((size_t)pool_cap);
+  if (B.reserve(V.ctx, st)) return 1;
   h.units = V.d_units; h.task_unit = ar.at<int32_t>(o_unit); h.task_lf = ar.at<int32_t>(o_lf); h.task_skip = ar.at<uint8_t>(o_skip);
   h.ref_off = ar.at<int32_t>(o_roff); h.ref_seq = ar.at<char>(o_rseq); h.kmer0 = ar.at<int32_t>(o_kmer); h.max_k = ar.at<int32_t>(o_maxk);
   h.seed = ar.at<int32_t>(o_seed); h.read_req = ar.at<int32_t>(o_rreq);
   h.flank_off = td->off[2]; h.flank_seq = td->arr[2]; h.flank_total = td->totals[2];
-  h.task_k = (int32_t*)(B.dev + r_k); h.task_flag = (int32_t*)(B.dev + r_flag); h.task_np = (int32_t*)(B.dev + r_np); h.task_size = (int32_t*)(B.dev + r_size);
-  h.task_at = (int32_t*)(B.dev + r_at);
-  h.pool = B.dev + d_pool; h.pool_used = (unsigned long long*)(B.dev + r_used); h.pool_cap = pool_cap;
+  h.task_k = B.dev<int32_t>(r_k); h.task_flag = B.dev<int32_t>(r_flag); h.task_np = B.dev<int32_t>(r_np); h.task_size = B.dev<int32_t>(r_size);
+  h.task_at = B.dev<int32_t>(r_at);
+  h.pool = B.dev<char>(d_pool); h.pool_used = B.dev<unsigned long long>(r_used); h.pool_cap = pool_cap;
   h.n_tasks = (int32_t)n_tasks; h.min_path_weight = P.min_path_weight; h.max_paths = P.max_paths;
   h.caps = flank_caps();
   // the run's inputs may still be on their way (a small run sends them asynchronously on its own stream)
-  if (V.ev_up && st != V.stream) FLK_HIP(hipStreamWaitEvent(st, V.ev_up, 0));
+  if (V.ev_up && st != V.stream) HS_HIP(hipStreamWaitEvent(st, V.ev_up, 0));
   if (ar.send(st)) return 1;
-  FLK_HIP(hipMemsetAsync(B.dev + r_used, 0, 8, st));
+  HS_HIP(hipMemsetAsync(B.dev<char>(r_used), 0, 8, st));
   hipLaunchKernelGGL(hs_flank_task_kernel, dim3((unsigned)n_tasks), dim3(HS_FLK_WAVE), 0, st, ar.at<hs_flk_dev_t>(o_args));
-  FLK_HIP(hipGetLastError());
-  FLK_HIP(hipMemcpyAsync(B.pin, B.dev, res_bytes, hipMemcpyDeviceToHost, st));
-  FLK_HIP(hipstr::wait_stream(st));
-  const int64_t used = std::min<int64_t>((int64_t)*(const unsigned long long*)(B.pin + r_used), pool_cap);
-  const char* pool = NULL;
-  if (used > 0){
-    B.pin2 = (char*)hipstr::pin_alloc(V.ctx, (size_t)used);
-    if (!B.pin2) return 1;
-    FLK_HIP(hipMemcpyAsync(B.pin2, B.dev + d_pool, (size_t)used, hipMemcpyDeviceToHost, st));
-    FLK_HIP(hipstr::wait_stream(st));
-    pool = B.pin2;
-  }
-  const int32_t *tk = (const int32_t*)(B.pin + r_k), *tf = (const int32_t*)(B.pin + r_flag), *tn = (const int32_t*)(B.pin + r_np),
-                *pa = (const int32_t*)(B.pin + r_at);
+  HS_HIP(hipGetLastError());
+  if (B.fetch()) return 1;
+  const int64_t used = std::min<int64_t>((int64_t)*B.host<unsigned long long>(r_used), pool_cap);
+  std::vector<char> pool_h((size_t)std::max<int64_t>(used, 0));       // the part of the pool in use, in a copy of its own
+  if (used > 0 && hipstr::fetch_to_host(V.ctx, st, pool_h.data(), B.dev<char>(d_pool), (size_t)used)) return 1;
+  const char* pool = pool_h.data();
+  const int32_t *tk = B.host<int32_t>(r_k), *tf = B.host<int32_t>(r_flag), *tn = B.host<int32_t>(r_np), *pa = B.host<int32_t>(r_at);
   g_last_flags.assign(tf, tf + nt);
-  g_last_sizes.assign((const int32_t*)(B.pin + r_size), (const int32_t*)(B.pin + r_size) + nt*HS_FLK_SIZES);
-  g_last[0] = n_tasks; g_last[4] = (int64_t)ar.total; g_last[5] = (int64_t)res_bytes + used;
+  g_last_sizes.assign(B.host<int32_t>(r_size), B.host<int32_t>(r_size) + nt*HS_FLK_SIZES);
+  g_last[0] = n_tasks; g_last[4] = (int64_t)ar.total; g_last[5] = (int64_t)B.res + used;
   size_t n_fall = 0;
   for (size_t t = 0; t < nt; t++){
     if (tf[t]){ n_fall++; continue; }

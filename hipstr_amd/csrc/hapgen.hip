@@ -415,15 +415,9 @@ static_assert(HS_HAPGEN_MAX_DISTINCT + 3 <= HS_HAPGEN_MAX_DISTINCT + 8, "entries
 // ------------------------------------------------------------------------------------------------------------------------ host side
 using hipstr::api_fail;
 
-struct HapgenLast { int64_t v[8]; double t[4]; };
-thread_local HapgenLast t_last = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}};
+thread_local hipstr::ChunkLast t_last;
 
-int64_t hapgen_budget(double ws_mib){
-  double mib = ws_mib > 0 ? ws_mib : (double)HS_HAPGEN_WS_MIB;
-  if (!(ws_mib > 0)) if (const char* e = getenv("HIPSTR_HAPGEN_WS_MIB")){ const double v = atof(e); if (v > 0) mib = v; }
-  const double bytes = mib*1048576.0;
-  return (int64_t)std::min(std::max(bytes, 4096.0), (double)HS_HAPGEN_MAX_LOCUS_BYTES);
-}
+int64_t hapgen_ws_bytes(double ws_mib){ return hipstr::chunk_budget(ws_mib, "HIPSTR_HAPGEN_WS_MIB", (double)HS_HAPGEN_WS_MIB, (double)HS_HAPGEN_MAX_LOCUS_BYTES); }
 
 // per locus: the route (1 = device) and the workspace it takes
 void hapgen_costs(const hipstr_batch_t* b, const hipstr_hapgen_request_t* rq, std::vector<uint8_t>& dev, std::vector<int64_t>& cost){
@@ -450,33 +444,18 @@ struct NoOutputs {
 
 int hapgen_fail(const char* who, const std::string& err){ return api_fail(std::string(who) + ": " + err); }
 
-#define HG_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-struct HapgenBlocks {          // the chunk's blocks go back to the caches however the chunk ends
-  hipstr::Ctx* ctx; hipStream_t st; char* dev = NULL; char* pin_up = NULL; char* pin_res = NULL; bool busy = false;
-  hipEvent_t e0 = NULL, e1 = NULL;
-  ~HapgenBlocks(){
-    if (busy) hipStreamSynchronize(st);
-    if (dev) hipstr::dev_free(ctx, dev);
-    if (pin_up) hipstr::pin_free(ctx, pin_up);
-    if (pin_res) hipstr::pin_free(ctx, pin_res);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-  }
-};
-
 int hapgen_device(const hipstr_batch_t* b, const hipstr_hapgen_request_t* rq, const int32_t* stop_all, hipstr_hapgen_out_t* out){
   const int nl = b->n_loci;
   hipstr::Ctx* ctx = hipstr::api_current_ctx();
   if (!ctx) return 1;
   if (hipstr::api_bind(ctx)) return 1;
   hipStream_t st = hipstr::ctx_stream(ctx);
-  HapgenLast last = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}};
+  hipstr::ChunkLast last;
   t_last = last;                                  // a call that fails on the way reports zeros, not the call before it
   int hash_bits = 64;
   if (const char* e = getenv("HIPSTR_DEBUG_HAPGEN_HASH_BITS")){ const int v = atoi(e); if (v >= 1 && v < 64) hash_bits = v; }
   const bool timing = getenv("HIPSTR_HAPGEN_TIMING") != NULL;
-  const int64_t budget = hapgen_budget(0.0);
+  const int64_t budget = hapgen_ws_bytes(0.0);
   std::vector<uint8_t> dev; std::vector<int64_t> cost;
   if (nl) hapgen_costs(b, rq, dev, cost);
   hipstr_hg::Sink sink{out, 0, 0, 0};
@@ -499,30 +478,22 @@ int hapgen_device(const hipstr_batch_t* b, const hipstr_hapgen_request_t* rq, co
     }
     if (2*B + 2*W > INT32_MAX || n64 + 3*(int64_t)nlc + 1 > INT32_MAX) return api_fail("hipstr_hapgen: a chunk of more than 2^31 bytes (lower HIPSTR_HAPGEN_WS_MIB)");
     const size_t n = (size_t)n64, NL = (size_t)nlc;
-    HapgenBlocks K; K.ctx = ctx; K.st = st;
-    size_t tot = 0;
-    auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
-    const char* R = NULL;
+    hipstr::ChunkBlocks K(ctx, st);
     size_t o_lres = 0, o_eo = 0, o_el = 0, o_dl = 0, o_dr = 0, o_dn = 0, o_ds = 0, o_df = 0, o_oo = 0, o_seq = 0;
     std::vector<int32_t> l_first_opt;
     if (n > 0){
       last.v[3]++; last.v[4] += (int64_t)n;
       // uploaded | workspace | results
-      const size_t u_start = take(n*4), u_stop = take(n*4), u_boff = take(n*4), u_coff = take((n + 1)*4), u_samp = take(n*4), u_rl = take(n*4), u_use = take(n),
-                   u_clen = take((size_t)NC*4), u_cop = take((size_t)NC), u_bases = take((size_t)B), u_lro = take((NL + 1)*4), u_rs0 = take(NL*4), u_rp0 = take(NL*4),
-                   u_per = take(NL*4), u_ns = take(NL*4), u_cf = take(NL*4), u_woff = take((NL + 1)*4), u_win = take((size_t)W), u_bnd = take(NL*16);
-      const size_t up_bytes = tot;
-      const size_t w_hash = take(n*8), w_osrc = take((n + NL)*4), w_olen = take((n + NL)*4), w_lopt = take((NL + 1)*4), w_lseq = take((NL + 1)*4);
-      const size_t res0 = tot;
-      o_lres = take(NL*HS_HAPGEN_LRES*4); o_eo = take(n*4); o_el = take(n*4); o_dl = take(n*4); o_dr = take(n*4); o_dn = take(n*4); o_ds = take(n*4);
-      o_df = take(n*8); o_oo = take((n + 3*NL + 1)*4); o_seq = take((size_t)(B + W));
-      const size_t res_bytes = tot - res0;
-      K.dev = (char*)hipstr::dev_alloc(ctx, tot);
-      if (!K.dev) return 1;
-      K.pin_up = (char*)hipstr::pin_alloc(ctx, up_bytes);
-      if (!K.pin_up) return 1;
-      K.pin_res = (char*)hipstr::pin_alloc(ctx, res_bytes);
-      if (!K.pin_res) return 1;
+      const size_t u_start = K.take(n*4), u_stop = K.take(n*4), u_boff = K.take(n*4), u_coff = K.take((n + 1)*4), u_samp = K.take(n*4), u_rl = K.take(n*4),
+                   u_use = K.take(n), u_clen = K.take((size_t)NC*4), u_cop = K.take((size_t)NC), u_bases = K.take((size_t)B), u_lro = K.take((NL + 1)*4),
+                   u_rs0 = K.take(NL*4), u_rp0 = K.take(NL*4), u_per = K.take(NL*4), u_ns = K.take(NL*4), u_cf = K.take(NL*4), u_woff = K.take((NL + 1)*4),
+                   u_win = K.take((size_t)W), u_bnd = K.take(NL*16);
+      K.end_upload();
+      const size_t w_hash = K.take(n*8), w_osrc = K.take((n + NL)*4), w_olen = K.take((n + NL)*4), w_lopt = K.take((NL + 1)*4), w_lseq = K.take((NL + 1)*4);
+      K.begin_results();
+      o_lres = K.take(NL*HS_HAPGEN_LRES*4); o_eo = K.take(n*4); o_el = K.take(n*4); o_dl = K.take(n*4); o_dr = K.take(n*4); o_dn = K.take(n*4); o_ds = K.take(n*4);
+      o_df = K.take(n*8); o_oo = K.take((n + 3*NL + 1)*4); o_seq = K.take((size_t)(B + W));
+      if (K.reserve()) return 1;
       const auto t0 = std::chrono::steady_clock::now();
       {
         char* U = K.pin_up;
@@ -570,28 +541,20 @@ int hapgen_device(const hipstr_batch_t* b, const hipstr_hapgen_request_t* rq, co
       d.n = (int32_t)n; d.nl = nlc; d.hash_bits = hash_bits;
       const size_t lds = hs_hapgen_lds_bytes(max_reads, max_samp);
       // (the largest size there is, the same in every call: calls of several threads cannot lower it under one another's launch)
-      HG_HIP(hipFuncSetAttribute((const void*)hs_hapgen_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+      HS_HIP(hipFuncSetAttribute((const void*)hs_hapgen_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)hs_hapgen_lds_bytes(HS_HAPGEN_LDS_READS, HS_HAPGEN_MAX_SAMPLES)));
-      if (timing){ HG_HIP(hipEventCreate(&K.e0)); HG_HIP(hipEventCreate(&K.e1)); }
-      K.busy = true;
-      HG_HIP(hipMemcpyAsync(D, K.pin_up, up_bytes, hipMemcpyHostToDevice, st));
-      if (timing) HG_HIP(hipEventRecord(K.e0, st));
+      if (K.upload(timing)) return 1;
       hipLaunchKernelGGL(hs_hapgen_extract_kernel, dim3((unsigned)((n + HG_NT - 1)/HG_NT)), dim3(HG_NT), 0, st, d);
       hipLaunchKernelGGL(hs_hapgen_hash_kernel, dim3((unsigned)((n + HG_NT/64 - 1)/(HG_NT/64))), dim3(HG_NT), 0, st, d);
       hipLaunchKernelGGL(hs_hapgen_group_kernel, dim3((unsigned)nlc), dim3(HG_NT), lds, st, d);
       hipLaunchKernelGGL(hs_hapgen_scan_kernel, dim3(1), dim3(HG_NT), 0, st, d);
       hipLaunchKernelGGL(hs_hapgen_copy_kernel, dim3((unsigned)nlc), dim3(HG_NT), 0, st, d);
-      HG_HIP(hipGetLastError());
-      if (timing) HG_HIP(hipEventRecord(K.e1, st));
-      HG_HIP(hipMemcpyAsync(K.pin_res, D + res0, res_bytes, hipMemcpyDeviceToHost, st));
-      HG_HIP(hipstr::wait_stream(st));
-      K.busy = false;
-      if (timing){ float ms = 0; HG_HIP(hipEventElapsedTime(&ms, K.e0, K.e1)); last.t[0] += ms; }
-      last.t[1] += (double)up_bytes; last.t[2] += (double)res_bytes;
-      R = K.pin_res - res0;
+      HS_HIP(hipGetLastError());
+      if (K.fetch(timing, &last.t[0])) return 1;
+      last.t[1] += (double)K.up_bytes; last.t[2] += (double)K.res_bytes();
       // where a device locus' options start in the chunk's opt_off: the options of the finished loci in front of it
       l_first_opt.assign(NL + 1, 0);
-      const int32_t* lres = (const int32_t*)(R + o_lres);
+      const int32_t* lres = K.host<int32_t>(o_lres);
       for (int lc = 0; lc < nlc; lc++){
         const int32_t* res = lres + HS_HAPGEN_LRES*lc;
         const bool done = lread[lc+1] > lread[lc] && res[HS_HG_STATUS] == 0 && res[HS_HG_REDO] == 0;
@@ -602,7 +565,7 @@ int hapgen_device(const hipstr_batch_t* b, const hipstr_hapgen_request_t* rq, co
       const int lc = l - l0, r0 = b->read_off[l], nr = b->read_off[l+1] - r0;
       if (!dev[l]){ last.v[1]++; hipstr_hg::locus_host(b, rq, stop_all, l, sink); continue; }
       if (nr == 0){ last.v[0]++; hipstr_hg::locus_host(b, rq, stop_all, l, sink); continue; }
-      const int32_t* res = (const int32_t*)(R + o_lres) + HS_HAPGEN_LRES*lc;
+      const int32_t* res = K.host<int32_t>(o_lres) + HS_HAPGEN_LRES*lc;
       if (res[HS_HG_REDO] == 2){ last.v[1]++; hipstr_hg::locus_host(b, rq, stop_all, l, sink); continue; }
       if (res[HS_HG_REDO]){ last.v[2]++; hipstr_hg::locus_host(b, rq, stop_all, l, sink); continue; }
       last.v[0]++;
@@ -610,8 +573,8 @@ int hapgen_device(const hipstr_batch_t* b, const hipstr_hapgen_request_t* rq, co
       out->status[l] = res[HS_HG_STATUS]; out->min_aln_start[l] = res[HS_HG_MIN]; out->max_aln_stop[l] = res[HS_HG_MAX];
       out->n_spanning[l] = res[HS_HG_SPAN]; out->n_samples_spanning[l] = res[HS_HG_SAMP]; out->n_distinct[l] = res[HS_HG_DIST];
       out->left_trim[l] = res[HS_HG_LT]; out->right_trim[l] = res[HS_HG_RT];
-      if (out->ext_off) memcpy(out->ext_off + r0, (const int32_t*)(R + o_eo) + cr0, (size_t)nr*4);
-      if (out->ext_len) memcpy(out->ext_len + r0, (const int32_t*)(R + o_el) + cr0, (size_t)nr*4);
+      if (out->ext_off) memcpy(out->ext_off + r0, K.host<int32_t>(o_eo) + cr0, (size_t)nr*4);
+      if (out->ext_len) memcpy(out->ext_len + r0, K.host<int32_t>(o_el) + cr0, (size_t)nr*4);
       if (res[HS_HG_STATUS] != 0){
         for (int k = 0; k < 3; k++) out->blk_start[3*l+k] = out->blk_end[3*l+k] = out->blk_nopts[3*l+k] = 0;
         continue;
@@ -620,16 +583,16 @@ int hapgen_device(const hipstr_batch_t* b, const hipstr_hapgen_request_t* rq, co
       out->blk_start[3*l] = res[HS_HG_B0S]; out->blk_end[3*l] = res[HS_HG_B1S]; out->blk_nopts[3*l] = 1;
       out->blk_start[3*l+1] = res[HS_HG_B1S]; out->blk_end[3*l+1] = res[HS_HG_B1E]; out->blk_nopts[3*l+1] = nopts;
       out->blk_start[3*l+2] = res[HS_HG_B1E]; out->blk_end[3*l+2] = res[HS_HG_B2E]; out->blk_nopts[3*l+2] = 1;
-      const int32_t* co = (const int32_t*)(R + o_oo) + l_first_opt[lc];
+      const int32_t* co = K.host<int32_t>(o_oo) + l_first_opt[lc];
       const int ne = nopts + 2, q0 = co[0], qn = co[ne] - q0;
       for (int e = 0; e < ne; e++) out->opt_off[sink.opts + e + 1] = (int32_t)(sink.seq + (co[e+1] - q0));
-      if (qn) memcpy(out->seq + sink.seq, R + o_seq + q0, (size_t)qn);
+      if (qn) memcpy(out->seq + sink.seq, K.host<char>(o_seq) + q0, (size_t)qn);
       sink.opts += ne; sink.seq += qn;
-      if (out->dist_len) memcpy(out->dist_len + sink.dist, (const int32_t*)(R + o_dl) + cr0, (size_t)D*4);
-      if (out->dist_reads) memcpy(out->dist_reads + sink.dist, (const int32_t*)(R + o_dn) + cr0, (size_t)D*4);
-      if (out->dist_strong) memcpy(out->dist_strong + sink.dist, (const int32_t*)(R + o_ds) + cr0, (size_t)D*4);
-      if (out->dist_frac) memcpy(out->dist_frac + sink.dist, (const double*)(R + o_df) + cr0, (size_t)D*8);
-      if (out->dist_rep){ const int32_t* dr = (const int32_t*)(R + o_dr) + cr0; for (int k = 0; k < D; k++) out->dist_rep[sink.dist + k] = dr[k] - cr0 + r0; }
+      if (out->dist_len) memcpy(out->dist_len + sink.dist, K.host<int32_t>(o_dl) + cr0, (size_t)D*4);
+      if (out->dist_reads) memcpy(out->dist_reads + sink.dist, K.host<int32_t>(o_dn) + cr0, (size_t)D*4);
+      if (out->dist_strong) memcpy(out->dist_strong + sink.dist, K.host<int32_t>(o_ds) + cr0, (size_t)D*4);
+      if (out->dist_frac) memcpy(out->dist_frac + sink.dist, K.host<double>(o_df) + cr0, (size_t)D*8);
+      if (out->dist_rep){ const int32_t* dr = K.host<int32_t>(o_dr) + cr0; for (int k = 0; k < D; k++) out->dist_rep[sink.dist + k] = dr[k] - cr0 + r0; }
       sink.dist += D;
     }
     l0 = l1;
@@ -689,7 +652,7 @@ extern "C" int hipstr_debug_hapgen_plan(const hipstr_batch_t* b, const hipstr_ha
   if (!b || !rq){ api_fail("hipstr_debug_hapgen_plan: null argument"); return -1; }
   { NoOutputs none; std::vector<int32_t> stop; std::string err; if (hipstr_hg::check(b, rq, &none.o, false, stop, err)){ hapgen_fail("hipstr_debug_hapgen_plan", err); return -1; } }
   const int nl = b->n_loci;
-  const int64_t budget = hapgen_budget(ws_mib);
+  const int64_t budget = hapgen_ws_bytes(ws_mib);
   std::vector<uint8_t> dev; std::vector<int64_t> cost;
   if (nl) hapgen_costs(b, rq, dev, cost);
   std::string s = "{\"thresholds\": {";

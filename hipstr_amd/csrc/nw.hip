@@ -171,9 +171,6 @@ __global__ void __launch_bounds__(64) hs_nw_walk(const hs_nw_dev_t* __restrict__
   d.lead_col[p] = col;
 }
 
-#define NW_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
-  hipstr::api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
-
 // ---- launch decisions: the one place each is taken.  hipstr_nw_align calls them, hipstr_debug_nw_plan reports them
 // (tests/test_stage_routes.py pins a case on each side of every limit)
 const int kNwRows[HS_NW_RUNGS] = { 1, 2, 3, 4, 6, 8, 12, 16, 24 };       // rows per lane of the fill kernel instantiations
@@ -208,29 +205,6 @@ template <typename Pairs> int nw_chunk_end(const Pairs& pairs, int p0, int n, in
   }
   return p1;
 }
-
-struct NwBufs {
-  std::vector<void*> p;
-  hipstr::Ctx* ctx = NULL;          // blocks come from (and return to) the context's cache: no hipMalloc / hipFree per call
-  // the cache serves other host threads: nothing this call queued may still be running on the blocks when they go back (error paths leave early)
-  hipStream_t streams[3] = {NULL, NULL, NULL}; int n_streams = 0;
-  void runs_on(hipStream_t st){ for (int i = 0; i < n_streams; i++) if (streams[i] == st) return; if (n_streams < 3) streams[n_streams++] = st; }
-  ~NwBufs(){ if (ctx){ for (int i = 0; i < n_streams; i++) hipStreamSynchronize(streams[i]); for (void* x : p) hipstr::dev_free(ctx, x); } }
-  template <typename T> int alloc(T** out, size_t count){
-    *out = NULL;
-    if (!ctx) ctx = hipstr::api_current_ctx();
-    if (!ctx) return 1;
-    *out = (T*)hipstr::dev_alloc(ctx, (count ? count : 1)*sizeof(T));
-    if (!*out) return 1;
-    p.push_back(*out);
-    return 0;
-  }
-  template <typename T> int put(T** out, const T* src, size_t count){
-    if (alloc(out, count)) return 1;
-    if (count) NW_HIP(hipMemcpy(*out, src, count*sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-  }
-};
 
 }  // namespace
 
@@ -267,7 +241,7 @@ extern "C" int hipstr_nw_align(const hipstr_nw_batch_t* nb, hipstr_nw_out_t* o){
     int64_t all = 0; for (int i = 0; i < n; i++) all += nw_pair_bytes(pairs[i].L1, pairs[i].L2);
     if (nw_asks_device(all)){
       size_t free_b = 0, total_b = 0;
-      NW_HIP(hipMemGetInfo(&free_b, &total_b));
+      HS_HIP(hipMemGetInfo(&free_b, &total_b));
       budget = std::min<int64_t>((int64_t)8 << 30, (int64_t)(free_b / 4));
     }
   }
@@ -288,7 +262,7 @@ extern "C" int hipstr_nw_align(const hipstr_nw_batch_t* nb, hipstr_nw_out_t* o){
       for (int i = p0; i < p1; i++) if (nw_rung(pairs[i].L2) == cl) items.push_back(i - p0);
     }
     cls_begin[HS_NW_RUNGS] = items.size();
-    NwBufs ws;
+    hipstr::ScratchBufs ws;
     ws.runs_on(T.stream);
     hs_nw_dev_t hc = h;
     if (ws.alloc(&hc.trace, tb) || ws.alloc(&hc.last, lf)) return 1;
@@ -318,12 +292,12 @@ extern "C" int hipstr_nw_align(const hipstr_nw_batch_t* nb, hipstr_nw_out_t* o){
 #undef NW_LAUNCH
     }
     hipLaunchKernelGGL(hs_nw_walk, dim3((np + 63)/64), dim3(64), 0, T.stream, d_args, np);
-    NW_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
     char* hostblk = (char*)hipstr::pin_alloc(T.ctx, r_end);
     if (!hostblk) return api_fail("out of pinned host memory");
     struct PinGuard { hipstr::Ctx* c; void* p; ~PinGuard(){ hipstr::pin_free(c, p); } } pin_guard{T.ctx, hostblk};
-    NW_HIP(hipMemcpyAsync(hostblk, d_res, r_end, hipMemcpyDeviceToHost, T.stream));
-    NW_HIP(hipstr::wait_stream(T.stream));
+    HS_HIP(hipMemcpyAsync(hostblk, d_res, r_end, hipMemcpyDeviceToHost, T.stream));
+    HS_HIP(hipstr::wait_stream(T.stream));
     const float* score = (const float*)(hostblk + r_score); const int32_t* bcol = (const int32_t*)(hostblk + r_bcol);
     const int32_t* lcol = (const int32_t*)(hostblk + r_lcol); const int32_t* nops = (const int32_t*)(hostblk + r_nops);
     struct { const char* p; const char* data() const { return p; } } ops{hostblk + r_ops};

@@ -242,15 +242,9 @@ static_assert(HS_POOL_NET == 8, "the sorting network of hs_pool_median_kernel is
 // ------------------------------------------------------------------------------------------------------------------------ host side
 using hipstr::api_fail;
 
-struct PoolLast { int64_t v[8]; double t[4]; };
-thread_local PoolLast t_last = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}};
+thread_local hipstr::ChunkLast t_last;
 
-int64_t pool_budget(double ws_mib){
-  double mib = ws_mib > 0 ? ws_mib : (double)HS_POOL_WS_MIB;
-  if (!(ws_mib > 0)) if (const char* e = getenv("HIPSTR_POOL_WS_MIB")){ const double v = atof(e); if (v > 0) mib = v; }
-  const double bytes = mib*1048576.0;
-  return (int64_t)std::min(std::max(bytes, 4096.0), (double)HS_POOL_MAX_LOCUS_BYTES);
-}
+int64_t pool_ws_bytes(double ws_mib){ return hipstr::chunk_budget(ws_mib, "HIPSTR_POOL_WS_MIB", (double)HS_POOL_WS_MIB, (double)HS_POOL_MAX_LOCUS_BYTES); }
 
 // per locus: the route (1 = device) and the workspace it takes
 void pool_costs(const hipstr_batch_t* b, std::vector<uint8_t>& dev, std::vector<int64_t>& cost){
@@ -275,33 +269,18 @@ int pool_check(const hipstr_batch_t* b, const hipstr_pool_out_t* out, const char
   return 0;
 }
 
-#define POOL_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-struct PoolBlocks {          // the chunk's blocks go back to the caches however the chunk ends
-  hipstr::Ctx* ctx; hipStream_t st; char* dev = NULL; char* pin_up = NULL; char* pin_res = NULL; bool busy = false;
-  hipEvent_t e0 = NULL, e1 = NULL;
-  ~PoolBlocks(){
-    if (busy) hipStreamSynchronize(st);
-    if (dev) hipstr::dev_free(ctx, dev);
-    if (pin_up) hipstr::pin_free(ctx, pin_up);
-    if (pin_res) hipstr::pin_free(ctx, pin_res);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-  }
-};
-
 int pool_reads_device(const hipstr_batch_t* b, hipstr_pool_out_t* out){
   const int nl = b->n_loci;
   hipstr::Ctx* ctx = hipstr::api_current_ctx();
   if (!ctx) return 1;
   if (hipstr::api_bind(ctx)) return 1;
   hipStream_t st = hipstr::ctx_stream(ctx);
-  PoolLast last = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0}};
+  hipstr::ChunkLast last;
   t_last = last;                                  // a call that fails on the way reports zeros, not the call before it
   int hash_bits = 64;
   if (const char* e = getenv("HIPSTR_DEBUG_POOL_HASH_BITS")){ const int v = atoi(e); if (v >= 1 && v < 64) hash_bits = v; }
   const bool timing = getenv("HIPSTR_POOL_TIMING") != NULL;
-  const int64_t budget = pool_budget(0.0);
+  const int64_t budget = pool_ws_bytes(0.0);
   std::vector<uint8_t> dev; std::vector<int64_t> cost;
   pool_costs(b, dev, cost);
   hipstr_pool::Sink sink{out, 0, 0};
@@ -322,33 +301,25 @@ int pool_reads_device(const hipstr_batch_t* b, hipstr_pool_out_t* out){
     }
     if (B > INT32_MAX || n64 > INT32_MAX) return api_fail("hipstr_pool_reads: a chunk of more than 2^31 bytes (lower HIPSTR_POOL_WS_MIB)");
     const size_t n = (size_t)n64;
-    PoolBlocks K; K.ctx = ctx; K.st = st;
-    size_t tot = 0;
-    auto take = [&](size_t bytes){ const size_t off = tot; tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
+    hipstr::ChunkBlocks K(ctx, st);
     const int32_t* r_pi = NULL, *r_np = NULL, *r_coll = NULL, *r_po = NULL, *r_qb = NULL, *r_rep = NULL, *r_size = NULL, *r_qoff = NULL; const char* r_quals = NULL;
     if (n > 0){
       last.v[6]++; last.v[7] += (int64_t)n;
       // uploaded | workspace | results
-      const size_t u_len = take(n*4), u_doff = take(n*4), u_lro = take(((size_t)nlc + 1)*4), u_bases = take((size_t)B), u_quals = take((size_t)B);
-      const size_t up_bytes = tot;
-      const size_t w_hash = take(n*8), w_mem = take(n*4), w_rep = take(n*4), w_size = take(n*4), w_qoff = take(n*4), w_moff = take(n*4),
-                   w_sl = take(n*4), w_qbytes = take((size_t)nlc*4);
-      const size_t res0 = tot;
-      const size_t o_pi = take(n*4), o_np = take((size_t)nlc*4), o_coll = take((size_t)nlc*4), o_po = take(((size_t)nlc + 1)*4),
-                   o_qb = take(((size_t)nlc + 1)*4), o_rep = take(n*4), o_size = take(n*4), o_qoff = take(n*4), o_quals = take((size_t)Bq);
-      const size_t res_bytes = tot - res0;
-      K.dev = (char*)hipstr::dev_alloc(ctx, tot);
-      if (!K.dev) return 1;
-      K.pin_up = (char*)hipstr::pin_alloc(ctx, up_bytes);
-      if (!K.pin_up) return 1;
-      K.pin_res = (char*)hipstr::pin_alloc(ctx, res_bytes);
-      if (!K.pin_res) return 1;
+      const size_t u_len = K.take(n*4), u_doff = K.take(n*4), u_lro = K.take(((size_t)nlc + 1)*4), u_bases = K.take((size_t)B), u_quals = K.take((size_t)B);
+      K.end_upload();
+      const size_t w_hash = K.take(n*8), w_mem = K.take(n*4), w_rep = K.take(n*4), w_size = K.take(n*4), w_qoff = K.take(n*4), w_moff = K.take(n*4),
+                   w_sl = K.take(n*4), w_qbytes = K.take((size_t)nlc*4);
+      K.begin_results();
+      const size_t o_pi = K.take(n*4), o_np = K.take((size_t)nlc*4), o_coll = K.take((size_t)nlc*4), o_po = K.take(((size_t)nlc + 1)*4),
+                   o_qb = K.take(((size_t)nlc + 1)*4), o_rep = K.take(n*4), o_size = K.take(n*4), o_qoff = K.take(n*4), o_quals = K.take((size_t)Bq);
+      if (K.reserve()) return 1;
       // the reads, every one on a 16-byte boundary, the last piece of its bases filled up with zeros
       const auto t0 = std::chrono::steady_clock::now();
       {
-        int32_t* len_h = (int32_t*)(K.pin_up + u_len), *doff_h = (int32_t*)(K.pin_up + u_doff);
-        memcpy(K.pin_up + u_lro, lread.data(), ((size_t)nlc + 1)*4);
-        char* bases_h = K.pin_up + u_bases, *quals_h = K.pin_up + u_quals;
+        int32_t* len_h = K.up<int32_t>(u_len), *doff_h = K.up<int32_t>(u_doff);
+        memcpy(K.up<char>(u_lro), lread.data(), ((size_t)nlc + 1)*4);
+        char* bases_h = K.up<char>(u_bases), *quals_h = K.up<char>(u_quals);
         size_t i = 0; int64_t off = 0;
         for (int l = l0; l < l1; l++){
           if (!dev[l]) continue;
@@ -374,27 +345,19 @@ int pool_reads_device(const hipstr_batch_t* b, hipstr_pool_out_t* out){
       d.n = (int32_t)n; d.nl = nlc; d.hash_bits = hash_bits;
       const size_t lds = hs_pool_lds_bytes(max_reads);
       // (the largest size there is, the same in every call: calls of several threads cannot lower it under one another's launch)
-      POOL_HIP(hipFuncSetAttribute((const void*)hs_pool_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hs_pool_lds_bytes(HS_POOL_LDS_READS)));
-      if (timing){ POOL_HIP(hipEventCreate(&K.e0)); POOL_HIP(hipEventCreate(&K.e1)); }
-      K.busy = true;
-      POOL_HIP(hipMemcpyAsync(D, K.pin_up, up_bytes, hipMemcpyHostToDevice, st));
-      if (timing) POOL_HIP(hipEventRecord(K.e0, st));
+      HS_HIP(hipFuncSetAttribute((const void*)hs_pool_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hs_pool_lds_bytes(HS_POOL_LDS_READS)));
+      if (K.upload(timing)) return 1;
       const unsigned per_wave = (unsigned)((n + HS_POOL_THREADS/64 - 1)/(HS_POOL_THREADS/64));
       hipLaunchKernelGGL(hs_pool_hash_kernel, dim3(per_wave), dim3(HS_POOL_THREADS), 0, st, d);
       hipLaunchKernelGGL(hs_pool_group_kernel, dim3((unsigned)nlc), dim3(HS_POOL_THREADS), lds, st, d);
       hipLaunchKernelGGL(hs_pool_scan_kernel, dim3(1), dim3(HS_POOL_THREADS), 0, st, d);
       hipLaunchKernelGGL(hs_pool_median_kernel, dim3(per_wave), dim3(HS_POOL_THREADS), 0, st, d);
-      POOL_HIP(hipGetLastError());
-      if (timing) POOL_HIP(hipEventRecord(K.e1, st));
-      POOL_HIP(hipMemcpyAsync(K.pin_res, D + res0, res_bytes, hipMemcpyDeviceToHost, st));
-      POOL_HIP(hipstr::wait_stream(st));
-      K.busy = false;
-      if (timing){ float ms = 0; POOL_HIP(hipEventElapsedTime(&ms, K.e0, K.e1)); last.t[0] += ms; }
-      last.t[1] += (double)up_bytes; last.t[2] += (double)res_bytes;
-      const char* R = K.pin_res - res0;
-      r_pi = (const int32_t*)(R + o_pi); r_np = (const int32_t*)(R + o_np); r_coll = (const int32_t*)(R + o_coll); r_po = (const int32_t*)(R + o_po);
-      r_qb = (const int32_t*)(R + o_qb); r_rep = (const int32_t*)(R + o_rep); r_size = (const int32_t*)(R + o_size); r_qoff = (const int32_t*)(R + o_qoff);
-      r_quals = R + o_quals;
+      HS_HIP(hipGetLastError());
+      if (K.fetch(timing, &last.t[0])) return 1;
+      last.t[1] += (double)K.up_bytes; last.t[2] += (double)K.res_bytes();
+      r_pi = K.host<int32_t>(o_pi); r_np = K.host<int32_t>(o_np); r_coll = K.host<int32_t>(o_coll); r_po = K.host<int32_t>(o_po);
+      r_qb = K.host<int32_t>(o_qb); r_rep = K.host<int32_t>(o_rep); r_size = K.host<int32_t>(o_size); r_qoff = K.host<int32_t>(o_qoff);
+      r_quals = K.host<char>(o_quals);
     }
     if (l0 == 0){ out->pool_off[0] = 0; out->pool_qual_off[0] = 0; }
     for (int l = l0; l < l1; l++){
@@ -485,7 +448,7 @@ extern "C" int hipstr_debug_pool_plan(const hipstr_batch_t* b, double ws_mib, ch
   if (!b){ api_fail("hipstr_debug_pool_plan: null argument"); return -1; }
   { std::string bad; if (hipstr::validate_tables(b, bad)){ api_fail("hipstr_debug_pool_plan: " + bad); return -1; } }
   const int nl = b->n_loci;
-  const int64_t budget = pool_budget(ws_mib);
+  const int64_t budget = pool_ws_bytes(ws_mib);
   std::vector<uint8_t> dev; std::vector<int64_t> cost;
   pool_costs(b, dev, cost);
   PoolArrays A(b);

@@ -989,31 +989,6 @@ __global__ void __launch_bounds__(64) hs_trace_compact(const hs_tdev_t* __restri
 }
 
 // ------------------------------------------------------------------ host side
-#define TR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess){ \
-  hipstr::api_fail(std::string(#call) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
-
-struct DevBufs {
-  std::vector<void*> p;
-  hipstr::Ctx* ctx = NULL;          // blocks come from (and return to) the context's cache: no hipMalloc / hipFree per call
-  // the cache serves other host threads: nothing this call queued may still be running on the blocks when they go back (error paths leave early)
-  hipStream_t streams[3] = {NULL, NULL, NULL}; int n_streams = 0;
-  void runs_on(hipStream_t st){ for (int i = 0; i < n_streams; i++) if (streams[i] == st) return; if (n_streams < 3) streams[n_streams++] = st; }
-  ~DevBufs(){ if (ctx){ for (int i = 0; i < n_streams; i++) hipStreamSynchronize(streams[i]); for (void* x : p) hipstr::dev_free(ctx, x); } }
-  template <typename T> int alloc(T** out, size_t count){
-    *out = NULL;
-    if (!ctx) ctx = hipstr::api_current_ctx();
-    if (!ctx) return 1;
-    *out = (T*)hipstr::dev_alloc(ctx, (count ? count : 1)*sizeof(T));
-    if (!*out) return 1;
-    p.push_back(*out);
-    return 0;
-  }
-  template <typename T> int put(T** out, const T* src, size_t count){
-    if (alloc(out, count)) return 1;
-    if (count) TR_HIP(hipMemcpy(*out, src, count*sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-  }
-};
 
 // ---- launch decisions: the one place each is taken.  hipstr_hmm_trace_seeded calls them, hipstr_debug_trace_plan reports them
 // (tests/test_stage_routes.py pins a case on each side of every limit)
@@ -1201,13 +1176,12 @@ static_assert(HS_TRACE_DEV_POOLS == HS_ASM_POOLS, "a resident pool per assembled
 struct TraceDevLayout {
   size_t ll, mxi, scal[5], off[HS_TRACE_DEV_POOLS], arr[HS_TRACE_DEV_ARRAYS], bytes;
   TraceDevLayout(size_t n, const int64_t tot[HS_TRACE_DEV_POOLS]){
-    size_t t = 0;
-    auto take = [&](size_t nb){ const size_t at = t; t = (t + (nb ? nb : 1) + 255) & ~(size_t)255; return at; };
-    ll = take(n*8); mxi = take(n*4);
-    for (int i = 0; i < 5; i++) scal[i] = take(n*4);
-    for (int p = 0; p < HS_TRACE_DEV_POOLS; p++) off[p] = take(((size_t)hs_asm_pool_n(p, (int)n) + 1)*4);
-    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) arr[a] = take((size_t)tot[TD_ARR_POOL[a]]*TD_ARR_ESZ[a]);
-    bytes = t;
+    hipstr::BlockPieces P;
+    ll = P.take(n*8); mxi = P.take(n*4);
+    for (int i = 0; i < 5; i++) scal[i] = P.take(n*4);
+    for (int p = 0; p < HS_TRACE_DEV_POOLS; p++) off[p] = P.take(((size_t)hs_asm_pool_n(p, (int)n) + 1)*4);
+    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) arr[a] = P.take((size_t)tot[TD_ARR_POOL[a]]*TD_ARR_ESZ[a]);
+    bytes = P.tot;
   }
 };
 // a handle of n requests and these totals on a fresh block of the context's cache; NULL + last error
@@ -1234,8 +1208,8 @@ struct TraceSegs {
 // call does with a chunk's pools and hipstr_trace_dev_fetch with the chosen arrays.
 struct HomePiece { const void* dev; size_t bytes; void* dst; size_t pin_off; };
 int copy_home(hipStream_t st, char* pin, const std::vector<HomePiece>& v){
-  for (const HomePiece& h : v) if (h.bytes) TR_HIP(hipMemcpyAsync(pin + h.pin_off, h.dev, h.bytes, hipMemcpyDeviceToHost, st));
-  TR_HIP(hipstr::wait_stream(st));
+  for (const HomePiece& h : v) if (h.bytes) HS_HIP(hipMemcpyAsync(pin + h.pin_off, h.dev, h.bytes, hipMemcpyDeviceToHost, st));
+  HS_HIP(hipstr::wait_stream(st));
   for (const HomePiece& h : v) if (h.bytes) memcpy(h.dst, pin + h.pin_off, h.bytes);
   return 0;
 }
@@ -1367,7 +1341,7 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
 
   const auto t_prep = now();
   // ---- static device data
-  DevBufs dev;
+  hipstr::ScratchBufs dev;
   dev.runs_on(T.stream);
   hs_tdev_t h; memset(&h, 0, sizeof h);
   const int total_bases = b->base_off[n_reads];
@@ -1428,7 +1402,7 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
     }
     if (trace_asks_device(rough)){
       size_t free_b = 0, total_b = 0;
-      TR_HIP(hipMemGetInfo(&free_b, &total_b));
+      HS_HIP(hipMemGetInfo(&free_b, &total_b));
       budget = std::min<int64_t>((int64_t)8 << 30, (int64_t)(free_b / 4));
     }
   }
@@ -1598,12 +1572,12 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
       ac.reqs = ch_arena.at<hs_areq_t>(o_areq); ac.nq = nq;
       for (int p = 0; p < HS_ASM_POOLS; p++) ac.base[p] = pool_total[p];
       hipEvent_t ev[2] = {NULL, NULL};
-      if (timing){ TR_HIP(hipEventCreate(&ev[0])); TR_HIP(hipEventCreate(&ev[1])); TR_HIP(hipEventRecord(ev[0], T.stream)); }
+      if (timing){ HS_HIP(hipEventCreate(&ev[0])); HS_HIP(hipEventCreate(&ev[1])); HS_HIP(hipEventRecord(ev[0], T.stream)); }
       hipLaunchKernelGGL(hs_trace_assemble, dim3(nq), dim3(64), 0, T.stream, d_args, ac);
       hipLaunchKernelGGL(hs_trace_scan, dim3(HS_ASM_POOLS + 1), dim3(64), 0, T.stream, ac);
       hipLaunchKernelGGL(hs_trace_compact, dim3(nq), dim3(64), 0, T.stream, d_args, ac);
-      if (timing) TR_HIP(hipEventRecord(ev[1], T.stream));
-      TR_HIP(hipGetLastError());
+      if (timing) HS_HIP(hipEventRecord(ev[1], T.stream));
+      HS_HIP(hipGetLastError());
       const auto c2 = now();
       struct PinGuard { hipstr::Ctx* c; void* p; ~PinGuard(){ hipstr::pin_free(c, p); } };
       if (res){
@@ -1612,8 +1586,8 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
         char* tb = (char*)hipstr::pin_alloc(T.ctx, ao_scal);
         if (!tb) return api_fail("out of pinned host memory");
         PinGuard tb_guard{T.ctx, tb};
-        TR_HIP(hipMemcpyAsync(tb, d_out, ao_scal, hipMemcpyDeviceToHost, T.stream));
-        TR_HIP(hipstr::wait_stream(T.stream));
+        HS_HIP(hipMemcpyAsync(tb, d_out, ao_scal, hipMemcpyDeviceToHost, T.stream));
+        HS_HIP(hipstr::wait_stream(T.stream));
         if (timing){ hipEventDestroy(ev[0]); hipEventDestroy(ev[1]); }
         const int64_t* tot = (const int64_t*)tb;
         if (*(const int32_t*)(tb + HS_ASM_POOLS*8) >= 0) return api_fail("internal error: inconsistent traceback operation string");
@@ -1626,15 +1600,15 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
         if (!sg) return 1;
         segs.v.push_back(sg); segs.q0.push_back(q0);
         auto d2d = [&](void* dst, const void* src, size_t nb){ return nb ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, T.stream) : hipSuccess; };
-        TR_HIP(d2d(sg->ll, hc.ll, (size_t)nq*8)); TR_HIP(d2d(sg->max_index, hc.max_index, (size_t)nq*4));
-        for (int i = 0; i < 5; i++) TR_HIP(d2d(sg->scal[i], ad.stutter_size + (size_t)i*max_nq, (size_t)nq*4));
+        HS_HIP(d2d(sg->ll, hc.ll, (size_t)nq*8)); HS_HIP(d2d(sg->max_index, hc.max_index, (size_t)nq*4));
+        for (int i = 0; i < 5; i++) HS_HIP(d2d(sg->scal[i], ad.stutter_size + (size_t)i*max_nq, (size_t)nq*4));
         for (int p = 0; p < HS_ASM_POOLS; p++){
-          TR_HIP(hipMemsetAsync(sg->off[p], 0, 4, T.stream));           // (the leading 0: the first chunk's is the result's)
-          TR_HIP(d2d(sg->off[p] + 1, ac.incl + hs_asm_pool_at(p, nq), (size_t)hs_asm_pool_n(p, nq)*4));
+          HS_HIP(hipMemsetAsync(sg->off[p], 0, 4, T.stream));           // (the leading 0: the first chunk's is the result's)
+          HS_HIP(d2d(sg->off[p] + 1, ac.incl + hs_asm_pool_at(p, nq), (size_t)hs_asm_pool_n(p, nq)*4));
         }
         const void* const dense[HS_TRACE_DEV_ARRAYS] = { ac.p_hap_aln, ac.p_str_seq, ac.p_flank, ac.p_indel_pos, ac.p_indel_size, ac.p_snp_pos, ac.p_snp_base,
                                                          ac.p_cig_op, ac.p_cig_len, ac.p_aln };
-        for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) TR_HIP(d2d(sg->arr[a], dense[a], (size_t)cnt[TD_ARR_POOL[a]]*TD_ARR_ESZ[a]));
+        for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) HS_HIP(d2d(sg->arr[a], dense[a], (size_t)cnt[TD_ARR_POOL[a]]*TD_ARR_ESZ[a]));
         for (int p = 0; p < HS_ASM_POOLS; p++) pool_total[p] = tot[p];
         q0 = q1;
         continue;
@@ -1643,11 +1617,11 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
       if (!hostblk) return api_fail("out of pinned host memory");
       PinGuard pin_guard{T.ctx, hostblk};
       char* hout = hostblk + o_nops;
-      TR_HIP(hipMemcpyAsync(hostblk, d_res, o_nops, hipMemcpyDeviceToHost, T.stream));                 // ll, max_index
-      TR_HIP(hipMemcpyAsync(hout, d_out, ao_i32, hipMemcpyDeviceToHost, T.stream));                    // totals, scalars, offsets
-      TR_HIP(hipstr::wait_stream(T.stream));
+      HS_HIP(hipMemcpyAsync(hostblk, d_res, o_nops, hipMemcpyDeviceToHost, T.stream));                 // ll, max_index
+      HS_HIP(hipMemcpyAsync(hout, d_out, ao_i32, hipMemcpyDeviceToHost, T.stream));                    // totals, scalars, offsets
+      HS_HIP(hipstr::wait_stream(T.stream));
       if (timing){
-        float kms = 0; TR_HIP(hipEventElapsedTime(&kms, ev[0], ev[1])); hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
+        float kms = 0; HS_HIP(hipEventElapsedTime(&kms, ev[0], ev[1])); hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
         fprintf(stderr, "  assemble + scan + compact of %d: %.3f ms on the device\n", nq, kms);
       }
       const int64_t* tot = (const int64_t*)hout;
@@ -1688,14 +1662,14 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
       ms_alloc += ms(c0, c1); ms_kernel += ms(c1, c2); ms_d2h += ms(c2, c3); ms_replay += ms(c3, c4);
       continue;
     }
-    TR_HIP(hipGetLastError());
+    HS_HIP(hipGetLastError());
     const auto c2 = now();
     // results through one pinned block (a pageable destination costs a staging copy per call and per array), in one copy behind the kernels
     char* hostblk = (char*)hipstr::pin_alloc(T.ctx, o_end);
     if (!hostblk) return api_fail("out of pinned host memory");
     struct PinGuard { hipstr::Ctx* c; void* p; ~PinGuard(){ hipstr::pin_free(c, p); } } pin_guard{T.ctx, hostblk};
-    TR_HIP(hipMemcpyAsync(hostblk, d_res, o_ops + (size_t)(n_ops ? n_ops : 1), hipMemcpyDeviceToHost, T.stream));
-    TR_HIP(hipstr::wait_stream(T.stream));
+    HS_HIP(hipMemcpyAsync(hostblk, d_res, o_ops + (size_t)(n_ops ? n_ops : 1), hipMemcpyDeviceToHost, T.stream));
+    HS_HIP(hipstr::wait_stream(T.stream));
     const double* ll = (const double*)(hostblk + o_ll); const int32_t* mxi = (const int32_t*)(hostblk + o_mxi);
     const int32_t* nops = (const int32_t*)(hostblk + o_nops); const int32_t* ssz = (const int32_t*)(hostblk + o_ssz); const int32_t* spos = (const int32_t*)(hostblk + o_spos);
     const char* opsbuf_p = hostblk + o_ops;
@@ -1852,19 +1826,19 @@ static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req
       struct Drop { hipstr_trace_dev* t; hipStream_t st; ~Drop(){ if (t){ hipStreamSynchronize(st); trace_dev_drop(t); } } } drop{td, T.stream};
       auto d2d = [&](void* dst, const void* src, size_t nb){ return nb ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, T.stream) : hipSuccess; };
       int64_t at[HS_ASM_POOLS] = {0, 0, 0, 0, 0, 0, 0};
-      for (int p = 0; p < HS_ASM_POOLS; p++) TR_HIP(hipMemsetAsync(td->off[p], 0, 4, T.stream));
+      for (int p = 0; p < HS_ASM_POOLS; p++) HS_HIP(hipMemsetAsync(td->off[p], 0, 4, T.stream));
       for (size_t c = 0; c < segs.v.size(); c++){
         const hipstr_trace_dev* sg = segs.v[c]; const int q0 = segs.q0[c], nq = sg->n_req;
-        TR_HIP(d2d(td->ll + q0, sg->ll, (size_t)nq*8)); TR_HIP(d2d(td->max_index + q0, sg->max_index, (size_t)nq*4));
-        for (int i = 0; i < 5; i++) TR_HIP(d2d(td->scal[i] + q0, sg->scal[i], (size_t)nq*4));
-        for (int p = 0; p < HS_ASM_POOLS; p++) TR_HIP(d2d(td->off[p] + hs_asm_pool_n(p, q0) + 1, sg->off[p] + 1, (size_t)hs_asm_pool_n(p, nq)*4));
+        HS_HIP(d2d(td->ll + q0, sg->ll, (size_t)nq*8)); HS_HIP(d2d(td->max_index + q0, sg->max_index, (size_t)nq*4));
+        for (int i = 0; i < 5; i++) HS_HIP(d2d(td->scal[i] + q0, sg->scal[i], (size_t)nq*4));
+        for (int p = 0; p < HS_ASM_POOLS; p++) HS_HIP(d2d(td->off[p] + hs_asm_pool_n(p, q0) + 1, sg->off[p] + 1, (size_t)hs_asm_pool_n(p, nq)*4));
         for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++){
           const int p = TD_ARR_POOL[a];
-          TR_HIP(d2d(td->arr[a] + (size_t)at[p]*TD_ARR_ESZ[a], sg->arr[a], (size_t)sg->totals[p]*TD_ARR_ESZ[a]));
+          HS_HIP(d2d(td->arr[a] + (size_t)at[p]*TD_ARR_ESZ[a], sg->arr[a], (size_t)sg->totals[p]*TD_ARR_ESZ[a]));
         }
         for (int p = 0; p < HS_ASM_POOLS; p++) at[p] += sg->totals[p];
       }
-      TR_HIP(hipstr::wait_stream(T.stream));
+      HS_HIP(hipstr::wait_stream(T.stream));
       drop.t = NULL;
     }
     if (hipstr::wait_stream(T.stream) != hipSuccess){ trace_dev_drop(td); return api_fail("hipstr_hmm_trace_resident: the device failed"); }
@@ -1963,8 +1937,8 @@ extern "C" int hipstr_debug_trace_dev_from_host(const hipstr_trace_out_t* tr, in
     put(L.off[p], off_src[p], ((size_t)hs_asm_pool_n(p, n_req) + 1)*4);
     for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) put(L.arr[a], arr_src[a], (size_t)tot[p]*TD_ARR_ESZ[a]);
   }
-  TR_HIP(hipMemcpyAsync(td->block, pin, L.bytes, hipMemcpyHostToDevice, T.stream));
-  TR_HIP(hipstr::wait_stream(T.stream));
+  HS_HIP(hipMemcpyAsync(td->block, pin, L.bytes, hipMemcpyHostToDevice, T.stream));
+  HS_HIP(hipstr::wait_stream(T.stream));
   td->groups = 0;
   if (tr->ll && tr->max_index && scal_src[0] && scal_src[1] && scal_src[2] && scal_src[3] && scal_src[4]) td->groups |= HIPSTR_TRACE_F_SCALARS;
   const uint32_t bit[HS_TRACE_DEV_POOLS] = { HIPSTR_TRACE_F_HAP_ALN, HIPSTR_TRACE_F_STR_SEQ, HIPSTR_TRACE_F_FLANKS, HIPSTR_TRACE_F_INDELS, HIPSTR_TRACE_F_SNPS, 0, 0 };
