@@ -1152,14 +1152,6 @@ void stitch_dir(const char* hap_aln, int hlen, const std::string& read_aln, int 
   }
 }
 
-bool put_pool(char* pool, int32_t* off, int idx, const std::string& s, int cap){
-  off[idx+1] = off[idx];
-  if ((int64_t)off[idx] + (int64_t)s.size() > cap) return false;
-  memcpy(pool + off[idx], s.data(), s.size());
-  off[idx+1] = off[idx] + (int32_t)s.size();
-  return true;
-}
-
 struct ReqOut {                    // one request's results, built by a worker thread, copied into the flat pools in order
   bool ok = true;
   std::string hap_aln, aln_str;
@@ -1172,6 +1164,9 @@ struct ReqOut {                    // one request's results, built by a worker t
 // same layout for the chunk's requests and elements, so the segment of a call of one chunk IS the result.
 const int TD_ARR_POOL[HS_TRACE_DEV_ARRAYS] = {0, 1, 2, 3, 3, 4, 4, 5, 5, 6};
 const int TD_ARR_ESZ[HS_TRACE_DEV_ARRAYS]  = {1, 1, 1, 4, 4, 4, 1, 1, 4, 1};
+// the fetch group (HIPSTR_TRACE_F_*) of every pool
+const uint32_t TD_POOL_BIT[HS_TRACE_DEV_POOLS] = { HIPSTR_TRACE_F_HAP_ALN, HIPSTR_TRACE_F_STR_SEQ, HIPSTR_TRACE_F_FLANKS, HIPSTR_TRACE_F_INDELS, HIPSTR_TRACE_F_SNPS,
+                                                   HIPSTR_TRACE_F_STITCH, HIPSTR_TRACE_F_STITCH };
 static_assert(HS_TRACE_DEV_POOLS == HS_ASM_POOLS, "a resident pool per assembled pool");
 struct TraceDevLayout {
   size_t ll, mxi, scal[5], off[HS_TRACE_DEV_POOLS], arr[HS_TRACE_DEV_ARRAYS], bytes;
@@ -1214,10 +1209,709 @@ int copy_home(hipStream_t st, char* pin, const std::vector<HomePiece>& v){
   return 0;
 }
 
-}  // namespace
+// ---- the guards of the entry points below: a block or a handle goes back on every way out, after the stream that may still work on it
+// (ResultBlocks' rule, api_internal.h: on the normal path the stream has been waited for already and the wait costs a few microseconds)
+struct PinBlock {
+  hipstr::Ctx* ctx; hipStream_t st; char* p;
+  PinBlock(hipstr::Ctx* c, hipStream_t s, size_t bytes) : ctx(c), st(s), p((char*)hipstr::pin_alloc(c, bytes)) {}
+  PinBlock(const PinBlock&) = delete;
+  ~PinBlock(){ if (p){ hipStreamSynchronize(st); hipstr::pin_free(ctx, p); } }
+};
+struct TraceDevGuard {             // a handle under construction: release() hands it to the caller
+  hipstr_trace_dev* t; hipStream_t st;
+  ~TraceDevGuard(){ if (t){ hipStreamSynchronize(st); trace_dev_drop(t); } }
+  hipstr_trace_dev* release(){ hipstr_trace_dev* r = t; t = NULL; return r; }
+};
+hipError_t d2d(hipStream_t st, void* dst, const void* src, size_t nb){ return nb ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, st) : hipSuccess; }
 
-static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
-                      const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o, hipstr_trace_dev** res);
+// ---- the arrays of a hipstr_trace_out_t, enumerated once: scalars, offsets in pool order, arrays in TD_ARR_POOL's order.  (The struct is
+// all pointers, so a const one serves as a source as well.)
+struct TraceOutView {
+  double* ll; int32_t* max_index;
+  int32_t* scal[5]; int32_t* off[HS_TRACE_DEV_POOLS]; void* arr[HS_TRACE_DEV_ARRAYS];
+  explicit TraceOutView(const hipstr_trace_out_t* t)
+    : ll(t->ll), max_index(t->max_index), scal{t->stutter_size, t->flank_ins, t->flank_del, t->aln_start, t->aln_stop},
+      off{t->hap_aln_off, t->str_seq_off, t->flank_seq_off, t->indel_off, t->snp_off, t->cigar_off, t->aln_str_off},
+      arr{t->hap_aln, t->str_seq, t->flank_seq, t->indel_pos, t->indel_size, t->snp_pos, t->snp_base, t->cigar_op, t->cigar_len, t->aln_str} {}
+};
+// the dense pools of a device-assembled chunk, in the same order
+struct AsmDense { const char* p[HS_TRACE_DEV_ARRAYS]; };
+AsmDense asm_dense(const hs_adev_t& a){
+  return AsmDense{{a.p_hap_aln, a.p_str_seq, a.p_flank, (const char*)a.p_indel_pos, (const char*)a.p_indel_size, (const char*)a.p_snp_pos, a.p_snp_base,
+                   a.p_cig_op, (const char*)a.p_cig_len, a.p_aln}};
+}
+
+// ---- what a request list means: the one walk, for the call and for both plans.  It makes every refusal that depends on the batch and the
+// list alone, in this order: per locus the period, then blocks without options; per request the read, the allele, the seed (trace_seed_of),
+// and for a (locus, allele) pair not seen before its blocks in order, then the flanks' total.
+struct TracePair { int32_t locus, allele, opt[3], len[3]; };      // a distinct pair: the option (counted over the batch) and the bases of each block
+struct TraceRequests {
+  std::vector<int32_t> locus, seed, len, pair, compact_off;       // per request; compact_off: its read among the requested reads, first come first
+  std::vector<TracePair> pairs;
+  std::vector<int64_t> need;       // workspace bytes of a request: trace_side_ws of both sides
+  int64_t rough = 0;               // bound of the call's decision bytes: what trace_asks_device judges
+  int64_t wanted = 0;              // bases of the distinct reads requested: what trace_compact_reads judges
+  int cols(int q, int sd) const { return sd ? len[q] - seed[q] - 1 : seed[q]; }       // read columns of a side
+  int rows(int q, int sd, int x) const { return pairs[pair[q]].len[sd ? 2-x : x]; }   // bases of block x in the side's orientation
+};
+const char* trace_resolve(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele, const int32_t* req_seed, TraceRequests& R){
+  const int n_loci = b->n_loci, n_reads = b->read_off[n_loci];
+  std::vector<int32_t> opt_base(n_loci + 1, 0);           // first option (over all blocks) of every locus
+  for (int l = 0; l < n_loci; l++){
+    if (b->period[l] < 1 || b->period[l] > 9) return "STR period must be in [1,9] (stutter_model.h:38)";
+    int cnt = 0;
+    for (int k = 0; k < 3; k++){
+      if (b->blk_nopts[3*l+k] < 1) return "haplotype block without options";
+      cnt += b->blk_nopts[3*l+k];
+    }
+    opt_base[l+1] = opt_base[l] + cnt;
+  }
+  R.locus.resize(n_req); R.seed.resize(n_req); R.len.resize(n_req); R.pair.resize(n_req); R.compact_off.resize(n_req); R.need.resize(n_req);
+  std::map<int64_t, int> slot;                           // (locus, allele) -> entry of `pairs`
+  std::vector<int32_t> at(n_req ? (size_t)n_reads : 0, -1);      // read -> offset among the requested reads
+  for (int q = 0; q < n_req; q++){
+    const int r = req_read[q], k = req_allele[q];
+    if (r < 0 || r >= n_reads) return "request names a read outside the batch";
+    const int l = (int)(std::upper_bound(b->read_off, b->read_off + n_loci + 1, r) - b->read_off) - 1;
+    const int32_t* nopts = b->blk_nopts + 3*l;
+    if (k < 0 || k >= nopts[0]*nopts[1]*nopts[2]) return "request names an allele outside its locus";
+    int s;
+    if (const char* why = trace_seed_of(b, l, r, req_seed, q, s)) return why;
+    const int len = b->base_off[r+1] - b->base_off[r];
+    R.locus[q] = l; R.seed[q] = s; R.len[q] = len;
+    const int64_t key = ((int64_t)l << 32) | (uint32_t)k;
+    std::map<int64_t, int>::iterator hit = slot.find(key);
+    if (hit == slot.end()){
+      TracePair p; p.locus = l; p.allele = k;
+      int32_t oi[3];
+      hipstr::allele_options(nopts, k, oi);
+      for (int x = 0, cur = opt_base[l]; x < 3; cur += nopts[x], x++){
+        p.opt[x] = cur + oi[x]; p.len[x] = b->opt_off[p.opt[x]+1] - b->opt_off[p.opt[x]];
+        if (p.len[x] < 1) return x == 1 ? "empty STR allele is not supported" : "empty flank sequence";
+        if (x == 1 && p.len[x] > HS_MAX_STR_BP) return "STR allele longer than 2047 bp is not supported";
+      }
+      if (p.len[0] + 1 + p.len[2] > 4095) return "flanks longer than 4094 bases in total are not supported";
+      hit = slot.insert(std::make_pair(key, (int)R.pairs.size())).first;
+      R.pairs.push_back(p);
+    }
+    R.pair[q] = hit->second;
+    const TracePair& p = R.pairs[hit->second];
+    R.need[q] = trace_side_ws(p.len[0], p.len[2], s) + trace_side_ws(p.len[2], p.len[0], len - s - 1);
+    R.rough += (int64_t)(p.len[0] + p.len[2] + 2)*len;
+    if (at[r] < 0){ at[r] = (int32_t)R.wanted; R.wanted += len; }
+    R.compact_off[q] = at[r];
+  }
+  return NULL;
+}
+// the slots of a request of a device-assembled call (hlen: its hap_to_ref string's length, -1 without)
+TraceAsmCaps trace_req_asm_caps(const hipstr_batch_t* b, const TraceRequests& R, int q, int hlen){
+  const int F0 = R.rows(q, 0, 0), B = R.rows(q, 0, 1), F2 = R.rows(q, 0, 2), period = b->period[R.locus[q]];
+  return trace_asm_caps(trace_ops_cap(R.cols(q, 0), F0, F2, B, period), trace_ops_cap(R.cols(q, 1), F2, F0, B, period), R.len[q], F0, F2, hlen);
+}
+
+// ---- the launches of a chunk: the one derivation, for the call and for the plan.  Sides are launched grouped by columns-per-lane class
+// (`items`: chunk-relative side indices in that order); the static classes in one launch for the requests of a locus or two
+// (hs_trace_fill_mixed), else a launch per class.
+struct TraceLaunch { int cl, first, count; };       // the class (0: hs_trace_fill_mixed; its kernel otherwise: trace_fill_cols), first item, sides
+struct TraceLaunches {
+  std::vector<int32_t> items;
+  int cnt[HS_MAX_COLS + 1];        // sides per class, [1 .. HS_MAX_COLS]
+  bool mixed;
+  std::vector<TraceLaunch> fills;
+};
+void trace_launches(const TraceRequests& R, int q0, int q1, TraceLaunches& L){
+  L.items.clear(); L.fills.clear();
+  int n_cls = 0, first[HS_MAX_COLS + 1];
+  for (int cl = 1; cl <= HS_MAX_COLS; cl++){
+    first[cl] = (int)L.items.size();
+    for (int si = 0; si < 2*(q1 - q0); si++) if (trace_col_class(R.cols(q0 + si/2, si & 1)) == cl) L.items.push_back(si);
+    L.cnt[cl] = (int)L.items.size() - first[cl];
+    n_cls += cl <= HS_TRACE_STATIC_CLASSES && L.cnt[cl] > 0;
+  }
+  L.mixed = trace_mixed_launch(n_cls, q1 - q0);
+  if (L.mixed) L.fills.push_back(TraceLaunch{0, 0, first[HS_TRACE_STATIC_CLASSES + 1]});
+  for (int cl = L.mixed ? HS_TRACE_STATIC_CLASSES + 1 : 1; cl <= HS_MAX_COLS; cl++)
+    if (L.cnt[cl]) L.fills.push_back(TraceLaunch{cl, first[cl], L.cnt[cl]});
+}
+// an entry of the list on its way; 0, or 1 + last error
+int trace_launch_fill(const TraceLaunches& L, const TraceLaunch& f, hipStream_t ks, const hs_tdev_t* d_args){
+  static void (*const fill[HS_TRACE_STATIC_CLASSES])(const hs_tdev_t*, int) = { hs_trace_fill<1>, hs_trace_fill<2>, hs_trace_fill<3>, hs_trace_fill<4>, hs_trace_fill<5>, hs_trace_fill<6> };
+  const int cols = trace_fill_cols(f.cl);
+  int bad = 0;
+  if (f.cl == 0){
+    hs_tcls_t cls;
+    for (int cl = 1, end = 0; cl <= HS_TRACE_STATIC_CLASSES; cl++){ end += L.cnt[cl]; cls.end[cl-1] = end; }
+    hipLaunchKernelGGL(hs_trace_fill_mixed, dim3(f.count), dim3(64), 0, ks, d_args, cls);
+  }
+  else if (cols <= HS_TRACE_STATIC_CLASSES) hipLaunchKernelGGL(fill[cols-1], dim3(f.count), dim3(64), 0, ks, d_args, f.first);
+  else bad = cols == 8 ? launch_fill_long<8>(f.count, ks, d_args, f.first) : cols == 12 ? launch_fill_long<12>(f.count, ks, d_args, f.first) : launch_fill_long<16>(f.count, ks, d_args, f.first);
+  return bad ? hipstr::api_fail("hipFuncSetAttribute (traceback LDS) failed") : 0;
+}
+
+// ================================================================== the traceback call, stage by stage
+// What every stage reads: the caller's arguments and the context's tables.
+struct TraceCtx {
+  const hipstr_batch_t* b; int32_t n_req; const int32_t *req_read, *req_allele; const char* const* hap_to_ref;
+  bool on_device, timing;
+  hipstr::ApiTables T; const hipstr::HostTables* HT;
+};
+// HIPSTR_TRACE_TIMING: the call's milliseconds by stage; lap() is the time since the last lap
+struct TraceTimes {
+  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+  double prep = 0, fixed = 0, upload = 0, kernel = 0, d2h = 0, replay = 0, total = 0;
+  double lap(){ const auto t = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double, std::milli>(t - last).count(); last = t; total += d; return d; }
+};
+
+// ---- stage 2: the alleles of the distinct pairs: block strings in both orientations, rows under the allele's own homopolymer context,
+// STR options; with hap_to_ref (a device-assembled call) the pool of the pairs' strings.  NULL or the refusal.
+struct AllelePreps {
+  std::vector<AllelePrep> v;       // by pair
+  std::vector<hs_row_t> rows;
+  hipstr::Prepared P;              // only its STR-option pools are used
+  std::string h2r_pool;
+};
+const char* trace_prepare_alleles(const hipstr_batch_t* b, const TraceRequests& R, const char* const* hap_to_ref, AllelePreps& A){
+  A.v.resize(R.pairs.size());
+  for (size_t i = 0; i < R.pairs.size(); i++){
+    const TracePair& p = R.pairs[i]; AllelePrep& ap = A.v[i];
+    for (int x = 0; x < 3; x++){
+      ap.seq[0][x].assign(b->seq + b->opt_off[p.opt[x]], (size_t)p.len[x]);
+      ap.seq[1][2-x].assign(ap.seq[0][x].rbegin(), ap.seq[0][x].rend());
+    }
+    for (int sd = 0; sd < 2; sd++){
+      std::vector<hs_row_t> lead, trail;
+      hipstr::fresh_flank_rows(ap.seq[sd], lead, trail);
+      ap.lead_off[sd] = A.rows.size();  A.rows.insert(A.rows.end(), lead.begin(), lead.end());
+      ap.trail_off[sd] = A.rows.size(); A.rows.insert(A.rows.end(), trail.begin(), trail.end());
+      ap.stropt[sd] = A.P.stropts.size();
+      hipstr::append_stropt(ap.seq[sd][1], b->period[p.locus], b->stutter + 6*p.locus, A.P);
+    }
+    if (hap_to_ref){
+      const char* s2 = hap_to_ref[b->hap_off[p.locus] + p.allele];
+      ap.h2r_off = (int32_t)A.h2r_pool.size(); ap.h2r_len = (int32_t)strlen(s2);
+      A.h2r_pool.append(s2, (size_t)ap.h2r_len);
+      if (A.h2r_pool.size() > 0x7fffffff) return "too many requests for one call; split the request list";
+    }
+  }
+  return NULL;
+}
+
+// What the fill and walk kernels leave — score, seed position, operation counts, artifact size and position per side, the operation
+// strings — is one device block with the layout of the pinned block it is copied to: one copy per chunk.
+struct TraceResBlock { size_t ll = 0, mxi = 0, nops = 0, ssz = 0, spos = 0, ops = 0, end = 0; char* d = NULL; };
+// The records of a device-assembled chunk, again with the layout of the pinned block: totals and the first failure | five scalars per
+// request | the running offsets | int32 pools | char pools.
+struct TraceAsmBlock { size_t scal = 0, incl = 0, i32 = 0, chr = 0, end = 0; char* d = NULL; };
+// What stages 3 and 4 leave for the chunks.
+struct TraceWork {
+  hipstr::HostArena st_arena;      // stage 3
+  bool compact_reads = false;
+  int64_t budget;                  // stage 4: bytes of decision matrices per chunk
+  std::vector<hs_tside_t> sides;
+  int max_nq = 0;
+  hs_tdev_t hc = {};               // the static tables (stage 3) and the workspace
+  TraceResBlock res;
+  std::vector<TraceAsmCaps> acaps; // device assembly: slots per request, the staging and the result block
+  TraceAsmBlock aout;
+  hs_adev_t ad = {};               // blk_start, blk_end, h2r (stage 3); staging and the result block's pieces
+};
+// ---- stage 3: everything that does not change from chunk to chunk, in one pinned block and one copy: the alleles' tables and the reads'
+// bases and qualities — only those of the requested reads when they are a small part of the batch (a few loci of a large batch: the whole
+// batch's 150 MB cost more than the call's kernels); a device-assembled call adds the block coordinates and the hap_to_ref pool.
+int trace_upload_static(const TraceCtx& C, const TraceRequests& R, const AllelePreps& A, TraceWork& W){
+  const hipstr_batch_t* b = C.b;
+  const int n_loci = b->n_loci, total_bases = b->base_off[b->read_off[n_loci]];
+  std::vector<char> up_bases, up_quals;
+  W.compact_reads = trace_compact_reads(R.wanted, total_bases);
+  if (W.compact_reads){
+    up_bases.resize((size_t)R.wanted); up_quals.resize((size_t)R.wanted);
+    for (int q = 0; q < C.n_req; q++){
+      const int r = C.req_read[q];
+      memcpy(up_bases.data() + R.compact_off[q], b->bases + b->base_off[r], (size_t)R.len[q]);
+      memcpy(up_quals.data() + R.compact_off[q], b->quals + b->base_off[r], (size_t)R.len[q]);
+    }
+  }
+  const char* const src_bases = W.compact_reads ? up_bases.data() : b->bases;
+  const char* const src_quals = W.compact_reads ? up_quals.data() : b->quals;
+  const size_t n_up = W.compact_reads ? up_bases.size() : (size_t)total_bases;
+  hipstr::HostArena& ar = W.st_arena; const hipstr::Prepared& P = A.P; const bool dv = C.on_device;
+  const size_t o_bs = dv ? ar.add(b->blk_start, 3*(size_t)n_loci*sizeof(int32_t)) : 0, o_be = dv ? ar.add(b->blk_end, 3*(size_t)n_loci*sizeof(int32_t)) : 0,
+               o_h2r = dv ? ar.add(A.h2r_pool.data(), A.h2r_pool.size()) : 0;
+  const size_t o_rows = ar.add(A.rows.data(), A.rows.size()*sizeof(hs_row_t)), o_so = ar.add(P.stropts.data(), P.stropts.size()*sizeof(hs_stropt_t)),
+               o_vis = ar.add(P.visits.data(), P.visits.size()*sizeof(hs_visit_t)), o_f64 = ar.add(P.f64pool.data(), P.f64pool.size()*sizeof(double)),
+               o_chars = ar.add(P.chars.data(), P.chars.size()), o_bases = ar.add(src_bases, n_up), o_quals = ar.add(src_quals, n_up);
+  if (ar.reserve(C.T.ctx)) return hipstr::api_fail("out of device or pinned host memory");
+  if (ar.send(C.T.stream)) return 1;
+  hs_tdev_t& h = W.hc;
+  h.rows = ar.at<hs_row_t>(o_rows); h.stropts = ar.at<hs_stropt_t>(o_so); h.visits = ar.at<hs_visit_t>(o_vis);
+  h.f64pool = ar.at<double>(o_f64); h.chars = ar.at<char>(o_chars); h.bases = ar.at<char>(o_bases); h.quals = ar.at<char>(o_quals);
+  if (dv){ W.ad.blk_start = ar.at<int32_t>(o_bs); W.ad.blk_end = ar.at<int32_t>(o_be); W.ad.h2r = ar.at<char>(o_h2r); }
+  h.int_log = C.T.int_log; h.qual_correct = C.T.qual_correct; h.qual_error = C.T.qual_error; h.m2m = C.T.m2m; h.m2i = C.T.m2i;
+  h.log_thresh = C.HT->log_thresh;
+  return 0;
+}
+
+// device assembly: slots per request, the staging and the result block sized for the largest chunk
+int trace_alloc_assembly(const TraceCtx& C, const TraceRequests& R, const AllelePreps& A, hipstr::ScratchBufs& dev, TraceWork& W){
+  const int n_req = C.n_req;
+  W.acaps.resize(n_req);
+  for (int q = 0; q < n_req; q++) W.acaps[q] = trace_req_asm_caps(C.b, R, q, A.v[R.pair[q]].h2r_len);
+  int64_t mx_cap[5] = {0, 0, 0, 0, 0};                  // per chunk at most: hap_aln, seq, indel, snp, stitched entries
+  for (int q0 = 0; q0 < n_req; ){
+    const int q1 = trace_chunk_end(R.need, q0, W.budget);
+    int64_t c[5] = {0, 0, 0, 0, 0};
+    for (int q = q0; q < q1; q++){ const TraceAsmCaps& a = W.acaps[q]; c[0] += a.hap_aln; c[1] += a.seq; c[2] += a.indel; c[3] += a.snp; c[4] += a.stitched; }
+    for (int i = 0; i < 5; i++) mx_cap[i] = std::max(mx_cap[i], c[i]);
+    q0 = q1;
+  }
+  for (int i = 0; i < 5; i++) if (2*mx_cap[i] > 0x7fffffff) return hipstr::api_fail("too many requests for one call; split the request list");
+  const size_t nqm = (size_t)W.max_nq, n_in = (size_t)mx_cap[2], n_sn = (size_t)mx_cap[3], n_fa = (size_t)mx_cap[4];
+  hs_adev_t& ad = W.ad; TraceAsmBlock& B = W.aout;
+  if (dev.alloc(&ad.st_indel_pos, n_in) || dev.alloc(&ad.st_indel_size, n_in) || dev.alloc(&ad.st_snp_pos, n_sn) || dev.alloc(&ad.st_cig_len, n_fa) ||
+      dev.alloc(&ad.st_snp_base, n_sn) || dev.alloc(&ad.st_fa, n_fa) || dev.alloc(&ad.st_cig_op, n_fa) || dev.alloc(&ad.st_aln, n_fa) ||
+      dev.alloc(&ad.lens, 8*nqm) || dev.alloc(&ad.excl, 8*nqm) || dev.alloc(&ad.rng, 3*nqm) || dev.alloc(&ad.fail, nqm)) return 1;
+  B.scal = 64; B.incl = B.scal + 5*nqm*4; B.i32 = B.incl + 8*nqm*4;
+  B.chr = B.i32 + (2*n_in + n_sn + n_fa)*4;
+  B.end = B.chr + (size_t)mx_cap[0] + 3*(size_t)mx_cap[1] + n_sn + 2*n_fa;
+  if (dev.alloc(&B.d, B.end)) return 1;
+  ad.totals = (int64_t*)B.d; ad.first_fail = (int32_t*)(B.d + HS_ASM_POOLS*8);
+  int32_t* sc = (int32_t*)(B.d + B.scal);
+  ad.stutter_size = sc; ad.flank_ins = sc + nqm; ad.flank_del = sc + 2*nqm; ad.aln_start = sc + 3*nqm; ad.aln_stop = sc + 4*nqm;
+  ad.incl = (int32_t*)(B.d + B.incl);
+  int32_t* pi = (int32_t*)(B.d + B.i32);
+  ad.p_indel_pos = pi; ad.p_indel_size = pi + n_in; ad.p_snp_pos = pi + 2*n_in; ad.p_cig_len = pi + 2*n_in + n_sn;
+  char* pc = B.d + B.chr;
+  ad.p_hap_aln = pc; ad.p_str_seq = pc + mx_cap[0]; ad.p_flank = ad.p_str_seq + mx_cap[1]; ad.p_snp_base = ad.p_flank + 2*mx_cap[1];
+  ad.p_cig_op = ad.p_snp_base + n_sn; ad.p_aln = ad.p_cig_op + n_fa;
+  ad.dense_cap[0] = mx_cap[0]; ad.dense_cap[1] = mx_cap[1]; ad.dense_cap[2] = 2*mx_cap[1]; ad.dense_cap[3] = mx_cap[2]; ad.dense_cap[4] = mx_cap[3];
+  ad.dense_cap[5] = ad.dense_cap[6] = mx_cap[4];
+  return 0;
+}
+// ---- stage 4: the budget of a chunk, the sides, and the workspace and result blocks sized for the largest chunk once and reused
+// (the query costs as much as a small call's kernels: only a call whose matrices could exceed 256 MiB asks — an upper bound from the
+//  longest read and the flank lengths of the first allele is enough to tell)
+int trace_workspace(const TraceCtx& C, const TraceRequests& R, const AllelePreps& A, hipstr::ScratchBufs& dev, TraceWork& W){
+  W.budget = (int64_t)HS_TRACE_BUDGET_MIB << 20;
+  if (trace_asks_device(R.rough)){
+    size_t free_b = 0, total_b = 0;
+    HS_HIP(hipMemGetInfo(&free_b, &total_b));
+    W.budget = std::min<int64_t>((int64_t)8 << 30, (int64_t)(free_b / 4));
+  }
+  W.budget = trace_env_budget(W.budget);
+  W.sides.resize(2*(size_t)C.n_req);
+  for (int q = 0; q < C.n_req; q++){
+    const AllelePrep& ap = A.v[R.pair[q]];
+    for (int sd = 0; sd < 2; sd++){
+      hs_tside_t& S = W.sides[2*q+sd];
+      memset(&S, 0, sizeof S);
+      S.base_off = W.compact_reads ? R.compact_off[q] : C.b->base_off[C.req_read[q]]; S.len = R.len[q]; S.seed = R.seed[q]; S.side = sd;
+      S.n = R.cols(q, sd);
+      S.lead_off = ap.lead_off[sd]; S.F0 = R.rows(q, sd, 0);
+      S.trail_off = ap.trail_off[sd]; S.F2 = R.rows(q, sd, 2);
+      S.stropt = ap.stropt[sd];
+      S.ops_cap = trace_ops_cap(S.n, S.F0, S.F2, R.rows(q, sd, 1), C.b->period[R.locus[q]]);
+    }
+    if (R.need[q] > W.budget) return hipstr::api_fail("one traceback needs more workspace than the device offers");
+  }
+  // workspaces are sized for the largest chunk once and reused
+  const std::vector<hs_tside_t>& sides = W.sides;
+  int64_t max_mat = 0, max_art = 0, max_ops = 0, max_lc = 0;
+  {
+    int64_t mat = 0, art = 0, ops = 0, lc = 0; int nq = 0;
+    for (int q = 0; q < C.n_req; q++){
+      if (mat + R.need[q] > W.budget){ mat = art = ops = lc = 0; nq = 0; }
+      mat += R.need[q]; art += 2*(int64_t)(sides[2*q].n + sides[2*q+1].n); ops += sides[2*q].ops_cap + sides[2*q+1].ops_cap; nq++;
+      lc += 2*(int64_t)(sides[2*q].F0 + 1 + sides[2*q].F2);
+      max_mat = std::max(max_mat, mat); max_art = std::max(max_art, art); max_ops = std::max(max_ops, ops); max_lc = std::max(max_lc, lc);
+      W.max_nq = std::max(W.max_nq, nq);
+    }
+  }
+  if (max_art > 0x7fffffff || max_ops > 0x7fffffff || max_lc > 0x7fffffff) return hipstr::api_fail("too many requests for one call; split the request list");
+  hs_tdev_t& hc = W.hc; TraceResBlock& B = W.res;
+  if (dev.alloc(&hc.dec, max_mat) || dev.alloc(&hc.lastcol, max_lc) || dev.alloc(&hc.arts, max_art) || dev.alloc(&hc.side_prob, 2*(size_t)W.max_nq)) return 1;
+  const size_t nqm = (size_t)W.max_nq;
+  B.mxi = B.ll + nqm*8; B.nops = B.mxi + nqm*4; B.ssz = B.nops + 2*nqm*4; B.spos = B.ssz + 2*nqm*4;
+  B.ops = (B.spos + 2*nqm*4 + 15) & ~(size_t)15; B.end = B.ops + (size_t)(max_ops ? max_ops : 1);
+  if (dev.alloc(&B.d, B.end)) return 1;
+  hc.ll = (double*)(B.d + B.ll); hc.max_index = (int32_t*)(B.d + B.mxi); hc.n_ops = (int32_t*)(B.d + B.nops);
+  hc.str_size = (int32_t*)(B.d + B.ssz); hc.str_pos = (int32_t*)(B.d + B.spos); hc.ops = B.d + B.ops;
+  return C.on_device ? trace_alloc_assembly(C, R, A, dev, W) : 0;
+}
+
+
+// ---- stage 5, per chunk: lay out the sides, upload, launch, then one of the three finishers
+struct TraceEvents { hipEvent_t e[2] = {NULL, NULL}; ~TraceEvents(){ for (hipEvent_t x : e) if (x) hipEventDestroy(x); } };
+struct TraceChunk {
+  int q0, q1, nq; int64_t n_ops = 0;
+  TraceLaunches L;
+  hipstr::HostArena arena;         // this chunk's sides, launch order and argument block
+  const hs_tdev_t* d_args = NULL;
+  hs_adev_t ac;                    // device assembly: the call's pointers, this chunk's requests, the totals of the chunks done
+  TraceEvents ev;                  // around the assembly kernels, when the call is timed
+  TraceChunk(int a, int b) : q0(a), q1(b), nq(b - a) {}
+};
+int trace_chunk_upload(const TraceCtx& C, const TraceRequests& R, const AllelePreps& A, TraceWork& W, const int64_t pool_total[HS_ASM_POOLS], TraceChunk& Ch){
+  const int q0 = Ch.q0, q1 = Ch.q1, nq = Ch.nq;
+  int64_t mat = 0, n_art = 0, n_ops = 0, n_lc = 0;
+  for (int q = q0; q < q1; q++){
+    for (int sd = 0; sd < 2; sd++){
+      hs_tside_t& S = W.sides[2*q+sd];
+      S.dec_off = mat; mat += trace_side_ws(S.F0, S.F2, S.n);
+      S.lc_off = (int32_t)n_lc; n_lc += S.F0 + 1 + S.F2;
+      S.art_off = (int32_t)n_art; n_art += 2*S.n;
+      S.ops_off = (int32_t)n_ops; n_ops += S.ops_cap;
+    }
+  }
+  Ch.n_ops = n_ops;
+  trace_launches(R, q0, q1, Ch.L);
+  hs_tdev_t hcc = W.hc;
+  std::vector<hs_areq_t> areqs;
+  if (C.on_device){
+    areqs.resize(nq);
+    int64_t at_in = 0, at_sn = 0, at_fa = 0;
+    for (int q = q0; q < q1; q++){
+      hs_areq_t& Q = areqs[q-q0]; const AllelePrep& ap = A.v[R.pair[q]]; const TraceAsmCaps& c = W.acaps[q];
+      Q.loc = R.locus[q]; Q.h2r_off = ap.h2r_off; Q.h2r_len = ap.h2r_len;
+      Q.indel_cap = c.indel; Q.snp_cap = c.snp; Q.fa_cap = c.stitched;
+      Q.indel_off = at_in; Q.snp_off = at_sn; Q.fa_off = at_fa;
+      at_in += c.indel; at_sn += c.snp; at_fa += c.stitched;
+    }
+  }
+  hipstr::HostArena& ar = Ch.arena;
+  const size_t o_sides = ar.add(W.sides.data() + 2*q0, 2*(size_t)nq*sizeof(hs_tside_t)), o_items = ar.add(Ch.L.items.data(), Ch.L.items.size()*sizeof(int32_t)),
+               o_args = ar.add(&hcc, sizeof hcc), o_areq = C.on_device ? ar.add(areqs.data(), areqs.size()*sizeof(hs_areq_t)) : 0;
+  // (the argument block points into the arena it travels in: sizes first, then the pointers, then the copy)
+  if (ar.reserve(C.T.ctx)) return hipstr::api_fail("out of device or pinned host memory");
+  hcc.sides = ar.at<hs_tside_t>(o_sides); hcc.items = ar.at<int32_t>(o_items);
+  if (ar.send(C.T.stream)) return 1;
+  Ch.d_args = ar.at<hs_tdev_t>(o_args);
+  if (C.on_device){
+    Ch.ac = W.ad;
+    Ch.ac.reqs = ar.at<hs_areq_t>(o_areq); Ch.ac.nq = nq;
+    for (int p = 0; p < HS_ASM_POOLS; p++) Ch.ac.base[p] = pool_total[p];
+  }
+  return 0;
+}
+// the fill kernels of the launch list, the walk; device assembly: assemble, offsets, compaction
+int trace_chunk_launch(const TraceCtx& C, TraceChunk& Ch){
+  const hipStream_t st = C.T.stream;
+  for (const TraceLaunch& f : Ch.L.fills) if (trace_launch_fill(Ch.L, f, st, Ch.d_args)) return 1;
+  hipLaunchKernelGGL(hs_trace_walk, dim3(Ch.nq), dim3(64), 0, st, Ch.d_args, 0);
+  if (C.on_device){
+    if (C.timing){ HS_HIP(hipEventCreate(&Ch.ev.e[0])); HS_HIP(hipEventCreate(&Ch.ev.e[1])); HS_HIP(hipEventRecord(Ch.ev.e[0], st)); }
+    hipLaunchKernelGGL(hs_trace_assemble, dim3(Ch.nq), dim3(64), 0, st, Ch.d_args, Ch.ac);
+    hipLaunchKernelGGL(hs_trace_scan, dim3(HS_ASM_POOLS + 1), dim3(64), 0, st, Ch.ac);
+    hipLaunchKernelGGL(hs_trace_compact, dim3(Ch.nq), dim3(64), 0, st, Ch.d_args, Ch.ac);
+    if (C.timing) HS_HIP(hipEventRecord(Ch.ev.e[1], st));
+  }
+  HS_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- finisher 1: the operation strings come home and the host replays them (HapAligner.cpp:642-707) and stitches
+struct ChunkFetched { const double* ll; const int32_t *mxi, *nops, *ssz, *spos; const char* ops; };      // a chunk's results in its pinned block
+// one request: qi its place in the chunk, S its two sides
+void replay_request(const TraceCtx& C, const TraceRequests& RQ, const AllelePrep& ap, const hs_tside_t* S, int q, const ChunkFetched& F, int qi, ReqOut& R){
+  const hipstr_batch_t* b = C.b;
+  const int r = C.req_read[q], sb = RQ.seed[q], l = RQ.locus[q], len = RQ.len[q];
+  const char* bases = b->bases + b->base_off[r];
+  const char* quals = b->quals + b->base_off[r];
+  const int max_index = F.mxi[qi];
+  const int blen3[3] = { (int)ap.seq[0][0].size(), (int)ap.seq[0][1].size(), (int)ap.seq[0][2].size() };
+  const int H = blen3[0] + blen3[1] + blen3[2];
+  // left retrace, then the seed base joins the flank it sits in, then the right retrace (HapAligner.cpp:642-684)
+  std::string side_ops[2];
+  int seed_block = 0;
+  for (int x = 0, crd = max_index; x < 3; x++){ if (crd < blen3[x]){ seed_block = x; break; } crd -= blen3[x]; }
+  for (int sd = 0; sd < 2 && R.ok; sd++){
+    const int cnt = F.nops[2*qi+sd];
+    if (cnt > S[sd].ops_cap){ R.ok = false; break; }
+    side_ops[sd].assign(F.ops + S[sd].ops_off, cnt);
+    if (sd == 1 && seed_block != 1) R.acc.flank[seed_block].push_back(bases[sb]);
+    const int mx = sd ? H-1-max_index : max_index;
+    if (mx == 0) continue;                         // this side is all soft clips
+    const int n = S[sd].n;
+    std::string rd(n, ' '); std::vector<double> lc(n);
+    for (int j = 0; j < n; j++){
+      const int src = sd ? len-1-j : j;
+      rd[j] = bases[src]; lc[j] = C.HT->qual_correct[(uint8_t)quals[src]];
+    }
+    int blk = 0, crd = mx;
+    for (int x = 0; x < 3; x++){ const int bl = ap.seq[sd][x].size(); if (crd < bl){ blk = x; break; } crd -= bl; }
+    int block, base;
+    if (crd == 0){ block = blk-1; base = (int)ap.seq[sd][block].size()-1; } else { block = blk; base = crd-1; }
+    if (!replay_side(b, l, ap.seq[sd], sd != 0, rd, lc, side_ops[sd], F.ssz[2*qi+sd], F.spos[2*qi+sd], block, base, R.acc)) R.ok = false;
+  }
+  if (!R.ok) return;
+  R.hap_aln.assign(side_ops[0].rbegin(), side_ops[0].rend());
+  R.hap_aln.push_back('M');
+  R.hap_aln += side_ops[1];
+  if (C.hap_to_ref == NULL) return;
+  // ---- stitch_alignment_trace (AlignmentTraceback.cpp:55-144)
+  const std::string& full = R.hap_aln;
+  const char* h2r = C.hap_to_ref[b->hap_off[l] + C.req_allele[q]];
+  const int hlen = (int)strlen(h2r);
+  int hap_index = max_index, hai = 0; int32_t seed_pos = b->blk_start[3*l];
+  while (hap_index > 0 && hai < hlen){
+    if (h2r[hai] == 'M' || h2r[hai] == 'I') hap_index--;
+    if (h2r[hai] == 'M' || h2r[hai] == 'D') seed_pos++;
+    hai++;
+  }
+  while (hai < hlen && h2r[hai] == 'D') hai++;
+  int sbase = sb, rai = 0;
+  while (sbase > 0 && rai < (int)full.size()){
+    if (full[rai] == 'M' || full[rai] == 'I' || full[rai] == 'S') sbase--;
+    rai++;
+  }
+  while (rai < (int)full.size() && full[rai] == 'D') rai++;
+  std::string la, ra;
+  stitch_dir(h2r, hlen, full, hai-1, rai-1, -1, la);
+  std::reverse(la.begin(), la.end());
+  stitch_dir(h2r, hlen, full, hai+1, rai+1, 1, ra);
+  std::string fa = la + "M" + ra;
+  for (size_t i = 0; i < fa.size(); i++){ if (fa[i] == 'I') fa[i] = 'S'; else break; }
+  int32_t start = seed_pos, stop = seed_pos;
+  for (char ch : la) if (ch == 'D' || ch == 'M') start--;
+  for (char ch : ra) if (ch == 'D' || ch == 'M') stop++;
+  R.aln_start = start; R.aln_stop = stop;
+  char cc = fa[0]; int num = 1;
+  for (size_t i = 1; i <= fa.size(); i++){
+    if (i == fa.size() || fa[i] != cc){
+      R.cigar.push_back(std::make_pair(cc, (int32_t)num));
+      if (i < fa.size()){ cc = fa[i]; num = 1; }
+    } else num++;
+  }
+  int ri = 0;
+  for (char ch : fa){
+    if (ch == 'S') ri++;
+    else if (ch == 'M' || ch == 'I') R.aln_str.push_back(bases[ri++]);
+    else R.aln_str.push_back('-');
+  }
+}
+int finish_host_replay(const TraceCtx& C, const TraceRequests& RQ, const AllelePreps& A, const TraceWork& W, const TraceChunk& Ch, hipstr_trace_out_t* o, TraceTimes& tm){
+  const int q0 = Ch.q0, q1 = Ch.q1, nq = Ch.nq; const TraceResBlock& B = W.res;
+  // results through one pinned block (a pageable destination costs a staging copy per call and per array), in one copy behind the kernels
+  PinBlock pin(C.T.ctx, C.T.stream, B.end);
+  if (!pin.p) return hipstr::api_fail("out of pinned host memory");
+  HS_HIP(hipMemcpyAsync(pin.p, B.d, B.ops + (size_t)(Ch.n_ops ? Ch.n_ops : 1), hipMemcpyDeviceToHost, C.T.stream));
+  HS_HIP(hipstr::wait_stream(C.T.stream));
+  const ChunkFetched F = { (const double*)(pin.p + B.ll), (const int32_t*)(pin.p + B.mxi), (const int32_t*)(pin.p + B.nops), (const int32_t*)(pin.p + B.ssz),
+                           (const int32_t*)(pin.p + B.spos), pin.p + B.ops };
+  tm.d2h += tm.lap();
+  // request by request; independent, so spread over host threads.  The replay is ~1.7 us of string work per request; the host threads are
+  // a persistent pool (a few microseconds to wake), so a locus' hundred requests are already worth sharing: blocks of 24 requests
+  std::vector<ReqOut> res(nq);
+  int nthreads = std::max(1, std::min(hipstr::host_threads(), nq / 24));
+  if (const char* e = getenv("HIPSTR_TRACE_THREADS")) nthreads = std::max(1, std::min(atoi(e), std::max(1, nq / 16)));
+  auto run_parallel = [&](const std::function<void(int,int)>& fn){
+    if (nthreads <= 1){ fn(q0, q1); return; }
+    hipstr::parallel_for(nthreads, nthreads, [&](int t){ fn(q0 + (int)((int64_t)nq*t/nthreads), q0 + (int)((int64_t)nq*(t+1)/nthreads)); });
+  };
+  const double ms_setup = tm.lap();
+  run_parallel([&](int qa, int qb){ for (int q = qa; q < qb; q++) replay_request(C, RQ, A.v[RQ.pair[q]], &W.sides[2*q], q, F, q-q0, res[q-q0]); });
+  const double ms_work = tm.lap();
+  if (hipstr::api_profile_on()) hipstr::api_profile_add(hipstr::PB_TRACE_REPLAY, ms_work*1e-3);
+  // ---- the caller's flat pools: offsets in request order (serial prefix sums), then the bytes (parallel again)
+  const TraceOutView V(o);
+  const int64_t cap = o->cap_chars;
+  for (int q = q0; q < q1; q++){
+    const ReqOut& R = res[q-q0];
+    if (!R.ok) return hipstr::api_fail("internal error: inconsistent traceback operation string");
+    const size_t f0 = R.acc.flank[0].size(), f2 = R.acc.flank[2].size();
+    const size_t n[HS_ASM_POOLS] = { R.hap_aln.size(), R.acc.str_set ? R.acc.str_seq.size() : 0, f0 + f2, R.acc.indels.size(), R.acc.snps.size(), R.cigar.size(), R.aln_str.size() };
+    bool full = false;
+    for (int p = 0; p < HS_ASM_POOLS; p++){
+      int32_t* at = V.off[p] + hs_asm_pool_n(p, q);
+      full = full || (int64_t)at[0] + (int64_t)n[p] > cap;
+      if (p == 2){ at[1] = at[0] + (int32_t)f0; at[2] = at[1] + (int32_t)f2; }
+      else at[1] = at[0] + (int32_t)n[p];
+    }
+    if (full) return hipstr::api_fail("hipstr_trace_out_t pools are too small (cap_chars)");
+  }
+  const double ms_offsets = tm.lap();
+  run_parallel([&](int qa, int qb){
+    for (int q = qa; q < qb; q++){
+      const ReqOut& R = res[q-q0];
+      o->ll[q] = F.ll[q-q0]; o->max_index[q] = F.mxi[q-q0];
+      memcpy(o->hap_aln + o->hap_aln_off[q], R.hap_aln.data(), R.hap_aln.size());
+      o->stutter_size[q] = R.acc.str_set ? R.acc.stutter_size : HIPSTR_NO_STR_DATA;
+      if (R.acc.str_set) memcpy(o->str_seq + o->str_seq_off[q], R.acc.str_seq.data(), R.acc.str_seq.size());
+      memcpy(o->flank_seq + o->flank_seq_off[2*q], R.acc.flank[0].data(), R.acc.flank[0].size());
+      memcpy(o->flank_seq + o->flank_seq_off[2*q+1], R.acc.flank[2].data(), R.acc.flank[2].size());
+      o->flank_ins[q] = R.acc.flank_ins; o->flank_del[q] = R.acc.flank_del;
+      for (size_t i = 0; i < R.acc.indels.size(); i++){ o->indel_pos[o->indel_off[q] + i] = R.acc.indels[i].first; o->indel_size[o->indel_off[q] + i] = R.acc.indels[i].second; }
+      for (size_t i = 0; i < R.acc.snps.size(); i++){ o->snp_pos[o->snp_off[q] + i] = R.acc.snps[i].first; o->snp_base[o->snp_off[q] + i] = R.acc.snps[i].second; }
+      o->aln_start[q] = R.aln_start; o->aln_stop[q] = R.aln_stop;
+      for (size_t i = 0; i < R.cigar.size(); i++){ o->cigar_op[o->cigar_off[q] + i] = R.cigar[i].first; o->cigar_len[o->cigar_off[q] + i] = R.cigar[i].second; }
+      memcpy(o->aln_str + o->aln_str_off[q], R.aln_str.data(), R.aln_str.size());
+    }
+  });
+  const double ms_copy = tm.lap();
+  // a request's results are a dozen small heap blocks: let the threads that made them give them back, not this one at scope exit
+  run_parallel([&](int qa, int qb){ for (int q = qa; q < qb; q++){ ReqOut none; std::swap(none, res[q-q0]); } });
+  const double ms_release = tm.lap();
+  if (C.timing) fprintf(stderr, "  replay of %d: setup %.3f work %.3f offsets %.3f copy %.3f release %.3f (threads %d)\n", nq, ms_setup, ms_work, ms_offsets, ms_copy, ms_release, nthreads);
+  tm.replay += ms_setup + ms_work + ms_offsets + ms_copy + ms_release;
+  return 0;
+}
+
+// ---- finisher 2: the records were assembled on the device; the totals, then every pool and array in one copy each to the caller's buffers
+int finish_to_caller(const TraceCtx& C, const TraceWork& W, const TraceChunk& Ch, int64_t pool_total[HS_ASM_POOLS], hipstr_trace_out_t* o, TraceTimes& tm){
+  const int q0 = Ch.q0, nq = Ch.nq; const TraceResBlock& B = W.res; const TraceAsmBlock& AB = W.aout;
+  PinBlock pin(C.T.ctx, C.T.stream, B.nops + AB.end);
+  if (!pin.p) return hipstr::api_fail("out of pinned host memory");
+  char* hout = pin.p + B.nops;
+  HS_HIP(hipMemcpyAsync(pin.p, B.d, B.nops, hipMemcpyDeviceToHost, C.T.stream));                  // ll, max_index
+  HS_HIP(hipMemcpyAsync(hout, AB.d, AB.i32, hipMemcpyDeviceToHost, C.T.stream));                  // totals, scalars, offsets
+  HS_HIP(hipstr::wait_stream(C.T.stream));
+  if (C.timing){
+    float kms = 0; HS_HIP(hipEventElapsedTime(&kms, Ch.ev.e[0], Ch.ev.e[1]));
+    fprintf(stderr, "  assemble + scan + compact of %d: %.3f ms on the device\n", nq, kms);
+  }
+  const int64_t* tot = (const int64_t*)hout;
+  const int32_t first_fail = *(const int32_t*)(hout + HS_ASM_POOLS*8);
+  const int32_t* incl = (const int32_t*)(hout + AB.incl);
+  const int64_t cap = o->cap_chars;
+  // the host path's order: request by request, an inconsistent operation string before a full pool
+  int first_full = -1;
+  { bool over = false; for (int p = 0; p < HS_ASM_POOLS; p++) over = over || tot[p] > cap;
+    if (over) for (int q = 0; q < nq && first_full < 0; q++) for (int p = 0; p < HS_ASM_POOLS; p++){
+      const int i = hs_asm_pool_at(p, nq) + (p == 2 ? 2*q+1 : q);
+      // (the offsets are 32-bit: one that wrapped is past any capacity too)
+      if (incl[i] > cap || incl[i] < 0){ first_full = q; break; }
+    }
+    if (over && first_full < 0) first_full = 0; }
+  if (first_fail >= 0 && (first_full < 0 || first_fail <= first_full)) return hipstr::api_fail("internal error: inconsistent traceback operation string");
+  if (first_full >= 0) return hipstr::api_fail("hipstr_trace_out_t pools are too small (cap_chars)");
+  tm.d2h += tm.lap();
+  const TraceOutView V(o); const AsmDense dense = asm_dense(W.ad);
+  std::vector<HomePiece> home;
+  for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++){
+    const int p = TD_ARR_POOL[a]; const size_t esz = TD_ARR_ESZ[a];
+    home.push_back(HomePiece{dense.p[a], (size_t)(tot[p] - pool_total[p])*esz, (char*)V.arr[a] + (size_t)pool_total[p]*esz, (size_t)(dense.p[a] - AB.d)});
+  }
+  if (copy_home(C.T.stream, hout, home)) return 1;
+  memcpy(V.ll + q0, pin.p + B.ll, (size_t)nq*8); memcpy(V.max_index + q0, pin.p + B.mxi, (size_t)nq*4);
+  const int32_t* sc = (const int32_t*)(hout + AB.scal);
+  for (int i = 0; i < 5; i++) memcpy(V.scal[i] + q0, sc + (size_t)i*W.max_nq, (size_t)nq*4);
+  for (int p = 0; p < HS_ASM_POOLS; p++)
+    memcpy(V.off[p] + hs_asm_pool_n(p, q0) + 1, incl + hs_asm_pool_at(p, nq), (size_t)hs_asm_pool_n(p, nq)*4);
+  for (int p = 0; p < HS_ASM_POOLS; p++) pool_total[p] = tot[p];
+  tm.replay += tm.lap();
+  return 0;
+}
+
+// ---- finisher 3: the records stay.  Only the totals block comes home; the chunk's dense pieces go device-to-device into a segment of
+// exactly their size (the next chunk's kernels reuse the staging and result blocks: they queue behind these copies on the same stream)
+int finish_resident(const TraceCtx& C, const TraceWork& W, const TraceChunk& Ch, int64_t pool_total[HS_ASM_POOLS], TraceSegs& segs){
+  const int nq = Ch.nq; const hipStream_t st = C.T.stream;
+  int64_t tot[HS_ASM_POOLS], cnt[HS_ASM_POOLS];
+  {
+    PinBlock tb(C.T.ctx, st, W.aout.scal);
+    if (!tb.p) return hipstr::api_fail("out of pinned host memory");
+    HS_HIP(hipMemcpyAsync(tb.p, W.aout.d, W.aout.scal, hipMemcpyDeviceToHost, st));
+    HS_HIP(hipstr::wait_stream(st));
+    if (*(const int32_t*)(tb.p + HS_ASM_POOLS*8) >= 0) return hipstr::api_fail("internal error: inconsistent traceback operation string");
+    memcpy(tot, tb.p, sizeof tot);
+  }
+  for (int p = 0; p < HS_ASM_POOLS; p++){
+    if (tot[p] > 0x7fffffff) return hipstr::api_fail("too many requests for one call; split the request list");      // (the offsets are 32-bit)
+    cnt[p] = tot[p] - pool_total[p];
+  }
+  hipstr_trace_dev* sg = trace_dev_new(C.T.ctx, st, nq, cnt);
+  if (!sg) return 1;
+  segs.v.push_back(sg); segs.q0.push_back(Ch.q0);
+  HS_HIP(d2d(st, sg->ll, W.hc.ll, (size_t)nq*8)); HS_HIP(d2d(st, sg->max_index, W.hc.max_index, (size_t)nq*4));
+  for (int i = 0; i < 5; i++) HS_HIP(d2d(st, sg->scal[i], W.ad.stutter_size + (size_t)i*W.max_nq, (size_t)nq*4));
+  for (int p = 0; p < HS_ASM_POOLS; p++){
+    HS_HIP(hipMemsetAsync(sg->off[p], 0, 4, st));           // (the leading 0: the first chunk's is the result's)
+    HS_HIP(d2d(st, sg->off[p] + 1, W.ad.incl + hs_asm_pool_at(p, nq), (size_t)hs_asm_pool_n(p, nq)*4));
+  }
+  const AsmDense dense = asm_dense(W.ad);
+  for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) HS_HIP(d2d(st, sg->arr[a], dense.p[a], (size_t)cnt[TD_ARR_POOL[a]]*TD_ARR_ESZ[a]));
+  for (int p = 0; p < HS_ASM_POOLS; p++) pool_total[p] = tot[p];
+  return 0;
+}
+
+// ---- stage 6, the resident form: the handle.  One chunk: its segment is the result, nothing is copied twice.  Several (or none: the empty
+// call): the segments side by side in flat arrays, then the segments go back (TraceSegs).
+int join_segments(const TraceCtx& C, TraceSegs& segs, const int64_t pool_total[HS_ASM_POOLS], hipstr_trace_dev** res){
+  const hipStream_t st = C.T.stream;
+  TraceDevGuard g{NULL, st};
+  if (segs.v.size() == 1){ g.t = segs.v[0]; segs.v.clear(); }
+  else {
+    hipstr_trace_dev* td = g.t = trace_dev_new(C.T.ctx, st, C.n_req, pool_total);
+    if (!td) return 1;
+    int64_t at[HS_ASM_POOLS] = {0, 0, 0, 0, 0, 0, 0};
+    for (int p = 0; p < HS_ASM_POOLS; p++) HS_HIP(hipMemsetAsync(td->off[p], 0, 4, st));
+    for (size_t c = 0; c < segs.v.size(); c++){
+      const hipstr_trace_dev* sg = segs.v[c]; const int q0 = segs.q0[c], nq = sg->n_req;
+      HS_HIP(d2d(st, td->ll + q0, sg->ll, (size_t)nq*8)); HS_HIP(d2d(st, td->max_index + q0, sg->max_index, (size_t)nq*4));
+      for (int i = 0; i < 5; i++) HS_HIP(d2d(st, td->scal[i] + q0, sg->scal[i], (size_t)nq*4));
+      for (int p = 0; p < HS_ASM_POOLS; p++) HS_HIP(d2d(st, td->off[p] + hs_asm_pool_n(p, q0) + 1, sg->off[p] + 1, (size_t)hs_asm_pool_n(p, nq)*4));
+      for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++){
+        const int p = TD_ARR_POOL[a];
+        HS_HIP(d2d(st, td->arr[a] + (size_t)at[p]*TD_ARR_ESZ[a], sg->arr[a], (size_t)sg->totals[p]*TD_ARR_ESZ[a]));
+      }
+      for (int p = 0; p < HS_ASM_POOLS; p++) at[p] += sg->totals[p];
+    }
+    HS_HIP(hipstr::wait_stream(st));
+  }
+  if (hipstr::wait_stream(st) != hipSuccess) return hipstr::api_fail("hipstr_hmm_trace_resident: the device failed");
+  g.t->n_req = C.n_req; g.t->groups = HIPSTR_TRACE_F_ALL; g.t->checked = true;
+  *res = g.release();
+  return 0;
+}
+
+// flags 0: the host replays the operation strings; HIPSTR_TRACE_ASSEMBLE_DEVICE: hs_trace_assemble / _scan / _compact build the records, which
+// go to the caller's buffers (o) or stay on the device (res: a handle, complete when the call returns)
+int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+               const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o, hipstr_trace_dev** res){
+  hipstr::ApiTimer prof_t(hipstr::PB_TRACE);
+  using hipstr::api_fail;
+  if (!b || (!o && !res) || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return api_fail("null argument");
+  if (b->n_loci < 1) return api_fail("hipstr_hmm_trace needs at least one locus");
+  { std::string bad; if (hipstr::validate_tables(b, bad)) return api_fail(bad); }
+  TraceCtx C = { b, n_req, req_read, req_allele, hap_to_ref, (flags & HIPSTR_TRACE_ASSEMBLE_DEVICE) != 0, getenv("HIPSTR_TRACE_TIMING") != NULL };
+  TraceTimes tm;
+  if (hipstr::api_device_tables(&C.T)) return 1;
+  C.HT = &hipstr::host_tables();
+  // ---- 1: what the request list means, or why it is refused
+  TraceRequests R;
+  if (const char* why = trace_resolve(b, n_req, req_read, req_allele, req_seed, R)) return api_fail(why);
+  if (o){ const TraceOutView V(o); for (int p = 0; p < HS_TRACE_DEV_POOLS; p++) V.off[p][0] = 0; }
+  int64_t pool_total[HS_ASM_POOLS] = {0, 0, 0, 0, 0, 0, 0};       // device assembly: totals of the chunks done
+  TraceSegs segs; segs.st = C.T.stream;                          // resident result: a segment per chunk
+  if (n_req == 0) return res ? join_segments(C, segs, pool_total, res) : 0;      // (no segments: a valid empty handle, the seven leading zeros)
+  // ---- 2: the alleles of its distinct (locus, allele) pairs
+  AllelePreps A;
+  if (const char* why = trace_prepare_alleles(b, R, C.on_device ? hap_to_ref : NULL, A)) return api_fail(why);
+  tm.prep = tm.lap();
+  // ---- 3, 4: the static upload; the budget, the sides, the workspace
+  hipstr::ScratchBufs dev;
+  dev.runs_on(C.T.stream);
+  TraceWork W;
+  if (trace_upload_static(C, R, A, W) || trace_workspace(C, R, A, dev, W)) return 1;
+  tm.fixed = tm.lap();
+  // ---- 5: chunks of requests whose matrices fit the budget
+  for (int q0 = 0; q0 < n_req; ){
+    TraceChunk Ch(q0, trace_chunk_end(R.need, q0, W.budget));
+    if (trace_chunk_upload(C, R, A, W, pool_total, Ch)) return 1;
+    tm.upload += tm.lap();
+    if (trace_chunk_launch(C, Ch)) return 1;
+    tm.kernel += tm.lap();
+    if (res ? finish_resident(C, W, Ch, pool_total, segs) : C.on_device ? finish_to_caller(C, W, Ch, pool_total, o, tm) : finish_host_replay(C, R, A, W, Ch, o, tm)) return 1;
+    q0 = Ch.q1;
+  }
+  // ---- 6
+  if (res && join_segments(C, segs, pool_total, res)) return 1;
+  if (C.timing)
+    fprintf(stderr, "hipstr_hmm_trace: %d requests; prep %.3f ms, static upload+alloc %.3f, chunk upload %.3f, kernels %.3f, d2h %.3f, replay %.3f, total %.3f\n",
+            n_req, tm.prep, tm.fixed, tm.upload, tm.kernel, tm.d2h, tm.replay, (tm.lap(), tm.total));
+  return 0;
+}
+
+}  // namespace
 
 extern "C" int hipstr_hmm_trace(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                 const char* const* hap_to_ref, hipstr_trace_out_t* o){
@@ -1243,614 +1937,6 @@ extern "C" int hipstr_hmm_trace_resident(const hipstr_batch_t* b, int32_t n_req,
   return trace_call(b, n_req, req_read, req_allele, req_seed, hap_to_ref, HIPSTR_TRACE_ASSEMBLE_DEVICE, NULL, td);
 }
 
-// flags 0: the host replays the operation strings; HIPSTR_TRACE_ASSEMBLE_DEVICE: hs_trace_assemble / _scan / _compact build the records, which
-// go to the caller's buffers (o) or stay on the device (res: a handle, complete when the call returns)
-static int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
-                      const int32_t* req_seed, const char* const* hap_to_ref, uint32_t flags, hipstr_trace_out_t* o, hipstr_trace_dev** res){
-  hipstr::ApiTimer prof_t(hipstr::PB_TRACE);
-  const bool on_device = (flags & HIPSTR_TRACE_ASSEMBLE_DEVICE) != 0;
-  using hipstr::api_fail;
-  if (!b || (!o && !res) || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return api_fail("null argument");
-  if (b->n_loci < 1) return api_fail("hipstr_hmm_trace needs at least one locus");
-  { std::string bad; if (hipstr::validate_tables(b, bad)) return api_fail(bad); }
-  const bool timing = getenv("HIPSTR_TRACE_TIMING") != NULL;
-  auto now = [](){ return std::chrono::steady_clock::now(); };
-  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b){ return std::chrono::duration<double, std::milli>(b - a).count(); };
-  const auto t_begin = now();
-  hipstr::ApiTables T;
-  if (hipstr::api_device_tables(&T)) return 1;
-  const hipstr::HostTables& HT = hipstr::host_tables();
-  const int n_loci = b->n_loci;
-  const int n_reads = b->read_off[n_loci];
-  std::vector<int32_t> opt_base(n_loci + 1, 0);           // first option (over all blocks) of every locus
-  for (int l = 0; l < n_loci; l++){
-    if (b->period[l] < 1 || b->period[l] > 9) return api_fail("STR period must be in [1,9] (stutter_model.h:38)");
-    int cnt = 0;
-    for (int k = 0; k < 3; k++){
-      if (b->blk_nopts[3*l+k] < 1) return api_fail("haplotype block without options");
-      cnt += b->blk_nopts[3*l+k];
-    }
-    opt_base[l+1] = opt_base[l] + cnt;
-  }
-  if (o){
-    o->hap_aln_off[0] = o->str_seq_off[0] = o->flank_seq_off[0] = o->indel_off[0] = o->snp_off[0] = 0;
-    o->cigar_off[0] = o->aln_str_off[0] = 0;
-  }
-  if (n_req == 0 && res){                                  // a valid empty handle: the seven leading zeros
-    const int64_t none[HS_TRACE_DEV_POOLS] = {0, 0, 0, 0, 0, 0, 0};
-    hipstr_trace_dev* td = trace_dev_new(T.ctx, T.stream, 0, none);
-    if (!td) return 1;
-    for (int p = 0; p < HS_TRACE_DEV_POOLS; p++)
-      if (hipMemsetAsync(td->off[p], 0, 4, T.stream) != hipSuccess){ hipStreamSynchronize(T.stream); trace_dev_drop(td); return api_fail("hipMemsetAsync failed"); }
-    if (hipstr::wait_stream(T.stream) != hipSuccess){ trace_dev_drop(td); return api_fail("hipstr_hmm_trace_resident: the device failed"); }
-    td->groups = HIPSTR_TRACE_F_ALL; td->checked = true;
-    *res = td;
-    return 0;
-  }
-  if (n_req == 0) return 0;
-
-  // ---- per request: locus, seed, allele rows (own homopolymer context), sizes
-  hipstr::Prepared P;              // only its row / STR-option pools are used
-  std::vector<hs_row_t> rows;
-  std::map<int64_t, int> allele_slot;                    // (locus, allele) -> entry of `alleles`
-  std::vector<AllelePrep> alleles;
-  std::vector<int32_t> seeds(n_req), req_locus(n_req), req_ap(n_req);
-  std::string h2r_pool;                                  // device assembly: the hap_to_ref strings of the distinct (locus, allele) pairs requested
-  for (int q = 0; q < n_req; q++){
-    const int r = req_read[q], k = req_allele[q];
-    if (r < 0 || r >= n_reads) return api_fail("request names a read outside the batch");
-    const int l = (int)(std::upper_bound(b->read_off, b->read_off + n_loci + 1, r) - b->read_off) - 1;
-    const int32_t* nopts = b->blk_nopts + 3*l;
-    const int A = nopts[0]*nopts[1]*nopts[2];
-    if (k < 0 || k >= A) return api_fail("request names an allele outside its locus");
-    int s;
-    if (const char* why = trace_seed_of(b, l, r, req_seed, q, s)) return api_fail(why);
-    seeds[q] = s; req_locus[q] = l;
-    const int64_t key = ((int64_t)l << 32) | (uint32_t)k;
-    std::map<int64_t, int>::iterator hit = allele_slot.find(key);
-    if (hit != allele_slot.end()){ req_ap[q] = hit->second; continue; }
-    AllelePrep ap;
-    int32_t oi[3];
-    hipstr::allele_options(nopts, k, oi);
-    for (int x = 0, cur = opt_base[l]; x < 3; cur += nopts[x], x++){
-      const int oidx = cur + oi[x];
-      const std::string sq(b->seq + b->opt_off[oidx], b->opt_off[oidx+1] - b->opt_off[oidx]);
-      if (sq.empty()) return api_fail(x == 1 ? "empty STR allele is not supported" : "empty flank sequence");
-      if (x == 1 && sq.size() > HS_MAX_STR_BP) return api_fail("STR allele longer than 2047 bp is not supported");
-      ap.seq[0][x] = sq;
-      ap.seq[1][2-x] = std::string(sq.rbegin(), sq.rend());
-    }
-    if (ap.seq[0][0].size() + 1 + ap.seq[0][2].size() > 4095) return api_fail("flanks longer than 4094 bases in total are not supported");
-    for (int sd = 0; sd < 2; sd++){
-      std::vector<hs_row_t> lead, trail;
-      hipstr::fresh_flank_rows(ap.seq[sd], lead, trail);
-      ap.lead_off[sd] = rows.size();  rows.insert(rows.end(), lead.begin(), lead.end());
-      ap.trail_off[sd] = rows.size(); rows.insert(rows.end(), trail.begin(), trail.end());
-      ap.stropt[sd] = P.stropts.size();
-      hipstr::append_stropt(ap.seq[sd][1], b->period[l], b->stutter + 6*l, P);
-    }
-    if (on_device && hap_to_ref){
-      const char* s2 = hap_to_ref[b->hap_off[l] + k];
-      ap.h2r_off = (int32_t)h2r_pool.size(); ap.h2r_len = (int32_t)strlen(s2);
-      h2r_pool.append(s2, (size_t)ap.h2r_len);
-      if (h2r_pool.size() > 0x7fffffff) return api_fail("too many requests for one call; split the request list");
-    }
-    req_ap[q] = allele_slot[key] = (int)alleles.size();
-    alleles.push_back(ap);
-  }
-
-  const auto t_prep = now();
-  // ---- static device data
-  hipstr::ScratchBufs dev;
-  dev.runs_on(T.stream);
-  hs_tdev_t h; memset(&h, 0, sizeof h);
-  const int total_bases = b->base_off[n_reads];
-  // the reads' bases and qualities go up with the call: only those of the requested reads when they are a small part of the batch (a few
-  // loci of a large batch: the whole batch's 150 MB cost more than the call's kernels)
-  std::vector<int32_t> up_off(n_req);                  // a request's read in the uploaded arrays
-  std::vector<char> up_bases, up_quals;
-  bool compact_reads = false;
-  {
-    int64_t wanted = 0;
-    std::vector<int32_t> at((size_t)n_reads, -1);       // read -> offset in the compact arrays
-    for (int q = 0; q < n_req; q++){
-      const int r = req_read[q];
-      if (at[r] < 0){ at[r] = (int32_t)wanted; wanted += b->base_off[r+1] - b->base_off[r]; }
-    }
-    if (trace_compact_reads(wanted, total_bases)){
-      compact_reads = true;
-      up_bases.resize((size_t)wanted); up_quals.resize((size_t)wanted);
-      for (int q = 0; q < n_req; q++){
-        const int r = req_read[q], len = b->base_off[r+1] - b->base_off[r];
-        up_off[q] = at[r];
-        memcpy(up_bases.data() + at[r], b->bases + b->base_off[r], (size_t)len);
-        memcpy(up_quals.data() + at[r], b->quals + b->base_off[r], (size_t)len);
-      }
-    } else
-      for (int q = 0; q < n_req; q++) up_off[q] = b->base_off[req_read[q]];
-  }
-  const char* const src_bases = compact_reads ? up_bases.data() : b->bases;
-  const char* const src_quals = compact_reads ? up_quals.data() : b->quals;
-  const size_t n_up = compact_reads ? up_bases.size() : (size_t)total_bases;
-  hipstr::HostArena st_arena;                     // every table of the call: one pinned block, one copy
-  hs_adev_t ad; memset(&ad, 0, sizeof ad);
-  {
-    // device assembly: the block coordinates of every locus and the hap_to_ref pool travel with the tables
-    const size_t o_bs = on_device ? st_arena.add(b->blk_start, 3*(size_t)n_loci*sizeof(int32_t)) : 0, o_be = on_device ? st_arena.add(b->blk_end, 3*(size_t)n_loci*sizeof(int32_t)) : 0,
-                 o_h2r = on_device ? st_arena.add(h2r_pool.data(), h2r_pool.size()) : 0;
-    const size_t o_rows = st_arena.add(rows.data(), rows.size()*sizeof(hs_row_t)), o_so = st_arena.add(P.stropts.data(), P.stropts.size()*sizeof(hs_stropt_t)),
-                 o_vis = st_arena.add(P.visits.data(), P.visits.size()*sizeof(hs_visit_t)), o_f64 = st_arena.add(P.f64pool.data(), P.f64pool.size()*sizeof(double)),
-                 o_chars = st_arena.add(P.chars.data(), P.chars.size()), o_bases = st_arena.add(src_bases, n_up), o_quals = st_arena.add(src_quals, n_up);
-    if (st_arena.reserve(T.ctx)) return api_fail("out of device or pinned host memory");
-    if (st_arena.send(T.stream)) return 1;
-    h.rows = st_arena.at<hs_row_t>(o_rows); h.stropts = st_arena.at<hs_stropt_t>(o_so); h.visits = st_arena.at<hs_visit_t>(o_vis);
-    h.f64pool = st_arena.at<double>(o_f64); h.chars = st_arena.at<char>(o_chars); h.bases = st_arena.at<char>(o_bases); h.quals = st_arena.at<char>(o_quals);
-    if (on_device){ ad.blk_start = st_arena.at<int32_t>(o_bs); ad.blk_end = st_arena.at<int32_t>(o_be); ad.h2r = st_arena.at<char>(o_h2r); }
-  }
-  h.int_log = T.int_log; h.qual_correct = T.qual_correct; h.qual_error = T.qual_error; h.m2m = T.m2m; h.m2i = T.m2i;
-  h.log_thresh = HT.log_thresh;
-
-  // ---- chunks of requests whose matrices fit the workspace budget
-  // (the query costs as much as a small call's kernels: only a call whose matrices could exceed 256 MiB asks — an upper bound from the
-  //  longest read and the flank lengths of the first allele is enough to tell)
-  int64_t budget = (int64_t)HS_TRACE_BUDGET_MIB << 20;                                   // bytes of decision matrices per chunk
-  {
-    int64_t rough = 0;
-    for (int q = 0; q < n_req; q++){
-      const int r = req_read[q]; const AllelePrep& ap = alleles[req_ap[q]];
-      rough += (int64_t)(ap.seq[0][0].size() + ap.seq[0][2].size() + 2)*(b->base_off[r+1] - b->base_off[r]);
-    }
-    if (trace_asks_device(rough)){
-      size_t free_b = 0, total_b = 0;
-      HS_HIP(hipMemGetInfo(&free_b, &total_b));
-      budget = std::min<int64_t>((int64_t)8 << 30, (int64_t)(free_b / 4));
-    }
-  }
-  budget = trace_env_budget(budget);
-  std::vector<hs_tside_t> sides(2*(size_t)n_req);
-  std::vector<int64_t> need(n_req);
-  for (int q = 0; q < n_req; q++){
-    const int r = req_read[q];
-    const AllelePrep& ap = alleles[req_ap[q]];
-    const int len = b->base_off[r+1] - b->base_off[r];
-    need[q] = 0;
-    for (int sd = 0; sd < 2; sd++){
-      hs_tside_t& S = sides[2*q+sd];
-      memset(&S, 0, sizeof S);
-      S.base_off = up_off[q]; S.len = len; S.seed = seeds[q]; S.side = sd;
-      S.n = sd ? len - seeds[q] - 1 : seeds[q];
-      S.lead_off = ap.lead_off[sd]; S.F0 = ap.seq[sd][0].size();
-      S.trail_off = ap.trail_off[sd]; S.F2 = ap.seq[sd][2].size();
-      S.stropt = ap.stropt[sd];
-      S.ops_cap = trace_ops_cap(S.n, S.F0, S.F2, (int)ap.seq[sd][1].size(), b->period[req_locus[q]]);
-      need[q] += trace_side_ws(S.F0, S.F2, S.n);
-    }
-    if (need[q] > budget) return api_fail("one traceback needs more workspace than the device offers");
-  }
-
-  // workspaces are sized for the largest chunk once and reused
-  int64_t max_mat = 0, max_art = 0, max_ops = 0, max_lc = 0; int max_nq = 0;
-  {
-    int64_t mat = 0, art = 0, ops = 0, lc = 0; int nq = 0;
-    for (int q = 0; q < n_req; q++){
-      if (mat + need[q] > budget){ mat = art = ops = lc = 0; nq = 0; }
-      mat += need[q]; art += 2*(int64_t)(sides[2*q].n + sides[2*q+1].n); ops += sides[2*q].ops_cap + sides[2*q+1].ops_cap; nq++;
-      lc += 2*(int64_t)(sides[2*q].F0 + 1 + sides[2*q].F2);
-      max_mat = std::max(max_mat, mat); max_art = std::max(max_art, art); max_ops = std::max(max_ops, ops); max_lc = std::max(max_lc, lc);
-      max_nq = std::max(max_nq, nq);
-    }
-  }
-  if (max_art > 0x7fffffff || max_ops > 0x7fffffff || max_lc > 0x7fffffff) return api_fail("too many requests for one call; split the request list");
-  hs_tdev_t hc = h;
-  if (dev.alloc(&hc.dec, max_mat) || dev.alloc(&hc.lastcol, max_lc) || dev.alloc(&hc.arts, max_art) || dev.alloc(&hc.side_prob, 2*(size_t)max_nq)) return 1;
-  // what comes back — score, seed position, operation counts, artifact size and position per side, the operation strings — is one
-  // device block with the layout of the pinned block it is copied to: one copy per chunk
-  const size_t o_ll = 0, o_mxi = o_ll + (size_t)max_nq*8, o_nops = o_mxi + (size_t)max_nq*4, o_ssz = o_nops + 2*(size_t)max_nq*4, o_spos = o_ssz + 2*(size_t)max_nq*4,
-               o_ops = (o_spos + 2*(size_t)max_nq*4 + 15) & ~(size_t)15, o_end = o_ops + (size_t)(max_ops ? max_ops : 1);
-  char* d_res;
-  if (dev.alloc(&d_res, o_end)) return 1;
-  hc.ll = (double*)(d_res + o_ll); hc.max_index = (int32_t*)(d_res + o_mxi); hc.n_ops = (int32_t*)(d_res + o_nops);
-  hc.str_size = (int32_t*)(d_res + o_ssz); hc.str_pos = (int32_t*)(d_res + o_spos); hc.ops = d_res + o_ops;
-
-  // ---- device assembly: slots per request, staging and the result block sized for the largest chunk
-  std::vector<TraceAsmCaps> acaps;
-  int64_t mx_cap[5] = {0, 0, 0, 0, 0};                  // per chunk at most: hap_aln, seq, indel, snp, stitched entries
-  size_t ao_scal = 0, ao_incl = 0, ao_i32 = 0, ao_chr = 0, ao_end = 0;
-  char* d_out = NULL;
-  if (on_device){
-    acaps.resize(n_req);
-    for (int q = 0; q < n_req; q++){
-      const hs_tside_t& SL = sides[2*q];
-      acaps[q] = trace_asm_caps(SL.ops_cap, sides[2*q+1].ops_cap, SL.len, SL.F0, SL.F2, alleles[req_ap[q]].h2r_len);
-    }
-    for (int q0 = 0; q0 < n_req; ){
-      const int q1 = trace_chunk_end(need, q0, budget);
-      int64_t c[5] = {0, 0, 0, 0, 0};
-      for (int q = q0; q < q1; q++){ c[0] += acaps[q].hap_aln; c[1] += acaps[q].seq; c[2] += acaps[q].indel; c[3] += acaps[q].snp; c[4] += acaps[q].stitched; }
-      for (int i = 0; i < 5; i++) mx_cap[i] = std::max(mx_cap[i], c[i]);
-      q0 = q1;
-    }
-    for (int i = 0; i < 5; i++) if (2*mx_cap[i] > 0x7fffffff) return api_fail("too many requests for one call; split the request list");
-    const size_t nqm = (size_t)max_nq, n_in = (size_t)mx_cap[2], n_sn = (size_t)mx_cap[3], n_fa = (size_t)mx_cap[4];
-    if (dev.alloc(&ad.st_indel_pos, n_in) || dev.alloc(&ad.st_indel_size, n_in) || dev.alloc(&ad.st_snp_pos, n_sn) || dev.alloc(&ad.st_cig_len, n_fa) ||
-        dev.alloc(&ad.st_snp_base, n_sn) || dev.alloc(&ad.st_fa, n_fa) || dev.alloc(&ad.st_cig_op, n_fa) || dev.alloc(&ad.st_aln, n_fa) ||
-        dev.alloc(&ad.lens, 8*nqm) || dev.alloc(&ad.excl, 8*nqm) || dev.alloc(&ad.rng, 3*nqm) || dev.alloc(&ad.fail, nqm)) return 1;
-    // the result block, with the layout of the pinned block it is copied to: totals and the first failure | five scalars per request |
-    // the running offsets | int32 pools | char pools
-    ao_scal = 64; ao_incl = ao_scal + 5*nqm*4; ao_i32 = ao_incl + 8*nqm*4;
-    ao_chr = ao_i32 + (2*n_in + n_sn + n_fa)*4;
-    ao_end = ao_chr + (size_t)mx_cap[0] + 3*(size_t)mx_cap[1] + n_sn + 2*n_fa;
-    if (dev.alloc(&d_out, ao_end)) return 1;
-    ad.totals = (int64_t*)d_out; ad.first_fail = (int32_t*)(d_out + HS_ASM_POOLS*8);
-    int32_t* sc = (int32_t*)(d_out + ao_scal);
-    ad.stutter_size = sc; ad.flank_ins = sc + nqm; ad.flank_del = sc + 2*nqm; ad.aln_start = sc + 3*nqm; ad.aln_stop = sc + 4*nqm;
-    ad.incl = (int32_t*)(d_out + ao_incl);
-    int32_t* pi = (int32_t*)(d_out + ao_i32);
-    ad.p_indel_pos = pi; ad.p_indel_size = pi + n_in; ad.p_snp_pos = pi + 2*n_in; ad.p_cig_len = pi + 2*n_in + n_sn;
-    char* pc = d_out + ao_chr;
-    ad.p_hap_aln = pc; ad.p_str_seq = pc + mx_cap[0]; ad.p_flank = ad.p_str_seq + mx_cap[1]; ad.p_snp_base = ad.p_flank + 2*mx_cap[1];
-    ad.p_cig_op = ad.p_snp_base + n_sn; ad.p_aln = ad.p_cig_op + n_fa;
-    ad.dense_cap[0] = mx_cap[0]; ad.dense_cap[1] = mx_cap[1]; ad.dense_cap[2] = 2*mx_cap[1]; ad.dense_cap[3] = mx_cap[2]; ad.dense_cap[4] = mx_cap[3];
-    ad.dense_cap[5] = ad.dense_cap[6] = mx_cap[4];
-  }
-  int64_t pool_total[HS_ASM_POOLS] = {0, 0, 0, 0, 0, 0, 0};       // totals of the chunks done
-  TraceSegs segs; segs.st = T.stream;                            // resident result: a segment per chunk
-
-  const auto t_static = now();
-  double ms_alloc = 0, ms_kernel = 0, ms_d2h = 0, ms_replay = 0;
-  for (int q0 = 0; q0 < n_req; ){
-    const auto c0 = now();
-    const int q1 = trace_chunk_end(need, q0, budget);
-    int64_t mat = 0; int64_t n_art = 0, n_ops = 0, n_lc = 0;
-    for (int q = q0; q < q1; q++){
-      for (int sd = 0; sd < 2; sd++){
-        hs_tside_t& S = sides[2*q+sd];
-        S.dec_off = mat; mat += trace_side_ws(S.F0, S.F2, S.n);
-        S.lc_off = (int32_t)n_lc; n_lc += S.F0 + 1 + S.F2;
-        S.art_off = (int32_t)n_art; n_art += 2*S.n;
-        S.ops_off = (int32_t)n_ops; n_ops += S.ops_cap;
-      }
-    }
-    const int nq = q1 - q0;
-    // launch order: sides grouped by columns-per-lane class
-    std::vector<int32_t> items; int cls_begin[HS_MAX_COLS+1];
-    for (int cl = 1; cl <= HS_MAX_COLS; cl++){
-      cls_begin[cl-1] = items.size();
-      for (int si = 2*q0; si < 2*q1; si++) if (trace_col_class(sides[si].n) == cl) items.push_back(si - 2*q0);
-    }
-    cls_begin[HS_MAX_COLS] = items.size();
-    hipstr::HostArena ch_arena;                     // this chunk's sides, launch order and argument block
-    hs_tdev_t hcc = hc;
-    std::vector<hs_areq_t> areqs;
-    if (on_device){
-      areqs.resize(nq);
-      int64_t at_in = 0, at_sn = 0, at_fa = 0;
-      for (int q = q0; q < q1; q++){
-        hs_areq_t& R = areqs[q-q0]; const AllelePrep& ap = alleles[req_ap[q]]; const TraceAsmCaps& c = acaps[q];
-        R.loc = req_locus[q]; R.h2r_off = ap.h2r_off; R.h2r_len = ap.h2r_len;
-        R.indel_cap = c.indel; R.snp_cap = c.snp; R.fa_cap = c.stitched;
-        R.indel_off = at_in; R.snp_off = at_sn; R.fa_off = at_fa;
-        at_in += c.indel; at_sn += c.snp; at_fa += c.stitched;
-      }
-    }
-    const size_t o_sides = ch_arena.add(sides.data() + 2*q0, 2*(size_t)nq*sizeof(hs_tside_t)), o_items = ch_arena.add(items.data(), items.size()*sizeof(int32_t)),
-                 o_args = ch_arena.add(&hcc, sizeof hcc), o_areq = on_device ? ch_arena.add(areqs.data(), areqs.size()*sizeof(hs_areq_t)) : 0;
-    // (the argument block points into the arena it travels in: sizes first, then the pointers, then the copy)
-    if (ch_arena.reserve(T.ctx)) return api_fail("out of device or pinned host memory");
-    hcc.sides = ch_arena.at<hs_tside_t>(o_sides); hcc.items = ch_arena.at<int32_t>(o_items);
-    if (ch_arena.send(T.stream)) return 1;
-    const hs_tdev_t* d_args = ch_arena.at<hs_tdev_t>(o_args);
-    const auto c1 = now();
-    // the fill kernels of the column classes: one launch per class for calls of many loci, ONE launch for the requests of a locus or two (hs_trace_fill_mixed)
-    int n_cls = 0; for (int cl = 1; cl <= HS_TRACE_STATIC_CLASSES; cl++) n_cls += (cls_begin[cl] - cls_begin[cl-1]) > 0;
-    const bool mixed = trace_mixed_launch(n_cls, nq);
-    if (mixed){
-      hs_tcls_t cls;
-      for (int cl = 1; cl <= HS_TRACE_STATIC_CLASSES; cl++) cls.end[cl-1] = cls_begin[cl];
-      hipLaunchKernelGGL(hs_trace_fill_mixed, dim3(cls_begin[HS_TRACE_STATIC_CLASSES]), dim3(64), 0, T.stream, d_args, cls);
-    }
-    for (int cl = mixed ? HS_TRACE_STATIC_CLASSES + 1 : 1; cl <= HS_MAX_COLS; cl++){
-      const int cnt = cls_begin[cl] - cls_begin[cl-1];
-      if (cnt == 0) continue;
-      hipStream_t ks = T.stream;
-      switch (trace_fill_cols(cl)){
-        case 1: hipLaunchKernelGGL(hs_trace_fill<1>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
-        case 2: hipLaunchKernelGGL(hs_trace_fill<2>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
-        case 3: hipLaunchKernelGGL(hs_trace_fill<3>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
-        case 4: hipLaunchKernelGGL(hs_trace_fill<4>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
-        case 5: hipLaunchKernelGGL(hs_trace_fill<5>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
-        case 6: hipLaunchKernelGGL(hs_trace_fill<6>, dim3(cnt), dim3(64), 0, ks, d_args, cls_begin[cl-1]); break;
-        case 8: if (launch_fill_long<8>(cnt, ks, d_args, cls_begin[cl-1])) return api_fail("hipFuncSetAttribute (traceback LDS) failed"); break;
-        case 12: if (launch_fill_long<12>(cnt, ks, d_args, cls_begin[cl-1])) return api_fail("hipFuncSetAttribute (traceback LDS) failed"); break;
-        default: if (launch_fill_long<16>(cnt, ks, d_args, cls_begin[cl-1])) return api_fail("hipFuncSetAttribute (traceback LDS) failed"); break;
-      }
-    }
-    hipLaunchKernelGGL(hs_trace_walk, dim3(nq), dim3(64), 0, T.stream, d_args, 0);
-    if (on_device){
-      // ---- the records on the device: assemble, offsets, compaction; then the totals, then every pool and array in one copy each
-      hs_adev_t ac = ad;
-      ac.reqs = ch_arena.at<hs_areq_t>(o_areq); ac.nq = nq;
-      for (int p = 0; p < HS_ASM_POOLS; p++) ac.base[p] = pool_total[p];
-      hipEvent_t ev[2] = {NULL, NULL};
-      if (timing){ HS_HIP(hipEventCreate(&ev[0])); HS_HIP(hipEventCreate(&ev[1])); HS_HIP(hipEventRecord(ev[0], T.stream)); }
-      hipLaunchKernelGGL(hs_trace_assemble, dim3(nq), dim3(64), 0, T.stream, d_args, ac);
-      hipLaunchKernelGGL(hs_trace_scan, dim3(HS_ASM_POOLS + 1), dim3(64), 0, T.stream, ac);
-      hipLaunchKernelGGL(hs_trace_compact, dim3(nq), dim3(64), 0, T.stream, d_args, ac);
-      if (timing) HS_HIP(hipEventRecord(ev[1], T.stream));
-      HS_HIP(hipGetLastError());
-      const auto c2 = now();
-      struct PinGuard { hipstr::Ctx* c; void* p; ~PinGuard(){ hipstr::pin_free(c, p); } };
-      if (res){
-        // ---- the records stay: only the totals block comes home; the chunk's dense pieces go device-to-device into a segment of exactly
-        // their size (the next chunk's kernels reuse the staging and result blocks: they queue behind these copies on the same stream)
-        char* tb = (char*)hipstr::pin_alloc(T.ctx, ao_scal);
-        if (!tb) return api_fail("out of pinned host memory");
-        PinGuard tb_guard{T.ctx, tb};
-        HS_HIP(hipMemcpyAsync(tb, d_out, ao_scal, hipMemcpyDeviceToHost, T.stream));
-        HS_HIP(hipstr::wait_stream(T.stream));
-        if (timing){ hipEventDestroy(ev[0]); hipEventDestroy(ev[1]); }
-        const int64_t* tot = (const int64_t*)tb;
-        if (*(const int32_t*)(tb + HS_ASM_POOLS*8) >= 0) return api_fail("internal error: inconsistent traceback operation string");
-        int64_t cnt[HS_ASM_POOLS];
-        for (int p = 0; p < HS_ASM_POOLS; p++){
-          if (tot[p] > 0x7fffffff) return api_fail("too many requests for one call; split the request list");      // (the offsets are 32-bit)
-          cnt[p] = tot[p] - pool_total[p];
-        }
-        hipstr_trace_dev* sg = trace_dev_new(T.ctx, T.stream, nq, cnt);
-        if (!sg) return 1;
-        segs.v.push_back(sg); segs.q0.push_back(q0);
-        auto d2d = [&](void* dst, const void* src, size_t nb){ return nb ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, T.stream) : hipSuccess; };
-        HS_HIP(d2d(sg->ll, hc.ll, (size_t)nq*8)); HS_HIP(d2d(sg->max_index, hc.max_index, (size_t)nq*4));
-        for (int i = 0; i < 5; i++) HS_HIP(d2d(sg->scal[i], ad.stutter_size + (size_t)i*max_nq, (size_t)nq*4));
-        for (int p = 0; p < HS_ASM_POOLS; p++){
-          HS_HIP(hipMemsetAsync(sg->off[p], 0, 4, T.stream));           // (the leading 0: the first chunk's is the result's)
-          HS_HIP(d2d(sg->off[p] + 1, ac.incl + hs_asm_pool_at(p, nq), (size_t)hs_asm_pool_n(p, nq)*4));
-        }
-        const void* const dense[HS_TRACE_DEV_ARRAYS] = { ac.p_hap_aln, ac.p_str_seq, ac.p_flank, ac.p_indel_pos, ac.p_indel_size, ac.p_snp_pos, ac.p_snp_base,
-                                                         ac.p_cig_op, ac.p_cig_len, ac.p_aln };
-        for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) HS_HIP(d2d(sg->arr[a], dense[a], (size_t)cnt[TD_ARR_POOL[a]]*TD_ARR_ESZ[a]));
-        for (int p = 0; p < HS_ASM_POOLS; p++) pool_total[p] = tot[p];
-        q0 = q1;
-        continue;
-      }
-      char* hostblk = (char*)hipstr::pin_alloc(T.ctx, o_nops + ao_end);
-      if (!hostblk) return api_fail("out of pinned host memory");
-      PinGuard pin_guard{T.ctx, hostblk};
-      char* hout = hostblk + o_nops;
-      HS_HIP(hipMemcpyAsync(hostblk, d_res, o_nops, hipMemcpyDeviceToHost, T.stream));                 // ll, max_index
-      HS_HIP(hipMemcpyAsync(hout, d_out, ao_i32, hipMemcpyDeviceToHost, T.stream));                    // totals, scalars, offsets
-      HS_HIP(hipstr::wait_stream(T.stream));
-      if (timing){
-        float kms = 0; HS_HIP(hipEventElapsedTime(&kms, ev[0], ev[1])); hipEventDestroy(ev[0]); hipEventDestroy(ev[1]);
-        fprintf(stderr, "  assemble + scan + compact of %d: %.3f ms on the device\n", nq, kms);
-      }
-      const int64_t* tot = (const int64_t*)hout;
-      const int32_t first_fail = *(const int32_t*)(hout + HS_ASM_POOLS*8);
-      const int32_t* incl = (const int32_t*)(hout + ao_incl);
-      const int64_t cap = o->cap_chars;
-      // the host path's order: request by request, an inconsistent operation string before a full pool
-      int first_full = -1;
-      { bool over = false; for (int p = 0; p < HS_ASM_POOLS; p++) over = over || tot[p] > cap;
-        if (over) for (int q = 0; q < nq && first_full < 0; q++) for (int p = 0; p < HS_ASM_POOLS; p++){
-          const int i = hs_asm_pool_at(p, nq) + (p == 2 ? 2*q+1 : q);
-          // (the offsets are 32-bit: one that wrapped is past any capacity too)
-          if (incl[i] > cap || incl[i] < 0){ first_full = q; break; }
-        }
-        if (over && first_full < 0) first_full = 0; }
-      if (first_fail >= 0 && (first_full < 0 || first_fail <= first_full)) return api_fail("internal error: inconsistent traceback operation string");
-      if (first_full >= 0) return api_fail("hipstr_trace_out_t pools are too small (cap_chars)");
-      const auto c3 = now();
-      struct Pool { int p; const void* dev; size_t esz; void* dst; };
-      const Pool pools[] = {
-        {0, ac.p_hap_aln, 1, o->hap_aln}, {1, ac.p_str_seq, 1, o->str_seq}, {2, ac.p_flank, 1, o->flank_seq},
-        {3, ac.p_indel_pos, 4, o->indel_pos}, {3, ac.p_indel_size, 4, o->indel_size}, {4, ac.p_snp_pos, 4, o->snp_pos}, {4, ac.p_snp_base, 1, o->snp_base},
-        {5, ac.p_cig_op, 1, o->cigar_op}, {5, ac.p_cig_len, 4, o->cigar_len}, {6, ac.p_aln, 1, o->aln_str} };
-      std::vector<HomePiece> home;
-      for (const Pool& pl : pools)
-        home.push_back(HomePiece{pl.dev, (size_t)(tot[pl.p] - pool_total[pl.p])*pl.esz, (char*)pl.dst + (size_t)pool_total[pl.p]*pl.esz, (size_t)((const char*)pl.dev - d_out)});
-      if (copy_home(T.stream, hout, home)) return 1;
-      memcpy(o->ll + q0, hostblk + o_ll, (size_t)nq*8); memcpy(o->max_index + q0, hostblk + o_mxi, (size_t)nq*4);
-      const int32_t* sc = (const int32_t*)(hout + ao_scal);
-      int32_t* const scal_dst[5] = { o->stutter_size, o->flank_ins, o->flank_del, o->aln_start, o->aln_stop };
-      for (int i = 0; i < 5; i++) memcpy(scal_dst[i] + q0, sc + (size_t)i*max_nq, (size_t)nq*4);
-      int32_t* const off_dst[HS_ASM_POOLS] = { o->hap_aln_off, o->str_seq_off, o->flank_seq_off, o->indel_off, o->snp_off, o->cigar_off, o->aln_str_off };
-      for (int p = 0; p < HS_ASM_POOLS; p++)
-        memcpy(off_dst[p] + (p == 2 ? 2*q0 : q0) + 1, incl + hs_asm_pool_at(p, nq), (size_t)hs_asm_pool_n(p, nq)*4);
-      for (int p = 0; p < HS_ASM_POOLS; p++) pool_total[p] = tot[p];
-      q0 = q1;
-      const auto c4 = now();
-      ms_alloc += ms(c0, c1); ms_kernel += ms(c1, c2); ms_d2h += ms(c2, c3); ms_replay += ms(c3, c4);
-      continue;
-    }
-    HS_HIP(hipGetLastError());
-    const auto c2 = now();
-    // results through one pinned block (a pageable destination costs a staging copy per call and per array), in one copy behind the kernels
-    char* hostblk = (char*)hipstr::pin_alloc(T.ctx, o_end);
-    if (!hostblk) return api_fail("out of pinned host memory");
-    struct PinGuard { hipstr::Ctx* c; void* p; ~PinGuard(){ hipstr::pin_free(c, p); } } pin_guard{T.ctx, hostblk};
-    HS_HIP(hipMemcpyAsync(hostblk, d_res, o_ops + (size_t)(n_ops ? n_ops : 1), hipMemcpyDeviceToHost, T.stream));
-    HS_HIP(hipstr::wait_stream(T.stream));
-    const double* ll = (const double*)(hostblk + o_ll); const int32_t* mxi = (const int32_t*)(hostblk + o_mxi);
-    const int32_t* nops = (const int32_t*)(hostblk + o_nops); const int32_t* ssz = (const int32_t*)(hostblk + o_ssz); const int32_t* spos = (const int32_t*)(hostblk + o_spos);
-    const char* opsbuf_p = hostblk + o_ops;
-    const auto c3 = now();
-
-    // ---- replay (HapAligner.cpp:642-707) + stitch, request by request; independent, so spread over host threads
-    std::vector<ReqOut> res(nq);
-    auto work = [&](int qa, int qb){
-      for (int q = qa; q < qb; q++){
-        ReqOut& R = res[q-q0];
-        const int r = req_read[q], sb = seeds[q], l = req_locus[q];
-        const AllelePrep& ap = alleles[req_ap[q]];
-        const int len = b->base_off[r+1] - b->base_off[r];
-        const char* bases = b->bases + b->base_off[r];
-        const char* quals = b->quals + b->base_off[r];
-        const int max_index = mxi[q-q0];
-        const int blen3[3] = { (int)ap.seq[0][0].size(), (int)ap.seq[0][1].size(), (int)ap.seq[0][2].size() };
-        const int H = blen3[0] + blen3[1] + blen3[2];
-        // left retrace, then the seed base joins the flank it sits in, then the right retrace (HapAligner.cpp:642-684)
-        std::string side_ops[2];
-        int seed_block = 0;
-        for (int x = 0, crd = max_index; x < 3; x++){ if (crd < blen3[x]){ seed_block = x; break; } crd -= blen3[x]; }
-        for (int sd = 0; sd < 2 && R.ok; sd++){
-          const hs_tside_t& S = sides[2*q+sd];
-          const int cnt = nops[2*(q-q0)+sd];
-          if (cnt > S.ops_cap){ R.ok = false; break; }
-          side_ops[sd].assign(opsbuf_p + S.ops_off, cnt);
-          if (sd == 1 && seed_block != 1) R.acc.flank[seed_block].push_back(bases[sb]);
-          const int mx = sd ? H-1-max_index : max_index;
-          if (mx == 0) continue;                         // this side is all soft clips
-          std::string rd(S.n, ' '); std::vector<double> lc(S.n);
-          for (int j = 0; j < S.n; j++){
-            const int src = sd ? len-1-j : j;
-            rd[j] = bases[src]; lc[j] = HT.qual_correct[(uint8_t)quals[src]];
-          }
-          int blk = 0, crd = mx;
-          for (int x = 0; x < 3; x++){ const int bl = ap.seq[sd][x].size(); if (crd < bl){ blk = x; break; } crd -= bl; }
-          int block, base;
-          if (crd == 0){ block = blk-1; base = (int)ap.seq[sd][block].size()-1; } else { block = blk; base = crd-1; }
-          if (!replay_side(b, l, ap.seq[sd], sd != 0, rd, lc, side_ops[sd], ssz[2*(q-q0)+sd], spos[2*(q-q0)+sd], block, base, R.acc)) R.ok = false;
-        }
-        if (!R.ok) continue;
-        R.hap_aln.assign(side_ops[0].rbegin(), side_ops[0].rend());
-        R.hap_aln.push_back('M');
-        R.hap_aln += side_ops[1];
-        if (hap_to_ref == NULL) continue;
-        // ---- stitch_alignment_trace (AlignmentTraceback.cpp:55-144)
-        const std::string& full = R.hap_aln;
-        const char* h2r = hap_to_ref[b->hap_off[l] + req_allele[q]];
-        const int hlen = (int)strlen(h2r);
-        int hap_index = max_index, hai = 0; int32_t seed_pos = b->blk_start[3*l];
-        while (hap_index > 0 && hai < hlen){
-          if (h2r[hai] == 'M' || h2r[hai] == 'I') hap_index--;
-          if (h2r[hai] == 'M' || h2r[hai] == 'D') seed_pos++;
-          hai++;
-        }
-        while (hai < hlen && h2r[hai] == 'D') hai++;
-        int sbase = sb, rai = 0;
-        while (sbase > 0 && rai < (int)full.size()){
-          if (full[rai] == 'M' || full[rai] == 'I' || full[rai] == 'S') sbase--;
-          rai++;
-        }
-        while (rai < (int)full.size() && full[rai] == 'D') rai++;
-        std::string la, ra;
-        stitch_dir(h2r, hlen, full, hai-1, rai-1, -1, la);
-        std::reverse(la.begin(), la.end());
-        stitch_dir(h2r, hlen, full, hai+1, rai+1, 1, ra);
-        std::string fa = la + "M" + ra;
-        for (size_t i = 0; i < fa.size(); i++){ if (fa[i] == 'I') fa[i] = 'S'; else break; }
-        int32_t start = seed_pos, stop = seed_pos;
-        for (char ch : la) if (ch == 'D' || ch == 'M') start--;
-        for (char ch : ra) if (ch == 'D' || ch == 'M') stop++;
-        R.aln_start = start; R.aln_stop = stop;
-        char cc = fa[0]; int num = 1;
-        for (size_t i = 1; i <= fa.size(); i++){
-          if (i == fa.size() || fa[i] != cc){
-            R.cigar.push_back(std::make_pair(cc, (int32_t)num));
-            if (i < fa.size()){ cc = fa[i]; num = 1; }
-          } else num++;
-        }
-        int ri = 0;
-        for (char ch : fa){
-          if (ch == 'S') ri++;
-          else if (ch == 'M' || ch == 'I') R.aln_str.push_back(bases[ri++]);
-          else R.aln_str.push_back('-');
-        }
-      }
-    };
-    // the replay is ~1.7 us of string work per request; the host threads are a persistent pool (a few microseconds to wake), so a
-    // locus' hundred requests are already worth sharing: blocks of 24 requests
-    int nthreads = std::max(1, std::min(hipstr::host_threads(), nq / 24));
-    if (const char* e = getenv("HIPSTR_TRACE_THREADS")) nthreads = std::max(1, std::min(atoi(e), std::max(1, nq / 16)));
-    auto run_parallel = [&](const std::function<void(int,int)>& fn){
-      if (nthreads <= 1){ fn(q0, q1); return; }
-      hipstr::parallel_for(nthreads, nthreads, [&](int t){ fn(q0 + (int)((int64_t)nq*t/nthreads), q0 + (int)((int64_t)nq*(t+1)/nthreads)); });
-    };
-    const auto r0t = now();
-    run_parallel(work);
-    const auto r1t = now();
-    if (hipstr::api_profile_on()) hipstr::api_profile_add(hipstr::PB_TRACE_REPLAY, std::chrono::duration<double>(r1t - r0t).count());
-    // ---- the caller's flat pools: offsets in request order (serial prefix sums), then the bytes (parallel again)
-    for (int q = q0; q < q1; q++){
-      const ReqOut& R = res[q-q0];
-      if (!R.ok) return api_fail("internal error: inconsistent traceback operation string");
-      o->hap_aln_off[q+1] = o->hap_aln_off[q] + (int32_t)R.hap_aln.size();
-      o->str_seq_off[q+1] = o->str_seq_off[q] + (int32_t)(R.acc.str_set ? R.acc.str_seq.size() : 0);
-      o->flank_seq_off[2*q+1] = o->flank_seq_off[2*q] + (int32_t)R.acc.flank[0].size();
-      o->flank_seq_off[2*q+2] = o->flank_seq_off[2*q+1] + (int32_t)R.acc.flank[2].size();
-      o->indel_off[q+1] = o->indel_off[q] + (int32_t)R.acc.indels.size();
-      o->snp_off[q+1] = o->snp_off[q] + (int32_t)R.acc.snps.size();
-      o->cigar_off[q+1] = o->cigar_off[q] + (int32_t)R.cigar.size();
-      o->aln_str_off[q+1] = o->aln_str_off[q] + (int32_t)R.aln_str.size();
-      const int64_t cap = o->cap_chars;
-      if ((int64_t)o->hap_aln_off[q] + (int64_t)R.hap_aln.size() > cap || (int64_t)o->str_seq_off[q] + (int64_t)R.acc.str_seq.size() > cap ||
-          (int64_t)o->flank_seq_off[2*q] + (int64_t)(R.acc.flank[0].size() + R.acc.flank[2].size()) > cap ||
-          (int64_t)o->indel_off[q] + (int64_t)R.acc.indels.size() > cap || (int64_t)o->snp_off[q] + (int64_t)R.acc.snps.size() > cap ||
-          (int64_t)o->cigar_off[q] + (int64_t)R.cigar.size() > cap || (int64_t)o->aln_str_off[q] + (int64_t)R.aln_str.size() > cap)
-        return api_fail("hipstr_trace_out_t pools are too small (cap_chars)");
-    }
-    auto copy_out = [&](int qa, int qb){
-      for (int q = qa; q < qb; q++){
-        const ReqOut& R = res[q-q0];
-        o->ll[q] = ll[q-q0]; o->max_index[q] = mxi[q-q0];
-        memcpy(o->hap_aln + o->hap_aln_off[q], R.hap_aln.data(), R.hap_aln.size());
-        o->stutter_size[q] = R.acc.str_set ? R.acc.stutter_size : HIPSTR_NO_STR_DATA;
-        if (R.acc.str_set) memcpy(o->str_seq + o->str_seq_off[q], R.acc.str_seq.data(), R.acc.str_seq.size());
-        memcpy(o->flank_seq + o->flank_seq_off[2*q], R.acc.flank[0].data(), R.acc.flank[0].size());
-        memcpy(o->flank_seq + o->flank_seq_off[2*q+1], R.acc.flank[2].data(), R.acc.flank[2].size());
-        o->flank_ins[q] = R.acc.flank_ins; o->flank_del[q] = R.acc.flank_del;
-        for (size_t i = 0; i < R.acc.indels.size(); i++){ o->indel_pos[o->indel_off[q] + i] = R.acc.indels[i].first; o->indel_size[o->indel_off[q] + i] = R.acc.indels[i].second; }
-        for (size_t i = 0; i < R.acc.snps.size(); i++){ o->snp_pos[o->snp_off[q] + i] = R.acc.snps[i].first; o->snp_base[o->snp_off[q] + i] = R.acc.snps[i].second; }
-        o->aln_start[q] = R.aln_start; o->aln_stop[q] = R.aln_stop;
-        for (size_t i = 0; i < R.cigar.size(); i++){ o->cigar_op[o->cigar_off[q] + i] = R.cigar[i].first; o->cigar_len[o->cigar_off[q] + i] = R.cigar[i].second; }
-        memcpy(o->aln_str + o->aln_str_off[q], R.aln_str.data(), R.aln_str.size());
-      }
-    };
-    const auto r2t = now();
-    run_parallel(copy_out);
-    const auto r3t = now();
-    // a request's results are a dozen small heap blocks: let the threads that made them give them back, not this one at scope exit
-    run_parallel([&](int qa, int qb){ for (int q = qa; q < qb; q++){ ReqOut none; std::swap(none, res[q-q0]); } });
-    if (timing) fprintf(stderr, "  replay of %d: setup %.3f work %.3f offsets %.3f copy %.3f release %.3f (threads %d)\n", nq, ms(c3, r0t), ms(r0t, r1t), ms(r1t, r2t), ms(r2t, r3t), ms(r3t, now()), nthreads);
-    q0 = q1;
-    const auto c4 = now();
-    ms_alloc += ms(c0, c1); ms_kernel += ms(c1, c2); ms_d2h += ms(c2, c3); ms_replay += ms(c3, c4);
-  }
-  if (res){
-    hipstr_trace_dev* td = NULL;
-    if (segs.v.size() == 1){ td = segs.v[0]; segs.v.clear(); }       // one chunk: its segment is the result, nothing is copied twice
-    else {
-      // several chunks: the segments side by side in flat arrays, then the segments go back
-      td = trace_dev_new(T.ctx, T.stream, n_req, pool_total);
-      if (!td) return 1;
-      struct Drop { hipstr_trace_dev* t; hipStream_t st; ~Drop(){ if (t){ hipStreamSynchronize(st); trace_dev_drop(t); } } } drop{td, T.stream};
-      auto d2d = [&](void* dst, const void* src, size_t nb){ return nb ? hipMemcpyAsync(dst, src, nb, hipMemcpyDeviceToDevice, T.stream) : hipSuccess; };
-      int64_t at[HS_ASM_POOLS] = {0, 0, 0, 0, 0, 0, 0};
-      for (int p = 0; p < HS_ASM_POOLS; p++) HS_HIP(hipMemsetAsync(td->off[p], 0, 4, T.stream));
-      for (size_t c = 0; c < segs.v.size(); c++){
-        const hipstr_trace_dev* sg = segs.v[c]; const int q0 = segs.q0[c], nq = sg->n_req;
-        HS_HIP(d2d(td->ll + q0, sg->ll, (size_t)nq*8)); HS_HIP(d2d(td->max_index + q0, sg->max_index, (size_t)nq*4));
-        for (int i = 0; i < 5; i++) HS_HIP(d2d(td->scal[i] + q0, sg->scal[i], (size_t)nq*4));
-        for (int p = 0; p < HS_ASM_POOLS; p++) HS_HIP(d2d(td->off[p] + hs_asm_pool_n(p, q0) + 1, sg->off[p] + 1, (size_t)hs_asm_pool_n(p, nq)*4));
-        for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++){
-          const int p = TD_ARR_POOL[a];
-          HS_HIP(d2d(td->arr[a] + (size_t)at[p]*TD_ARR_ESZ[a], sg->arr[a], (size_t)sg->totals[p]*TD_ARR_ESZ[a]));
-        }
-        for (int p = 0; p < HS_ASM_POOLS; p++) at[p] += sg->totals[p];
-      }
-      HS_HIP(hipstr::wait_stream(T.stream));
-      drop.t = NULL;
-    }
-    if (hipstr::wait_stream(T.stream) != hipSuccess){ trace_dev_drop(td); return api_fail("hipstr_hmm_trace_resident: the device failed"); }
-    td->n_req = n_req; td->groups = HIPSTR_TRACE_F_ALL; td->checked = true;
-    *res = td;
-  }
-  if (timing)
-    fprintf(stderr, "hipstr_hmm_trace: %d requests; prep %.3f ms, static upload+alloc %.3f, chunk upload %.3f, kernels %.3f, d2h %.3f, replay %.3f, total %.3f\n",
-            n_req, ms(t_begin, t_prep), ms(t_prep, t_static), ms_alloc, ms_kernel, ms_d2h, ms_replay, ms(t_begin, now()));
-  return 0;
-}
-
 // ---- the resident result's own entry points
 extern "C" int hipstr_trace_dev_sizes(const hipstr_trace_dev_t* td, int32_t* n_req, int64_t totals[7]){
   if (!td || !n_req || !totals) return hipstr::api_fail("null argument");
@@ -1865,33 +1951,28 @@ extern "C" int hipstr_trace_dev_fetch(hipstr_trace_dev_t* td, uint32_t fields, h
   if (!td || !o) return api_fail("null argument");
   if (fields & ~td->groups) return api_fail("hipstr_trace_dev_fetch: the handle does not hold a chosen group");
   const size_t n = (size_t)td->n_req;
+  const TraceOutView V(o);
   std::vector<HomePiece> home; size_t pin_bytes = 0; bool null_dst = false;
   auto want = [&](const void* dev, size_t nb, void* dst){
     if (nb && !dst) null_dst = true;
     home.push_back(HomePiece{dev, nb, dst, pin_bytes}); pin_bytes = (pin_bytes + nb + 255) & ~(size_t)255;
   };
   if (fields & HIPSTR_TRACE_F_SCALARS){
-    want(td->ll, n*8, o->ll); want(td->max_index, n*4, o->max_index);
-    int32_t* const dst[5] = { o->stutter_size, o->flank_ins, o->flank_del, o->aln_start, o->aln_stop };
-    for (int i = 0; i < 5; i++) want(td->scal[i], n*4, dst[i]);
+    want(td->ll, n*8, V.ll); want(td->max_index, n*4, V.max_index);
+    for (int i = 0; i < 5; i++) want(td->scal[i], n*4, V.scal[i]);
   }
-  int32_t* const off_dst[HS_TRACE_DEV_POOLS] = { o->hap_aln_off, o->str_seq_off, o->flank_seq_off, o->indel_off, o->snp_off, o->cigar_off, o->aln_str_off };
-  void* const arr_dst[HS_TRACE_DEV_ARRAYS] = { o->hap_aln, o->str_seq, o->flank_seq, o->indel_pos, o->indel_size, o->snp_pos, o->snp_base, o->cigar_op, o->cigar_len, o->aln_str };
-  const uint32_t pool_bit[HS_TRACE_DEV_POOLS] = { HIPSTR_TRACE_F_HAP_ALN, HIPSTR_TRACE_F_STR_SEQ, HIPSTR_TRACE_F_FLANKS, HIPSTR_TRACE_F_INDELS, HIPSTR_TRACE_F_SNPS,
-                                                  HIPSTR_TRACE_F_STITCH, HIPSTR_TRACE_F_STITCH };
   for (int p = 0; p < HS_TRACE_DEV_POOLS; p++){
-    if (!(fields & pool_bit[p])) continue;
+    if (!(fields & TD_POOL_BIT[p])) continue;
     if (td->totals[p] > (int64_t)o->cap_chars) return api_fail("hipstr_trace_out_t pools are too small (cap_chars)");
-    want(td->off[p], ((size_t)hs_asm_pool_n(p, (int)n) + 1)*4, off_dst[p]);
-    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) want(td->arr[a], (size_t)td->totals[p]*TD_ARR_ESZ[a], arr_dst[a]);
+    want(td->off[p], ((size_t)hs_asm_pool_n(p, (int)n) + 1)*4, V.off[p]);
+    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) want(td->arr[a], (size_t)td->totals[p]*TD_ARR_ESZ[a], V.arr[a]);
   }
   if (null_dst) return api_fail("null output array");
   if (pin_bytes == 0) return 0;
   if (hipstr::api_bind(td->ctx)) return 1;
-  char* pin = (char*)hipstr::pin_alloc(td->ctx, pin_bytes);
-  if (!pin) return api_fail("out of pinned host memory");
-  struct PinGuard { hipstr::Ctx* c; void* p; hipStream_t st; ~PinGuard(){ hipStreamSynchronize(st); hipstr::pin_free(c, p); } } pin_guard{td->ctx, pin, td->stream};
-  return copy_home(td->stream, pin, home);
+  PinBlock pin(td->ctx, td->stream, pin_bytes);
+  if (!pin.p) return api_fail("out of pinned host memory");
+  return copy_home(td->stream, pin.p, home);
 }
 
 extern "C" void hipstr_trace_dev_free(hipstr_trace_dev_t* td){
@@ -1908,96 +1989,70 @@ extern "C" int hipstr_debug_trace_dev_from_host(const hipstr_trace_out_t* tr, in
   if (out) *out = NULL;
   if (!tr || !out || n_req < 0) return api_fail("null argument");
   const size_t n = (size_t)n_req;
-  const int32_t* const off_src[HS_TRACE_DEV_POOLS] = { tr->hap_aln_off, tr->str_seq_off, tr->flank_seq_off, tr->indel_off, tr->snp_off, tr->cigar_off, tr->aln_str_off };
-  const void* const arr_src[HS_TRACE_DEV_ARRAYS] = { tr->hap_aln, tr->str_seq, tr->flank_seq, tr->indel_pos, tr->indel_size, tr->snp_pos, tr->snp_base, tr->cigar_op, tr->cigar_len, tr->aln_str };
-  const int32_t* const scal_src[5] = { tr->stutter_size, tr->flank_ins, tr->flank_del, tr->aln_start, tr->aln_stop };
+  const TraceOutView V(tr);
   int64_t tot[HS_TRACE_DEV_POOLS]; bool pool_ok[HS_TRACE_DEV_POOLS];
   for (int p = 0; p < HS_TRACE_DEV_POOLS; p++){
-    tot[p] = off_src[p] ? std::max<int64_t>(0, off_src[p][hs_asm_pool_n(p, n_req)]) : 0;
-    pool_ok[p] = off_src[p] != NULL;
-    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p && tot[p] > 0 && !arr_src[a]) pool_ok[p] = false;
+    tot[p] = V.off[p] ? std::max<int64_t>(0, V.off[p][hs_asm_pool_n(p, n_req)]) : 0;
+    pool_ok[p] = V.off[p] != NULL;
+    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p && tot[p] > 0 && !V.arr[a]) pool_ok[p] = false;
     if (!pool_ok[p]) tot[p] = 0;
   }
   hipstr::ApiTables T;
   if (hipstr::api_device_tables(&T)) return 1;
-  hipstr_trace_dev* td = trace_dev_new(T.ctx, T.stream, n_req, tot);
+  TraceDevGuard g{trace_dev_new(T.ctx, T.stream, n_req, tot), T.stream};
+  hipstr_trace_dev* td = g.t;
   if (!td) return 1;
-  struct Drop { hipstr_trace_dev* t; hipStream_t st; ~Drop(){ if (t){ hipStreamSynchronize(st); trace_dev_drop(t); } } } drop{td, T.stream};
   const TraceDevLayout L(n, tot);
-  char* pin = (char*)hipstr::pin_alloc(T.ctx, L.bytes);
-  if (!pin) return api_fail("out of pinned host memory");
-  struct PinGuard { hipstr::Ctx* c; void* p; hipStream_t st; ~PinGuard(){ hipStreamSynchronize(st); hipstr::pin_free(c, p); } } pin_guard{T.ctx, pin, T.stream};
-  auto put = [&](size_t at, const void* src, size_t nb){ if (src && nb) memcpy(pin + at, src, nb); };
-  put(L.ll, tr->ll, n*8); put(L.mxi, tr->max_index, n*4);
-  if (!tr->ll) td->ll = NULL;
-  if (!tr->max_index) td->max_index = NULL;
-  for (int i = 0; i < 5; i++){ put(L.scal[i], scal_src[i], n*4); if (!scal_src[i]) td->scal[i] = NULL; }
+  PinBlock pin(T.ctx, T.stream, L.bytes);
+  if (!pin.p) return api_fail("out of pinned host memory");
+  auto put = [&](size_t at, const void* src, size_t nb){ if (src && nb) memcpy(pin.p + at, src, nb); };
+  put(L.ll, V.ll, n*8); put(L.mxi, V.max_index, n*4);
+  if (!V.ll) td->ll = NULL;
+  if (!V.max_index) td->max_index = NULL;
+  bool scalars = V.ll && V.max_index;
+  for (int i = 0; i < 5; i++){ put(L.scal[i], V.scal[i], n*4); if (!V.scal[i]){ td->scal[i] = NULL; scalars = false; } }
+  uint32_t held = 0, lacking = 0;                 // group bits with a pool present / with a pool absent (a group of two pools needs both)
   for (int p = 0; p < HS_TRACE_DEV_POOLS; p++){
+    (pool_ok[p] ? held : lacking) |= TD_POOL_BIT[p];
     if (!pool_ok[p]){ td->off[p] = NULL; for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) td->arr[a] = NULL; continue; }
-    put(L.off[p], off_src[p], ((size_t)hs_asm_pool_n(p, n_req) + 1)*4);
-    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) put(L.arr[a], arr_src[a], (size_t)tot[p]*TD_ARR_ESZ[a]);
+    put(L.off[p], V.off[p], ((size_t)hs_asm_pool_n(p, n_req) + 1)*4);
+    for (int a = 0; a < HS_TRACE_DEV_ARRAYS; a++) if (TD_ARR_POOL[a] == p) put(L.arr[a], V.arr[a], (size_t)tot[p]*TD_ARR_ESZ[a]);
   }
-  HS_HIP(hipMemcpyAsync(td->block, pin, L.bytes, hipMemcpyHostToDevice, T.stream));
+  HS_HIP(hipMemcpyAsync(td->block, pin.p, L.bytes, hipMemcpyHostToDevice, T.stream));
   HS_HIP(hipstr::wait_stream(T.stream));
-  td->groups = 0;
-  if (tr->ll && tr->max_index && scal_src[0] && scal_src[1] && scal_src[2] && scal_src[3] && scal_src[4]) td->groups |= HIPSTR_TRACE_F_SCALARS;
-  const uint32_t bit[HS_TRACE_DEV_POOLS] = { HIPSTR_TRACE_F_HAP_ALN, HIPSTR_TRACE_F_STR_SEQ, HIPSTR_TRACE_F_FLANKS, HIPSTR_TRACE_F_INDELS, HIPSTR_TRACE_F_SNPS, 0, 0 };
-  for (int p = 0; p < 5; p++) if (pool_ok[p]) td->groups |= bit[p];
-  if (pool_ok[5] && pool_ok[6]) td->groups |= HIPSTR_TRACE_F_STITCH;
+  td->groups = (scalars ? HIPSTR_TRACE_F_SCALARS : 0) | (held & ~lacking);
   td->checked = false;
-  drop.t = NULL;
-  *out = td;
+  *out = g.release();
   return 0;
 }
 
-// Diagnostics (host only): the chunks, fill kernels and walk forms hipstr_hmm_trace_seeded would launch for a request list, from the same
-// decisions (trace_seed_of, trace_compact_reads, trace_side_ws, trace_chunk_end, trace_col_class, trace_mixed_launch, trace_fill_cols,
-// hs_walk_in_lds), as one JSON object.
+namespace {
+// what both plans check before they resolve the request list, as the call does; NULL or the refusal
+const char* plan_resolve(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele, const int32_t* req_seed,
+                         TraceRequests& R, std::string& err){
+  if (!b || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return "null argument";
+  if (b->n_loci < 1) return "hipstr_hmm_trace needs at least one locus";
+  if (hipstr::validate_tables(b, err)) return err.c_str();
+  return trace_resolve(b, n_req, req_read, req_allele, req_seed, R);
+}
+int plan_bad(const char* why){ hipstr::api_fail(why); return -1; }
+int plan_out(const std::string& o, char* json, int cap){
+  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
+  return (int)o.size();
+}
+}  // namespace
+
+// Diagnostics (host only): the chunks, fill kernels and walk forms hipstr_hmm_trace_seeded would launch for a request list, from what the
+// call itself runs on (trace_resolve, trace_compact_reads, trace_chunk_end, trace_launches, hs_walk_in_lds), as one JSON object.
 extern "C" int hipstr_debug_trace_plan(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                        const int32_t* req_seed, double ws_mib, char* json, int cap){
-  using hipstr::api_fail;
-  auto bad = [](const char* why){ hipstr::api_fail(why); return -1; };
-  if (!b || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return bad("null argument");
-  if (b->n_loci < 1) return bad("hipstr_hmm_trace needs at least one locus");
-  { std::string err; if (hipstr::validate_tables(b, err)) return bad(err.c_str()); }
-  const int n_loci = b->n_loci, n_reads = b->read_off[n_loci];
-  std::vector<int32_t> opt_base(n_loci + 1, 0);
-  for (int l = 0; l < n_loci; l++){
-    int cnt = 0;
-    for (int k = 0; k < 3; k++){
-      if (b->blk_nopts[3*l+k] < 1) return bad("haplotype block without options");
-      cnt += b->blk_nopts[3*l+k];
-    }
-    opt_base[l+1] = opt_base[l] + cnt;
-  }
-  struct Rq { int nL, nR, F0, F2; };
-  std::vector<Rq> rq(n_req);
-  std::vector<int64_t> need(n_req);
-  std::vector<char> seen((size_t)n_reads, 0);
-  int64_t wanted = 0, rough = 0;
-  for (int q = 0; q < n_req; q++){
-    const int r = req_read[q], k = req_allele[q];
-    if (r < 0 || r >= n_reads) return bad("request names a read outside the batch");
-    const int l = (int)(std::upper_bound(b->read_off, b->read_off + n_loci + 1, r) - b->read_off) - 1;
-    const int32_t* nopts = b->blk_nopts + 3*l;
-    if (k < 0 || k >= nopts[0]*nopts[1]*nopts[2]) return bad("request names an allele outside its locus");
-    int s;
-    if (const char* why = trace_seed_of(b, l, r, req_seed, q, s)) return bad(why);
-    const int len = b->base_off[r+1] - b->base_off[r];
-    int32_t oi[3]; int F[3];
-    hipstr::allele_options(nopts, k, oi);
-    for (int x = 0, cur = opt_base[l]; x < 3; cur += nopts[x], x++) F[x] = b->opt_off[cur + oi[x] + 1] - b->opt_off[cur + oi[x]];
-    if (F[0] < 1 || F[2] < 1) return bad("empty flank sequence");
-    if (F[1] < 1) return bad("empty STR allele is not supported");
-    rq[q].nL = s; rq[q].nR = len - s - 1; rq[q].F0 = F[0]; rq[q].F2 = F[2];
-    need[q] = trace_side_ws(F[0], F[2], rq[q].nL) + trace_side_ws(F[2], F[0], rq[q].nR);
-    rough += (int64_t)(F[0] + F[2] + 2)*len;
-    if (!seen[r]){ seen[r] = 1; wanted += len; }
-  }
+  TraceRequests R; std::string err;
+  if (const char* why = plan_resolve(b, n_req, req_read, req_allele, req_seed, R, err)) return plan_bad(why);
   // (a call that would ask the device for its free memory: the plan takes the budget it was given, else the default)
   const int64_t budget = ws_mib > 0 ? (int64_t)(ws_mib*1048576.0) : trace_env_budget((int64_t)HS_TRACE_BUDGET_MIB << 20);
-  for (int q = 0; q < n_req; q++) if (need[q] > budget) return bad("one traceback needs more workspace than the device offers");
-  const bool compact = n_req > 0 && trace_compact_reads(wanted, b->base_off[n_reads]);
+  for (int q = 0; q < n_req; q++) if (R.need[q] > budget) return plan_bad("one traceback needs more workspace than the device offers");
+  const int64_t total_bases = b->base_off[b->read_off[b->n_loci]];
+  const bool compact = n_req > 0 && trace_compact_reads(R.wanted, total_bases);
   std::string o; char buf[256];
   auto put = [&](const char* fmt, auto... a){ snprintf(buf, sizeof buf, fmt, a...); o += buf; };
   put("{\"thresholds\": {\"HS_MAX_COLS\": %d, \"HS_TRACE_STATIC_CLASSES\": %d, \"HS_TRACE_MIXED_MAX_REQ\": %d, \"HS_WALK_LDS\": %d, \"HS_TRACE_BUDGET_MIB\": %d, \"max_side\": %d, \"fill_cols\": [",
@@ -2008,40 +2063,40 @@ extern "C" int hipstr_debug_trace_plan(const hipstr_batch_t* b, int32_t n_req, c
   for (int cl = HS_TRACE_STATIC_CLASSES + 1, last = 0; cl <= HS_MAX_COLS; cl++) if (trace_fill_cols(cl) != last){ last = trace_fill_cols(cl); put("\"hs_trace_fill_long<%d>\", ", last); }
   put("\"hs_trace_fill_mixed\", \"walk_lds\", \"walk_workspace\", \"reads_compact\", \"reads_whole\", \"trace_one_chunk\", \"trace_chunks\"], "
       "\"compact_reads\": %s, \"wanted_bases\": %lld, \"total_bases\": %lld, \"budget\": %lld, \"asks_device\": %s, \"chunks\": [",
-      compact ? "true" : "false", (long long)wanted, (long long)b->base_off[n_reads], (long long)budget, trace_asks_device(rough) ? "true" : "false");
+      compact ? "true" : "false", (long long)R.wanted, (long long)total_bases, (long long)budget, trace_asks_device(R.rough) ? "true" : "false");
+  TraceLaunches L;
   for (int q0 = 0; q0 < n_req; ){
-    const int q1 = trace_chunk_end(need, q0, budget), nq = q1 - q0;
-    int cnt[HS_MAX_COLS + 1] = {0}; int64_t mat = 0; int n_lds = 0, n_ws = 0;
-    for (int q = q0; q < q1; q++){ cnt[trace_col_class(rq[q].nL)]++; cnt[trace_col_class(rq[q].nR)]++; mat += need[q]; }
-    int n_cls = 0, n_static = 0;
-    for (int cl = 1; cl <= HS_TRACE_STATIC_CLASSES; cl++){ n_cls += cnt[cl] > 0; n_static += cnt[cl]; }
-    const bool mixed = trace_mixed_launch(n_cls, nq);
+    const int q1 = trace_chunk_end(R.need, q0, budget), nq = q1 - q0;
+    int64_t mat = 0; int n_lds = 0, n_ws = 0;
+    for (int q = q0; q < q1; q++) mat += R.need[q];
+    trace_launches(R, q0, q1, L);
     put("%s{\"q0\": %d, \"q1\": %d, \"bytes\": %lld, \"classes\": [", q0 ? ", " : "", q0, q1, (long long)mat);
-    for (int cl = 1; cl <= HS_MAX_COLS; cl++) put("%s%d", cl > 1 ? ", " : "", cnt[cl]);
-    put("], \"mixed\": %s, \"launch\": [", mixed ? "true" : "false");
-    bool first = true;
-    if (mixed){ put("[\"hs_trace_fill_mixed\", %d]", n_static); first = false; }
-    for (int cl = mixed ? HS_TRACE_STATIC_CLASSES + 1 : 1; cl <= HS_MAX_COLS; cl++){
-      if (!cnt[cl]) continue;
-      if (cl <= HS_TRACE_STATIC_CLASSES) put("%s[\"hs_trace_fill<%d>\", %d]", first ? "" : ", ", cl, cnt[cl]);
-      else put("%s[\"hs_trace_fill_long<%d>\", %d]", first ? "" : ", ", trace_fill_cols(cl), cnt[cl]);
-      first = false;
+    for (int cl = 1; cl <= HS_MAX_COLS; cl++) put("%s%d", cl > 1 ? ", " : "", L.cnt[cl]);
+    put("], \"mixed\": %s, \"launch\": [", L.mixed ? "true" : "false");
+    for (const TraceLaunch& f : L.fills){
+      if (f.cl == 0) put("[\"hs_trace_fill_mixed\", %d], ", f.count);
+      else put(f.cl <= HS_TRACE_STATIC_CLASSES ? "[\"hs_trace_fill<%d>\", %d], " : "[\"hs_trace_fill_long<%d>\", %d], ", trace_fill_cols(f.cl), f.count);
     }
     // per request: [left columns, right columns, flank rows + 1, left walk, right walk] (walk: 1 = decisions copied to LDS, 0 = read in the workspace)
-    put("%s[\"hs_trace_walk\", %d]], \"requests\": [", first ? "" : ", ", nq);
+    put("[\"hs_trace_walk\", %d]], \"requests\": [", nq);
     for (int q = q0; q < q1; q++){
-      const Rq& R = rq[q];
-      const bool wl = hs_walk_in_lds(hs_trace_side_bytes(R.F0, R.F2, R.nL)), wr = hs_walk_in_lds(hs_trace_side_bytes(R.F2, R.F0, R.nR));
+      const int nL = R.cols(q, 0), nR = R.cols(q, 1), F0 = R.rows(q, 0, 0), F2 = R.rows(q, 0, 2);
+      const bool wl = hs_walk_in_lds(hs_trace_side_bytes(F0, F2, nL)), wr = hs_walk_in_lds(hs_trace_side_bytes(F2, F0, nR));
       n_lds += wl + wr; n_ws += !wl + !wr;
-      put("%s[%d, %d, %d, %d, %d]", q > q0 ? ", " : "", R.nL, R.nR, R.F0 + 1 + R.F2, wl ? 1 : 0, wr ? 1 : 0);
+      put("%s[%d, %d, %d, %d, %d]", q > q0 ? ", " : "", nL, nR, F0 + 1 + F2, wl ? 1 : 0, wr ? 1 : 0);
     }
     o += "], \"routes\": [";
     put("\"%s\", \"%s\"", (q0 == 0 && q1 == n_req) ? "trace_one_chunk" : "trace_chunks", compact ? "reads_compact" : "reads_whole");
-    if (mixed) o += ", \"hs_trace_fill_mixed\"";
-    for (int cl = 1; cl <= HS_MAX_COLS; cl++){
-      if (!cnt[cl]) continue;
-      if (cl <= HS_TRACE_STATIC_CLASSES) put(mixed ? ", \"mixed<%d>\"" : ", \"hs_trace_fill<%d>\"", cl);
-      else if (cl == HS_TRACE_STATIC_CLASSES + 1 || trace_fill_cols(cl) != trace_fill_cols(cl-1) || !cnt[cl-1]) put(", \"hs_trace_fill_long<%d>\"", trace_fill_cols(cl));
+    if (L.mixed){
+      o += ", \"hs_trace_fill_mixed\"";
+      for (int cl = 1; cl <= HS_TRACE_STATIC_CLASSES; cl++) if (L.cnt[cl]) put(", \"mixed<%d>\"", cl);
+    }
+    for (size_t i = 0; i < L.fills.size(); i++){
+      const TraceLaunch& f = L.fills[i];
+      if (f.cl >= 1 && f.cl <= HS_TRACE_STATIC_CLASSES) put(", \"hs_trace_fill<%d>\"", f.cl);
+      // (a long kernel is named once for a run of adjacent classes it serves)
+      else if (f.cl > HS_TRACE_STATIC_CLASSES && !(i > 0 && L.fills[i-1].cl == f.cl - 1 && trace_fill_cols(f.cl - 1) == trace_fill_cols(f.cl)))
+        put(", \"hs_trace_fill_long<%d>\"", trace_fill_cols(f.cl));
     }
     if (n_lds) o += ", \"walk_lds\"";
     if (n_ws) o += ", \"walk_workspace\"";
@@ -2049,50 +2104,23 @@ extern "C" int hipstr_debug_trace_plan(const hipstr_batch_t* b, int32_t n_req, c
     q0 = q1;
   }
   o += "]}";
-  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
-  return (int)o.size();
+  return plan_out(o, json, cap);
 }
-// Diagnostics (host only): the slots and the staging route of every request of a device-assembled call, from trace_ops_cap, trace_asm_caps
+// Diagnostics (host only): the slots and the staging route of every request of a device-assembled call, from trace_resolve, trace_req_asm_caps
 // and hs_asm_in_lds — the functions hipstr_hmm_trace_ex and hs_trace_assemble call.
 extern "C" int hipstr_debug_trace_assemble_plan(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                                 const int32_t* req_seed, const char* const* hap_to_ref, char* json, int cap){
-  auto bad = [](const char* why){ hipstr::api_fail(why); return -1; };
-  if (!b || n_req < 0 || (n_req > 0 && (!req_read || !req_allele))) return bad("null argument");
-  if (b->n_loci < 1) return bad("hipstr_hmm_trace needs at least one locus");
-  { std::string err; if (hipstr::validate_tables(b, err)) return bad(err.c_str()); }
-  const int n_loci = b->n_loci, n_reads = b->read_off[n_loci];
-  std::vector<int32_t> opt_base(n_loci + 1, 0);
-  for (int l = 0; l < n_loci; l++){
-    if (b->period[l] < 1 || b->period[l] > 9) return bad("STR period must be in [1,9] (stutter_model.h:38)");
-    int cnt = 0;
-    for (int k = 0; k < 3; k++){
-      if (b->blk_nopts[3*l+k] < 1) return bad("haplotype block without options");
-      cnt += b->blk_nopts[3*l+k];
-    }
-    opt_base[l+1] = opt_base[l] + cnt;
-  }
+  TraceRequests R; std::string err;
+  if (const char* why = plan_resolve(b, n_req, req_read, req_allele, req_seed, R, err)) return plan_bad(why);
   std::string o; char buf[256];
   auto put = [&](const char* fmt, auto... a){ snprintf(buf, sizeof buf, fmt, a...); o += buf; };
   put("{\"thresholds\": {\"HS_ASM_LDS\": %d}, \"routes\": [\"assemble_lds\", \"assemble_hbm\"], "
       "\"fields\": [\"hap_aln\", \"seq\", \"indel\", \"snp\", \"stitched\", \"lds_bytes\", \"in_lds\"], \"requests\": [", HS_ASM_LDS);
   int n_lds = 0, n_hbm = 0;
   for (int q = 0; q < n_req; q++){
-    const int r = req_read[q], k = req_allele[q];
-    if (r < 0 || r >= n_reads) return bad("request names a read outside the batch");
-    const int l = (int)(std::upper_bound(b->read_off, b->read_off + n_loci + 1, r) - b->read_off) - 1;
-    const int32_t* nopts = b->blk_nopts + 3*l;
-    if (k < 0 || k >= nopts[0]*nopts[1]*nopts[2]) return bad("request names an allele outside its locus");
-    int s;
-    if (const char* why = trace_seed_of(b, l, r, req_seed, q, s)) return bad(why);
-    const int len = b->base_off[r+1] - b->base_off[r];
-    int32_t oi[3]; int F[3];
-    hipstr::allele_options(nopts, k, oi);
-    for (int x = 0, cur = opt_base[l]; x < 3; cur += nopts[x], x++) F[x] = b->opt_off[cur + oi[x] + 1] - b->opt_off[cur + oi[x]];
-    if (F[0] < 1 || F[2] < 1) return bad("empty flank sequence");
-    if (F[1] < 1) return bad("empty STR allele is not supported");
-    const int hlen = hap_to_ref ? (int)strlen(hap_to_ref[b->hap_off[l] + k]) : -1;
-    const TraceAsmCaps c = trace_asm_caps(trace_ops_cap(s, F[0], F[2], F[1], b->period[l]), trace_ops_cap(len - s - 1, F[2], F[0], F[1], b->period[l]),
-                                          len, F[0], F[2], hlen);
+    const TracePair& p = R.pairs[R.pair[q]];
+    const int hlen = hap_to_ref ? (int)strlen(hap_to_ref[b->hap_off[p.locus] + p.allele]) : -1;
+    const TraceAsmCaps c = trace_req_asm_caps(b, R, q, hlen);
     const bool lds = hs_asm_in_lds(c.lds_bytes);
     n_lds += lds; n_hbm += !lds;
     put("%s[%d, %d, %d, %d, %d, %d, %d]", q ? ", " : "", c.hap_aln, c.seq, c.indel, c.snp, c.stitched, c.lds_bytes, lds ? 1 : 0);
@@ -2101,7 +2129,6 @@ extern "C" int hipstr_debug_trace_assemble_plan(const hipstr_batch_t* b, int32_t
   if (n_lds) o += "\"assemble_lds\"";
   if (n_hbm) o += n_lds ? ", \"assemble_hbm\"" : "\"assemble_hbm\"";
   o += "]}";
-  if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
-  return (int)o.size();
+  return plan_out(o, json, cap);
 }
 #endif  // HIPSTR_NO_DEBUG_ABI

@@ -214,6 +214,31 @@ def trace_over_budget():
     return TraceCall("over_budget", batch, [0], [0], [512], 1, None)
 
 
+TraceRefusal = collections.namedtuple("TraceRefusal", "name batch rr aa seeds message")
+
+
+def trace_refusals(T):
+    """Request lists the call refuses from the batch and the list alone, one read and one or two alleles each, with the call's message.
+    Every one gets past validate_tables ("haplotype block without options" does not: that one is validate_tables' own)."""
+    m = T["max_side"]
+    def locus(lf, strs, rf, n=40, period=3, lf_opts=None):
+        b = capi.Batch()
+        util.simple_locus(lf, strs, rf, period, [(("ACGT" * (n // 4 + 1))[:n], None, 0, True, [("M", n)])], batch=b, lf_opts=lf_opts)
+        return b.finalize()
+    L, S, R = "ACGTTGCAAC" * 3, "CAG" * 8, "TGCATTGACA" * 3
+    plain = locus(L, [S, S + "CAG"], R)
+    return [TraceRefusal("period_10", locus(L, [S], R, period=10), [0], [0], [20], "STR period must be in [1,9] (stutter_model.h:38)"),
+            TraceRefusal("str_2048", locus(L, [S, "CA" * 1024], R), [0], [1], [20], "STR allele longer than 2047 bp is not supported"),
+            TraceRefusal("flanks_4095", locus("A" * 2047, [S], "C" * 2048), [0], [0], [20], "flanks longer than 4094 bases in total are not supported"),
+            TraceRefusal("empty_str", locus(L, [S, ""], R), [0], [1], [20], "empty STR allele is not supported"),
+            TraceRefusal("empty_flank", locus(L, [S], R, lf_opts=[""]), [0], [1], [20], "empty flank sequence"),
+            TraceRefusal("read_outside", plain, [1], [0], [20], "request names a read outside the batch"),
+            TraceRefusal("allele_outside", plain, [0], [2], [20], "request names an allele outside its locus"),
+            TraceRefusal("seed_0", plain, [0], [0], [0], "seed base must leave at least one base on either side (HapAligner.cpp:316)"),
+            TraceRefusal("seed_last", plain, [0], [1], [39], "seed base must leave at least one base on either side (HapAligner.cpp:316)"),
+            TraceRefusal("side_over", locus(L, [S], R, n=m + 3), [0], [0], [m + 1], "traceback of a read side longer than %d bases is not supported" % m)]
+
+
 def trace_calls(lib, T):
     calls = [trace_boundary_sides(T)] + [trace_single_class(T, cl) for cl in range(1, T["HS_TRACE_STATIC_CLASSES"] + 1)]
     calls += [trace_many_requests(T, 0), trace_many_requests(T, 1), trace_walk_limit(lib, T), trace_repack(0), trace_repack(1),

@@ -81,6 +81,25 @@ def test_trace_side_beyond_the_limit_is_refused(hmm_host, lim):
         capi.trace_plan(hmm_host, b.ptr, [0], [0], [1])
 
 
+def test_both_trace_plans_refuse_what_the_call_refuses(hmm_host, lim):
+    """The plans resolve a request list with the call's own walk, so each refusal the call makes from the batch and the list alone is
+    theirs too, word for word: a period of 10, an STR allele of 2048 bp, flanks of 2047 + 2048 bases, an empty STR block and an empty
+    flank, a read outside, an allele outside, a seed of 0 and of len - 1, a side over max_side.  (All of them can be built; the GPU
+    twin, test_trace_assemble_gpu.py::test_errors_flags_and_the_empty_call, runs the same lists through the three calls.)"""
+    cases = sc.trace_refusals(lim["trace"])
+    assert len({c.name for c in cases}) == 10
+    for c in cases:
+        for plan in (lambda: capi.trace_plan(hmm_host, c.batch.ptr, c.rr, c.aa, c.seeds),
+                     lambda: capi.trace_assemble_plan(hmm_host, c.batch.ptr, c.rr, c.aa, c.seeds)):
+            with pytest.raises(RuntimeError) as e:
+                plan()
+            assert str(e.value).endswith("failed: " + c.message), (c.name, str(e.value))
+    # each list is refused for its own reason only: one request beside it passes both plans
+    ok = cases[5]
+    assert len(capi.trace_plan(hmm_host, ok.batch.ptr, [0], [1], [20])["chunks"]) == 1
+    assert len(capi.trace_assemble_plan(hmm_host, ok.batch.ptr, [0], [1], [20])["requests"]) == 1
+
+
 # ------------------------------------------------------------------ Needleman-Wunsch
 def test_nw_routes_on_each_side_of_their_thresholds(hmm_host, oracle, lim):
     N = lim["nw"]

@@ -314,6 +314,18 @@ def test_errors_flags_and_the_empty_call(hmm, oracle):
     seeded = capi.run_trace(hmm, "hipstr_hmm_", sb.ptr, rr, aa, h2r, unpack=False, req_seed=[-2] * 5)      # HIPSTR_SEED_AUTO
     zero = capi.run_trace(hmm, "hipstr_hmm_", sb.ptr, rr, aa, h2r, unpack=False, flags=0)
     assert_raw_equal(zero, seeded, 5, "flags=0")
+    # one walk over the request list behind the plans and the three calls: the refusals of tests/test_stage_routes.py, the plan's words
+    for c in src.trace_refusals(capi.trace_plan(hmm, sb.ptr, [], [])["thresholds"]):
+        with pytest.raises(RuntimeError) as planned:
+            capi.trace_plan(hmm, c.batch.ptr, c.rr, c.aa, c.seeds)
+        said = str(planned.value).split("failed: ", 1)[1]
+        assert said == c.message
+        for call in (lambda: capi.run_trace(hmm, "hipstr_hmm_", c.batch.ptr, c.rr, c.aa, None, req_seed=c.seeds, flags=0),
+                     lambda: capi.run_trace(hmm, "hipstr_hmm_", c.batch.ptr, c.rr, c.aa, None, req_seed=c.seeds, flags=DEVICE),
+                     lambda: capi.run_trace_resident(hmm, c.batch.ptr, c.rr, c.aa, None, req_seed=c.seeds)):
+            with pytest.raises(RuntimeError) as e:
+                call()
+            assert str(e.value).endswith(said), (c.name, str(e.value))
 
 
 def test_a_request_beyond_the_lds_threshold_reads_hbm(hmm, oracle):
