@@ -848,10 +848,11 @@ int hipstr::results_wait(hipstr_dev_batch_t* dev){
   HS_HIP(hipEventSynchronize(dev->ev_d2h));
   return 0;
 }
-void hipstr::scatter_loci(const hipstr_dev_batch_t* dev, int l0, int l1, double* aln_probs, int32_t* seeds){
+void hipstr::scatter_loci(const hipstr_dev_batch_t* dev, int l0, int l1, double* aln_probs, int32_t* seeds, const double* from, bool whole){
   const hipstr::Prepared& P = dev->prep;
   if (l1 <= l0) return;
-  const int64_t out0 = P.loci[l0].out_off; const int r0 = P.loci[l0].read_begin;
+  if (!from) from = dev->host_out;
+  const int64_t out0 = whole ? 0 : P.loci[l0].out_off; const int r0 = whole ? 0 : P.loci[l0].read_begin;
   for (int li = l0; li < l1; li++){
     const hs_locus_t& loc = P.loci[li];
     const int A = loc.n_alleles;
@@ -860,7 +861,7 @@ void hipstr::scatter_loci(const hipstr_dev_batch_t* dev, int l0, int l1, double*
     bool plain = all_haps;
     for (int i = 0; plain && i < loc.n_reads; i++) plain = P.realign_read[loc.read_begin + i] && P.seeds[loc.read_begin + i] >= 0;
     if (plain){
-      memcpy(aln_probs + (loc.out_off - out0), dev->host_out + loc.out_off, sizeof(double)*(size_t)loc.n_reads*(size_t)A);
+      memcpy(aln_probs + (loc.out_off - out0), from + loc.out_off, sizeof(double)*(size_t)loc.n_reads*(size_t)A);
       memcpy(seeds + (loc.read_begin - r0), P.seeds.data() + loc.read_begin, sizeof(int32_t)*(size_t)loc.n_reads);
       continue;
     }
@@ -869,7 +870,7 @@ void hipstr::scatter_loci(const hipstr_dev_batch_t* dev, int l0, int l1, double*
       if (!P.realign_read[r]) continue;                       // HapAligner.cpp:326-329
       seeds[r - r0] = P.seeds[r];
       double* dst = aln_probs + (loc.out_off - out0) + (int64_t)i*A;
-      const double* src = dev->host_out + loc.out_off + (int64_t)i*A;
+      const double* src = from + loc.out_off + (int64_t)i*A;
       if (P.seeds[r] == -1){ for (int k = 0; k < A; k++) dst[k] = 0; continue; }   // HapAligner.cpp:333-337
       if (all_haps) memcpy(dst, src, sizeof(double)*(size_t)A);
       else for (int k = 0; k < A; k++) if (P.realign_hap[loc.hap_begin + k]) dst[k] = src[k];   // HapAligner.cpp:615-619
@@ -1047,32 +1048,18 @@ int hipstr_hmm_fetch(hipstr_dev_batch_t* dev, double* aln_probs, int32_t* seeds)
   const hipstr::Prepared& P = dev->prep;
   Ctx* ctx = dev->ctx;
   if (dev->foreign_stream) HS_HIP(hipDeviceSynchronize());         // a pass was launched on a stream of the caller's
+  hipstr::ScratchBufs S; S.ctx = ctx; S.runs_on(dev->stream);
   double* tmp = NULL;
   if (P.n_out){
-    tmp = (double*)ctx->pin_cache.get((size_t)P.n_out*sizeof(double));
-    if (!tmp) return 1;
-    if (hipMemcpyAsync(tmp, dev->h.aln_probs, (size_t)P.n_out*sizeof(double), hipMemcpyDeviceToHost, dev->stream) != hipSuccess){
-      ctx->pin_cache.put(tmp); return fail("hipMemcpyAsync (device to host) failed"); }
+    if (S.alloc_pinned(&tmp, (size_t)P.n_out)) return 1;
+    if (hipMemcpyAsync(tmp, dev->h.aln_probs, (size_t)P.n_out*sizeof(double), hipMemcpyDeviceToHost, dev->stream) != hipSuccess)
+      return fail("hipMemcpyAsync (device to host) failed");
   }
-  if (hipstr::wait_stream(dev->stream) != hipSuccess){ ctx->pin_cache.put(tmp); return fail("hipStreamSynchronize failed"); }
+  if (hipstr::wait_stream(dev->stream) != hipSuccess) return fail("hipStreamSynchronize failed");
   // the reference's output contract, locus by locus (loci are independent: shared among the host threads)
-  auto scatter = [&](int li){
-    const hs_locus_t& loc = P.loci[li];
-    const int A = loc.n_alleles;
-    const bool all_haps = loc.n_re == A;
-    for (int i = 0; i < loc.n_reads; i++){
-      const int r = loc.read_begin + i;
-      if (!P.realign_read[r]) continue;                       // HapAligner.cpp:326-329
-      seeds[r] = P.seeds[r];
-      double* dst = aln_probs + loc.out_off + (int64_t)i*A;
-      const double* src = tmp + loc.out_off + (int64_t)i*A;
-      if (P.seeds[r] == -1){ for (int k = 0; k < A; k++) dst[k] = 0; continue; }   // HapAligner.cpp:333-337
-      if (all_haps) memcpy(dst, src, sizeof(double)*(size_t)A);
-      else for (int k = 0; k < A; k++) if (P.realign_hap[loc.hap_begin + k]) dst[k] = src[k];   // HapAligner.cpp:615-619
-    }
-  };
-  hipstr::parallel_for((int)P.loci.size(), P.n_out > (1 << 20) ? hipstr::host_threads() : 1, scatter);
-  ctx->pin_cache.put(tmp);
+  hipstr::parallel_for((int)P.loci.size(), P.n_out > (1 << 20) ? hipstr::host_threads() : 1,
+                       [&](int li){ hipstr::scatter_loci(dev, li, li + 1, aln_probs, seeds, tmp, true); });
+  S.release(tmp);
   return 0;
 }
 
@@ -1115,14 +1102,21 @@ double ApiTimer::now(){ return std::chrono::duration<double>(std::chrono::steady
 }
 #ifndef HIPSTR_NO_DEBUG_ABI      // diagnostics (include/hipstr_hmm_debug.h): tests, fuzzers, bench.py — not the drop-in ABI
 int64_t hipstr_debug_driver_allocs(void){ return g_driver_allocs.load(); }
+namespace {
+// the result of a debug primitive: the launch's stream waited for, then one synchronous copy (up to 1 GiB: not through the pinned cache)
+int prim_fetch(hipStream_t st, void* dst, const void* src, size_t bytes){
+  return hipstr::wait_stream(st) == hipSuccess && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
+}
+}
 int hipstr_debug_cr_math(int which, const double* x, double* y, int64_t n){
   if (!x || !y || n < 0) return fail("null argument");
   if (n == 0) return 0;
   Ctx* c = current_ctx();
   if (!c || bind(c)) return 1;
-  double* dx = (double*)c->dev_cache.get((size_t)n*8); double* dy = (double*)c->dev_cache.get((size_t)n*8);
-  int rc = 1;
-  if (dx && dy && hipMemcpy(dx, x, (size_t)n*8, hipMemcpyHostToDevice) == hipSuccess){
+  hipstr::ScratchBufs S; S.ctx = c; S.runs_on(c->stream);
+  double *dx, *dy;
+  int rc = S.put(&dx, x, (size_t)n) || S.alloc(&dy, (size_t)n);
+  if (!rc){
     const auto t0 = std::chrono::steady_clock::now();
     const int reps = getenv("HIPSTR_TIMING") ? 10 : 1;
     for (int r = 0; r < reps; r++)
@@ -1130,9 +1124,8 @@ int hipstr_debug_cr_math(int which, const double* x, double* y, int64_t n){
     if (reps > 1 && hipstr::wait_stream(c->stream) == hipSuccess)
       fprintf(stderr, "hipstr_debug_cr_math: %s of %lld arguments x %d launches: %.3f ms per launch\n", which ? "log" : "exp", (long long)n, reps,
               1e3*std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()/reps);
-    if (hipstr::wait_stream(c->stream) == hipSuccess && hipMemcpy(y, dy, (size_t)n*8, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    rc = prim_fetch(c->stream, y, dy, (size_t)n*8);
   }
-  c->dev_cache.put(dx); c->dev_cache.put(dy);
   return rc ? fail("hipstr_debug_cr_math: device call failed") : 0;
 }
 // float_lse.h on the device and, the _host forms, on the host (tests/test_float_lse_gpu.py, tests/test_float_lse.py)
@@ -1157,13 +1150,13 @@ int hipstr_debug_float_fn(int which, uint32_t bits_lo, int64_t count, uint32_t* 
   if (count == 0) return 0;
   Ctx* c = current_ctx();
   if (!c || bind(c)) return 1;
-  uint32_t* d = (uint32_t*)c->dev_cache.get((size_t)count*4);
-  int rc = 1;
-  if (d){
+  hipstr::ScratchBufs S; S.ctx = c; S.runs_on(c->stream);
+  uint32_t* d;
+  int rc = S.alloc(&d, (size_t)count);
+  if (!rc){
     hipLaunchKernelGGL(hs_float_fn_kernel, dim3((unsigned)((count + 255)/256)), dim3(256), 0, c->stream, which, bits_lo, count, d);
-    if (hipstr::wait_stream(c->stream) == hipSuccess && hipMemcpy(out_bits, d, (size_t)count*4, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    rc = prim_fetch(c->stream, out_bits, d, (size_t)count*4);
   }
-  c->dev_cache.put(d);
   return rc ? fail("hipstr_debug_float_fn: device call failed") : 0;
 }
 int hipstr_debug_float_fn_host(int which, uint32_t bits_lo, int64_t count, uint32_t* out_bits){
@@ -1189,13 +1182,13 @@ int hipstr_debug_fast_lse2(const double* a, const double* b, double* out, int64_
   if (n == 0) return 0;
   Ctx* c = current_ctx();
   if (!c || bind(c)) return 1;
-  double* da = (double*)c->dev_cache.get((size_t)n*8); double* db = (double*)c->dev_cache.get((size_t)n*8); double* dy = (double*)c->dev_cache.get((size_t)n*8);
-  int rc = 1;
-  if (da && db && dy && hipMemcpy(da, a, (size_t)n*8, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(db, b, (size_t)n*8, hipMemcpyHostToDevice) == hipSuccess){
+  hipstr::ScratchBufs S; S.ctx = c; S.runs_on(c->stream);
+  double *da, *db, *dy;
+  int rc = S.put(&da, a, (size_t)n) || S.put(&db, b, (size_t)n) || S.alloc(&dy, (size_t)n);
+  if (!rc){
     hipLaunchKernelGGL(hs_fast_lse2_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, c->stream, (const double*)da, (const double*)db, dy, n, hipstr::host_tables().log_thresh);
-    if (hipstr::wait_stream(c->stream) == hipSuccess && hipMemcpy(out, dy, (size_t)n*8, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    rc = prim_fetch(c->stream, out, dy, (size_t)n*8);
   }
-  c->dev_cache.put(da); c->dev_cache.put(db); c->dev_cache.put(dy);
   return rc ? fail("hipstr_debug_fast_lse2: device call failed") : 0;
 }
 int hipstr_debug_fast_lse2_host(const double* a, const double* b, double* out, int64_t n){
@@ -1210,13 +1203,13 @@ int hipstr_debug_fast_lse_vec(const double* v, const int64_t* row_off, double* o
   Ctx* c = current_ctx();
   if (!c || bind(c)) return 1;
   const size_t nv = (size_t)row_off[n_rows];
-  double* dv = (double*)c->dev_cache.get(nv*8); int64_t* dr = (int64_t*)c->dev_cache.get((size_t)(n_rows + 1)*8); double* dy = (double*)c->dev_cache.get((size_t)n_rows*8);
-  int rc = 1;
-  if (dv && dr && dy && hipMemcpy(dv, v, nv*8, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dr, row_off, (size_t)(n_rows + 1)*8, hipMemcpyHostToDevice) == hipSuccess){
+  hipstr::ScratchBufs S; S.ctx = c; S.runs_on(c->stream);
+  double *dv, *dy; int64_t* dr;
+  int rc = S.put(&dv, v, nv) || S.put(&dr, row_off, (size_t)n_rows + 1) || S.alloc(&dy, (size_t)n_rows);
+  if (!rc){
     hipLaunchKernelGGL(hs_fast_lse_vec_kernel, dim3((unsigned)((n_rows + 63)/64)), dim3(64), 0, c->stream, (const double*)dv, (const int64_t*)dr, dy, n_rows, hipstr::host_tables().log_thresh);
-    if (hipstr::wait_stream(c->stream) == hipSuccess && hipMemcpy(out, dy, (size_t)n_rows*8, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    rc = prim_fetch(c->stream, out, dy, (size_t)n_rows*8);
   }
-  c->dev_cache.put(dv); c->dev_cache.put(dr); c->dev_cache.put(dy);
   return rc ? fail("hipstr_debug_fast_lse_vec: device call failed") : 0;
 }
 int hipstr_debug_fast_lse_vec_host(const double* v, const int64_t* row_off, double* out, int64_t n_rows){
@@ -1549,22 +1542,16 @@ struct PostRun {
   Ctx* ctx = NULL;
   hipStream_t stream = NULL;        // the creating thread's stream
   std::vector<hs_post_unit_t> units;
-  std::vector<void*> allocs;        // device blocks from the context's cache
+  hipstr::ScratchBufs blocks;       // the run's blocks of the context's caches: back when the run goes, behind `stream`
   hs_post_dev_t h;
   hs_post_dev_t* d_args = NULL;
   int64_t n_post = 0, n_samp = 0, n_ll = 0;
   int n_reads = 0;
   // small runs (a locus or a few: everything under 4 MiB): inputs and argument block travel in ONE pinned block with one copy, the three
-  // results sit next to each other in the same device block and come back with one copy
-  void* pin_in = NULL; size_t res_bytes = 0, res_total_off = 0, res_map_off = 0;
+  // results sit next to each other in the same device block and come back with one copy of res_bytes from log_post on
+  size_t res_bytes = 0;
   hipEvent_t ev_up = NULL;          // small runs: recorded on `stream` behind the asynchronous upload; a launch on another stream waits for it
-  ~PostRun(){
-    if (ctx && ev_up) ctx->put_event(ev_up, false);
-    if (!ctx || (allocs.empty() && !pin_in) || bind(ctx)) return;
-    hipStreamSynchronize(stream);           // the blocks are handed to the next user
-    for (void* p : allocs) ctx->dev_cache.put(p);
-    if (pin_in) ctx->pin_cache.put(pin_in);
-  }
+  ~PostRun(){ if (ctx){ ctx->put_event(ev_up, false); bind(ctx); } }
 };
 
 // The (locus, sample) units of a posterior batch and the totals of its arrays (host only: hipstr_debug_post_plan builds the same units).
@@ -1611,64 +1598,42 @@ int post_setup(const hipstr_post_batch_t* pb, const double* dev_ll, PostRun& R){
   R.n_reads = pb->n_loci ? pb->read_off[pb->n_loci] : 0;
   memset(&R.h, 0, sizeof R.h);
   if (!dev_ll && !pb->log_aln_probs) return fail("no log_aln_probs given");
-  {
-    struct Piece { const void* src; size_t bytes, off; };
-    std::vector<Piece> in; size_t tot = 0;
-    auto add = [&](const void* src, size_t bytes){ const size_t off = tot; in.push_back(Piece{src, bytes, off}); tot = (tot + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off; };
-    const size_t o_units = add(R.units.data(), R.units.size()*sizeof(hs_post_unit_t)), o_p1 = add(pb->log_p1, sizeof(double)*R.n_reads),
-                 o_p2 = add(pb->log_p2, sizeof(double)*R.n_reads), o_w = add(pb->read_weight, sizeof(int32_t)*R.n_reads),
-                 o_prior = pb->log_prior ? add(pb->log_prior, sizeof(double)*R.n_post) : 0,
-                 o_ll = dev_ll ? 0 : add(pb->log_aln_probs, sizeof(double)*R.n_ll), o_args = add(&R.h, sizeof R.h);
-    const size_t in_total = tot;
-    const size_t o_post = tot; tot += ((size_t)sizeof(double)*R.n_post + 255) & ~(size_t)255;
-    const size_t o_tot = tot;  tot += ((size_t)sizeof(double)*R.n_samp + 255) & ~(size_t)255;
-    const size_t o_map = tot;  tot += ((size_t)sizeof(int32_t)*2*R.n_samp + 255) & ~(size_t)255;
-    if (tot < ((size_t)4 << 20)){
-      char* dblk = (char*)ctx->dev_cache.get(tot);
-      if (!dblk) return 1;
-      R.allocs.push_back(dblk);
-      char* pin = (char*)ctx->pin_cache.get(in_total);
-      if (!pin) return 1;
-      R.pin_in = pin;
-      R.h.units = (const hs_post_unit_t*)(dblk + o_units); R.h.log_p1 = (const double*)(dblk + o_p1); R.h.log_p2 = (const double*)(dblk + o_p2);
-      R.h.read_weight = (const int32_t*)(dblk + o_w);
-      if (pb->log_prior) R.h.log_prior = (const double*)(dblk + o_prior);
-      R.h.log_aln_probs = dev_ll ? dev_ll : (const double*)(dblk + o_ll);
-      R.h.log_post = (double*)(dblk + o_post); R.h.sample_total = (double*)(dblk + o_tot); R.h.map_gt = (int32_t*)(dblk + o_map);
-      R.h.log_thresh = T.log_thresh; R.h.log_half = T.log_half;
-      R.d_args = (hs_post_dev_t*)(dblk + o_args);
-      for (const Piece& pc : in) if (pc.bytes && pc.src) memcpy(pin + pc.off, pc.src, pc.bytes);      // (the argument block last in the list: filled in by now)
-      HS_HIP(hipMemcpyAsync(dblk, pin, in_total, hipMemcpyHostToDevice, R.stream));
-      R.ev_up = ctx->get_event(false);
-      if (!R.ev_up) return fail("hipEventCreate failed");
-      HS_HIP(hipEventRecord(R.ev_up, R.stream));
-      R.res_bytes = tot - o_post; R.res_total_off = o_tot - o_post; R.res_map_off = o_map - o_post;
-      return 0;
-    }
-  }
-  auto up = [&](const void* src, size_t bytes, void** out){
-    *out = ctx->dev_cache.get(bytes ? bytes : 1);
-    if (!*out) return 1;
-    R.allocs.push_back(*out);
-    if (src && bytes && hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, R.stream) != hipSuccess) return fail("hipMemcpy failed");
+  R.h.log_aln_probs = dev_ll; R.h.log_thresh = T.log_thresh; R.h.log_half = T.log_half;
+  R.blocks.ctx = ctx; R.blocks.runs_on(R.stream);
+  // The run's pieces, once: what the kernels read — the argument block last, it holds the addresses of all the others — then what they
+  // write.  at[i] is the pointer that receives piece i's device address.  The two forms differ only in where a piece lives and how it travels.
+  hipstr::HostPieces lay; std::vector<void**> at;
+  auto piece = [&](auto* where, const void* src, size_t bytes){ at.push_back((void**)where); lay.add(src, bytes); };
+  piece(&R.h.units, R.units.data(), R.units.size()*sizeof(hs_post_unit_t));
+  piece(&R.h.log_p1, pb->log_p1, sizeof(double)*R.n_reads);
+  piece(&R.h.log_p2, pb->log_p2, sizeof(double)*R.n_reads);
+  piece(&R.h.read_weight, pb->read_weight, sizeof(int32_t)*R.n_reads);
+  if (pb->log_prior) piece(&R.h.log_prior, pb->log_prior, sizeof(double)*R.n_post);
+  if (!dev_ll) piece(&R.h.log_aln_probs, pb->log_aln_probs, sizeof(double)*R.n_ll);
+  piece(&R.d_args, &R.h, sizeof R.h);
+  const size_t in_total = lay.total;
+  piece(&R.h.log_post, NULL, sizeof(double)*R.n_post);
+  piece(&R.h.sample_total, NULL, sizeof(double)*R.n_samp);
+  piece(&R.h.map_gt, NULL, sizeof(int32_t)*2*R.n_samp);
+  if (lay.total < ((size_t)4 << 20)){
+    // small form: a piece is an offset in the one device block; the inputs are staged in one pinned block and sent with one copy
+    char *dblk, *pin;
+    if (R.blocks.alloc(&dblk, lay.total) || R.blocks.alloc_pinned(&pin, in_total)) return 1;
+    for (size_t i = 0; i < at.size(); i++) *at[i] = dblk + lay.pieces[i].off;
+    lay.pack(pin);
+    HS_HIP(hipMemcpyAsync(dblk, pin, in_total, hipMemcpyHostToDevice, R.stream));
+    R.ev_up = ctx->get_event(false);
+    if (!R.ev_up) return fail("hipEventCreate failed");
+    HS_HIP(hipEventRecord(R.ev_up, R.stream));
+    R.res_bytes = lay.total - in_total;
     return 0;
-  };
-  void* p;
-  if (up(R.units.data(), R.units.size()*sizeof(hs_post_unit_t), &p)) return 1; R.h.units = (const hs_post_unit_t*)p;
-  if (up(pb->log_p1, sizeof(double)*R.n_reads, &p)) return 1; R.h.log_p1 = (const double*)p;
-  if (up(pb->log_p2, sizeof(double)*R.n_reads, &p)) return 1; R.h.log_p2 = (const double*)p;
-  if (up(pb->read_weight, sizeof(int32_t)*R.n_reads, &p)) return 1; R.h.read_weight = (const int32_t*)p;
-  if (pb->log_prior){ if (up(pb->log_prior, sizeof(double)*R.n_post, &p)) return 1; R.h.log_prior = (const double*)p; }
-  if (dev_ll) R.h.log_aln_probs = dev_ll;
-  else {
-    if (!pb->log_aln_probs) return fail("no log_aln_probs given");
-    if (up(pb->log_aln_probs, sizeof(double)*R.n_ll, &p)) return 1; R.h.log_aln_probs = (const double*)p;
   }
-  if (up(NULL, sizeof(double)*R.n_post, &p)) return 1; R.h.log_post = (double*)p;
-  if (up(NULL, sizeof(double)*R.n_samp, &p)) return 1; R.h.sample_total = (double*)p;
-  if (up(NULL, sizeof(int32_t)*2*R.n_samp, &p)) return 1; R.h.map_gt = (int32_t*)p;
-  R.h.log_thresh = T.log_thresh; R.h.log_half = T.log_half;
-  if (up(&R.h, sizeof R.h, &p)) return 1; R.d_args = (hs_post_dev_t*)p;
+  // large form: a piece is a block of its own, copied from the caller's array
+  for (size_t i = 0; i < at.size(); i++) if (R.blocks.alloc((char**)at[i], lay.pieces[i].bytes)) return 1;
+  for (size_t i = 0; i < at.size(); i++){
+    const hipstr::HostPieces::Piece& pc = lay.pieces[i];
+    if (pc.src && pc.bytes && hipMemcpyAsync(*at[i], pc.src, pc.bytes, hipMemcpyHostToDevice, R.stream) != hipSuccess) return fail("hipMemcpy failed");
+  }
   HS_HIP(hipstr::wait_stream(R.stream));       // the sources are the caller's (pageable) arrays: done with them before returning
   return 0;
 }
@@ -1803,13 +1768,14 @@ int hipstr_post_fetch(hipstr_post_dev_t* pd, double* log_post, double* sample_to
   if (pd->foreign_stream) HS_HIP(hipDeviceSynchronize());
   if (!(R.res_bytes && !pd->foreign_stream)) HS_HIP(hipstr::wait_stream(R.stream));      // (the small form's one copy is ordered behind the kernel on the same stream)
   if (!R.units.empty() && R.res_bytes){
-    char* pin = (char*)R.ctx->pin_cache.get(R.res_bytes);
-    if (!pin) return 1;
-    if (hipMemcpyAsync(pin, R.h.log_post, R.res_bytes, hipMemcpyDeviceToHost, R.stream) != hipSuccess || hipstr::wait_stream(R.stream) != hipSuccess){
-      R.ctx->pin_cache.put(pin); return fail("device-to-host copy failed"); }
-    memcpy(log_post, pin, sizeof(double)*R.n_post); memcpy(sample_total_ll, pin + R.res_total_off, sizeof(double)*R.n_samp);
-    memcpy(map_gt, pin + R.res_map_off, sizeof(int32_t)*2*R.n_samp);
-    R.ctx->pin_cache.put(pin);
+    char* pin;
+    if (R.blocks.alloc_pinned(&pin, R.res_bytes)) return 1;
+    if (hipMemcpyAsync(pin, R.h.log_post, R.res_bytes, hipMemcpyDeviceToHost, R.stream) != hipSuccess || hipstr::wait_stream(R.stream) != hipSuccess)
+      return fail("device-to-host copy failed");          // (the block goes back with the run, behind the stream)
+    const char* base = (const char*)R.h.log_post;
+    memcpy(log_post, pin, sizeof(double)*R.n_post); memcpy(sample_total_ll, pin + ((const char*)R.h.sample_total - base), sizeof(double)*R.n_samp);
+    memcpy(map_gt, pin + ((const char*)R.h.map_gt - base), sizeof(int32_t)*2*R.n_samp);
+    R.blocks.release(pin);
   } else if (!R.units.empty()){
     if (fetch_array(R.ctx, R.stream, log_post, R.h.log_post, sizeof(double)*R.n_post) ||
         fetch_array(R.ctx, R.stream, sample_total_ll, R.h.sample_total, sizeof(double)*R.n_samp) ||
@@ -1918,27 +1884,28 @@ int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hi
   lap("units");
   if (bind(R.ctx)) return 1;
   Ctx* ctx = R.ctx;
-  std::vector<void*> tmp;
-  struct Free { Ctx* c; hipStream_t st; std::vector<void*>& v; ~Free(){ hipStreamSynchronize(st); for (void* p : v) c->dev_cache.put(p); } } guard{ctx, R.stream, tmp};
-  auto dalloc = [&](size_t bytes, void** outp) -> int { *outp = ctx->dev_cache.get(bytes ? bytes : 1); if (!*outp) return 1; tmp.push_back(*outp); return 0; };
   hs_gt_dev_t h; memset(&h, 0, sizeof h);
-  void* p;
-  if (dalloc(units.size()*sizeof(hs_gt_unit_t), &p)) return 1; HS_HIP(hipMemcpy(p, units.data(), units.size()*sizeof(hs_gt_unit_t), hipMemcpyHostToDevice)); h.units = (const hs_gt_unit_t*)p;
-  if (dalloc((size_t)map_off*4, &p)) return 1; HS_HIP(hipMemcpy(p, rq->hap_to_allele, (size_t)map_off*4, hipMemcpyHostToDevice)); h.h2a = (const int32_t*)p;
-  if (dalloc(gmem.size()*4, &p)) return 1; HS_HIP(hipMemcpy(p, gmem.data(), gmem.size()*4, hipMemcpyHostToDevice)); h.gmem = (const int32_t*)p;
-  if (dalloc(goff.size()*4, &p)) return 1; HS_HIP(hipMemcpy(p, goff.data(), goff.size()*4, hipMemcpyHostToDevice)); h.goff = (const int32_t*)p;
+  hipstr::HostArena ar;
+  const size_t o_units = ar.add(units.data(), units.size()*sizeof(hs_gt_unit_t)), o_h2a = ar.add(rq->hap_to_allele, (size_t)map_off*4),
+               o_gmem = ar.add(gmem.data(), gmem.size()*4), o_goff = ar.add(goff.data(), goff.size()*4), o_args = ar.add(&h, sizeof h);
+  if (ar.reserve(ctx)) return 1;
+  // the per-sample results, back to back (one copy home); then the variant pairs' totals and the optional outputs, which can be large
+  hipstr::ResultBlocks B;
+  const size_t r_hap = B.take((size_t)so*2*4), r_gt = B.take((size_t)so*2*4), r_five = B.take((size_t)so*5*8);
+  B.end_results();
+  const size_t d_tot = B.take((size_t)tot*8), d_gls = any ? B.take((size_t)g*8) : 0, d_pls = rq->calc_pls ? B.take((size_t)g*4) : 0,
+               d_pgls = rq->calc_phased_gls ? B.take((size_t)pg*8) : 0;
+  if (B.reserve(ctx, R.stream)) return 1;
+  h.units = ar.at<hs_gt_unit_t>(o_units); h.h2a = ar.at<int32_t>(o_h2a); h.gmem = ar.at<int32_t>(o_gmem); h.goff = ar.at<int32_t>(o_goff);
   h.log_post = R.h.log_post; h.sample_total = R.h.sample_total; h.map_gt = R.h.map_gt;
-  if (dalloc((size_t)tot*8, &p)) return 1; h.tot = (double*)p;
-  if (dalloc((size_t)so*2*4, &p)) return 1; h.best_gt = (int32_t*)p;
-  double* five = NULL;
-  if (dalloc((size_t)so*5*8, &p)) return 1; five = (double*)p;
+  h.tot = B.dev<double>(d_tot); h.best_gt = B.dev<int32_t>(r_gt);
+  double* five = B.dev<double>(r_five);
   h.log_phased = five; h.log_unphased = five + so; h.hap_log_phased = five + 2*(size_t)so; h.hap_log_unphased = five + 3*(size_t)so; h.gl_diff = five + 4*(size_t)so;
-  if (any){ if (dalloc((size_t)g*8, &p)) return 1; h.gls = (double*)p; }
-  if (rq->calc_pls){ if (dalloc((size_t)g*4, &p)) return 1; h.pls = (int32_t*)p; }
-  if (rq->calc_phased_gls){ if (dalloc((size_t)pg*8, &p)) return 1; h.pgls = (double*)p; }
+  if (any) h.gls = B.dev<double>(d_gls);
+  if (rq->calc_pls) h.pls = B.dev<int32_t>(d_pls);
+  if (rq->calc_phased_gls) h.pgls = B.dev<double>(d_pgls);
   h.calc_any = any; h.calc_gls = rq->calc_gls; h.calc_pls = rq->calc_pls; h.calc_pgls = rq->calc_phased_gls;
   h.log_thresh = T.log_thresh;
-  if (dalloc(sizeof h, &p)) return 1; HS_HIP(hipMemcpy(p, &h, sizeof h, hipMemcpyHostToDevice));
   const bool host_libm = getenv("HIPSTR_DEBUG_HOST_LIBM") && atoi(getenv("HIPSTR_DEBUG_HOST_LIBM")) != 0;      // see hipstr_post_launch
   std::vector<double> h_tot;
   if (host_libm){
@@ -1960,18 +1927,18 @@ int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hi
     }
     HS_HIP(hipMemcpy(h.tot, h_tot.data(), sizeof(double)*(size_t)tot, hipMemcpyHostToDevice));
     h.tot_given = 1;
-    HS_HIP(hipMemcpy(p, &h, sizeof h, hipMemcpyHostToDevice));
   }
   if (pd->foreign_stream) HS_HIP(hipDeviceSynchronize());          // the posterior kernel may still be running on a stream of the caller's
-  hipLaunchKernelGGL(hs_genotype_kernel, dim3((unsigned)units.size()), dim3(256), 0, R.stream, (const hs_gt_dev_t*)p);
+  if (ar.send(R.stream)) return 1;                                 // (the argument block is complete by now)
+  hipLaunchKernelGGL(hs_genotype_kernel, dim3((unsigned)units.size()), dim3(256), 0, R.stream, (const hs_gt_dev_t*)ar.at<hs_gt_dev_t>(o_args));
   HS_HIP(hipGetLastError());
+  HS_HIP(hipMemcpyAsync(B.dev<char>(r_hap), R.h.map_gt, (size_t)so*2*4, hipMemcpyDeviceToDevice, R.stream));       // best_hap travels with the rest
   lap("setup");
-  HS_HIP(hipstr::wait_stream(R.stream));
+  if (B.fetch()) return 1;
   lap("kernel");
-  HS_HIP(hipMemcpy(out->best_hap, R.h.map_gt, (size_t)so*2*4, hipMemcpyDeviceToHost));
-  HS_HIP(hipMemcpy(out->best_gt, h.best_gt, (size_t)so*2*4, hipMemcpyDeviceToHost));
-  HS_HIP(hipMemcpy(out->log_phased_post, h.log_phased, (size_t)so*8, hipMemcpyDeviceToHost));
-  HS_HIP(hipMemcpy(out->log_unphased_post, h.log_unphased, (size_t)so*8, hipMemcpyDeviceToHost));
+  const double* hf = B.host<double>(r_five);
+  memcpy(out->best_hap, B.host<char>(r_hap), (size_t)so*2*4); memcpy(out->best_gt, B.host<char>(r_gt), (size_t)so*2*4);
+  memcpy(out->log_phased_post, hf, (size_t)so*8); memcpy(out->log_unphased_post, hf + so, (size_t)so*8);
   if (host_libm)                                          // the exact pair log_sum_exp of the two phasings (mathops.cpp:52-57) with the host libm
     for (const hs_gt_unit_t& u : units){
       const int ga = out->best_gt[2*u.samp_index], gb = out->best_gt[2*u.samp_index+1];
@@ -1979,9 +1946,8 @@ int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hi
       const double lp = h_tot[u.tot_off + (int64_t)u.n_variants*ga + gb], alt = h_tot[u.tot_off + (int64_t)u.n_variants*gb + ga];
       out->log_unphased_post[u.samp_index] = (lp > alt) ? lp + log(1 + exp(alt - lp)) : alt + log(1 + exp(lp - alt));
     }
-  HS_HIP(hipMemcpy(out->hap_log_phased_post, h.hap_log_phased, (size_t)so*8, hipMemcpyDeviceToHost));
-  HS_HIP(hipMemcpy(out->hap_log_unphased_post, h.hap_log_unphased, (size_t)so*8, hipMemcpyDeviceToHost));
-  if (any) HS_HIP(hipMemcpy(out->gl_diff, h.gl_diff, (size_t)so*8, hipMemcpyDeviceToHost));
+  memcpy(out->hap_log_phased_post, hf + 2*(size_t)so, (size_t)so*8); memcpy(out->hap_log_unphased_post, hf + 3*(size_t)so, (size_t)so*8);
+  if (any) memcpy(out->gl_diff, hf + 4*(size_t)so, (size_t)so*8);
   if (rq->calc_gls && fetch_array(ctx, R.stream, out->gls, h.gls, (size_t)g*8)) return 1;
   if (rq->calc_pls && fetch_array(ctx, R.stream, out->pls, h.pls, (size_t)g*4)) return 1;
   if (rq->calc_phased_gls && fetch_array(ctx, R.stream, out->phased_gls, h.pgls, (size_t)pg*8)) return 1;
@@ -2501,11 +2467,13 @@ struct hipstr_read_matrix {
   int32_t n_loci = 0; int64_t n_reads = 0, n_ll = 0, n_groups = 0, n_waves = 0;
   std::vector<int32_t> n_alleles, read_off, pool_index, pool_max, group_off;      // pool_max: largest pool_index of a locus (-1: no reads)
   std::vector<int64_t> mat_off;
+  hipstr::ScratchBufs blocks;                  // the five blocks below: back when the matrix goes, behind `stream`
   double* d_ll = NULL; int32_t* d_seeds = NULL;
   char* d_static = NULL; size_t o_groups = 0, o_pool = 0, o_waves = 0;            // mate groups | pool_index | wavefront list, device
   char* d_stage = NULL; char* pin_stage = NULL; size_t stage_bytes = 0;           // what a scatter sends: locus records | copy_read | realign_hap flags
   hipEvent_t ev_stage = NULL, ev_done = NULL;  // the staging block's last copy has left it / the matrix' last kernel has run
   bool stage_sent = false;
+  ~hipstr_read_matrix(){ if (ctx){ ctx->put_event(ev_stage, false); ctx->put_event(ev_done, false); bind(ctx); } }
 };
 
 namespace {
@@ -2536,26 +2504,22 @@ size_t rm_stage_bytes(const hipstr_read_matrix* rm){
   return (((size_t)rm->n_loci*sizeof(hs_rm_locus_t) + 255) & ~(size_t)255) + (((size_t)rm->n_reads + 255) & ~(size_t)255) + sumA + 256;
 }
 
-// host arrays -> device through a pinned block of the cache, on the matrix' stream; returns when the copy has landed
+// host arrays -> device through a pinned block of the cache, on the matrix' stream; returns when the copy has landed (a copy that failed
+// may still be in flight: its block goes back with the matrix)
 int rm_send(hipstr_read_matrix* rm, void* dst, const void* src, size_t bytes){
   if (!bytes) return 0;
-  char* pin = (char*)rm->ctx->pin_cache.get(bytes);
-  if (!pin) return 1;
+  char* pin;
+  if (rm->blocks.alloc_pinned(&pin, bytes)) return 1;
   memcpy(pin, src, bytes);
-  const bool ok = hipMemcpyAsync(dst, pin, bytes, hipMemcpyHostToDevice, rm->stream) == hipSuccess && hipstr::wait_stream(rm->stream) == hipSuccess;
-  rm->ctx->pin_cache.put(pin);
-  return ok ? 0 : fail("host-to-device copy failed");
+  if (hipMemcpyAsync(dst, pin, bytes, hipMemcpyHostToDevice, rm->stream) != hipSuccess || hipstr::wait_stream(rm->stream) != hipSuccess)
+    return fail("host-to-device copy failed");
+  rm->blocks.release(pin);
+  return 0;
 }
 
 void rm_release(hipstr_read_matrix* rm){
   if (!rm) return;
   { std::lock_guard<std::mutex> g(g_rm_m); if (rm->d_ll) g_rm.erase(rm->d_ll); }
-  if (rm->ctx && bind(rm->ctx) == 0){
-    hipStreamSynchronize(rm->stream);          // the blocks are handed to the next user
-    rm->ctx->dev_cache.put(rm->d_ll); rm->ctx->dev_cache.put(rm->d_seeds); rm->ctx->dev_cache.put(rm->d_static); rm->ctx->dev_cache.put(rm->d_stage);
-    rm->ctx->pin_cache.put(rm->pin_stage);
-  }
-  if (rm->ctx){ rm->ctx->put_event(rm->ev_stage, false); rm->ctx->put_event(rm->ev_done, false); }
   delete rm;
 }
 }  // namespace
@@ -2608,13 +2572,10 @@ hipstr_read_matrix_t* hipstr_rm_create(const hipstr_read_layout_t* lay, const do
   rm->o_groups = 0; rm->o_pool = (G*4 + 255) & ~(size_t)255; rm->o_waves = (rm->o_pool + (size_t)R*4 + 255) & ~(size_t)255;
   const size_t static_bytes = rm->o_waves + G*sizeof(hs_rm_wave_t) + 256;
   rm->stage_bytes = rm_stage_bytes(rm);
-  rm->d_ll = (double*)ctx->dev_cache.get((size_t)(n_ll ? n_ll : 1)*sizeof(double));
-  rm->d_seeds = (int32_t*)ctx->dev_cache.get((size_t)(R ? R : 1)*sizeof(int32_t));
-  rm->d_static = (char*)ctx->dev_cache.get(static_bytes);
-  rm->d_stage = (char*)ctx->dev_cache.get(rm->stage_bytes);
-  rm->pin_stage = (char*)ctx->pin_cache.get(rm->stage_bytes);
+  rm->blocks.ctx = ctx; rm->blocks.runs_on(rm->stream);
+  bool ok = !(rm->blocks.alloc(&rm->d_ll, (size_t)n_ll) || rm->blocks.alloc(&rm->d_seeds, (size_t)R) || rm->blocks.alloc(&rm->d_static, static_bytes) ||
+              rm->blocks.alloc(&rm->d_stage, rm->stage_bytes) || rm->blocks.alloc_pinned(&rm->pin_stage, rm->stage_bytes));
   rm->ev_stage = ctx->get_event(false); rm->ev_done = ctx->get_event(false);
-  bool ok = rm->d_ll && rm->d_seeds && rm->d_static && rm->d_stage && rm->pin_stage;
   if (ok && (!rm->ev_stage || !rm->ev_done)){ ok = false; g_err = "hipEventCreate failed"; }
   if (ok){
     std::vector<char> img(static_bytes, 0);
@@ -2742,13 +2703,14 @@ int hipstr_rm_remap(hipstr_read_matrix_t* rm, const int32_t* new_n_alleles, cons
   rm_waves(newA, rows.data(), waves);
   { std::vector<int64_t> cnt(nl); for (int l = 0; l < nl; l++) cnt[l] = rm->group_off[l+1] - rm->group_off[l]; rm_waves(newA, cnt.data(), swaves); }
   const int64_t n_new = new_off[nl];
-  double* nll = (double*)ctx->dev_cache.get((size_t)(n_new ? n_new : 1)*sizeof(double));
-  if (!nll) return 1;
+  double* nll;
+  if (rm->blocks.alloc(&nll, (size_t)n_new)) return 1;
+  bool ok;
   {
     hipstr::HostArena ar;             // (waits for the stream when it goes)
     const size_t o_loci = ar.add(loci.data(), loci.size()*sizeof(hs_rm_remap_locus_t)), o_inv = ar.add(inv.data(), inv.size()*4),
                  o_w = ar.add(waves.data(), waves.size()*sizeof(hs_rm_wave_t)), o_sw = ar.add(swaves.data(), swaves.size()*sizeof(hs_rm_wave_t));
-    bool ok = ar.reserve(ctx) == 0 && ar.send(st) == 0;
+    ok = ar.reserve(ctx) == 0 && ar.send(st) == 0;
     if (ok && !waves.empty()){
       hs_rm_remap_t a; memset(&a, 0, sizeof a);
       a.waves = ar.at<hs_rm_wave_t>(o_w); a.loci = ar.at<hs_rm_remap_locus_t>(o_loci); a.inv = ar.at<int32_t>(o_inv);
@@ -2759,17 +2721,17 @@ int hipstr_rm_remap(hipstr_read_matrix_t* rm, const int32_t* new_n_alleles, cons
     if (ok && !swaves.empty())
       ok = hipMemcpyAsync(rm->d_static + rm->o_waves, ar.at<char>(o_sw), swaves.size()*sizeof(hs_rm_wave_t), hipMemcpyDeviceToDevice, st) == hipSuccess;
     if (ok) ok = hipEventRecord(rm->ev_done, st) == hipSuccess && hipstr::wait_stream(st) == hipSuccess;
-    if (!ok){ hipStreamSynchronize(st); ctx->dev_cache.put(nll); return g_err.empty() ? fail("hipstr_rm_remap: launch failed") : 1; }
   }
+  if (!ok){ rm->blocks.release(nll); return g_err.empty() ? fail("hipstr_rm_remap: launch failed") : 1; }
   { std::lock_guard<std::mutex> g(g_rm_m); g_rm.erase(rm->d_ll); g_rm[nll] = rm; }
-  ctx->dev_cache.put(rm->d_ll);          // (the stream is idle: nothing reads the old matrix any more)
-  rm->d_ll = nll; rm->n_ll = n_new; rm->n_alleles.swap(newA); rm->mat_off.swap(new_off); rm->n_waves = (int64_t)swaves.size();
+  rm->blocks.replace(&rm->d_ll, nll);    // (the stream is idle: nothing reads the old matrix any more)
+  rm->n_ll = n_new; rm->n_alleles.swap(newA); rm->mat_off.swap(new_off); rm->n_waves = (int64_t)swaves.size();
   const size_t need = rm_stage_bytes(rm);
   if (need > rm->stage_bytes){           // more haplotype flags than the staging blocks hold
-    char* d = (char*)ctx->dev_cache.get(need); char* p = (char*)ctx->pin_cache.get(need);
-    if (!d || !p){ ctx->dev_cache.put(d); ctx->pin_cache.put(p); return 1; }
-    ctx->dev_cache.put(rm->d_stage); ctx->pin_cache.put(rm->pin_stage);
-    rm->d_stage = d; rm->pin_stage = p; rm->stage_bytes = need; rm->stage_sent = false;
+    char *d, *p;
+    if (rm->blocks.alloc(&d, need) || rm->blocks.alloc_pinned(&p, need)) return 1;      // (a block already taken goes back with the matrix)
+    rm->blocks.replace(&rm->d_stage, d); rm->blocks.replace(&rm->pin_stage, p);
+    rm->stage_bytes = need; rm->stage_sent = false;
   }
   return 0;
 }

@@ -45,25 +45,20 @@ void  pin_free(Ctx* ctx, void* p);
 
 
 // Host arrays that travel together: packed into ONE pinned block and sent with ONE asynchronous copy (a synchronous hipMemcpy from
-// pageable memory costs 10-20 us each; the traceback and Needleman-Wunsch calls of a locus had ten of them).  add() returns a piece's offset;
-// after send() the piece sits at dev + offset.  Both blocks go back to the context's caches when the arena dies; the caches serve other
+// pageable memory costs 10-20 us each; the traceback and Needleman-Wunsch calls of a locus had ten of them).  add() (the list of
+// pieces and its arithmetic: HostPieces, block_pieces.h) returns a piece's offset; after send() the piece sits at dev + offset.  Both blocks go back to the context's caches when the arena dies; the caches serve other
 // host threads, so the arena first waits for the stream its copy went to (an error path may leave while the copy is in flight; on the
 // normal path the results were fetched already and the wait costs a few microseconds).
-struct HostArena {
-  struct Piece { const void* src; size_t bytes, off; };
-  std::vector<Piece> pieces; size_t total = 0;
+struct HostArena : HostPieces {
   Ctx* ctx = NULL; char* pin = NULL; char* dev = NULL;
   hipStream_t sent_on = NULL; bool sent = false;
   ~HostArena(){ if (ctx){ if (sent) hipStreamSynchronize(sent_on); if (pin) pin_free(ctx, pin); if (dev) dev_free(ctx, dev); } }
-  size_t add(const void* src, size_t bytes){
-    const size_t off = total; pieces.push_back(Piece{src, bytes, off}); total = (total + (bytes ? bytes : 1) + 255) & ~(size_t)255; return off;
-  }
   int reserve(Ctx* c){        // blocks only (the caller still has pointers into `dev` to fill in before the pieces are packed)
     ctx = c; pin = (char*)pin_alloc(ctx, total ? total : 256); dev = (char*)dev_alloc(ctx, total ? total : 256);
     return (pin && dev) ? 0 : 1;
   }
   int send(hipStream_t st){   // pack and copy
-    for (const Piece& pc : pieces) if (pc.bytes && pc.src) memcpy(pin + pc.off, pc.src, pc.bytes);
+    pack(pin);
     sent_on = st; sent = true;
     return (total && hipMemcpyAsync(dev, pin, total, hipMemcpyHostToDevice, st) != hipSuccess) ? api_fail("hipMemcpyAsync (host to device) failed") : 0;
   }
@@ -75,30 +70,46 @@ struct HostArena {
 // On the normal path the results were fetched through wait_stream already and that wait costs a few microseconds; hipStreamSynchronize
 // is the backstop of the error paths.
 
-// Device scratch arrays of a chunked call (traceback, Needleman-Wunsch, the stutter EM): one cache block each, all of them back when the
-// call leaves, behind every stream it was told about.
+// Cache blocks with one owner — the device scratch arrays of a chunked call (traceback, Needleman-Wunsch, the stutter EM), the blocks of a
+// resident handle (a posterior run, a read matrix): one cache block each, device or pinned, all of them back when the owner goes, behind
+// every stream it was told about.  release() gives one back earlier — the caller has waited for whatever used it — and replace() puts a
+// new block in its place; an owner that holds nothing any more has nothing to wait for.
 struct ScratchBufs {
-  std::vector<void*> p;
+  std::vector<void*> p, pin;        // device blocks, pinned blocks
   Ctx* ctx = NULL;                  // taken on first use: blocks come from (and return to) the context's cache, no hipMalloc / hipFree per call
   hipStream_t streams[3] = {NULL, NULL, NULL}; int n_streams = 0;
   void runs_on(hipStream_t st){ for (int i = 0; i < n_streams; i++) if (streams[i] == st) return; if (n_streams < 3) streams[n_streams++] = st; }
   ScratchBufs(){}
   ScratchBufs(const ScratchBufs&) = delete;
-  ~ScratchBufs(){ if (ctx){ for (int i = 0; i < n_streams; i++) hipStreamSynchronize(streams[i]); for (void* x : p) dev_free(ctx, x); } }
-  template <typename T> int alloc(T** out, size_t count){
+  ~ScratchBufs(){
+    if (!ctx || (p.empty() && pin.empty())) return;
+    for (int i = 0; i < n_streams; i++) hipStreamSynchronize(streams[i]);
+    for (void* x : p) dev_free(ctx, x);
+    for (void* x : pin) pin_free(ctx, x);
+  }
+  template <typename T> int alloc(T** out, size_t count, bool pinned = false){
     *out = NULL;
     if (!ctx) ctx = api_current_ctx();
     if (!ctx) return 1;
-    *out = (T*)dev_alloc(ctx, (count ? count : 1)*sizeof(T));
+    const size_t bytes = (count ? count : 1)*sizeof(T);
+    *out = (T*)(pinned ? pin_alloc(ctx, bytes) : dev_alloc(ctx, bytes));
     if (!*out) return 1;
-    p.push_back(*out);
+    (pinned ? pin : p).push_back(*out);
     return 0;
   }
+  template <typename T> int alloc_pinned(T** out, size_t count){ return alloc(out, count, true); }
   template <typename T> int put(T** out, const T* src, size_t count){
     if (alloc(out, count)) return 1;
     if (count) HS_HIP(hipMemcpy(*out, src, count*sizeof(T), hipMemcpyHostToDevice));
     return 0;
   }
+  void release(void* x){
+    auto it = std::find(p.begin(), p.end(), x);
+    if (it != p.end()){ p.erase(it); dev_free(ctx, x); return; }
+    it = std::find(pin.begin(), pin.end(), x);
+    if (it != pin.end()){ pin.erase(it); pin_free(ctx, x); }
+  }
+  template <typename T> void replace(T** slot, T* fresh){ release(*slot); *slot = fresh; }
 };
 
 // The results of a one-shot call: the pieces that come home first, back to back (take, then end_results), then what stays on the device;
@@ -218,7 +229,9 @@ int  fetch_begin(hipstr_dev_batch* dev, hipStream_t compute_stream, hipStream_t 
 int  fetch_poll(hipstr_dev_batch* dev);         // queues the copy back of a batch whose kernels are done (0 queued or nothing pending, 1 still running, -1 error)
 int  results_wait(hipstr_dev_batch* dev);
 double batch_prepare_seconds(const hipstr_dev_batch* dev);      // wall time of the batch's prepare_batch
-void scatter_loci(const hipstr_dev_batch* dev, int l0, int l1, double* aln_probs, int32_t* seeds);   // outputs based at locus l0
+// the reference's output contract for loci [l0, l1) of a batch whose results lie at `src` (NULL: where the batch's own copy back landed);
+// aln_probs / seeds are based at locus l0, or at the batch's first locus when `whole`
+void scatter_loci(const hipstr_dev_batch* dev, int l0, int l1, double* aln_probs, int32_t* seeds, const double* src = NULL, bool whole = false);
 void free_landed(hipstr_dev_batch* dev, bool landed);
 hipStream_t ctx_stream(Ctx* c);
 int ctx_device(Ctx* c);

@@ -5,7 +5,12 @@ the device cache, out[6] for the pinned one.  With the input handles alive both 
 again: (a) after a normal return, (b) after the return-3 path — a capacity one too small, found after the results were fetched — and (c)
 after a refusal found only after blocks were taken and work was queued (the check kernel's verdict on a decreasing str_seq_off; a read
 that enters the EM without STR data).  The cases are the smallest ones of the stages' own test modules; what the calls compute is held to
-its yardsticks there."""
+its yardsticks there.
+
+The handles themselves are balanced around their whole life, freed early (before a launch, an align, a scatter) included: the posterior
+run in both of its forms (hipstr_post_upload / launch / fetch / free, hipstr_post_run, hipstr_post_extract), the read matrix
+(hipstr_rm_create / scatter / remap / fetch / free, a refused remap) and the forward handle (hipstr_hmm_upload / align / fetch / free,
+hipstr_hmm_process_reads); so are the four debug entry points of the float and cr_math primitives."""
 import ctypes as C
 from contextlib import contextmanager
 
@@ -19,6 +24,7 @@ import hapgen_cases as hc
 import pool_cases as pc
 import test_assign_gpu as ta
 import test_census_gpu as tc
+import test_readmat_gpu as trm
 import test_trace_assemble_gpu as tta
 from em_cases import em_case
 from nw_cases import nw_pairs
@@ -62,10 +68,128 @@ def handle(td):
         td.close()
 
 
+def small_pb():
+    """Two loci, three samples, eleven reads."""
+    row = lambda A, h: [(-1.0 if k == h else -30.0) - 0.01 * k for k in range(A)]
+    return ta.make_pb([(3, [[(-0.5, -0.5, row(3, 0))] * 3, [(-0.2, -0.9, row(3, 2))] * 2]), (2, [[(-0.5, -0.5, row(2, 1))] * 6])])[0]
+
+
+def large_pb():
+    """One locus of 64 haplotypes and 128 samples, one read per sample: the results alone are 128 x 64 x 64 x 8 B = 4 MiB, so the run takes
+    the form with a block per array."""
+    rng = np.random.default_rng(11)
+    return capi.PostBatch([64], [128], [0, 128], np.arange(128), -rng.random(128), -rng.random(128), np.ones(128, np.int32), -50 * rng.random(128 * 64))
+
+
+def post_results(pb):
+    S = int(pb.samp_off[-1])
+    k = [np.zeros(int(pb.post_off[-1])), np.zeros(S), np.zeros(2 * S, np.int32), np.zeros(pb.struct.n_loci)]
+    return k, [a.ctypes.data_as(t) for a, t in zip(k, (capi._f64p, capi._f64p, capi._i32p, capi._f64p))]
+
+
+@pytest.mark.parametrize("make", [small_pb, large_pb], ids=["small", "large"])
+def test_posterior_run(hmm, make):
+    """Upload, launch, fetch, free; upload then free; hipstr_post_run — the three ways give the same results."""
+    pb = make()
+    assert (int(pb.post_off[-1]) * 8 >= 4 << 20) == (make is large_pb)
+    with balanced(hmm, "hipstr_post_upload, launch, fetch, free"):
+        with launched(hmm, pb) as pd:
+            got, ptrs = post_results(pb)
+            assert hmm.hipstr_post_fetch(pd, *ptrs) == 0, hmm.hipstr_last_error().decode()
+    with balanced(hmm, "hipstr_post_upload, free"):
+        with launched(hmm, pb, launch=False):
+            pass
+    with balanced(hmm, "hipstr_post_run"):
+        one, ptrs = post_results(pb)
+        assert hmm.hipstr_post_run(pb.ptr, None, *ptrs) == 0, hmm.hipstr_last_error().decode()
+    for a, b in zip(got, one):
+        assert np.array_equal(a, b)
+    assert np.all(got[2] >= 0) and np.all(np.isfinite(got[0])) and np.all(got[1] < 0)
+
+
+def test_post_extract(hmm):
+    """The small run, two variants on three and on two haplotypes: every optional output, then none."""
+    pb = small_pb()
+    kw = dict(n_variants=[2, 2], hap_to_allele=[0, 1, 1, 0, 1])
+    with balanced(hmm, "hipstr_post_extract, gls + pls + phased_gls"):
+        full = capi.run_gt_extract(hmm, "hipstr_", pb, **kw)
+    with balanced(hmm, "hipstr_post_extract, no optional output"):
+        bare = capi.run_gt_extract(hmm, "hipstr_", pb, calc_gls=False, calc_pls=False, calc_phased_gls=False, **kw)
+    for k in ("best_hap", "best_gt", "log_phased_post", "log_unphased_post", "hap_log_phased_post", "hap_log_unphased_post"):
+        assert np.array_equal(full[k], bare[k]), k
+    assert np.all(full["best_gt"] >= 0) and np.all(full["best_gt"] < 2) and full["best_hap"].tolist() == [[0, 0], [2, 2], [1, 1]] and full["best_gt"].tolist() == [[0, 0], [1, 1], [1, 1]]
+    assert all(len(g) == 3 and np.isfinite(g).all() for g in full["gls"]) and all(min(p) == 0 for p in full["pls"])
+
+
+def test_read_matrix(hmm):
+    """Two loci of 3 and 4 haplotypes, seven and two reads, three mate pairs: created without initial values, filled from an aligned batch,
+    a remap that raises the first locus' haplotype count (more flags than the staging blocks hold: they are replaced), one that lowers it."""
+    small = trm.pooled_batch(trm.SHAPES1[1:3], [5, 2], [None, None])
+    A = [3, 4]; ro = [0, 7, 9]; pool = [0, 1, 2, 3, 4, 4, 0, 0, 1]; mates = [0, 1, 0, 0, 0, 1, 0, 0, 1]
+    dev = trm.upload_and_align(hmm, small)
+    try:
+        with balanced(hmm, "hipstr_rm_create, scatter, remap, remap, fetch, free"):
+            with handle(capi.ReadMatrix(hmm, A, ro, pool, mates)) as rm:
+                rm.scatter(dev)
+                before, seeds = rm.fetch()
+                rm.remap([5, 4], [4, 0, 2] + [0, 1, 2, 3])
+                rm.remap([2, 4], [0, -1, -1, -1, 1] + [0, 1, 2, 3])
+                after, seeds2 = rm.fetch()
+            rows = before[:21].reshape(7, 3)
+            assert np.array_equal(after[:14].reshape(7, 2), rows[:, [1, 0]]) and np.array_equal(after[14:], before[21:]) and np.array_equal(seeds, seeds2)
+            assert np.all(before != trm.UNALIGNED) and np.all(seeds >= 0)
+        with balanced(hmm, "hipstr_rm_create, free"):
+            capi.ReadMatrix(hmm, A, ro, pool, mates).close()
+        with balanced(hmm, "hipstr_rm_remap refused, free"):
+            with handle(capi.ReadMatrix(hmm, A, ro, pool, mates)) as rm:
+                with pytest.raises(RuntimeError, match="two old columns mapped to one new column"):
+                    rm.remap([3, 4], [0, 1, 1] + [0, 1, 2, 3])
+    finally:
+        hmm.hipstr_hmm_free(dev)
+
+
+def test_forward_handle(hmm):
+    """One locus: upload, align, fetch, free; upload, free; hipstr_hmm_process_reads."""
+    sb = capi.SynthBatch(n_loci=1, reads_per_locus=20, n_str_alleles=4, seed=2)
+    n_reads, n_out, _ = capi.batch_dims(sb.ptr)
+    probs = np.full(n_out, np.nan); seeds = np.full(n_reads, -7, np.int32)
+    with balanced(hmm, "hipstr_hmm_upload, align, fetch, free"):
+        dev = hmm.hipstr_hmm_upload(sb.ptr); assert dev, hmm.hipstr_last_error().decode()
+        try:
+            assert hmm.hipstr_hmm_align(dev, None) == 0
+            assert hmm.hipstr_hmm_fetch(dev, probs.ctypes.data_as(capi._f64p), seeds.ctypes.data_as(capi._i32p)) == 0, hmm.hipstr_last_error().decode()
+        finally:
+            hmm.hipstr_hmm_free(dev)
+    with balanced(hmm, "hipstr_hmm_upload, free"):
+        dev = hmm.hipstr_hmm_upload(sb.ptr); assert dev, hmm.hipstr_last_error().decode()
+        hmm.hipstr_hmm_free(dev)
+    with balanced(hmm, "hipstr_hmm_process_reads"):
+        one, s1 = capi.run_align(hmm, "hipstr_hmm_", sb.ptr)
+    assert np.array_equal(one, probs, equal_nan=True) and np.array_equal(s1, seeds) and (seeds >= 0).sum() > 10
+
+
+def test_debug_primitives(hmm):
+    """Three arguments each."""
+    x = np.array([-1.5, 0.25, 3.0]); y = np.zeros(3)
+    with balanced(hmm, "hipstr_debug_cr_math"):
+        assert hmm.hipstr_debug_cr_math(0, x.ctypes.data_as(capi._f64p), y.ctypes.data_as(capi._f64p), 3) == 0, hmm.hipstr_last_error().decode()
+    assert np.allclose(y, np.exp(x), rtol=1e-12, atol=0)
+    with balanced(hmm, "hipstr_debug_float_fn"):
+        got = capi.float_fn(hmm, "hipstr_debug_float_fn", "fastexp", 0x3f800000, 3)
+    assert np.array_equal(got, capi.float_fn(hmm, "hipstr_debug_float_fn_host", "fastexp", 0x3f800000, 3))
+    a = np.array([-1.0, -20.0, -3.0]); b = np.array([-2.0, -1.0, -3.0])
+    with balanced(hmm, "hipstr_debug_fast_lse2"):
+        got = capi.fast_lse2(hmm, "hipstr_debug_fast_lse2", a, b)
+    assert np.array_equal(got, capi.fast_lse2(hmm, "hipstr_debug_fast_lse2_host", a, b))
+    rows = [np.array([-1.0]), np.array([-2.0, -1.0, -30.0]), np.array([-3.0, -3.0])]
+    with balanced(hmm, "hipstr_debug_fast_lse_vec"):
+        got = capi.fast_lse_vec(hmm, "hipstr_debug_fast_lse_vec", rows)
+    assert np.array_equal(got, capi.fast_lse_vec(hmm, "hipstr_debug_fast_lse_vec_host", rows))
+
+
 def test_post_assign(hmm):
     """Two loci, three samples, eleven reads in six pools: the request list has three entries."""
-    row = lambda A, h: [(-1.0 if k == h else -30.0) - 0.01 * k for k in range(A)]
-    pb, _ = ta.make_pb([(3, [[(-0.5, -0.5, row(3, 0))] * 3, [(-0.2, -0.9, row(3, 2))] * 2]), (2, [[(-0.5, -0.5, row(2, 1))] * 6])])
+    pb = small_pb()
     n = int(pb.a["read_off"][-1]); ns = int(pb.samp_off[-1])
     seed = np.full(n, 3, np.int32); seed[1] = -1
     pool = np.array([0, 1, 0, 1, 2] + [0, 1, 2, 0, 1, 2], np.int32); pool_off = np.array([0, 3, 6], np.int32)
