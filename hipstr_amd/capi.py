@@ -452,6 +452,157 @@ def run_census(lib, pd_or_pb, bptr, seed, read_req, req_read, trace, hap_to_alle
     return out
 
 
+# ---- the allele-set update between two rounds (hipstr_alleles_apply / _step): the constants are include/hipstr_hmm.h's HIPSTR_PHASE_* / HIPSTR_ALLELES_*
+PHASE_ADD, PHASE_UNCALLED, PHASE_UNSPANNED, PHASE_DONE, PHASE_ABORTED = range(5)
+ALLELES_ON_HOST = 1
+
+
+class HipstrAllelesRequest(C.Structure):
+    _fields_ = [("pooled", C.POINTER(HipstrBatch)), ("locus_on", _u8p), ("keep", _u8p), ("keep_blocks", C.c_uint32), ("add_off", _i32p),
+                ("add_seq_off", _i32p), ("add_seq", C.c_char_p)]
+
+
+class HipstrAllelesStepOut(C.Structure):
+    _fields_ = [("status", _i32p), ("n_added", _i32p), ("n_removed", _i32p), ("n_affected_blocks", _i32p), ("any_added", C.c_int32)]
+
+
+def _alleles_sigs(lib):
+    _sig(lib.hipstr_alleles_apply, C.c_void_p, [C.POINTER(HipstrAllelesRequest)])
+    _sig(lib.hipstr_alleles_apply_host, C.c_void_p, [C.POINTER(HipstrAllelesRequest)])
+    _sig(lib.hipstr_alleles_step, C.c_void_p, [C.POINTER(HipstrBatch), C.POINTER(HipstrCensusOut), _i32p, C.c_int32, C.c_uint32, C.POINTER(HipstrAllelesStepOut)])
+    for nm in ("hipstr_alleles_batch", "hipstr_alleles_batch_all"):
+        _sig(getattr(lib, nm), C.POINTER(HipstrBatch), [C.c_void_p])
+    _sig(lib.hipstr_alleles_mapping, _i32p, [C.c_void_p]); _sig(lib.hipstr_alleles_new_n_alleles, _i32p, [C.c_void_p])
+    _sig(lib.hipstr_alleles_hap_to_allele, _i32p, [C.c_void_p, C.c_int]); _sig(lib.hipstr_alleles_added, _u8p, [C.c_void_p])
+    _sig(lib.hipstr_alleles_free, None, [C.c_void_p])
+    _sig(lib.hipstr_debug_alleles_hash_bits, C.c_int, [C.c_int])
+    for nm, typ in (("hipstr_debug_alleles_last", C.c_int64), ("hipstr_debug_alleles_last_timing", C.c_double), ("hipstr_debug_alleles_limits", C.c_int64)):
+        _sig(getattr(lib, nm), C.c_int, [C.POINTER(typ)])
+    _sig(lib.hipstr_last_error, C.c_char_p, [])
+
+
+def _batch_ptr(bptr):
+    return C.cast(bptr, C.POINTER(HipstrBatch)) if not hasattr(bptr, "_obj") else C.pointer(bptr._obj)
+
+
+class Alleles:
+    """A hipstr_alleles_t: its arrays copied into numpy (mapping, new_n_alleles, h2a[3], added, realign_hap, blk_nopts, opt_off, seq, hap_off),
+    .ptr / .ptr_all the two batches for the calls that follow (valid until free(); the pooled batch it came from must outlive it)."""
+
+    def __init__(self, lib, h, old_bptr, keepalive):
+        self.lib, self.h, self._keep = lib, h, (old_bptr, keepalive)
+        old = old_bptr.contents
+        nl = int(old.n_loci)
+        self.ptr, self.ptr_all = lib.hipstr_alleles_batch(h), lib.hipstr_alleles_batch_all(h)
+        nb = self.ptr.contents
+        arr = lambda p, n, dt: (np.ctypeslib.as_array(p, shape=(n,)).astype(dt) if n else np.zeros(0, dt))
+        old_A = int(old.hap_off[nl]) if nl else 0
+        self.hap_off = arr(nb.hap_off, nl + 1, np.int32) if nl else np.zeros(1, np.int32)
+        new_A = int(self.hap_off[-1])
+        self.blk_nopts = arr(nb.blk_nopts, 3 * nl, np.int32)
+        n_opts = int(self.blk_nopts.sum())
+        self.opt_off = arr(nb.opt_off, n_opts + 1, np.int32) if nl else np.zeros(1, np.int32)
+        self.seq = C.string_at(nb.seq, int(self.opt_off[-1])) if nl else b""
+        self.realign_hap = arr(nb.realign_hap, new_A, np.uint8)
+        self.all_mask_is_null = not bool(self.ptr_all.contents.realign_hap)
+        self.mapping = arr(lib.hipstr_alleles_mapping(h), old_A, np.int32)
+        self.new_n_alleles = arr(lib.hipstr_alleles_new_n_alleles(h), nl, np.int32)
+        self.h2a = [arr(lib.hipstr_alleles_hap_to_allele(h, k), new_A, np.int32) for k in range(3)]
+        self.added = arr(lib.hipstr_alleles_added(h), nl, np.uint8)
+
+    def options(self):
+        """per locus the three blocks' option strings (bytes)"""
+        out = []; o = 0
+        for l in range(len(self.new_n_alleles)):
+            blocks = []
+            for k in range(3):
+                n = int(self.blk_nopts[3 * l + k])
+                blocks.append([self.seq[self.opt_off[o + i]:self.opt_off[o + i + 1]] for i in range(n)]); o += n
+            out.append(blocks)
+        return out
+
+    def arrays(self):
+        """every output array, for comparisons between the two forms"""
+        return dict(hap_off=self.hap_off, blk_nopts=self.blk_nopts, opt_off=self.opt_off, seq=np.frombuffer(self.seq, np.uint8), realign_hap=self.realign_hap,
+                    mapping=self.mapping, new_n_alleles=self.new_n_alleles, h2a0=self.h2a[0], h2a1=self.h2a[1], h2a2=self.h2a[2], added=self.added)
+
+    def free(self):
+        if self.h:
+            self.lib.hipstr_alleles_free(self.h); self.h = None; self.ptr = self.ptr_all = None
+
+    def __del__(self):
+        self.free()
+
+
+def alleles_last(lib):
+    """hipstr_debug_alleles_last as a dict"""
+    _alleles_sigs(lib)
+    v = (C.c_int64 * 8)()
+    assert lib.hipstr_debug_alleles_last(v) == 0
+    return dict(device_loci=int(v[0]), host_loci=int(v[1]), probes=int(v[2]), compares=int(v[3]), identity_loci=int(v[4]), chunks=int(v[5]))
+
+
+def alleles_limits(lib):
+    _alleles_sigs(lib)
+    v = (C.c_int64 * 4)()
+    assert lib.hipstr_debug_alleles_limits(v) == 0
+    return dict(threads=int(v[0]), max_haps=int(v[1]), max_opts=int(v[2]), slots=int(v[3]))
+
+
+def run_alleles_apply(lib, bptr, locus_on=None, keep=None, keep_blocks=7, add=None, host=False, raw=None):
+    """hipstr_alleles_apply (host=True: _apply_host) -> Alleles.  bptr: the pooled batch (Batch.ptr).  keep: uint8 per old option or None;
+    add: per locus three lists of bytes, or None.  raw: dict(add_off, add_seq_off, add_seq) handed over as given instead of `add` (the
+    refusals' tests).  Raises RuntimeError with hipstr_last_error() on a refusal."""
+    _alleles_sigs(lib)
+    bp = _batch_ptr(bptr)
+    nl = int(bp.contents.n_loci)
+    u8 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.uint8))
+    k = dict(locus_on=u8(locus_on), keep=u8(keep))
+    if raw is not None:
+        k["add_off"], k["add_seq_off"], k["add_seq"] = np.ascontiguousarray(raw["add_off"], np.int32), np.ascontiguousarray(raw["add_seq_off"], np.int32), raw["add_seq"] + b"\0"
+    elif add is not None:
+        assert len(add) == nl
+        flat = [s for L in add for blk in L for s in blk]
+        k["add_off"] = np.concatenate([[0], np.cumsum([len(blk) for L in add for blk in L])]).astype(np.int32)
+        k["add_seq_off"] = np.concatenate([[0], np.cumsum([len(s) for s in flat])]).astype(np.int32)
+        k["add_seq"] = b"".join(flat) + b"\0"
+    rq = HipstrAllelesRequest(bp, _ptr(k["locus_on"], _u8p), _ptr(k["keep"], _u8p), int(keep_blocks), _ptr(k.get("add_off"), _i32p),
+                              _ptr(k.get("add_seq_off"), _i32p), k.get("add_seq"))
+    h = (lib.hipstr_alleles_apply_host if host else lib.hipstr_alleles_apply)(C.byref(rq))
+    if not h:
+        raise RuntimeError("hipstr_alleles_apply%s failed: %s" % ("_host" if host else "", lib.hipstr_last_error().decode()))
+    return Alleles(lib, h, bp, (bptr, k, rq))
+
+
+def run_alleles_step(lib, bptr, census, phase, max_total_haplotypes=0, host=False):
+    """hipstr_alleles_step -> Alleles with .status, .n_added, .n_removed, .n_affected_blocks (int32 per locus) and .any_added.  census:
+    run_census's dict (cand, new_n_haps, called, spanned are read).  phase: int32 array, updated in place unless the call is refused."""
+    _alleles_sigs(lib)
+    bp = _batch_ptr(bptr)
+    nl = int(bp.contents.n_loci)
+    assert isinstance(phase, np.ndarray) and phase.dtype == np.int32 and len(phase) == nl
+    flat = [s for L in census["cand"] for s in L]
+    k = dict(cand_off=np.concatenate([[0], np.cumsum([len(L) for L in census["cand"]])]).astype(np.int32),
+             cand_seq_off=np.concatenate([[0], np.cumsum([len(s) for s in flat])]).astype(np.int32), cand_seq=b"".join(flat) + b"\0",
+             new_n_haps=np.ascontiguousarray(np.asarray(census["new_n_haps"], np.int64)).reshape(-1),
+             called=np.ascontiguousarray(np.asarray(census["called"], np.uint8)), spanned=np.ascontiguousarray(np.asarray(census["spanned"], np.uint8)))
+    cen = HipstrCensusOut()
+    cen.cand_off = _ptr(k["cand_off"], _i32p); cen.cand_seq_off = _ptr(k["cand_seq_off"], _i32p); cen.cand_seq = k["cand_seq"]
+    cen.new_n_haps = k["new_n_haps"].ctypes.data_as(C.POINTER(C.c_int64)) if nl else None
+    cen.called = _ptr(k["called"], _u8p); cen.spanned = _ptr(k["spanned"], _u8p)
+    o = dict((nm, np.full(max(nl, 1), UNTOUCHED, np.int32)) for nm in ("status", "n_added", "n_removed", "n_affected_blocks"))
+    so = HipstrAllelesStepOut(*[o[nm].ctypes.data_as(_i32p) for nm in ("status", "n_added", "n_removed", "n_affected_blocks")], -1)
+    h = lib.hipstr_alleles_step(bp, C.byref(cen), phase.ctypes.data_as(_i32p), int(max_total_haplotypes), ALLELES_ON_HOST if host else 0, C.byref(so))
+    if not h:
+        e = RuntimeError("hipstr_alleles_step failed: %s" % lib.hipstr_last_error().decode())
+        e.outputs = dict(o, any_added=int(so.any_added))
+        raise e
+    a = Alleles(lib, h, bp, (bptr, k, cen))
+    a.status, a.n_added, a.n_removed, a.n_affected_blocks = [o[nm][:nl] for nm in ("status", "n_added", "n_removed", "n_affected_blocks")]
+    a.any_added = int(so.any_added)
+    return a
+
+
 # ---- the resident traceback result (hipstr_hmm_trace_resident, hipstr_trace_dev_*): the constants are include/hipstr_hmm.h's HIPSTR_TRACE_F_*
 TRACE_F_SCALARS, TRACE_F_HAP_ALN, TRACE_F_STR_SEQ, TRACE_F_FLANKS, TRACE_F_INDELS, TRACE_F_SNPS, TRACE_F_STITCH, TRACE_F_ALL = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x7f
 # the arrays of every group: (name, kind, pool) — kind "f8" / "i4" per request, "off" an offset array, "i4p" / "chr" a pool array of pool `pool`
@@ -504,6 +655,7 @@ class TraceDev:
 def run_trace_resident(lib, bptr, req_read, req_allele, hap_to_ref=None, req_seed=None, flags=0):
     """hipstr_hmm_trace_resident -> TraceDev.  Raises with hipstr_last_error() when the call fails (the handle it left must then be NULL)."""
     _trace_dev_sigs(lib)
+    _alleles_sigs(lib)
     rr = np.ascontiguousarray(np.asarray(req_read, np.int32)); aa = np.ascontiguousarray(np.asarray(req_allele, np.int32))
     ss = None if req_seed is None else np.ascontiguousarray(np.asarray(req_seed, np.int32))
     h2r = None if hap_to_ref is None else (C.c_char_p * len(hap_to_ref))(*hap_to_ref)

@@ -616,7 +616,8 @@ int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read
  *   mathops.cpp:10) best = v1 > v2 ? hap_a : hap_b (:280-284 — a third tie rule, neither HIPSTR_ASSIGN_VCF's nor HIPSTR_ASSIGN_RETRACE's);
  *   spanned[hap_to_allele[1][best]] = 1.  Reads of a sample without a MAP pair mark nothing.
  * called / spanned are zeroed by the call for the blocks it writes and left untouched for blocks whose hap_to_allele is NULL; the caller applies
- * allele_index >= 1 and the check_* choice of :305-311.  Building the new Haplotype and allele_mapping from the candidates stays with the caller.
+ * allele_index >= 1 and the check_* choice of :305-311, or hands the census to hipstr_alleles_step, which builds the new Haplotype and allele_mapping;
+ * copy_read and the re-keying of the trace cache through allele_mapping (:401-409) stay with the caller.
  * Refused (non-zero, hipstr_last_error(); checked on the host before any launch, nothing is written): a run that was not launched, pooled->n_loci
  * that differs from the run's, hap_off that disagrees with the run's allele counts, read_req outside [-1, n_req), a read whose request belongs to
  * another locus, requests not grouped by locus in locus order (hipstr_post_assign emits them so), str_seq_off that decreases, a hap_to_allele
@@ -986,6 +987,85 @@ const hipstr_batch_t*  hipstr_hapgen_batch_batch(const hipstr_hapgen_batch_t* h)
 const int32_t*         hipstr_hapgen_batch_locus(const hipstr_hapgen_batch_t* h);
 const int32_t*         hipstr_hapgen_batch_status(const hipstr_hapgen_batch_t* h);
 void hipstr_hapgen_batch_free(hipstr_hapgen_batch_t* h);
+
+/*
+ * The allele-set update between two rounds of SeqStutterGenotyper::genotype for a batch of loci: the body of add_and_remove_alleles
+ * (seq_stutter_genotyper.cpp:330-369) — the new blocks, the new Haplotype's strings, allele_mapping and realign_to_haplotype — without the
+ * matrix, the alignment or the trace cache.  What comes out feeds hipstr_rm_remap (allele_mapping, new_n_alleles), hipstr_hmm_upload
+ * (_batch), hipstr_hmm_trace_* / hipstr_post_census* / the next update (_batch_all, hap_to_allele).
+ * Per locus that is on: every block keeps its options whose keep flag is set, in their order (HapBlock::remove_alleles, HapBlock.h:138-147),
+ *   for the blocks keep_blocks names (bit b = block b); the strings of add_off's (locus, block) run go behind them in the order given
+ *   (add_alternate, :345-350) — a string the block already holds is added again, the empty string is a legal option.
+ * Haplotypes are enumerated as Haplotype::next visits them (Haplotype.cpp:157-196: a reflected mixed-radix Gray code, block 0 fastest);
+ *   a haplotype IS the bytes of its three options concatenated: two different option triples with equal bytes are one key (:331-336).
+ * allele_mapping[old k] = the LAST new haplotype with old k's bytes, where old k is the LAST old haplotype with those bytes; -1 for every
+ *   other old haplotype (:335, :365).  realign_hap[new j] = 0 iff some old haplotype has j's bytes — also when j's options are new (an
+ *   added string equal to a removed or a present one) — else 1 (:361-364).  hap_to_allele(b)[new j] = j's option in block b (:219-227).
+ * added[l] = 1 iff a string was added to locus l (:344-350, the condition of :397-398).
+ * A locus that is off (locus_on[l] == 0) takes the identity whatever its strings: blocks copied, allele_mapping[k] = k, realign_hap 0,
+ *   added 0; keep and add_off are not read for it (its add_off runs must still be there, and may be empty).
+ * :369 (the first haplotype keeps its bytes) holds by construction: option 0 of every block is kept.
+ * hipstr_alleles_apply works on the device, one workgroup per locus (alleles.hip): the host computes counts and offsets only, the device
+ *   gathers the new strings, hashes every option once (64-bit polynomial; a haplotype's hash follows from its three options'), puts the old
+ *   haplotypes into an LDS table and looks the new ones up; the hash only filters — equality is always decided on the bytes.  A locus of more
+ *   than 1024 haplotypes or 1024 options (before or after) takes the host code inside the same call.  hipstr_alleles_apply_host is that host
+ *   code for the whole batch; it needs no device.  Both give identical bytes in every output.  Device and pinned blocks come from the
+ *   context's caches: no allocation in steady state.
+ * Refused (NULL + hipstr_last_error(); checked on the host before any launch): NULL arguments, a block without options, opt_off / hap_off /
+ *   add_off / add_seq_off that decrease or do not start at 0, hap_off that is not the prefix sum of num_combs, a keep that drops option 0 of a
+ *   block it applies to in a locus that is on, a new num_combs (or the batch's sum) above INT32_MAX, more than INT32_MAX new sequence bytes.
+ * The result owns its arrays; the read-side pointers of its batches are borrowed from rq->pooled, which must outlive it.
+ */
+typedef struct hipstr_alleles_request {
+  const hipstr_batch_t* pooled;   /* the round's pooled batch: the haplotype side is read, the read side passed on */
+  const uint8_t* locus_on;        /* [n_loci], or NULL = every locus */
+  const uint8_t* keep;            /* [n_opts] opt_off's enumeration (hipstr_census_out_t::called / spanned), or NULL = keep everything */
+  uint32_t       keep_blocks;     /* bit b: keep applies to block b */
+  const int32_t* add_off;         /* [3*n_loci+1] strings to add per (locus, block), or NULL = none */
+  const int32_t* add_seq_off;     /* [add_off[3*n_loci]+1] */
+  const char*    add_seq;
+} hipstr_alleles_request_t;
+typedef struct hipstr_alleles hipstr_alleles_t;
+hipstr_alleles_t* hipstr_alleles_apply(const hipstr_alleles_request_t* rq);        /* on the device */
+hipstr_alleles_t* hipstr_alleles_apply_host(const hipstr_alleles_request_t* rq);   /* host only, no device needed */
+const hipstr_batch_t* hipstr_alleles_batch(const hipstr_alleles_t* a);             /* blk_nopts, opt_off, seq, hap_off rebuilt; realign_hap the new mask */
+const hipstr_batch_t* hipstr_alleles_batch_all(const hipstr_alleles_t* a);         /* the same with realign_hap = NULL */
+const int32_t* hipstr_alleles_mapping(const hipstr_alleles_t* a);                  /* [sum old A] allele_mapping */
+const int32_t* hipstr_alleles_new_n_alleles(const hipstr_alleles_t* a);            /* [n_loci] */
+const int32_t* hipstr_alleles_hap_to_allele(const hipstr_alleles_t* a, int block); /* [sum new A]; NULL for a block outside 0..2 */
+const uint8_t* hipstr_alleles_added(const hipstr_alleles_t* a);                    /* [n_loci] */
+void hipstr_alleles_free(hipstr_alleles_t* a);
+
+/*
+ * What genotype() does with one census (seq_stutter_genotyper.cpp:570-601, :647-663), driving the update above: per locus, by phase[l],
+ *   ADD with candidates (census->cand_off): new_n_haps > max_total_haplotypes -> phase ABORTED, the identity, status 1 (:591-595: the locus
+ *     genotype() returns false for); else the candidates — already in orderByLengthAndSequence order — are added to block 1, the phase stays.
+ *   ADD without candidates falls through to UNCALLED: in every block of more than one option the options >= 1 whose census->called is 0 are
+ *     dropped (:255, :305-311); if any was, the phase becomes UNSPANNED and the locus is done for this call; else it falls through to
+ *   UNSPANNED: block 1's options >= 1 whose census->spanned is 0 are dropped, the phase becomes DONE.
+ *   DONE / ABORTED: the identity.  A locus nothing is added to or dropped from takes the identity too.
+ * phase is read and written; max_total_haplotypes 0 = the reference's 1000; flags: HIPSTR_ALLELES_ON_HOST uses hipstr_alleles_apply_host,
+ * 0 the device.  out (caller's arrays, [n_loci] each): status (0, or 1 for a locus that aborted in this call), n_added, n_removed and
+ * n_affected_blocks (the numbers of the log lines :592 ff., :651, :660), any_added (whether to upload, align and scatter this round).
+ * Refused (NULL + hipstr_last_error(), phase and out untouched): what hipstr_alleles_apply refuses, a phase outside 0..4, cand_off that
+ * decreases, and a locus that reaches UNSPANNED with a flank block of more than one option (the census writes `spanned` for block 1 only).
+ * copy_read and the re-keying of the trace cache through allele_mapping (:401-409) stay with the caller.
+ */
+#define HIPSTR_PHASE_ADD       0
+#define HIPSTR_PHASE_UNCALLED  1
+#define HIPSTR_PHASE_UNSPANNED 2
+#define HIPSTR_PHASE_DONE      3
+#define HIPSTR_PHASE_ABORTED   4
+#define HIPSTR_ALLELES_ON_HOST 1u
+typedef struct hipstr_alleles_step_out {
+  int32_t* status;             /* [n_loci] */
+  int32_t* n_added;            /* [n_loci] */
+  int32_t* n_removed;          /* [n_loci] */
+  int32_t* n_affected_blocks;  /* [n_loci] */
+  int32_t  any_added;
+} hipstr_alleles_step_out_t;
+hipstr_alleles_t* hipstr_alleles_step(const hipstr_batch_t* pooled, const hipstr_census_out_t* census, int32_t* phase /* [n_loci] */,
+                                      int32_t max_total_haplotypes, uint32_t flags, hipstr_alleles_step_out_t* out);
 
 /* The diagnostics entry points (hipstr_debug_*: what the tests, the fuzzers and bench.py look inside the library with) are declared in
  * hipstr_hmm_debug.h — not part of the drop-in ABI; a build with -DHIPSTR_NO_DEBUG_ABI leaves them out of the library. */

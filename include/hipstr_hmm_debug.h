@@ -157,6 +157,19 @@ int hipstr_debug_hapgen_plan(const hipstr_batch_t* reads, const hipstr_hapgen_re
  * tests/test_hapgen_gpu.py and tools/hapgen_timing.py. */
 int hipstr_debug_hapgen_last(int64_t out[8]);
 int hipstr_debug_hapgen_last_timing(double out[4]);
+/* Diagnostics of hipstr_alleles_apply / _apply_host / _step.  hipstr_debug_alleles_hash_bits(bits): both forms keep that many low bits of
+ * a haplotype's hash from now on (process-wide; 0 = all 64): unequal strings share hashes at test sizes, which the byte comparison must
+ * tell apart.  hipstr_debug_alleles_last: the calling thread's last call: out[0] loci done on the device, out[1] loci done by the host code
+ * (all of them for the host form; for the device form the loci beyond a limit of hipstr_amd/csrc/alleles_layout.h), out[2] table probes,
+ * out[3] byte comparisons of two haplotypes, out[4] loci that took the identity, out[5] chunks, out[6..7] 0.  _last_timing: out[0]
+ * milliseconds between HIP events around the call's kernels (0 unless HIPSTR_ALLELES_TIMING is set), out[1] bytes sent to the device,
+ * out[2] bytes copied back, out[3] 0.  _limits: out[0] threads of the workgroup, out[1] most haplotypes and out[2] most options of a locus
+ * the device takes, out[3] table slots.  A refused call leaves the numbers of the call before it; one that failed on the way leaves zeros.
+ * Used by tests/test_alleles_*.py and tools/alleles_timing.py. */
+int hipstr_debug_alleles_hash_bits(int bits);
+int hipstr_debug_alleles_last(int64_t out[8]);
+int hipstr_debug_alleles_last_timing(double out[4]);
+int hipstr_debug_alleles_limits(int64_t out[4]);
 
 /* Diagnostics (host only): the decisions hipstr_em_train_dev takes (hipstr_amd/csrc/em_input_layout.h) for a batch of n_runs (locus, sample)
  * runs whose run in question has run_reads reads, and for a locus whose sizes (ref_allele included) lie in [lo, hi] and are n_sizes many:

@@ -44,7 +44,9 @@
 #undef protected
 #include "debruijn_graph.h"
 #include "SeqAlignment/AlignmentModel.h"
+#include "SeqAlignment/Haplotype.h"
 #include "SeqAlignment/HaplotypeGenerator.h"
+#include "SeqAlignment/RepeatBlock.h"
 #include "SeqAlignment/NeedlemanWunsch.h"
 #include "mathops.h"
 #include "null_ostream.h"
@@ -442,10 +444,83 @@ static int run_hapgen_cases(const char* in_path, FILE* out, int time_reps){
   return 0;
 }
 
+// [--allele-cases IN --out OUT] the reference's own HapBlock / RepeatBlock / Haplotype driven as add_and_remove_alleles drives them
+// (seq_stutter_genotyper.cpp:330-368) on cases read from a text file (tests/golden/make_golden_alleles.py writes the file from
+// tests/alleles_cases.py and stores the records as tests/golden/alleles_*.npz):
+//   case NAME PERIOD / 3 x "block B START END N SEQ..." / 3 x "remove B N INDEX..." / 3 x "add B N SEQ..."   ("-" = the empty string)
+// Written: "case NAME", "old N" and N lines "hap SEQ" in reset() / next() order, the three new blocks as "block B START END N SEQ...",
+// "new N" and N lines "hap SEQ" in visit order.  Data only.
+static int run_allele_cases(const char* in_path, FILE* out){
+  std::ifstream in(in_path);
+  if (!in){ perror(in_path); return 2; }
+  auto seq = [](const std::string& s){ return s == "-" ? std::string() : s; };
+  auto show = [](const std::string& s){ return s.empty() ? "-" : s.c_str(); };
+  std::string line;
+  while (std::getline(in, line)){
+    if (line.empty()) continue;
+    std::istringstream hd(line);
+    std::string word, name; int period = 0;
+    hd >> word >> name >> period;
+    if (word != "case" || !hd){ fprintf(stderr, "bad case line: %s\n", line.c_str()); return 2; }
+    StutterModel model(0.9, 0.05, 0.05, 0.7, 0.005, 0.005, period);
+    std::vector<HapBlock*> blocks;
+    for (int b = 0; b < 3; b++){
+      std::getline(in, line);
+      std::istringstream ls(line);
+      int idx = 0, start = 0, end = 0, n = 0; std::string s;
+      ls >> word >> idx >> start >> end >> n;
+      if (word != "block" || idx != b || !ls || n < 1){ fprintf(stderr, "bad block line: %s\n", line.c_str()); return 2; }
+      ls >> s;
+      HapBlock* blk = b == 1 ? new RepeatBlock(start, end, seq(s), period, &model) : new HapBlock(start, end, seq(s));
+      for (int o = 1; o < n; o++){ ls >> s; blk->add_alternate(seq(s)); }
+      blocks.push_back(blk);
+    }
+    std::vector< std::vector<int> > alleles_to_remove(3);
+    std::vector< std::vector<std::string> > alleles_to_add(3);
+    for (int b = 0; b < 3; b++){
+      std::getline(in, line);
+      std::istringstream ls(line);
+      int idx = 0, n = 0;
+      ls >> word >> idx >> n;
+      if (word != "remove" || idx != b || !ls){ fprintf(stderr, "bad remove line: %s\n", line.c_str()); return 2; }
+      for (int i = 0; i < n; i++){ int o = 0; ls >> o; alleles_to_remove[b].push_back(o); }
+    }
+    for (int b = 0; b < 3; b++){
+      std::getline(in, line);
+      std::istringstream ls(line);
+      int idx = 0, n = 0; std::string s;
+      ls >> word >> idx >> n;
+      if (word != "add" || idx != b || !ls){ fprintf(stderr, "bad add line: %s\n", line.c_str()); return 2; }
+      for (int i = 0; i < n; i++){ ls >> s; alleles_to_add[b].push_back(seq(s)); }
+    }
+    fprintf(out, "case %s\n", name.c_str());
+    Haplotype* haplotype = new Haplotype(blocks);
+    haplotype->reset();                                                                                            // :330-337
+    fprintf(out, "old %d\n", haplotype->num_combs());
+    do { fprintf(out, "hap %s\n", show(haplotype->get_seq())); } while (haplotype->next());
+    haplotype->reset();
+    std::vector<HapBlock*> updated_blocks;                                                                         // :340-350
+    for (size_t i = 0; i < blocks.size(); i++) updated_blocks.push_back(blocks[i]->remove_alleles(alleles_to_remove[i]));
+    for (size_t i = 0; i < updated_blocks.size(); i++)
+      for (size_t j = 0; j < alleles_to_add[i].size(); j++) updated_blocks[i]->add_alternate(alleles_to_add[i][j]);
+    for (size_t b = 0; b < updated_blocks.size(); b++){
+      fprintf(out, "block %zu %d %d %d", b, updated_blocks[b]->start(), updated_blocks[b]->end(), updated_blocks[b]->num_options());
+      for (int o = 0; o < updated_blocks[b]->num_options(); o++) fprintf(out, " %s", show(updated_blocks[b]->get_seq(o)));
+      fprintf(out, "\n");
+    }
+    Haplotype* updated_haplotype = new Haplotype(updated_blocks);                                                  // :354-368
+    fprintf(out, "new %d\n", updated_haplotype->num_combs());
+    do { fprintf(out, "hap %s\n", show(updated_haplotype->get_seq())); } while (updated_haplotype->next());
+    delete haplotype; delete updated_haplotype;
+    for (size_t i = 0; i < blocks.size(); i++){ delete blocks[i]; delete updated_blocks[i]; }
+  }
+  return 0;
+}
+
 extern "C" int flow_main(int argc, char** argv){
   LocusParams lp; lp.seed = 1; lp.n_samples = 10; lp.reads_per_sample = 9; lp.period = 4; lp.recompute = false; lp.reassemble = true; lp.nw = false; lp.dump_inputs = NULL;
   const char* out_path = NULL; int n_loci = 0, n_threads = 1; bool use_stream = false, profile = false;
-  const char* debruijn_cases = NULL, *hapgen_cases = NULL; int time_reps = 0;
+  const char* debruijn_cases = NULL, *hapgen_cases = NULL, *allele_cases = NULL; int time_reps = 0;
   for (int i = 1; i < argc; i++){
     if (!strcmp(argv[i], "--seed")) lp.seed = strtoull(argv[++i], NULL, 10);
     else if (!strcmp(argv[i], "--samples")) lp.n_samples = atoi(argv[++i]);
@@ -461,6 +536,7 @@ extern "C" int flow_main(int argc, char** argv){
     else if (!strcmp(argv[i], "--profile")) profile = true;                 // many-loci form: where the host threads' time went (MI355X build: library and adapter buckets)
     else if (!strcmp(argv[i], "--debruijn-cases")) debruijn_cases = argv[++i];  // the reference's DebruijnGraph on cases of a text file (see run_debruijn_cases)
     else if (!strcmp(argv[i], "--hapgen-cases")) hapgen_cases = argv[++i];      // the reference's HaplotypeGenerator on cases of a text file (see run_hapgen_cases)
+    else if (!strcmp(argv[i], "--allele-cases")) allele_cases = argv[++i];      // the reference's HapBlock / Haplotype on cases of a text file (see run_allele_cases)
     else if (!strcmp(argv[i], "--time")) time_reps = atoi(argv[++i]);           // with --hapgen-cases: build every case that many times more and report the seconds
     else if (!strcmp(argv[i], "--stream")) use_stream = true;               // MI355X build: alignment rounds of the loci in flight share batches
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -476,6 +552,13 @@ extern "C" int flow_main(int argc, char** argv){
     FILE* f = out_path ? fopen(out_path, "w") : stdout;
     if (!f){ perror(out_path); return 2; }
     const int rc = run_hapgen_cases(hapgen_cases, f, time_reps);
+    if (out_path) fclose(f);
+    return rc;
+  }
+  if (allele_cases){
+    FILE* f = out_path ? fopen(out_path, "w") : stdout;
+    if (!f){ perror(out_path); return 2; }
+    const int rc = run_allele_cases(allele_cases, f);
     if (out_path) fclose(f);
     return rc;
   }
