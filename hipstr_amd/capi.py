@@ -69,7 +69,7 @@ def run_nw(lib, prefix, pairs, use_ref_end_penalty=False, unpack=True, timing=No
     o = HipstrNwOut(score.ctypes.data_as(C.POINTER(C.c_float)), ok.ctypes.data_as(_u8p), ao.ctypes.data_as(i64p), C.cast(ra, C.c_char_p),
                     C.cast(qa, C.c_char_p), co.ctypes.data_as(i64p), C.cast(cop, C.c_char_p), cl.ctypes.data_as(_i32p), cap, cap)
     fn = getattr(lib, prefix + "nw_align")
-    fn.restype = C.c_int; fn.argtypes = [C.POINTER(HipstrNwBatch), C.POINTER(HipstrNwOut)]
+    _sig(fn, C.c_int, [C.POINTER(HipstrNwBatch), C.POINTER(HipstrNwOut)])
     t0 = time.perf_counter()
     rc = fn(C.byref(nb), C.byref(o))
     if timing is not None:
@@ -125,7 +125,7 @@ def run_em(lib, prefix, period, n_samples, read_off, sample_label, num_bps, log_
                        a["log_p1"].ctypes.data_as(_f64p), a["log_p2"].ctypes.data_as(_f64p), ref_allele, max_iter, min_ll_abs_change, min_ll_frac_change)
     trained = np.zeros(max(nl, 1), np.uint8); st = np.zeros(max(6 * nl, 6)); it = np.zeros(max(nl, 1), np.int32); ll = np.zeros(max(nl, 1))
     fn = getattr(lib, prefix + "em_train")
-    fn.restype = C.c_int; fn.argtypes = [C.POINTER(HipstrEmBatch), _u8p, _f64p, _i32p, _f64p]
+    _sig(fn, C.c_int, [C.POINTER(HipstrEmBatch), _u8p, _f64p, _i32p, _f64p])
     rc = fn(C.byref(eb), trained.ctypes.data_as(_u8p), st.ctypes.data_as(_f64p), it.ctypes.data_as(_i32p), ll.ctypes.data_as(_f64p))
     if rc != 0:
         why = lib.hipstr_last_error().decode() if prefix == "hipstr_" else ""
@@ -163,9 +163,8 @@ def run_gt_extract(lib, prefix, pb, n_variants, hap_to_allele, calc_gls=True, ca
     k["gls"] = np.zeros(max(gl_off[-1], 1)); k["pls"] = np.zeros(max(gl_off[-1], 1), np.int32); k["phased_gls"] = np.zeros(max(pgl_off[-1], 1))
     o = HipstrGtOut(*[k[f].ctypes.data_as(t) for f, t in HipstrGtOut._fields_])
     if prefix == "hipstr_":
-        lib.hipstr_post_extract.restype = C.c_int; lib.hipstr_post_extract.argtypes = [C.c_void_p, C.POINTER(HipstrGtRequest), C.POINTER(HipstrGtOut)]
-        lib.hipstr_gt_offsets.restype = C.c_int
-        lib.hipstr_gt_offsets.argtypes = [C.POINTER(HipstrPostBatch), C.POINTER(HipstrGtRequest), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        _sig(lib.hipstr_post_extract, C.c_int, [C.c_void_p, C.POINTER(HipstrGtRequest), C.POINTER(HipstrGtOut)])
+        _sig(lib.hipstr_gt_offsets, C.c_int, [C.POINTER(HipstrPostBatch), C.POINTER(HipstrGtRequest), C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
         go = np.zeros(S + 1, np.int64); pgo = np.zeros(S + 1, np.int64)
         i64p = C.POINTER(C.c_int64)
         assert lib.hipstr_gt_offsets(pb.ptr, C.byref(rq), go.ctypes.data_as(i64p), pgo.ctypes.data_as(i64p)) == 0
@@ -183,7 +182,7 @@ def run_gt_extract(lib, prefix, pb, n_variants, hap_to_allele, calc_gls=True, ca
             raise RuntimeError("hipstr_post_extract failed: " + lib.hipstr_last_error().decode())
     else:
         fn = getattr(lib, prefix + "gt_extract")
-        fn.restype = C.c_int; fn.argtypes = [C.POINTER(HipstrPostBatch), C.POINTER(HipstrGtRequest), C.POINTER(HipstrGtOut)]
+        _sig(fn, C.c_int, [C.POINTER(HipstrPostBatch), C.POINTER(HipstrGtRequest), C.POINTER(HipstrGtOut)])
         rc = fn(pb.ptr, C.byref(rq), C.byref(o))
         if rc != 0:
             raise RuntimeError("%sgt_extract failed rc=%d" % (prefix, rc))
@@ -1318,20 +1317,20 @@ def run_trace(lib, prefix, bptr, req_read, req_allele, hap_to_ref=None, cap=1 <<
         ss = np.ascontiguousarray(np.asarray(req_seed, np.int32)); keep["req_seed"] = ss
         extra, extra_t = [ss.ctypes.data_as(_i32p)], [_i32p]
     if flags is not None:
-        fn.restype = C.c_int; fn.argtypes = [_BP, C.c_int32, _i32p, _i32p, _i32p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(HipstrTraceOut)]
+        _sig(fn, C.c_int, [_BP, C.c_int32, _i32p, _i32p, _i32p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(HipstrTraceOut)])
         rc = fn(bptr, n, rr.ctypes.data_as(_i32p), aa.ctypes.data_as(_i32p), extra[0] if extra else None, h2r, int(flags), C.byref(o))
     elif prefix == "ref_":
-        fn.restype = C.c_int; fn.argtypes = [_BP, C.c_int32, _i32p, _i32p] + extra_t + [C.POINTER(HipstrTraceOut)]
+        _sig(fn, C.c_int, [_BP, C.c_int32, _i32p, _i32p] + extra_t + [C.POINTER(HipstrTraceOut)])
         rc = fn(bptr, n, rr.ctypes.data_as(_i32p), aa.ctypes.data_as(_i32p), *(extra + [C.byref(o)]))
     else:
-        fn.restype = C.c_int; fn.argtypes = [_BP, C.c_int32, _i32p, _i32p] + extra_t + [C.POINTER(C.c_char_p), C.POINTER(HipstrTraceOut)]
+        _sig(fn, C.c_int, [_BP, C.c_int32, _i32p, _i32p] + extra_t + [C.POINTER(C.c_char_p), C.POINTER(HipstrTraceOut)])
         rc = fn(bptr, n, rr.ctypes.data_as(_i32p), aa.ctypes.data_as(_i32p), *(extra + [h2r, C.byref(o)]))
     if timing is not None:
         timing["call_s"] = timing.get("call_s", 0.0) + time.perf_counter() - t_call
     if rc != 0:
         why = ""
         if prefix == "hipstr_hmm_":
-            lib.hipstr_last_error.restype = C.c_char_p
+            _sig(lib.hipstr_last_error, C.c_char_p, [])
             why = ": " + lib.hipstr_last_error().decode()
         raise RuntimeError("%strace failed rc=%d%s" % (prefix, rc, why))
     if not unpack:
@@ -1376,13 +1375,13 @@ def hap_aln_info(lib, prefix, bptr, cap=1 << 22):
     b = bptr.contents if hasattr(bptr, "contents") else (bptr._obj if hasattr(bptr, "_obj") else bptr)
     n = int(np.ctypeslib.as_array(b.hap_off, shape=(b.n_loci + 1,))[-1])
     fn = getattr(lib, prefix + "hap_aln_info")
-    fn.restype = C.c_int; fn.argtypes = [_BP, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
+    _sig(fn, C.c_int, [_BP, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)])
     buf = C.create_string_buffer(cap); offs = np.zeros(n + 1, np.int64)
     rc = fn(bptr, buf, cap, offs.ctypes.data_as(C.POINTER(C.c_int64)))
     if rc != 0:
         why = ""
         if prefix == "hipstr_":
-            lib.hipstr_last_error.restype = C.c_char_p
+            _sig(lib.hipstr_last_error, C.c_char_p, [])
             why = ": " + lib.hipstr_last_error().decode()
         raise RuntimeError("%shap_aln_info failed rc=%d%s" % (prefix, rc, why))
     raw = buf.raw[:int(offs[n])]          # .raw copies the whole buffer: take it once
@@ -1518,8 +1517,15 @@ class PostBatch:
 
 # ----------------------------------------------------------------------------- loaders
 def _sig(fn, restype, argtypes):
-    fn.restype = restype
-    fn.argtypes = argtypes
+    """The signature of an entry point, written once.  The wrappers bind on use, so they come here before every call: a signature that is
+    already in place is left alone — ctypes converts the arguments of a call through fn's argtypes, and another host thread may be in
+    that call (tests/test_threads_gpu.py)."""
+    argtypes = tuple(argtypes)
+    have = fn.argtypes
+    if have is None or tuple(have) != argtypes:
+        fn.argtypes = argtypes
+    if fn.restype is not restype:
+        fn.restype = restype
 
 
 _BP = C.POINTER(HipstrBatch)
@@ -1804,7 +1810,7 @@ def _why(lib, prefix):
     """': <hipstr_last_error()>' for the MI355X library's entry points."""
     if not prefix.startswith("hipstr_"):
         return ""
-    lib.hipstr_last_error.restype = C.c_char_p
+    _sig(lib.hipstr_last_error, C.c_char_p, [])
     return ": " + lib.hipstr_last_error().decode()
 
 
@@ -1818,7 +1824,7 @@ def run_align(lib, prefix, bptr, fill=np.nan, seed_in=None):
     if seed_in is not None:
         si = np.ascontiguousarray(np.asarray(seed_in, np.int32))
         fn = getattr(lib, prefix + "process_reads_seeded")
-        fn.restype = C.c_int; fn.argtypes = [_BP, _i32p, _f64p, _i32p]
+        _sig(fn, C.c_int, [_BP, _i32p, _f64p, _i32p])
         rc = fn(bptr, si.ctypes.data_as(_i32p), probs.ctypes.data_as(_f64p), seeds.ctypes.data_as(_i32p))
         if rc != 0:
             raise RuntimeError("%sprocess_reads_seeded failed rc=%d%s" % (prefix, rc, _why(lib, prefix)))

@@ -54,6 +54,29 @@ def test_bytes_decide_when_hashes_collide(lib, batch):
     assert last["compares"] > n64 and last["host_loci"] == 0, (last, n64)
 
 
+@pytest.mark.parametrize("batch", ["unit", "edges"])
+def test_alleles_on_poisoned_cache_blocks(lib, batch):
+    """tests/test_poison_gpu.py's protocol (its docstring has this kernel's entry): the chunk's device block and its two pinned blocks are
+    recycled cache blocks filled with 0xFF, 0x7F, 0x80 and 0x00 — every output array identical under the four bytes, the first result
+    the reference's records, no block fresh from the driver.  `edges` has the loci the host code does inside the device call: their
+    pieces of the result never pass through a block."""
+    import test_poison_gpu as tp
+    lib.hipstr_hmm_trim()                                           # what the tests before left: a fill then costs milliseconds
+    cases, recs = chk.golden(batch)
+    held = []
+    def run():
+        held.append(chk.apply_cases(lib, cases, host=False))
+        return held[-1].arrays()
+    try:
+        tp.poisoned(lib, run, "alleles " + batch)
+        chk.check_golden(held[1], cases, recs)                      # (held[0] is the warm-up)
+        last = capi.alleles_last(lib)
+        assert last["chunks"] == 1 and last["host_loci"] == sum(c["name"] in OVER for c in cases), last
+    finally:
+        for a in held:
+            a.free()
+
+
 def test_refusals(lib):
     chk.refusals(lib, host=False)
 

@@ -31,6 +31,14 @@ nobody wrote would spin for ever under a poison byte):
   EM (em.hip): no kernel waits.  hs_em_units and em_locus() compare blockIdx with counts[0] / next_counts[0], written by hs_em_compact (one
     workgroup, `d.next_counts[0] = base_n`) in the launch before; the host sizes the grids from a pinned copy of the counts it waits for
     with an event (hipMemcpyAsync + hipEventRecord + hipEventQuery), and its loop is bounded by max_iter + 2 rounds.
+  hs_alleles_kernel (alleles.hip): the claim loop of step 2 (`prev = atomicCAS(&s_lead[s], -1, i)`, on to the next slot while the slot is
+    another key's) and the probe loop of step 3 (`L = s_lead[s]; if (L < 0) break;`, the mapping through `s_val[s]`)
+    walk s_lead[] / s_val[], the haplotype table in LDS, not global memory: `for (i = t; i < HS_ALLELES_SLOTS; i += AL_NT){ s_lead[i] = -1;
+    s_val[i] = -1; }` at the top of the kernel writes every slot first (s_map[] and s_cnt[] beside it), a __syncthreads() stands between
+    that and step 2 and another between step 2 and step 3.  Neither loop spins on a word: both count `probe < HS_ALLELES_SLOTS`, and the
+    table is at most half full (the static_assert under the kernel), so an empty slot ends them earlier.  What bounds the other loops —
+    nopts, l_ohap / l_nhap, o_off / n_off, n_src — are uploaded pieces: ChunkBlocks::upload copies them in front of the kernel on the same
+    stream.  No block of the cache is waited on (tests/test_alleles_gpu.py::test_alleles_on_poisoned_cache_blocks).
   trace.hip, nw.hip, post_kernels.hip: no loop waits on memory.  The walks over decision bytes (hs_trace_walk, trace_assemble_serial,
     hs_nw_walk's `while (row > 0 && type >= 0)`) move towards row / column 0 with every byte they read, whatever it holds.
 
