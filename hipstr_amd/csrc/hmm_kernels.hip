@@ -2504,8 +2504,8 @@ __device__ __forceinline__ void str_group_body_p(const hs_dev_t& d, int item_beg
   int aCol = lds0 + 8*xx;                              // + 8 oDl + q XC 8: del_probs_[q] of this column
   int aZ = lds0 + 8*(offg + g);                        // the 0.0 in front of this lane's read (rowP and match_probs_ alike)
   // this column's read-end deletion sums (hs_nd_kernel): row r of the side's block + the column's distance from the read end
+  // (a column farther than the largest deletion from the read end takes every start value from the tables: it reads the row's last slot)
   const double* const ndp = d.ws_nd + (side ? d.ws[ai].nd[1] : d.ws[ai].nd[0]) + min(rj, SIXP - 1);
-  const bool nd_lane = rj < SIXP;                      // (a column farther than the largest deletion from the read end takes every start value from the tables)
   // ---- what an allele needs that is the same for every lane comes from its record (layout.h HS_GRP_REC_DWORDS) by scalar loads: the header of
   // the NEXT allele while this one is evaluated (its table and block are requested one allele ahead), the constants when they are needed
   typedef int hs_i16v __attribute__((ext_vector_type(16)));
@@ -2639,69 +2639,104 @@ __device__ __forceinline__ void str_group_body_p(const hs_dev_t& d, int item_beg
       double lp0_max = 0.0;
       const int B8 = 8*B;
       const int aTab = uni(lds0 + 8*(oTab + par*2*HS_TAB_CAP));
-      // the column's read-end deletion sums for the six sizes, requested now (from L2: hs_nd_kernel wrote them) and used after the insertions
-      double ndv[HS_MAXREP];
-#pragma unroll
-      for (int q = 0; q < HS_MAXREP; q++) ndv[q] = 0.0;
-      if (nd_lane){
-        const double* pr = ndp + (int64_t)row_cur*SIXP;
-#pragma unroll
-        for (int q = 0; q < HS_MAXREP; q++) ndv[q] = pr[-q*SIXP];       // size q: row (size-0 row) - q
-      }
       // the lane's column constants, opaque from here on: otherwise every address below that does not depend on the allele is computed once
       // in front of the allele loop and kept — in more registers than there are (they went to scratch memory)
       asm volatile("" : "+v"(aM), "+v"(aCol), "+v"(aZ), "+v"(j8p8), "+v"(rj));
       // (lp0 + A[e]) + G[e], e = tab_base + [bound > 0] + max(bound - U0, 0), everything in bytes
       // the allele's constants, in two stages of scalar loads (the scalar registers do not hold all of them next to everything else): the
       // lists' table bases and shapes (record dwords 8..15), the table's smallest Bnd (56..57), pmf[6..12] | prior_ins (28..43) for the
-      // unchanged size and the insertions; then pmf[0..5] (16..27) | prior_del[6] (44..55) for the deletions
+      // unchanged size and the insertions; then, under the last insertion term, pmf[0..5] (16..27) | prior_del[6] (44..55) for the deletions
       hs_i16v cA; hs_i8v_ cS; hs_i2v_ cD;
       const uint64_t ra = rec_addr(i);
       asm volatile("s_load_dwordx16 %0, %3, 0x70\n\ts_load_dwordx8 %1, %3, 0x20\n\ts_load_dwordx2 %2, %3, 0xe0\n\ts_waitcnt lgkmcnt(0)"
                    : "=&s"(cA), "=&s"(cS), "=&s"(cD) : "s"(ra) : "memory");
       auto pmf_hi = [&](int t) -> double { return __hiloint2double(cA[2*(t - 6) + 1], cA[2*(t - 6)]); };      // t = 6..13, a constant once unrolled
       const double tab_bmin = __hiloint2double(cD[1], cD[0]);
-      auto tab_eval = [&](double lp0, int lim8, int k) -> double {
+      const double prior_ins = pmf_hi(13);
+      // The twelve stutter terms go through a pipeline of two: the five LDS values of term k + 1 (TermLd) are addressed and requested in the
+      // same stage as the additions of term k, so that the integer address work and the requests sit between the dependent FP64 additions
+      // and a term's LDS round trip is behind it when its turn comes.  One scheduling barrier per STAGE: the scheduler sees two terms and
+      // no more (given all 13 it requests every table value up front, in more registers than there are).  The values added and their
+      // order inside a term are those of StutterAlignerClass.cpp:59-150; lp0_max sees the terms in the same order as before.
+      struct TermLd { double a, b, A, G, rp; };
+      auto tab_ld = [&](TermLd& t, int lim8, int k){
         const int stk = cS[k];
         const int tb8 = aTab + 8*(stk >> 16), u8 = 8*(stk & 0xffff);
         const int e8 = (min(lim8, 8) + max(lim8 - u8, 0)) + tb8;
-        const double A = ldb(e8), Gv = ldb(e8 + 8*HS_TAB_CAP);
-        lp0_max = fmax(lp0_max, fabs(lp0));
-        return (lp0 + A) + Gv;
+        t.A = ldb(e8); t.G = ldb(e8 + 8*HS_TAB_CAP);
       };
-      {
-        const int len8 = min(B8, j8p8);
-        terms[HS_MAXREP] = (pmf_hi(HS_MAXREP) + ldb(8*oMt + aM)) + ldb(8*oRowP + aM - len8);
-      }
-      const double prior_ins = pmf_hi(13);
-#pragma unroll
-      for (int q = 0; q < HS_MAXREP; q++){                 // insertion of D = (q+1) P (StutterAlignerClass.cpp:59-104)
+      auto tab_sum = [&](const TermLd& t, double lp0) -> double {
+        lp0_max = fmax(lp0_max, fabs(lp0));
+        return (lp0 + t.A) + t.G;
+      };
+      auto ins_ld = [&](TermLd& t, int q){                  // insertion of D = (q+1) P (StutterAlignerClass.cpp:59-104)
         const int D8 = 8*(q+1)*P;
         const int len8 = min(B8 + D8, j8p8);
-        const double li = ldb(8*oDl + 8*q*XC + aCol);      // ins_probs_[q] of this column (table phase above)
+        t.a = ldb(8*oDl + 8*q*XC + aCol);                  // ins_probs_[q] of this column (table phase above)
         // match_probs_ of column j - D if the segment is longer than the insertion (StutterAlignerClass.cpp:66), else the 0.0 in front of the read
-        const double lp0 = (prior_ins + li) + ldb(8*oMt + max(aM - D8, aZ));
-        const int lim8 = min(max(j8p8 - D8, 0), B8);       // min(max(0, len - D), B)
-        const double S = tab_eval(lp0, lim8, HS_MAXREP);
-        terms[HS_MAXREP + 1 + q] = (pmf_hi(HS_MAXREP + 1 + q) + S) + ldb(8*oRowP + aM - len8);
-        __builtin_amdgcn_sched_barrier(0);                // one term at a time: the scheduler otherwise requests every table value of the 13 terms up front, in more registers than there are
-      }
+        t.b = ldb(8*oMt + max(aM - D8, aZ));
+        tab_ld(t, min(max(j8p8 - D8, 0), B8), HS_MAXREP);  // min(max(0, len - D), B)
+        t.rp = ldb(8*oRowP + aM - len8);
+      };
+      auto ins_add = [&](const TermLd& t, int q){
+        const double lp0 = (prior_ins + t.a) + t.b;
+        terms[HS_MAXREP + 1 + q] = (pmf_hi(HS_MAXREP + 1 + q) + tab_sum(t, lp0)) + t.rp;
+        // the term is formed HERE: left to itself the compiler keeps the stage's first two additions and sinks the other four of every
+        // insertion term to the terms' first use behind the deletions, with the table values of all six held until then (127 registers
+        // and the additions no longer between the next term's requests; 94 with the term pinned to its stage)
+        asm volatile("" : "+v"(terms[HS_MAXREP + 1 + q]));
+      };
+      // deletion of aD = (q+1) P (StutterAlignerClass.cpp:106-150).  The term before it asks ahead, so a size the block does not hold
+      // (q = nv) is requested too and nothing is added: its segment length is clamped at 0 and its list's record entry is shape 0xffff at the
+      // table's end (prep.cpp), so the addresses stay inside the carve
+      auto del_ld = [&](TermLd& t, int q){
+        const int aD = (q+1)*P;
+        const int len8 = min(max(B8 - 8*aD, 0), j8p8);
+        // column j + |D|: past the read end the values are another read's (or nothing's) and not used
+        t.a = ldb(8*oMt + 8*aD + aM); t.b = ldb(8*oDl + 8*q*XC + 8*aD + aCol);
+        tab_ld(t, len8, q);
+        t.rp = ldb(8*oRowP + aM - len8);
+      };
+      // the column's read-end deletion sum of size q (from L2: hs_nd_kernel wrote it), requested two terms ahead of its deletion term, so
+      // that three are held and not six: row (size-0 row) - q, the column's distance from the read end clamped to the row (ndp) — an address
+      // every lane may read, so no branch cuts a stage; only lanes with rj < (q+1) P use the value
+      const double* const ndr = ndp + (int64_t)row_cur*SIXP;
+      auto nd_ld = [&](int q) -> double { return ndr[-q*SIXP]; };
       hs_i8v_ cE, cP; hs_i4v_ cF, cQ;
-      asm volatile("s_load_dwordx8 %0, %4, 0x40\n\ts_load_dwordx4 %1, %4, 0x60\n\ts_load_dwordx8 %2, %4, 0xb0\n\ts_load_dwordx4 %3, %4, 0xd0\n\ts_waitcnt lgkmcnt(0)"
-                   : "=&s"(cP), "=&s"(cQ), "=&s"(cE), "=&s"(cF) : "s"(ra) : "memory");
       auto pmf_lo = [&](int t) -> double { return t < 4 ? __hiloint2double(cP[2*t + 1], cP[2*t]) : __hiloint2double(cQ[2*(t - 4) + 1], cQ[2*(t - 4)]); };   // t = 0..5
       auto pd_at = [&](int q) -> double { return q < 4 ? __hiloint2double(cE[2*q + 1], cE[2*q]) : __hiloint2double(cF[2*(q - 4) + 1], cF[2*(q - 4)]); };
+      auto del_add = [&](const TermLd& t, int q, double nd){
+        const double dv = pd_at(q) + (t.a - t.b);
+        const double lp0 = (rj >= (q+1)*P) ? dv : nd;      // the segment ends inside the read: from the tables; else the read-end sum
+        terms[HS_MAXREP - 1 - q] = (pmf_lo(HS_MAXREP - 1 - q) + tab_sum(t, lp0)) + t.rp;
+      };
+      TermLd tl[2];
+      double ndv[3];
+      {
+        const int len8 = min(B8, j8p8);
+        const double m0 = ldb(8*oMt + aM), r0 = ldb(8*oRowP + aM - len8);
+        ins_ld(tl[0], 0);
+        terms[HS_MAXREP] = (pmf_hi(HS_MAXREP) + m0) + r0;
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #pragma unroll
-      for (int q = 0; q < HS_MAXREP; q++){                 // deletion of aD = (q+1) P (StutterAlignerClass.cpp:106-150)
-        const int aD = (q+1)*P;
+      for (int q = 0; q < HS_MAXREP; q++){                 // stage: requests of insertion q + 1 (under the last: of the first deletion), additions of insertion q
+        if (q == HS_MAXREP - 1){
+          // (the wait drains this stage's neighbours' requests once per allele; the record's lines are in the scalar cache by now)
+          asm volatile("s_load_dwordx8 %0, %4, 0x40\n\ts_load_dwordx4 %1, %4, 0x60\n\ts_load_dwordx8 %2, %4, 0xb0\n\ts_load_dwordx4 %3, %4, 0xd0\n\ts_waitcnt lgkmcnt(0)"
+                       : "=&s"(cP), "=&s"(cQ), "=&s"(cE), "=&s"(cF) : "s"(ra) : "memory");
+        }
+        if (q + 1 < HS_MAXREP) ins_ld(tl[(q + 1) & 1], q + 1); else del_ld(tl[(q + 1) & 1], 0);
+        if (q + 2 >= HS_MAXREP) ndv[(q + 2 - HS_MAXREP) % 3] = nd_ld(q + 2 - HS_MAXREP);
+        ins_add(tl[q & 1], q);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int q = 0; q < HS_MAXREP; q++){                 // stage: requests of deletion q + 1, additions of deletion q
         if (q >= nv){ terms[HS_MAXREP - 1 - q] = IMP; continue; }          // (wave-uniform) the block is shorter than this deletion (HapAligner.cpp:75-77)
-        const int len8 = min(B8 - 8*aD, j8p8);
-        // column j + |D|: past the read end the values are another read's (or nothing's) and not used
-        const double dsum = ldb(8*oMt + 8*aD + aM) - ldb(8*oDl + 8*q*XC + 8*aD + aCol);
-        const double dv = pd_at(q) + dsum;
-        const double lp0 = (rj >= aD) ? dv : ndv[q];       // the segment ends inside the read: from the tables; else the read-end sum
-        const double S = tab_eval(lp0, len8, q);
-        terms[HS_MAXREP - 1 - q] = (pmf_lo(HS_MAXREP - 1 - q) + S) + ldb(8*oRowP + aM - len8);
+        if (q + 1 < HS_MAXREP) del_ld(tl[(q + 1) & 1], q + 1);
+        if (q + 2 < HS_MAXREP) ndv[(q + 2) % 3] = nd_ld(q + 2);
+        del_add(tl[q & 1], q, ndv[q % 3]);
         __builtin_amdgcn_sched_barrier(0);
       }
       bool bad = !(lp0_max < tab_bmin);
