@@ -720,6 +720,146 @@ def trace_dev_from_host(lib, trace, n_req):
     return TraceDev(lib, h.value)
 
 
+# ---- the ragged gather of resident records and the trace cache built on it (hipstr_trace_dev_gather, hipstr_trace_cache_*)
+class HipstrTraceCacheStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_hits", "n_misses", "n_inserted", "n_segments", "n_live", "n_dead")]
+
+
+def _trace_cache_sigs(lib):
+    _trace_dev_sigs(lib)
+    vpp = C.POINTER(C.c_void_p)
+    _sig(lib.hipstr_trace_dev_gather, C.c_int, [C.c_int32, vpp, C.c_int32, _i32p, _i32p, vpp])
+    _sig(lib.hipstr_trace_cache_create, C.c_void_p, [C.c_int32, _i32p, _i32p])
+    _sig(lib.hipstr_trace_cache_round, C.c_int, [C.c_void_p, _BP, C.c_int32, _i32p, _i32p, _i32p, C.POINTER(C.c_char_p), _u8p, vpp, C.POINTER(HipstrTraceCacheStats)])
+    _sig(lib.hipstr_trace_cache_remap, C.c_int, [C.c_void_p, _i32p, _i32p])
+    _sig(lib.hipstr_trace_cache_clear, C.c_int, [C.c_void_p, _u8p])
+    _sig(lib.hipstr_trace_cache_compact, C.c_int, [C.c_void_p])
+    _sig(lib.hipstr_trace_cache_entries, C.c_int, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p])
+    _sig(lib.hipstr_trace_cache_view, C.c_int, [C.c_void_p, vpp])
+    _sig(lib.hipstr_trace_cache_stats, C.c_int, [C.c_void_p, C.POINTER(HipstrTraceCacheStats)])
+    _sig(lib.hipstr_trace_cache_free, None, [C.c_void_p])
+    _sig(lib.hipstr_debug_trace_cache_plan, C.c_int, [C.c_int64] * 4 + [C.POINTER(C.c_int64)])
+    _sig(lib.hipstr_debug_trace_gather_last, C.c_int, [_f64p])
+
+
+def trace_dev_gather(lib, sources, out_src, out_idx, n_src=None, n_out=None):
+    """hipstr_trace_dev_gather -> TraceDev.  sources: TraceDev objects (None: a NULL source).  Raises with hipstr_last_error() when the call
+    refuses (the handle it left must then be NULL).  n_src / n_out: counts other than the lists' lengths (the refusals)."""
+    _trace_cache_sigs(lib)
+    hs = (C.c_void_p * max(len(sources), 1))(*[None if s is None else s.h for s in sources])
+    os_ = np.ascontiguousarray(np.asarray(out_src, np.int32)); oi = np.ascontiguousarray(np.asarray(out_idx, np.int32))
+    h = C.c_void_p(0xdead)
+    rc = lib.hipstr_trace_dev_gather(len(sources) if n_src is None else n_src, hs, len(os_) if n_out is None else n_out, _ptr(os_, _i32p), _ptr(oi, _i32p), C.byref(h))
+    if rc != 0:
+        assert not h.value, "hipstr_trace_dev_gather failed and left a handle"
+        raise RuntimeError("hipstr_trace_dev_gather failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    assert h.value
+    return TraceDev(lib, h.value)
+
+
+def trace_gather_last(lib):
+    """hipstr_debug_trace_gather_last of the calling thread as a dict."""
+    _trace_cache_sigs(lib)
+    o = np.zeros(4)
+    assert lib.hipstr_debug_trace_gather_last(o.ctypes.data_as(_f64p)) == 0
+    return dict(kernel_ms=float(o[0]), bytes_up=int(o[1]), bytes_home=int(o[2]), n_out=int(o[3]))
+
+
+def trace_cache_plan(lib, n_out=0, n_live=0, n_dead=0, n_segments=0):
+    """hipstr_debug_trace_cache_plan (host only) as a dict."""
+    _trace_cache_sigs(lib)
+    o = np.zeros(12, np.int64)
+    if lib.hipstr_debug_trace_cache_plan(int(n_out), int(n_live), int(n_dead), int(n_segments), o.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
+        raise RuntimeError("hipstr_debug_trace_cache_plan failed: " + lib.hipstr_last_error().decode())
+    keys = ("len_workgroups", "scan_steps", "scan_steps_flank", "copy_workgroups", "pieces", "compact", "min_dead", "max_segments", "len_threads", "wave",
+            "totals_bytes", "pool_fits")
+    return {k: int(v) for k, v in zip(keys, o)}
+
+
+class TraceCache:
+    """hipstr_trace_cache_*: SeqStutterGenotyper's trace_cache_ for a batch of loci (include/hipstr_hmm.h).  Every call raises with
+    hipstr_last_error() when the library refuses it; `rc` is the last return code."""
+
+    def __init__(self, lib, pool_off, n_alleles, n_loci=None):
+        _trace_cache_sigs(lib)
+        self.lib = lib; self.h = None; self.rc = 0
+        po = None if pool_off is None else np.ascontiguousarray(np.asarray(pool_off, np.int32))
+        na = None if n_alleles is None else np.ascontiguousarray(np.asarray(n_alleles, np.int32))
+        self.h = lib.hipstr_trace_cache_create(len(na) if n_loci is None else n_loci, _ptr(po, _i32p), _ptr(na, _i32p))
+        if not self.h:
+            raise RuntimeError("hipstr_trace_cache_create failed: " + lib.hipstr_last_error().decode())
+
+    def _check(self, rc, what):
+        self.rc = rc
+        if rc != 0:
+            raise RuntimeError("%s failed rc=%d: %s" % (what, rc, self.lib.hipstr_last_error().decode()))
+
+    @staticmethod
+    def _stats(st):
+        return {k: int(getattr(st, k)) for k, _ in HipstrTraceCacheStats._fields_}
+
+    def round(self, bptr, req_read, req_allele, hap_to_ref=None, req_seed=None, locus_takes=None):
+        """hipstr_trace_cache_round -> (TraceDev, stats dict)."""
+        rr = np.ascontiguousarray(np.asarray(req_read, np.int32)); aa = np.ascontiguousarray(np.asarray(req_allele, np.int32))
+        ss = None if req_seed is None else np.ascontiguousarray(np.asarray(req_seed, np.int32))
+        lt = None if locus_takes is None else np.ascontiguousarray(np.asarray(locus_takes, np.uint8))
+        h2r = None if hap_to_ref is None else (C.c_char_p * len(hap_to_ref))(*hap_to_ref)
+        h = C.c_void_p(0xdead); st = HipstrTraceCacheStats()
+        rc = self.lib.hipstr_trace_cache_round(self.h, bptr, len(rr), _ptr(rr, _i32p), _ptr(aa, _i32p), _ptr(ss, _i32p), h2r, _ptr(lt, _u8p), C.byref(h), C.byref(st))
+        if rc != 0:
+            assert not h.value, "hipstr_trace_cache_round failed and left a handle"
+        self._check(rc, "hipstr_trace_cache_round")
+        return TraceDev(self.lib, h.value), self._stats(st)
+
+    def remap(self, new_n_alleles, allele_mapping):
+        i32 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.int32))
+        na = i32(new_n_alleles); am = i32(allele_mapping)
+        self._check(self.lib.hipstr_trace_cache_remap(self.h, _ptr(na, _i32p), _ptr(am, _i32p)), "hipstr_trace_cache_remap")
+
+    def clear(self, locus=None):
+        m = None if locus is None else np.ascontiguousarray(np.asarray(locus, np.uint8))
+        self._check(self.lib.hipstr_trace_cache_clear(self.h, _ptr(m, _u8p)), "hipstr_trace_cache_clear")
+
+    def compact(self):
+        self._check(self.lib.hipstr_trace_cache_compact(self.h), "hipstr_trace_cache_compact")
+
+    def entries(self, cap=None):
+        """(ent_read, ent_allele), sorted by (locus, pool, haplotype).  cap: the capacity handed to the call (default: what it needs)."""
+        n = np.zeros(1, np.int32)
+        if cap is None:
+            rc = self.lib.hipstr_trace_cache_entries(self.h, 0, n.ctypes.data_as(_i32p), None, None)
+            assert rc in (0, 3)
+            cap = int(n[0])
+        er = np.full(max(cap, 1), UNTOUCHED, np.int32); ea = np.full(max(cap, 1), UNTOUCHED, np.int32)
+        rc = self.lib.hipstr_trace_cache_entries(self.h, int(cap), n.ctypes.data_as(_i32p), er.ctypes.data_as(_i32p), ea.ctypes.data_as(_i32p))
+        self.n_entries = int(n[0])
+        self._check(rc, "hipstr_trace_cache_entries")
+        return er[:int(n[0])], ea[:int(n[0])]
+
+    def view(self):
+        h = C.c_void_p(0xdead)
+        rc = self.lib.hipstr_trace_cache_view(self.h, C.byref(h))
+        if rc != 0:
+            assert not h.value
+        self._check(rc, "hipstr_trace_cache_view")
+        return TraceDev(self.lib, h.value)
+
+    def stats(self):
+        st = HipstrTraceCacheStats()
+        self._check(self.lib.hipstr_trace_cache_stats(self.h, C.byref(st)), "hipstr_trace_cache_stats")
+        return self._stats(st)
+
+    def close(self):
+        if self.h:
+            self.lib.hipstr_trace_cache_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def assign_trace_stats_dev(lib, pb, read_req, td, best_hap, hap_to_allele, allele_bp_diff, n_variants, region_start, region_stop):
     """hipstr_assign_trace_stats_dev -> (n_stutter[n_samp], n_flank_indel[n_samp], ml_bp[n_reads]); the shape of run_assign_trace_stats with a
     TraceDev in the trace's place."""
@@ -1742,6 +1882,7 @@ def load_hmm():
     _sig(lib.hipstr_rm_free, None, [C.c_void_p])
     _sig(lib.hipstr_debug_rm_plan, C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_int64)])
     _trace_dev_sigs(lib)
+    _trace_cache_sigs(lib)
     _sig(lib.hipstr_post_census_dev, C.c_int, [C.c_void_p, C.POINTER(HipstrCensusRequest), C.c_void_p, C.POINTER(HipstrCensusOut)])
     _em_trace_sigs(lib)
     _pool_sigs(lib)

@@ -243,6 +243,10 @@ int ctx_device(Ctx* c);
 // hipstr_trace_out_t, offsets with their leading 0, pools dense.  Read-only once the creating call has returned (it waits for its stream).
 #define HS_TRACE_DEV_POOLS 7          // hap_aln, str_seq, flank_seq, indel, snp, cigar, aln_str: hipstr_trace_out_t's order
 #define HS_TRACE_DEV_ARRAYS 10        // the pools' arrays: hap_aln, str_seq, flank_seq, indel_pos, indel_size, snp_pos, snp_base, cigar_op, cigar_len, aln_str
+// the pool and the element size of every array, in that order: the one statement of it (trace.hip's host tables and trace_cache.hip's
+// device tables are both initialised from these lists)
+#define HS_TRACE_DEV_ARR_POOL_LIST {0, 1, 2, 3, 3, 4, 4, 5, 5, 6}
+#define HS_TRACE_DEV_ARR_ESZ_LIST  {1, 1, 1, 4, 4, 4, 1, 1, 4, 1}
 struct hipstr_trace_dev {
   hipstr::Ctx* ctx = NULL;
   hipStream_t stream = NULL;          // the creating thread's stream: fetches and the read counts are queued here
@@ -256,6 +260,12 @@ struct hipstr_trace_dev {
   int32_t* off[HS_TRACE_DEV_POOLS] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL};
   char* arr[HS_TRACE_DEV_ARRAYS] = {NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL};
 };
+namespace hipstr {
+// trace.hip, for trace_cache.hip: a handle of n requests and these pool totals on one fresh block of the context's device cache (groups and
+// checked are the maker's to set; NULL + last error on failure), and its way back (the caller has waited for whatever used the block)
+hipstr_trace_dev* trace_dev_make(Ctx* ctx, hipStream_t st, int32_t n, const int64_t tot[HS_TRACE_DEV_POOLS]);
+void trace_dev_release(hipstr_trace_dev* td);
+}  // namespace hipstr
 
 // ---- what hipstr_em_train_dev (em_input.hip) needs of a posterior run (api.hip) and of the stutter EM (em.hip)
 struct hs_post_unit_t; struct hipstr_post_dev; struct hipstr_em_batch;

@@ -1162,8 +1162,8 @@ struct ReqOut {                    // one request's results, built by a worker t
 
 // ---- the resident result (api_internal.h: hipstr_trace_dev): where every array lies in the handle's one block.  A chunk's segment has the
 // same layout for the chunk's requests and elements, so the segment of a call of one chunk IS the result.
-const int TD_ARR_POOL[HS_TRACE_DEV_ARRAYS] = {0, 1, 2, 3, 3, 4, 4, 5, 5, 6};
-const int TD_ARR_ESZ[HS_TRACE_DEV_ARRAYS]  = {1, 1, 1, 4, 4, 4, 1, 1, 4, 1};
+const int TD_ARR_POOL[HS_TRACE_DEV_ARRAYS] = HS_TRACE_DEV_ARR_POOL_LIST;
+const int TD_ARR_ESZ[HS_TRACE_DEV_ARRAYS]  = HS_TRACE_DEV_ARR_ESZ_LIST;
 // the fetch group (HIPSTR_TRACE_F_*) of every pool
 const uint32_t TD_POOL_BIT[HS_TRACE_DEV_POOLS] = { HIPSTR_TRACE_F_HAP_ALN, HIPSTR_TRACE_F_STR_SEQ, HIPSTR_TRACE_F_FLANKS, HIPSTR_TRACE_F_INDELS, HIPSTR_TRACE_F_SNPS,
                                                    HIPSTR_TRACE_F_STITCH, HIPSTR_TRACE_F_STITCH };
@@ -1912,6 +1912,10 @@ int trace_call(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, 
 }
 
 }  // namespace
+
+// what trace_cache.hip builds its gathered handles with (api_internal.h)
+hipstr_trace_dev* hipstr::trace_dev_make(hipstr::Ctx* ctx, hipStream_t st, int32_t n, const int64_t tot[HS_TRACE_DEV_POOLS]){ return trace_dev_new(ctx, st, n, tot); }
+void hipstr::trace_dev_release(hipstr_trace_dev* td){ trace_dev_drop(td); }
 
 extern "C" int hipstr_hmm_trace(const hipstr_batch_t* b, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
                                 const char* const* hap_to_ref, hipstr_trace_out_t* o){

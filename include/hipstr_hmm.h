@@ -528,6 +528,71 @@ int  hipstr_trace_dev_sizes(const hipstr_trace_dev_t* td, int32_t* n_req, int64_
 int  hipstr_trace_dev_fetch(hipstr_trace_dev_t* td, uint32_t fields, hipstr_trace_out_t* out);
 void hipstr_trace_dev_free(hipstr_trace_dev_t* td);
 
+/* A ragged gather of resident records: a NEW handle whose record q is record out_idx[q] of src[out_src[q]] — any selection, any order,
+ * repeats allowed.  The result has the layout of every hipstr_trace_dev_t and every consumer reads it unchanged (hipstr_trace_dev_fetch /
+ * _sizes, hipstr_post_census_dev, hipstr_assign_trace_stats_dev, hipstr_em_train_dev, hipstr_flank_assemble_dev); its offsets ascend by
+ * construction.  Three kernels on the calling thread's stream (lengths from the sources' offsets, a scan per pool, a wavefront per record
+ * that copies its pieces); out_src / out_idx and a pointer table of the sources go up, the 64-byte block of pool totals comes down.  No
+ * source is modified; the result is complete when the call returns, the caller frees it.  n_out == 0: a valid empty handle.
+ * Refused (non-zero, hipstr_last_error(), *td = NULL, nothing written): a negative count, a NULL source, sources of different devices
+ * (contexts), a source that lacks a group or was made by hipstr_debug_trace_dev_from_host, out_src / out_idx out of range, a pool of more
+ * than INT32_MAX elements ("too many requests for one call; split the request list"). */
+int  hipstr_trace_dev_gather(int32_t n_src, const hipstr_trace_dev_t* const* src, int32_t n_out, const int32_t* out_src, const int32_t* out_idx,
+                             hipstr_trace_dev_t** td);
+
+/*
+ * The trace cache of a batch of loci: trace_cache_ of SeqStutterGenotyper (seq_stutter_genotyper.cpp:805-841), which outlives the rounds
+ * of genotype() — a (pool, haplotype) pair is traced once, the first time a round asks for it, and add_and_remove_alleles re-keys the
+ * cache through allele_mapping (:401-409).  The keys — (locus, pool within the locus, haplotype) — live in a host table; the records
+ * stay on the device, in the segment the round that traced them left (one hipstr_hmm_trace_resident handle per round that missed).
+ * A cache belongs to the device (context) of the thread that creates it and makes its first round (creation itself is host only) and is
+ * used by one thread at a time; different caches on different threads are independent.
+ */
+typedef struct hipstr_trace_cache hipstr_trace_cache_t;
+typedef struct hipstr_trace_cache_stats {
+  int64_t n_hits;        /* requests of the round whose key the cache (or an earlier request of the same round) held */
+  int64_t n_misses;      /* requests the round traced: its distinct new keys                                         */
+  int64_t n_inserted;    /* of those, the keys the cache took (locus_takes)                                          */
+  int64_t n_segments;    /* segments the cache holds after the call                                                  */
+  int64_t n_live;        /* keys                                                                                     */
+  int64_t n_dead;        /* records of the segments no key names (any more)                                          */
+} hipstr_trace_cache_stats_t;
+/* pool_off: [n_loci+1] prefix sums of the POOLED reads (== the pooled batch's read_off); n_alleles: [n_loci] haplotypes per locus.
+ * Host only.  Refused (NULL + hipstr_last_error()): a negative count, pool_off that does not ascend from 0, an allele count below 1. */
+hipstr_trace_cache_t* hipstr_trace_cache_create(int32_t n_loci, const int32_t* pool_off, const int32_t* n_alleles);
+/* retrace_alignments for the batch: the requests (hipstr_post_assign(HIPSTR_ASSIGN_RETRACE)'s list: req_read a pooled read, req_allele a
+ * haplotype of its locus) are split into hits and misses by key; the misses — if any — are traced with ONE hipstr_hmm_trace_resident call
+ * on the compacted list (same pooled batch, same hap_to_ref, the misses' req_seed entries); *td receives one handle with a record for every
+ * request in request order (hipstr_trace_dev_gather; the caller frees it).  A hit is the record of the round that first asked for the key,
+ * as in the reference.  The cache keeps the new records of the loci with locus_takes[l] != 0 (NULL: all) — a locus that is done in
+ * genotype() still gets its records for the round, but its cache does not take them.  stats (or NULL): the counts above.  The call
+ * compacts the cache by itself when trace_cache_layout.h's rule says so (more than half of at least 4096 records dead, or more than 16
+ * segments).
+ * When the trace of the misses fails the cache is unchanged, *td = NULL, and return value and message are hipstr_hmm_trace_resident's for
+ * the full list (a hit cannot be refused, so the first refused miss is the first refused request).  Refused before anything is traced:
+ * NULL arguments, pooled->n_loci or pooled->read_off that differ from the cache's pool_off, a req_read outside the pooled reads, requests
+ * not grouped by locus in locus order, a req_allele outside the locus' current haplotype count. */
+int  hipstr_trace_cache_round(hipstr_trace_cache_t* tc, const hipstr_batch_t* pooled, int32_t n_req, const int32_t* req_read, const int32_t* req_allele,
+                              const int32_t* req_seed /* or NULL */, const char* const* hap_to_ref /* or NULL */,
+                              const uint8_t* locus_takes /* [n_loci] or NULL = all */, hipstr_trace_dev_t** td, hipstr_trace_cache_stats_t* stats /* or NULL */);
+/* seq_stutter_genotyper.cpp:401-409 with hipstr_rm_remap's arguments: every key's haplotype goes through allele_mapping ([sum of the OLD
+ * A_l]); a key mapped to -1 is dropped and its record becomes dead.  Host only.  Refused (nothing changes): what hipstr_rm_remap refuses —
+ * a count below 1, a mapping entry outside [-1, new A_l), two old haplotypes mapped to one new one. */
+int  hipstr_trace_cache_remap(hipstr_trace_cache_t* tc, const int32_t* new_n_alleles, const int32_t* allele_mapping);
+/* trace_cache_.clear() (:1579) for the loci with locus[l] != 0 (NULL: all).  The segments go back once no key is left. */
+int  hipstr_trace_cache_clear(hipstr_trace_cache_t* tc, const uint8_t* locus /* [n_loci] or NULL = all */);
+/* One gather of the live records, in the order of hipstr_trace_cache_entries, into a single segment: n_dead = 0, n_segments = 1 (0 for
+ * an empty cache).  Changes no record and no later round's result. */
+int  hipstr_trace_cache_compact(hipstr_trace_cache_t* tc);
+/* The keys, sorted by (locus, pool, haplotype): ent_read[i] the pooled read (pool_off[locus] + pool), ent_allele[i] the haplotype; *n
+ * their number.  Returns 3 (and *n) when cap is too small.  Host only. */
+int  hipstr_trace_cache_entries(const hipstr_trace_cache_t* tc, int32_t cap, int32_t* n, int32_t* ent_read, int32_t* ent_allele);
+/* The entries' records in that order as a new handle (the caller frees it): what the reference's final trace_cache_ holds. */
+int  hipstr_trace_cache_view(hipstr_trace_cache_t* tc, hipstr_trace_dev_t** td);
+/* n_segments, n_live and n_dead as they are now (the round's counts are 0).  Host only. */
+int  hipstr_trace_cache_stats(const hipstr_trace_cache_t* tc, hipstr_trace_cache_stats_t* stats);
+void hipstr_trace_cache_free(hipstr_trace_cache_t* tc);
+
 /*
  * Reads assigned to the MAP haplotypes and the per-sample read counts of a VCF record: the loop over the reads of
  * SeqStutterGenotyper::write_vcf_record (seq_stutter_genotyper.cpp:1079-1157) with the phase totals of :1355-1356, and the pick of

@@ -248,6 +248,17 @@ void hipstr_debug_stream_destroy(void* hip_stream);
 /* Diagnostics: the device's copy of a batch's STR-option records (what = 0: hs_stropt_t of hipstr_amd/csrc/layout.h), its f64 pool incl. the
  * part the device generated (1) or the per-allele records the device assembled (2).  Returns the table's size in bytes (-1 on failure). */
 int64_t hipstr_debug_fetch_table(hipstr_dev_batch_t* dev, int what, void* buf, int64_t cap_bytes);
+/* Diagnostics (host only): the decisions of hipstr_amd/csrc/trace_cache_layout.h for a gather of n_out records and a cache of n_live keys,
+ * n_dead dead records and n_segments segments.  out[0] workgroups of the lengths kernel, out[1] steps of 64 pieces the scan makes over a
+ * one-piece pool, out[2] over the flank pool (two pieces a record), out[3] workgroups of the copy kernel, out[4] pieces of all pools,
+ * out[5] 1 = hipstr_trace_cache_round compacts this cache by itself; then the compiled limits: out[6] HS_TC_COMPACT_MIN_DEAD, out[7]
+ * HS_TC_MAX_SEGMENTS, out[8] HS_TC_LEN_THREADS, out[9] HS_TC_WAVE, out[10] HS_TC_TOTALS_BYTES; out[11] 1 = a pool of n_out elements fits
+ * the 32-bit offsets.  Used by tests/test_trace_cache_host.py. */
+int hipstr_debug_trace_cache_plan(int64_t n_out, int64_t n_live, int64_t n_dead, int64_t n_segments, int64_t out[12]);
+/* Diagnostics: the calling thread's last gather (hipstr_trace_dev_gather, or the one inside hipstr_trace_cache_round / _view / _compact):
+ * out[0] milliseconds of its three kernels (measured with events when HIPSTR_TRACE_GATHER_TIMING is set, else 0), out[1] bytes sent up,
+ * out[2] bytes that came home, out[3] its records. */
+int hipstr_debug_trace_gather_last(double out[4]);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
