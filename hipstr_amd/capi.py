@@ -1138,6 +1138,108 @@ def flank_last(lib, n_tasks=0):
                 flags=fl[:n_tasks], sizes=sz[:4 * n_tasks].reshape(-1, 4))
 
 
+# ---- the record's numeric fields (hipstr_bias_pvalues, hipstr_record_fields and their host forms)
+class HipstrRecordRequest(C.Structure):
+    _fields_ = [("n_variants", _i32p), ("hap_to_allele", _i32p), ("sample_reported", _u8p), ("sample_masked", _u8p),
+                ("n_aligned", _i32p), ("n_snp", _i32p), ("n_stutter", _i32p), ("n_flank_indel", _i32p),
+                ("uniq_one", _i32p), ("uniq_two", _i32p), ("rv_uniq_one", _i32p), ("rv_uniq_two", _i32p), ("max_flank_indel_frac", C.c_float)]
+
+
+class HipstrRecordOut(C.Structure):
+    _fields_ = [("status", _i32p), ("gt", _i32p), ("ab", _f64p), ("dab", _i32p), ("fs", _f64p), ("n_skip", _i32p), ("n_filt", _i32p), ("an", _i32p),
+                ("dp", _i32p), ("dsnp", _i32p), ("dstutter", _i32p), ("dflankindel", _i32p), ("allele_count", _i32p)]
+
+
+RECORD_PASS, RECORD_NO_READS, RECORD_MASKED, RECORD_FLANK_INDEL_FRAC, RECORD_NOT_REPORTED = 0, 1, 2, 3, -1
+RECORD_NOT_APPLICABLE = 1.01
+RECORD_TABLE_READS = 5000
+RECORD_COUNTS = ("n_aligned", "n_snp", "n_stutter", "n_flank_indel", "uniq_one", "uniq_two", "rv_uniq_one", "rv_uniq_two")
+RECORD_NAMES = ("hipstr_bias_pvalues", "hipstr_bias_pvalues_host", "hipstr_record_fields", "hipstr_record_fields_host")
+
+
+def _record_sigs(lib):
+    pv = [C.c_int64, _i32p, _i32p, _i32p, _i32p, _f64p, _f64p]
+    _sig(lib.hipstr_bias_pvalues, C.c_int, pv)
+    _sig(lib.hipstr_bias_pvalues_host, C.c_int, pv)
+    _sig(lib.hipstr_record_fields, C.c_int, [C.c_void_p, C.POINTER(HipstrRecordRequest), C.POINTER(HipstrRecordOut)])
+    _sig(lib.hipstr_record_fields_host, C.c_int, [_PBP, _i32p, C.POINTER(HipstrRecordRequest), C.POINTER(HipstrRecordOut)])
+    _sig(lib.hipstr_debug_record_last, C.c_int, [C.POINTER(C.c_int64)])
+
+
+def bias_pvalues(lib, uniq_one, uniq_two, rv_uniq_one, rv_uniq_two, host=False, n=None):
+    """hipstr_bias_pvalues (host=True: hipstr_bias_pvalues_host) -> (ab, fs); what the call leaves untouched holds NaN.  An argument may be
+    None (a null pointer); n defaults to the length of uniq_one."""
+    _record_sigs(lib)
+    a = [None if x is None else np.ascontiguousarray(np.asarray(x, np.int32)) for x in (uniq_one, uniq_two, rv_uniq_one, rv_uniq_two)]
+    if n is None:
+        n = len(a[0])
+    ab = np.full(max(n, 1), np.nan); fs = np.full(max(n, 1), np.nan)
+    fn = lib.hipstr_bias_pvalues_host if host else lib.hipstr_bias_pvalues
+    rc = fn(int(n), *[_ptr(x, _i32p) for x in a], _ptr(ab, _f64p), _ptr(fs, _f64p))
+    if rc != 0:
+        raise RuntimeError("hipstr_bias_pvalues%s failed rc=%d: %s" % ("_host" if host else "", rc, lib.hipstr_last_error().decode()))
+    return ab[:max(n, 0)], fs[:max(n, 0)]
+
+
+def run_record_fields(lib, pb, n_variants, hap_to_allele, counts, map_gt=None, pd=None, sample_reported=None, sample_masked=None,
+                      max_flank_indel_frac=0.0, null_out=None):
+    """hipstr_record_fields_host (map_gt given: the host form on the PostBatch pb) or hipstr_record_fields (pd: a hipstr_post_dev_t handle
+    after hipstr_post_launch; None = pb is uploaded, launched and freed here) -> dict of the output arrays.  counts: dict of the eight
+    per-sample arrays of RECORD_COUNTS (a missing one is passed as NULL).  Integers the call leaves untouched hold UNTOUCHED, doubles NaN.
+    Raises with hipstr_last_error() when the call is refused; the exception's `raw` holds the arrays."""
+    _record_sigs(lib)
+    i32 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.int32))
+    u8 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.uint8))
+    nl = int(pb.struct.n_loci)
+    n_samp = int(pb.samp_off[-1])
+    keep = dict(n_variants=i32(n_variants), hap_to_allele=i32(hap_to_allele), sample_reported=u8(sample_reported), sample_masked=u8(sample_masked))
+    for nm in RECORD_COUNTS:
+        keep[nm] = i32(counts.get(nm))
+    rq = HipstrRecordRequest(*([_ptr(keep[f], t) for f, t in HipstrRecordRequest._fields_[:-1]] + [float(max_flank_indel_frac)]))
+    nv = int(np.sum(keep["n_variants"])) if keep["n_variants"] is not None else 0
+    k = dict(status=np.full(max(n_samp, 1), UNTOUCHED, np.int32), gt=np.full(max(2 * n_samp, 1), UNTOUCHED, np.int32), ab=np.full(max(n_samp, 1), np.nan),
+             dab=np.full(max(n_samp, 1), UNTOUCHED, np.int32), fs=np.full(max(n_samp, 1), np.nan), allele_count=np.full(max(nv, 1), UNTOUCHED, np.int32))
+    for nm in ("n_skip", "n_filt", "an", "dp", "dsnp", "dstutter", "dflankindel"):
+        k[nm] = np.full(max(nl, 1), UNTOUCHED, np.int32)
+    o = HipstrRecordOut(*[None if f == null_out else k[f].ctypes.data_as(t) for f, t in HipstrRecordOut._fields_])
+    if map_gt is not None:
+        mg = i32(np.asarray(map_gt).reshape(-1))
+        rc = lib.hipstr_record_fields_host(pb.ptr, _ptr(mg, _i32p), C.byref(rq), C.byref(o))
+        what = "hipstr_record_fields_host"
+    else:
+        what = "hipstr_record_fields"
+        own = pd is None
+        if own:
+            pd = lib.hipstr_post_upload(pb.ptr, None)
+            if not pd:
+                raise RuntimeError("hipstr_post_upload failed: " + lib.hipstr_last_error().decode())
+        try:
+            if own and lib.hipstr_post_launch(pd, None) != 0:
+                raise RuntimeError("hipstr_post_launch failed: " + lib.hipstr_last_error().decode())
+            rc = lib.hipstr_record_fields(pd, C.byref(rq), C.byref(o))
+        finally:
+            if own:
+                lib.hipstr_post_free(pd)
+    if rc != 0:
+        e = RuntimeError("%s failed rc=%d: %s" % (what, rc, lib.hipstr_last_error().decode()))
+        e.raw = k
+        raise e
+    out = {nm: k[nm][:n_samp] for nm in ("status", "ab", "dab", "fs")}
+    out["gt"] = k["gt"][:2 * n_samp].reshape(-1, 2)
+    out["allele_count"] = k["allele_count"][:nv]
+    for nm in ("n_skip", "n_filt", "an", "dp", "dsnp", "dstutter", "dflankindel"):
+        out[nm] = k[nm][:nl]
+    return out
+
+
+def record_last(lib):
+    """hipstr_debug_record_last -> dict(lanes, host_lanes, bytes_up, bytes_down)."""
+    _record_sigs(lib)
+    out = (C.c_int64 * 4)()
+    assert lib.hipstr_debug_record_last(out) == 0
+    return dict(lanes=int(out[0]), host_lanes=int(out[1]), bytes_up=int(out[2]), bytes_down=int(out[3]))
+
+
 class HipstrPoolOut(C.Structure):
     _fields_ = [("pool_index", _i32p), ("n_pools", _i32p), ("pool_off", _i32p), ("pool_rep", _i32p), ("pool_size", _i32p),
                 ("pool_qual_off", _i32p), ("pool_quals", C.POINTER(C.c_char))]

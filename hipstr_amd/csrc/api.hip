@@ -231,6 +231,7 @@ namespace hipstr {
 struct Ctx {
   int device = -1;
   double *int_log = NULL, *qc = NULL, *qe = NULL, *m2m = NULL, *m2i = NULL;
+  double* rec_table = NULL; std::mutex rec_m;      // record.hip's gamma table, made on its first call (ctx_record_table)
   hipStream_t stream = NULL;
   BlockCache dev_cache, pin_cache;
   // events are pooled like the blocks: a device batch needs five (hipEventCreate / Destroy cost ~10 us each: a tenth of a one-locus call)
@@ -516,6 +517,7 @@ void hipstr_hmm_shutdown(void){
     hipDeviceSynchronize();
     c->dev_cache.release(); c->pin_cache.release();
     hipFree(c->int_log); hipFree(c->qc); hipFree(c->qe); hipFree(c->m2m); hipFree(c->m2i);
+    if (c->rec_table) hipFree(c->rec_table);
     hipStreamDestroy(c->stream);
     delete c;
   }
@@ -891,6 +893,19 @@ void hipstr::free_landed(hipstr_dev_batch_t* dev, bool landed){
 double hipstr::batch_prepare_seconds(const hipstr_dev_batch_t* dev){ return dev ? dev->t_prepare : 0.0; }
 hipStream_t hipstr::ctx_stream(Ctx* c){ return c->stream; }
 int hipstr::ctx_device(Ctx* c){ return c->device; }
+int hipstr::ctx_record_table(Ctx* c, size_t count, void (*fill)(double*), const double** out){
+  std::lock_guard<std::mutex> lock(c->rec_m);
+  if (!c->rec_table){
+    std::vector<double> t(count);
+    fill(t.data());
+    if (bind(c)) return 1;
+    double* p = NULL;
+    if (upload_table(t, &p)){ if (p) hipFree(p); return 1; }
+    c->rec_table = p;
+  }
+  *out = c->rec_table;
+  return 0;
+}
 
 extern "C" {
 
@@ -1800,6 +1815,7 @@ void hipstr::post_view(const hipstr_post_dev* pd, PostView* v){
   v->ctx = R.ctx; v->stream = R.stream; v->ev_up = R.ev_up; v->d_units = R.h.units; v->units = R.units.data(); v->n_units = R.units.size();
   v->n_loci = pd->n_samples.size(); v->log_p1 = R.h.log_p1; v->log_p2 = R.h.log_p2; v->n_reads = R.n_reads; v->n_samp = R.n_samp;
   v->n_samples = pd->n_samples.data(); v->haploid = pd->haploid.data();
+  v->n_alleles = pd->n_alleles.data(); v->map_gt = R.h.map_gt; v->launched = pd->launched; v->foreign_stream = pd->foreign_stream;
 }
 void hipstr::PostView::locus_tables(std::vector<int32_t>& read_off, std::vector<int32_t>& unit_off) const {
   read_off.assign(n_loci + 1, 0); unit_off.assign(n_loci + 1, 0);

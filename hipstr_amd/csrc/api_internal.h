@@ -235,6 +235,9 @@ void scatter_loci(const hipstr_dev_batch* dev, int l0, int l1, double* aln_probs
 void free_landed(hipstr_dev_batch* dev, bool landed);
 hipStream_t ctx_stream(Ctx* c);
 int ctx_device(Ctx* c);
+// record.hip's constant table: `count` doubles written by `fill` and uploaded on the context's first request, the context's from then on
+// (freed by hipstr_hmm_shutdown with its other tables); 1 + last error on failure
+int ctx_record_table(Ctx* c, size_t count, void (*fill)(double*), const double** out);
 
 }  // namespace hipstr
 
@@ -280,6 +283,9 @@ struct PostView {                    // a posterior run after hipstr_post_upload
   int n_reads; int64_t n_samp;
   const int32_t* n_samples;          // [n_loci]
   const uint8_t* haploid;            // [n_loci]
+  const int32_t* n_alleles;          // [n_loci]
+  const int32_t* map_gt;             // device, [2*n_samp]: the MAP pairs, once the run was launched
+  bool launched, foreign_stream;     // hipstr_post_launch was called; on a stream of the caller's
   // per locus its reads [read_off[l], read_off[l+1]) and its units [unit_off[l], unit_off[l+1]), from the units (locus-major, one per sample)
   void locus_tables(std::vector<int32_t>& read_off, std::vector<int32_t>& unit_off) const;
 };

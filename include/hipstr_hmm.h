@@ -614,7 +614,7 @@ void hipstr_trace_cache_free(hipstr_trace_cache_t* tc);
  * read_req[r] names the request of read r.  Returns 3 with *n_req set (nothing else promised) when n_req > cap_req, as hipstr_stream_next
  * does for buffers that are too small.  Without pool_index the request outputs are left untouched.
  * Device and pinned blocks come from the context's caches: no allocation in steady state.  The AB and FS p-values (cephes bdtr, htslib's
- * kt_fisher_exact) stay with the host, computed from the counts returned here.
+ * kt_fisher_exact), the sample filters and the INFO totals are computed from the counts returned here by hipstr_record_fields (below).
  */
 #define HIPSTR_ASSIGN_VCF     0   /* write_vcf_record's rule, seq_stutter_genotyper.cpp:1094-1113 */
 #define HIPSTR_ASSIGN_RETRACE 1   /* retrace_alignments' rule, :823-825 */
@@ -658,6 +658,72 @@ int hipstr_assign_trace_stats(const hipstr_post_batch_t* pb, const int32_t* read
                               const int32_t* best_hap, const int32_t* hap_to_allele /* [sum A_l] */, const int32_t* allele_bp_diff /* [sum V_l], by variant */,
                               const int32_t* n_variants, const int32_t* region_start, const int32_t* region_stop /* [n_loci] */,
                               int32_t* n_stutter, int32_t* n_flank_indel /* [n_samp] */, int32_t* ml_bp /* [n_reads] */);
+
+/*
+ * The numeric fields of a VCF record that follow from those counts: SeqStutterGenotyper::write_vcf_record's three loops over the samples
+ * (seq_stutter_genotyper.cpp:1159-1187, :1238-1254, :1326-1375) with compute_allele_bias (:965-982).
+ *
+ * hipstr_bias_pvalues: the raw pair for n count quadruples.
+ *   ab[i] = compute_allele_bias(uniq_one[i], uniq_two[i]): 1 for an empty total, 0.0 for equal counts, else
+ *           log10(min(1.0, 2*bdtr(min, total, 0.5))) with cephes' bdtr (incbet: incbcf / incbd / pseries, gamma, lgam)
+ *   fs[i] = log10(min(1.0, two)) of htslib's kt_fisher_exact(u1 - rv1, rv1, u2 - rv2, rv2) (:1371-1374)
+ * _host (no device needed) restates both routines in the reference's operation order over the host's libm and equals the compiled reference
+ * bit for bit (tests/golden/record_pvalues.npz).  The device form runs one lane per quadruple with correctly rounded exp / log / log10
+ * (cr_math.h) and gamma / lgam / lgamma read from a table the host form filled; it differs from the host form only where the host's libm is
+ * not correctly rounded.  A quadruple whose counts exceed the table (uniq_one + uniq_two > HIPSTR_RECORD_TABLE_READS) is computed by the host
+ * form inside the same call.  Refused, nothing written: null arguments, n < 0, a negative count, rv_uniq > uniq.
+ *
+ * hipstr_record_fields (on a hipstr_post_dev_t after hipstr_post_launch; the MAP pairs are read where they lie) and
+ * hipstr_record_fields_host (map_gt: hipstr_post_fetch's, [2*n_samp]).  gt = hap_to_allele[map_gt].  Per sample (sample_total_ll's order):
+ *   status  the output loop's tests in its order (:1326-1352): HIPSTR_RECORD_NOT_REPORTED (not in sample_names: the record has no column
+ *           for it), else _NO_READS (n_aligned == 0), else _MASKED (sample_masked), else _FLANK_INDEL_FRAC
+ *           ((float)n_flank_indel > max_flank_indel_frac*(float)n_aligned in FLOAT arithmetic: MAX_FLANK_INDEL_FRAC is a float), else _PASS
+ *   gt[2]   the genotype of the MAP pair, -1 -1 for a sample without one; written for every sample
+ *   ab, dab (uniq_one + uniq_two), fs: for PASS samples of a diploid locus whose MAP HAPLOTYPES differ (:1363, :1369) as
+ *           hipstr_bias_pvalues gives them (an empty total gives ab = 1); everywhere else HIPSTR_RECORD_NOT_APPLICABLE (1.01) and dab 0
+ * Per locus:
+ *   n_skip, n_filt, an, allele_count[V] (block-option order): :1159-1187 — not reported and n_aligned == 0 pass by, then the flank fraction
+ *           counts into n_filt BEFORE the mask is looked at (a sample that is masked and over the fraction counts in NFILT), then a masked
+ *           sample counts into n_skip, and what is left adds its genotype's alleles (one for a haploid locus)
+ *   dp, dsnp, dstutter, dflankindel: :1238-1254 — reported samples, masked ones skipped FIRST, then those over the flank fraction; samples
+ *           without reads stay in
+ * Refused, nothing written: null arguments, a negative count or rv_uniq > uniq on ANY sample (not reported and masked ones included: the
+ * counts are checked before the filters are looked at), a negative max_flank_indel_frac, n_variants < 1,
+ * a hap_to_allele outside [0, V), map_gt outside [-1, A), a sample with reads that passes the filters and has no MAP pair, a haploid locus with a sample that adds to the allele counts and has gt[0] !=
+ * gt[1] (the reference asserts), a run that was not launched.  Uploads and results go through the context's caches.
+ */
+#define HIPSTR_RECORD_PASS             0
+#define HIPSTR_RECORD_NO_READS         1
+#define HIPSTR_RECORD_MASKED           2
+#define HIPSTR_RECORD_FLANK_INDEL_FRAC 3
+#define HIPSTR_RECORD_NOT_REPORTED     (-1)
+#define HIPSTR_RECORD_NOT_APPLICABLE   1.01
+#define HIPSTR_RECORD_TABLE_READS      5000    /* the reference's MAX_TOTAL_READS default per locus (hipstr_main.cpp) */
+int hipstr_bias_pvalues(int64_t n, const int32_t* uniq_one, const int32_t* uniq_two, const int32_t* rv_uniq_one, const int32_t* rv_uniq_two,
+                        double* ab, double* fs);
+int hipstr_bias_pvalues_host(int64_t n, const int32_t* uniq_one, const int32_t* uniq_two, const int32_t* rv_uniq_one, const int32_t* rv_uniq_two,
+                             double* ab, double* fs);
+typedef struct hipstr_record_request {
+  const int32_t* n_variants;      /* [n_loci] V                                                              */
+  const int32_t* hap_to_allele;   /* [sum A_l] as in hipstr_gt_request_t                                     */
+  const uint8_t* sample_reported; /* [n_samp] the sample is in sample_names, or NULL = all                   */
+  const uint8_t* sample_masked;   /* [n_samp] !call_sample_[s].empty(), or NULL = none                       */
+  const int32_t* n_aligned, *n_snp, *n_stutter, *n_flank_indel;             /* [n_samp] hipstr_post_assign(HIPSTR_ASSIGN_VCF),    */
+  const int32_t* uniq_one, *uniq_two, *rv_uniq_one, *rv_uniq_two;           /*          hipstr_assign_trace_stats(_dev)            */
+  float max_flank_indel_frac;     /* MAX_FLANK_INDEL_FRAC; 0 = the reference's 0.15f (genotyper.cpp:343)     */
+} hipstr_record_request_t;
+typedef struct hipstr_record_out {
+  int32_t* status;                /* [n_samp] HIPSTR_RECORD_*                                                */
+  int32_t* gt;                    /* [2*n_samp]                                                              */
+  double*  ab;                    /* [n_samp]                                                                */
+  int32_t* dab;                   /* [n_samp]                                                                */
+  double*  fs;                    /* [n_samp]                                                                */
+  int32_t* n_skip, *n_filt, *an;  /* [n_loci]                                                                */
+  int32_t* dp, *dsnp, *dstutter, *dflankindel;    /* [n_loci]                                                */
+  int32_t* allele_count;          /* [sum V_l], block-option order                                           */
+} hipstr_record_out_t;
+int hipstr_record_fields(hipstr_post_dev_t* pd, const hipstr_record_request_t* rq, hipstr_record_out_t* out);
+int hipstr_record_fields_host(const hipstr_post_batch_t* pb, const int32_t* map_gt, const hipstr_record_request_t* rq, hipstr_record_out_t* out);
 
 /*
  * The allele census between two rounds of SeqStutterGenotyper::genotype (seq_stutter_genotyper.cpp:603-671): what decides the next round's

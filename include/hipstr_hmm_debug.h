@@ -132,6 +132,11 @@ int hipstr_debug_flank_plan(const hipstr_post_batch_t* pb, const hipstr_flank_re
  * task as the kernel set them) and sizes (per task: most edges, most nodes, path records, strings that entered, as the kernel counted
  * them up to where it stopped) are filled for up to cap_tasks tasks and may be NULL.  A refused call leaves the numbers of the call before. */
 int hipstr_debug_flank_last(int64_t out[8], int32_t* flags, int32_t* sizes, int64_t cap_tasks);
+/* Diagnostics: the calling thread's last hipstr_bias_pvalues or hipstr_record_fields: out[0] lanes (quadruples or samples), out[1] those the
+ * host twin computed inside the call because their counts exceed the device's table, out[2] bytes sent to the device, out[3] bytes copied
+ * back.  A call that was refused, or that had nothing to do, leaves zeros.  Used by tests/test_record_gpu.py and
+ * tools/record_fields_timing.py. */
+int hipstr_debug_record_last(int64_t out[4]);
 /* Diagnostics: the calling thread's last hipstr_pool_reads (or hipstr_pool_batch on the device): out[0] loci pooled on the device, out[1]
  * loci the host pooled for their size, out[2] loci the host redid after a hash collision, out[3..5] pools of the device's loci by median
  * route (copy, net, radix), out[6] chunks, out[7] reads uploaded.  hipstr_debug_pool_last_timing: out[0] milliseconds between HIP events
