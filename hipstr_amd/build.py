@@ -11,8 +11,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hipstr_amd", "csrc")
-HIP_SOURCES = ["api.hip", "hmm_kernels.hip", "expand_kernels.hip", "post_kernels.hip", "assign.hip", "census.hip", "readmat.hip", "pool.hip", "pool_host.cpp", "hapgen.hip", "hapgen_host.cpp", "alleles.hip", "alleles_host.cpp", "prep.cpp", "trace.hip", "trace_cache.hip", "em.hip", "em_input.hip", "flank.hip", "flank_host.cpp", "record.hip", "record_host.cpp", "nw.hip", "batch_io.cpp", "stream.hip", "gather.cpp"]
-HIP_HEADERS = ["exports.map", "layout.h", "post_layout.h", "readmat_layout.h", "pool_layout.h", "pool_host.h", "hapgen_layout.h", "hapgen_host.h", "alleles_layout.h", "alleles_host.h", "census_layout.h", "em_layout.h", "em_input_layout.h", "trace_cache_layout.h", "flank_layout.h", "flank_task.h", "flank_host.h", "record_layout.h", "record_host.h", "prep.h", "device_common.h", "flank_sweep_step.h", "float_lse.h", "api_internal.h", "block_pieces.h", "cr_math.h", "cr_tables.inc", os.path.join("..", "..", "include", "hipstr_hmm.h"), os.path.join("..", "..", "include", "hipstr_hmm_debug.h")]
+HIP_SOURCES = ["api.hip", "hmm_kernels.hip", "expand_kernels.hip", "post_kernels.hip", "assign.hip", "census.hip", "readmat.hip", "pool.hip", "pool_host.cpp", "hapgen.hip", "hapgen_host.cpp", "alleles.hip", "alleles_host.cpp", "prep.cpp", "trace.hip", "trace_cache.hip", "em.hip", "em_input.hip", "flank.hip", "flank_host.cpp", "record.hip", "record_host.cpp", "record_reads.hip", "record_reads_host.cpp", "record_alleles.hip", "record_alleles_host.cpp", "nw.hip", "batch_io.cpp", "stream.hip", "gather.cpp"]
+HIP_HEADERS = ["exports.map", "layout.h", "post_layout.h", "readmat_layout.h", "pool_layout.h", "pool_host.h", "hapgen_layout.h", "hapgen_host.h", "alleles_layout.h", "alleles_host.h", "census_layout.h", "em_layout.h", "em_input_layout.h", "trace_cache_layout.h", "flank_layout.h", "flank_task.h", "flank_host.h", "record_layout.h", "record_host.h", "record_reads_layout.h", "record_reads_host.h", "record_alleles_layout.h", "record_alleles_host.h", "prep.h", "device_common.h", "flank_sweep_step.h", "float_lse.h", "api_internal.h", "block_pieces.h", "cr_math.h", "cr_tables.inc", os.path.join("..", "..", "include", "hipstr_hmm.h"), os.path.join("..", "..", "include", "hipstr_hmm_debug.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-honor-nans", "-mno-amdgpu-ieee", "-fPIC", "-shared", "-pthread", "-fvisibility=hidden", "-Wno-unused-result", "-Wno-unused-value"]
 
 

@@ -1240,6 +1240,269 @@ def record_last(lib):
     return dict(lanes=int(out[0]), host_lanes=int(out[1]), bytes_up=int(out[2]), bytes_down=int(out[3]))
 
 
+# ---- the record's alleles (hipstr_record_alleles and its host form)
+class HipstrRecordAllelesRequest(C.Structure):
+    _fields_ = [("region_start", _i32p), ("region_stop", _i32p), ("win_off", _i32p), ("window", C.c_char_p)]
+
+
+class HipstrRecordAllelesOut(C.Structure):
+    _fields_ = [("status", _i32p), ("pos", _i32p), ("left_trim", _i32p), ("right_trim", _i32p), ("allele_off", _i32p), ("alleles", C.c_void_p),
+                ("cap_alleles", C.c_int64), ("allele_bp_diff", _i32p), ("old_to_new", _i32p), ("new_to_old", _i32p),
+                ("lflank_off", _i32p), ("lflanks", C.c_void_p), ("cap_lflanks", C.c_int64), ("rflank_off", _i32p), ("rflanks", C.c_void_p), ("cap_rflanks", C.c_int64)]
+
+
+ALLELES_DUPLICATE, ALLELES_OUTSIDE_WINDOW, ALLELES_FLANK_ASSERT, ALLELES_DEVICE_OPTIONS, ALLELES_WIN_PAD = 1, 2, 4, 256, 40
+RECORD_ALLELES_NAMES = ("hipstr_record_alleles", "hipstr_record_alleles_host")
+
+
+def _record_alleles_sigs(lib):
+    a = [_BP, C.POINTER(HipstrRecordAllelesRequest), C.POINTER(HipstrRecordAllelesOut)]
+    _sig(lib.hipstr_record_alleles, C.c_int, a)
+    _sig(lib.hipstr_record_alleles_host, C.c_int, a)
+    _sig(lib.hipstr_debug_record_alleles_last, C.c_int, [C.POINTER(C.c_int64)])
+
+
+def alleles_window(chrom, region_start, region_stop):
+    """window[i] = chrom[region_start - 40 + i] for the bytes that exist up to region_stop + 40 (bytes; positions below 0 hold '.')."""
+    w0 = region_start - ALLELES_WIN_PAD
+    return b"." * max(0, -w0) + chrom[max(0, w0):max(0, region_stop + ALLELES_WIN_PAD)]
+
+
+def run_record_alleles(lib, loci, host=False, flanks=True, caps=None, null=()):
+    """hipstr_record_alleles (host=True: the _host form).  loci: dicts with region_start, region_stop, window (bytes) and blocks = three
+    (start, end, [option bytes]) -> list of dicts per locus (status, pos, left_trim, right_trim, alleles, bp_diff, old_to_new, new_to_old,
+    lflanks, rflanks).  caps: (alleles, lflanks, rflanks) capacities, default the header's bounds.  null: output fields to pass as NULL."""
+    _record_alleles_sigs(lib)
+    i32 = lambda x: np.ascontiguousarray(np.asarray(x, np.int32))
+    nl = len(loci)
+    starts = []; ends = []; nopts = []; off = [0]; seq = b""
+    for L in loci:
+        for st, en, opts in L["blocks"]:
+            starts.append(st); ends.append(en); nopts.append(len(opts))
+            for o in opts:
+                seq += o; off.append(len(seq))
+    keep = dict(blk_start=i32(starts), blk_end=i32(ends), blk_nopts=i32(nopts), opt_off=i32(off), seq=seq,
+                region_start=i32([L["region_start"] for L in loci]), region_stop=i32([L["region_stop"] for L in loci]),
+                win_off=i32(np.concatenate([[0], np.cumsum([len(L["window"]) for L in loci])])), window=b"".join(L["window"] for L in loci))
+    b = HipstrBatch(); b.n_loci = nl
+    for f in ("blk_start", "blk_end", "blk_nopts", "opt_off"):
+        setattr(b, f, _ptr(keep[f], _i32p))
+    b.seq = keep["seq"]
+    rq = HipstrRecordAllelesRequest(_ptr(keep["region_start"], _i32p), _ptr(keep["region_stop"], _i32p), _ptr(keep["win_off"], _i32p), keep["window"])
+    V = [len(L["blocks"][1][2]) for L in loci]; nv = sum(V)
+    n0 = sum(len(L["blocks"][0][2]) for L in loci); n2 = sum(len(L["blocks"][2][2]) for L in loci)
+    bound = lambda k: sum(sum(len(o) for o in L["blocks"][k][2]) + len(L["blocks"][k][2]) * len(L["blocks"][1][2][0]) for L in loci if L["blocks"][1][2])
+    if caps is None:
+        caps = (sum(v * (max([len(o) for o in L["blocks"][1][2]] + [0]) + len(L["window"]) + 1) for v, L in zip(V, loci)), bound(0), bound(2))
+    k = dict(status=np.full(max(nl, 1), UNTOUCHED, np.int32), pos=np.full(max(nl, 1), UNTOUCHED, np.int32), left_trim=np.full(max(nl, 1), UNTOUCHED, np.int32),
+             right_trim=np.full(max(nl, 1), UNTOUCHED, np.int32), allele_off=np.full(nv + 1, UNTOUCHED, np.int32), alleles=np.full(max(caps[0], 1), 0xEE, np.uint8),
+             allele_bp_diff=np.full(max(nv, 1), UNTOUCHED, np.int32), old_to_new=np.full(max(nv, 1), UNTOUCHED, np.int32), new_to_old=np.full(max(nv, 1), UNTOUCHED, np.int32),
+             lflank_off=np.full(n0 + 1, UNTOUCHED, np.int32), lflanks=np.full(max(caps[1], 1), 0xEE, np.uint8),
+             rflank_off=np.full(n2 + 1, UNTOUCHED, np.int32), rflanks=np.full(max(caps[2], 1), 0xEE, np.uint8))
+    o = HipstrRecordAllelesOut()
+    for f, t in HipstrRecordAllelesOut._fields_:
+        if f.startswith("cap_"):
+            setattr(o, f, int(caps[("cap_alleles", "cap_lflanks", "cap_rflanks").index(f)]))
+        elif f in null or (not flanks and f in ("lflank_off", "lflanks", "rflank_off", "rflanks")):
+            setattr(o, f, None)
+        else:
+            setattr(o, f, k[f].ctypes.data if t is C.c_void_p else k[f].ctypes.data_as(t))
+    fn = lib.hipstr_record_alleles_host if host else lib.hipstr_record_alleles
+    rc = fn(C.byref(b), C.byref(rq), C.byref(o))
+    if rc != 0:
+        e = RuntimeError("hipstr_record_alleles%s failed rc=%d: %s" % ("_host" if host else "", rc, lib.hipstr_last_error().decode()))
+        e.raw = k
+        raise e
+    out = []; v = 0; a0 = 0; a2 = 0
+    cut = lambda pool, offs, i: pool[offs[i]:offs[i + 1]].tobytes()
+    for l, L in enumerate(loci):
+        d = dict(status=int(k["status"][l]), pos=int(k["pos"][l]), left_trim=int(k["left_trim"][l]), right_trim=int(k["right_trim"][l]),
+                 alleles=[cut(k["alleles"], k["allele_off"], v + i) for i in range(V[l])], bp_diff=k["allele_bp_diff"][v:v + V[l]].tolist(),
+                 old_to_new=k["old_to_new"][v:v + V[l]].tolist(), new_to_old=k["new_to_old"][v:v + V[l]].tolist())
+        if flanks:
+            m0, m2 = len(L["blocks"][0][2]), len(L["blocks"][2][2])
+            d["lflanks"] = [cut(k["lflanks"], k["lflank_off"], a0 + i) for i in range(m0)]
+            d["rflanks"] = [cut(k["rflanks"], k["rflank_off"], a2 + i) for i in range(m2)]
+            a0 += m0; a2 += m2
+        v += V[l]
+        out.append(d)
+    return out
+
+
+def record_alleles_last(lib):
+    """hipstr_debug_record_alleles_last -> dict(loci, host_loci, bytes_up, bytes_down)."""
+    _record_alleles_sigs(lib)
+    out = (C.c_int64 * 4)()
+    assert lib.hipstr_debug_record_alleles_last(out) == 0
+    return dict(loci=int(out[0]), host_loci=int(out[1]), bytes_up=int(out[2]), bytes_down=int(out[3]))
+
+
+# ---- the genotype outputs in the record's allele order (hipstr_post_extract_vcf)
+class HipstrGtVcfOrder(C.Structure):
+    _fields_ = [("new_to_old", _i32p), ("old_to_new", _i32p), ("allele_bp_diff", _i32p), ("allele_count", _i32p), ("bp_diffs", _i32p), ("ac", _i32p)]
+
+
+def gt_offsets(pb, n_variants):
+    """(gl_off, pgl_off): [n_samp+1] starts of every sample's piece, as hipstr_gt_offsets gives them."""
+    nl = pb.struct.n_loci
+    hap = pb.a["haploid"] if pb.a["haploid"] is not None else np.zeros(nl, np.uint8)
+    gl_off = [0]; pgl_off = [0]
+    for l in range(nl):
+        V = int(n_variants[l])
+        for _ in range(int(pb.a["n_samples"][l])):
+            gl_off.append(gl_off[-1] + (V if hap[l] else V * (V + 1) // 2)); pgl_off.append(pgl_off[-1] + (V if hap[l] else V * V))
+    return np.asarray(gl_off, np.int64), np.asarray(pgl_off, np.int64)
+
+
+def run_post_extract_flat(lib, pb, n_variants, hap_to_allele, order=None, calc_gls=True, calc_pls=True, calc_phased_gls=True, pd=None,
+                          allele_bp_diff=None, allele_count=None, null=(), room_for_unrequested=True):
+    """hipstr_post_extract (order None) or hipstr_post_extract_vcf (order = (new_to_old, old_to_new), each [sum V]) on a launched run pd
+    (None: pb is uploaded, launched and freed here) -> dict of the FLAT output arrays (gl_off / pgl_off say where a sample's piece lies);
+    what the call leaves untouched holds UNTOUCHED / NaN.  With an order also bp_diffs / ac when their inputs are given.  null: names of
+    the order's fields to pass as NULL.  room_for_unrequested=False: an array that is not requested gets one element (the timing tools)."""
+    _sig(lib.hipstr_post_extract, C.c_int, [C.c_void_p, C.POINTER(HipstrGtRequest), C.POINTER(HipstrGtOut)])
+    _sig(lib.hipstr_post_extract_vcf, C.c_int, [C.c_void_p, C.POINTER(HipstrGtRequest), C.POINTER(HipstrGtVcfOrder), C.POINTER(HipstrGtOut)])
+    i32 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, np.int32))
+    S = int(pb.samp_off[-1])
+    nv = i32(n_variants); h2a = i32(hap_to_allele)
+    rq = HipstrGtRequest(_ptr(nv, _i32p), _ptr(h2a, _i32p), int(calc_gls), int(calc_pls), int(calc_phased_gls))
+    gl_off, pgl_off = gt_offsets(pb, nv)
+    k = dict(best_hap=np.full(max(2 * S, 2), UNTOUCHED, np.int32), best_gt=np.full(max(2 * S, 2), UNTOUCHED, np.int32))
+    for nm in ("log_phased_post", "log_unphased_post", "hap_log_phased_post", "hap_log_unphased_post", "gl_diff"):
+        k[nm] = np.full(max(S, 1), np.nan)
+    room = lambda want, n: max(int(n), 1) if (want or room_for_unrequested) else 1
+    k["gls"] = np.full(room(calc_gls, gl_off[-1]), np.nan); k["pls"] = np.full(room(calc_pls, gl_off[-1]), UNTOUCHED, np.int32)
+    k["phased_gls"] = np.full(room(calc_phased_gls, pgl_off[-1]), np.nan)
+    o = HipstrGtOut(*[k[f].ctypes.data_as(t) for f, t in HipstrGtOut._fields_])
+    tot_v = int(nv.sum())
+    keep = None
+    if order is not None:
+        keep = dict(new_to_old=i32(order[0]), old_to_new=i32(order[1]), allele_bp_diff=i32(allele_bp_diff), allele_count=i32(allele_count),
+                    bp_diffs=np.full(max(tot_v, 1), UNTOUCHED, np.int32), ac=np.full(max(tot_v, 1), UNTOUCHED, np.int32))
+        od = HipstrGtVcfOrder(*[None if f in null else _ptr(keep[f], t) for f, t in HipstrGtVcfOrder._fields_])
+    own = pd is None
+    if own:
+        pd = lib.hipstr_post_upload(pb.ptr, None)
+        if not pd:
+            raise RuntimeError("hipstr_post_upload failed: " + lib.hipstr_last_error().decode())
+    try:
+        if own and lib.hipstr_post_launch(pd, None) != 0:
+            raise RuntimeError("hipstr_post_launch failed: " + lib.hipstr_last_error().decode())
+        rc = lib.hipstr_post_extract(pd, C.byref(rq), C.byref(o)) if order is None else lib.hipstr_post_extract_vcf(pd, C.byref(rq), C.byref(od), C.byref(o))
+    finally:
+        if own:
+            lib.hipstr_post_free(pd)
+    if rc != 0:
+        e = RuntimeError("hipstr_post_extract%s failed rc=%d: %s" % ("" if order is None else "_vcf", rc, lib.hipstr_last_error().decode()))
+        e.raw = dict(k, **({} if keep is None else dict(bp_diffs=keep["bp_diffs"], ac=keep["ac"])))
+        raise e
+    out = dict(best_hap=k["best_hap"][:2 * S].reshape(-1, 2), best_gt=k["best_gt"][:2 * S].reshape(-1, 2), gl_off=gl_off, pgl_off=pgl_off)
+    for nm in ("log_phased_post", "log_unphased_post", "hap_log_phased_post", "hap_log_unphased_post", "gl_diff"):
+        out[nm] = k[nm][:S]
+    out["gls"] = k["gls"][:int(gl_off[-1])]; out["pls"] = k["pls"][:int(gl_off[-1])]; out["phased_gls"] = k["phased_gls"][:int(pgl_off[-1])]
+    if keep is not None:
+        out["bp_diffs"] = keep["bp_diffs"][:tot_v]; out["ac"] = keep["ac"][:tot_v]
+    return out
+
+
+# ---- the record's per-read sizes and per-sample histograms (hipstr_cigar_bp_diffs, hipstr_sample_histograms, hipstr_em_batch_from_bp_diffs)
+class HipstrCigarRequest(C.Structure):
+    _fields_ = [("n_loci", C.c_int32), ("read_off", _i32p), ("read_start", _i32p), ("cigar_off", _i32p), ("cigar_op", _u8p), ("cigar_len", _i32p),
+                ("region_start", _i32p), ("region_stop", _i32p), ("pad", _i32p)]
+
+
+CIGAR_DEVICE_RUNS = 4096
+HISTOGRAM_DEVICE_READS = 1024
+NO_ML_BP = -2 ** 31
+RECORD_READS_NAMES = ("hipstr_cigar_bp_diffs", "hipstr_cigar_bp_diffs_host", "hipstr_sample_histograms", "hipstr_sample_histograms_host",
+                      "hipstr_em_batch_from_bp_diffs")
+
+
+def _record_reads_sigs(lib):
+    cg = [C.POINTER(HipstrCigarRequest), _u8p, _i32p]
+    _sig(lib.hipstr_cigar_bp_diffs, C.c_int, cg)
+    _sig(lib.hipstr_cigar_bp_diffs_host, C.c_int, cg)
+    hs = [_PBP, _i32p, C.c_int32, _i32p, _i32p, _i32p]
+    _sig(lib.hipstr_sample_histograms, C.c_int, hs)
+    _sig(lib.hipstr_sample_histograms_host, C.c_int, hs)
+    _sig(lib.hipstr_em_batch_from_bp_diffs, C.c_int, [_PBP, _u8p, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _f64p, _f64p, _u8p])
+    _sig(lib.hipstr_debug_record_reads_last, C.c_int, [C.POINTER(C.c_int64)])
+
+
+def cigar_request(loci):
+    """loci: per locus (region_start, region_stop, pad, reads) with reads = [(start, [(op letter, length), ...]), ...] -> dict of the
+    request's arrays."""
+    read_off = [0]; start = []; coff = [0]; ops = []; lens = []
+    for _, _, _, reads in loci:
+        for s, runs in reads:
+            start.append(s)
+            ops += [ord(o) for o, _ in runs]; lens += [n for _, n in runs]
+            coff.append(len(ops))
+        read_off.append(len(start))
+    i32 = lambda x: np.ascontiguousarray(np.asarray(x, np.int64).astype(np.int32))
+    return dict(n_loci=len(loci), read_off=i32(read_off), read_start=i32(start), cigar_off=i32(coff), cigar_op=np.asarray(ops, np.uint8), cigar_len=i32(lens),
+                region_start=i32([l[0] for l in loci]), region_stop=i32([l[1] for l in loci]), pad=i32([l[2] for l in loci]))
+
+
+def run_cigar_bp_diffs(lib, rq, host=False, null=()):
+    """hipstr_cigar_bp_diffs (host=True: the _host form) on a dict of cigar_request's arrays -> (got, bp_diff); what the call leaves untouched
+    holds 0xEE / UNTOUCHED.  null: names of the request's arrays to pass as NULL, or "got" / "bp_diff"."""
+    _record_reads_sigs(lib)
+    n = int(rq["read_off"][-1])
+    got = np.full(max(n, 1), 0xEE, np.uint8); bp = np.full(max(n, 1), UNTOUCHED, np.int32)
+    st = HipstrCigarRequest(int(rq["n_loci"]), *[None if f in null else _ptr(rq[f], t) for f, t in HipstrCigarRequest._fields_[1:]])
+    fn = lib.hipstr_cigar_bp_diffs_host if host else lib.hipstr_cigar_bp_diffs
+    rc = fn(C.byref(st), None if "got" in null else _ptr(got, _u8p), None if "bp_diff" in null else _ptr(bp, _i32p))
+    if rc != 0:
+        e = RuntimeError("hipstr_cigar_bp_diffs%s failed rc=%d: %s" % ("_host" if host else "", rc, lib.hipstr_last_error().decode()))
+        e.raw = (got, bp)
+        raise e
+    return got[:n], bp[:n]
+
+
+def run_sample_histograms(lib, pb, value, skip, host=False):
+    """hipstr_sample_histograms (host=True: the _host form) on the sample layout of the PostBatch pb -> (pair_off, hist_value, hist_count),
+    the two pair arrays cut to pair_off[-1]; raw holds the whole buffers (UNTOUCHED where the call wrote nothing)."""
+    _record_reads_sigs(lib)
+    n = int(pb.struct.read_off[int(pb.struct.n_loci)]) if pb.struct.n_loci else 0
+    ns = int(pb.samp_off[-1])
+    v = None if value is None else np.ascontiguousarray(np.asarray(value, np.int32))
+    po = np.full(ns + 1, UNTOUCHED, np.int32); hv = np.full(max(n, 1), UNTOUCHED, np.int32); hc = np.full(max(n, 1), UNTOUCHED, np.int32)
+    fn = lib.hipstr_sample_histograms_host if host else lib.hipstr_sample_histograms
+    rc = fn(pb.ptr, _ptr(v, _i32p), int(skip), _ptr(po, _i32p), _ptr(hv, _i32p), _ptr(hc, _i32p))
+    if rc != 0:
+        e = RuntimeError("hipstr_sample_histograms%s failed rc=%d: %s" % ("_host" if host else "", rc, lib.hipstr_last_error().decode()))
+        e.raw = (po, hv, hc)
+        raise e
+    assert np.all(hv[po[-1]:] == UNTOUCHED) and np.all(hc[po[-1]:] == UNTOUCHED), "written behind the last pair"
+    return po, hv[:po[-1]], hc[:po[-1]]
+
+
+def em_batch_from_bp_diffs(lib, pb, got, bp_diff, region_start, region_stop, min_total_reads):
+    """hipstr_em_batch_from_bp_diffs -> dict(read_off, sample_label, num_bps, log_p1, log_p2, too_few)."""
+    _record_reads_sigs(lib)
+    nl = int(pb.struct.n_loci)
+    n = int(pb.struct.read_off[nl]) if nl else 0
+    g = np.ascontiguousarray(np.asarray(got, np.uint8)); b = np.ascontiguousarray(np.asarray(bp_diff, np.int32))
+    rs = np.ascontiguousarray(np.asarray(region_start, np.int32)); re_ = np.ascontiguousarray(np.asarray(region_stop, np.int32))
+    ro = np.full(nl + 1, UNTOUCHED, np.int32); sl = np.full(max(n, 1), UNTOUCHED, np.int32); nb = np.full(max(n, 1), UNTOUCHED, np.int32)
+    p1 = np.full(max(n, 1), np.nan); p2 = np.full(max(n, 1), np.nan); few = np.full(max(nl, 1), 0xEE, np.uint8)
+    rc = lib.hipstr_em_batch_from_bp_diffs(pb.ptr, _ptr(g, _u8p), _ptr(b, _i32p), _ptr(rs, _i32p), _ptr(re_, _i32p), int(min_total_reads),
+                                           _ptr(ro, _i32p), _ptr(sl, _i32p), _ptr(nb, _i32p), _ptr(p1, _f64p), _ptr(p2, _f64p), _ptr(few, _u8p))
+    if rc != 0:
+        raise RuntimeError("hipstr_em_batch_from_bp_diffs failed rc=%d: %s" % (rc, lib.hipstr_last_error().decode()))
+    m = int(ro[-1])
+    return dict(read_off=ro, sample_label=sl[:m], num_bps=nb[:m], log_p1=p1[:m], log_p2=p2[:m], too_few=few[:nl])
+
+
+def record_reads_last(lib):
+    """hipstr_debug_record_reads_last -> dict(items, host_items, bytes_up, bytes_down)."""
+    _record_reads_sigs(lib)
+    out = (C.c_int64 * 4)()
+    assert lib.hipstr_debug_record_reads_last(out) == 0
+    return dict(items=int(out[0]), host_items=int(out[1]), bytes_up=int(out[2]), bytes_down=int(out[3]))
+
+
 class HipstrPoolOut(C.Structure):
     _fields_ = [("pool_index", _i32p), ("n_pools", _i32p), ("pool_off", _i32p), ("pool_rep", _i32p), ("pool_size", _i32p),
                 ("pool_qual_off", _i32p), ("pool_quals", C.POINTER(C.c_char))]

@@ -39,6 +39,8 @@ extern "C" __global__ void hs_posterior_kernel(const hs_post_dev_t* dp);
 extern "C" __global__ void hs_posterior_accumulate_kernel(const hs_post_dev_t* dp);
 extern "C" __global__ void hs_posterior_finish_kernel(const hs_post_dev_t* dp);
 extern "C" __global__ void hs_genotype_kernel(const hs_gt_dev_t* dp);
+extern "C" __global__ void hs_gt_permute_kernel(const hs_gt_perm_dev_t* dp);
+extern "C" __global__ void hs_gt_gather_kernel(const hs_gt_perm_dev_t* dp);
 extern "C" __global__ void hs_cr_math_kernel(int which, const double* x, double* y, int64_t n);
 extern "C" __global__ void hs_float_fn_kernel(int which, uint32_t bits_lo, int64_t count, uint32_t* out);
 extern "C" __global__ void hs_fast_lse2_kernel(const double* a, const double* b, double* out, int64_t n, double thr);
@@ -1852,7 +1854,9 @@ int hipstr_gt_offsets(const hipstr_post_batch_t* pb, const hipstr_gt_request_t* 
   return 0;
 }
 
-int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hipstr_gt_out_t* out){
+// hipstr_post_extract (order == NULL) and hipstr_post_extract_vcf: the same units, launch and fetches; with an order, hs_gt_permute_kernel
+// runs behind the genotype kernel and the fetches read its pieces.
+static int post_extract_run(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, const hipstr_gt_vcf_order_t* order, hipstr_gt_out_t* out){
   hipstr::ApiTimer prof_t(hipstr::PB_POST_EXTRACT);
   if (!pd || !rq || !out || !rq->n_variants || !rq->hap_to_allele) return fail("null argument");
   if (!out->best_hap || !out->best_gt || !out->log_phased_post || !out->log_unphased_post || !out->hap_log_phased_post || !out->hap_log_unphased_post)
@@ -1896,21 +1900,59 @@ int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hi
     }
     po += (int64_t)S*A*A; map_off += A;
   }
-  if (units.empty()) return 0;
+  // the VCF order: per locus a permutation with the reference allele first and its inverse; per unit where its locus' entries begin
+  std::vector<int32_t> unit_var, n2o_abs;
+  size_t n_var = 0;
+  if (order){
+    if (!order->new_to_old || !order->old_to_new) return fail("null argument");
+    if ((order->allele_bp_diff && !order->bp_diffs) || (order->allele_count && !order->ac)) return fail("requested output array missing");
+    unit_var.reserve(units.size());
+    for (size_t l = 0; l < n_loci; l++){
+      const int V = rq->n_variants[l];
+      const int32_t* n2o = order->new_to_old + n_var; const int32_t* o2n = order->old_to_new + n_var;
+      if (n2o[0] != 0) return fail("hipstr_post_extract_vcf: new_to_old[0] must be 0 (the reference allele stays first)");
+      for (int i = 0; i < V; i++){
+        if (n2o[i] < 0 || n2o[i] >= V || o2n[n2o[i]] != i) return fail("hipstr_post_extract_vcf: new_to_old is not a permutation with old_to_new its inverse");
+        n2o_abs.push_back((int32_t)n_var + n2o[i]);
+      }
+      for (int s = 0; s < pd->n_samples[l]; s++) unit_var.push_back((int32_t)n_var);
+      n_var += (size_t)V;
+    }
+  }
+  if (units.empty()){
+    if (order) for (size_t v = 0; v < n_var; v++){
+      if (order->allele_bp_diff) order->bp_diffs[v] = order->allele_bp_diff[n2o_abs[v]];
+      if (order->allele_count) order->ac[v] = order->allele_count[n2o_abs[v]];
+    }
+    return 0;
+  }
   lap("units");
   if (bind(R.ctx)) return 1;
   Ctx* ctx = R.ctx;
   hs_gt_dev_t h; memset(&h, 0, sizeof h);
+  hs_gt_perm_dev_t hp; memset(&hp, 0, sizeof hp);
   hipstr::HostArena ar;
   const size_t o_units = ar.add(units.data(), units.size()*sizeof(hs_gt_unit_t)), o_h2a = ar.add(rq->hap_to_allele, (size_t)map_off*4),
                o_gmem = ar.add(gmem.data(), gmem.size()*4), o_goff = ar.add(goff.data(), goff.size()*4), o_args = ar.add(&h, sizeof h);
+  size_t o_uvar = 0, o_n2o = 0, o_o2n = 0, o_abs = 0, o_bp = 0, o_ac = 0, o_pargs = 0;
+  if (order){
+    o_uvar = ar.add(unit_var.data(), unit_var.size()*4); o_n2o = ar.add(order->new_to_old, n_var*4); o_o2n = ar.add(order->old_to_new, n_var*4);
+    o_abs = ar.add(n2o_abs.data(), n_var*4);
+    if (order->allele_bp_diff) o_bp = ar.add(order->allele_bp_diff, n_var*4);
+    if (order->allele_count) o_ac = ar.add(order->allele_count, n_var*4);
+    o_pargs = ar.add(&hp, sizeof hp);
+  }
   if (ar.reserve(ctx)) return 1;
   // the per-sample results, back to back (one copy home); then the variant pairs' totals and the optional outputs, which can be large
   hipstr::ResultBlocks B;
   const size_t r_hap = B.take((size_t)so*2*4), r_gt = B.take((size_t)so*2*4), r_five = B.take((size_t)so*5*8);
+  const size_t r_bp = order && order->allele_bp_diff ? B.take(n_var*4) : 0, r_ac = order && order->allele_count ? B.take(n_var*4) : 0;
   B.end_results();
   const size_t d_tot = B.take((size_t)tot*8), d_gls = any ? B.take((size_t)g*8) : 0, d_pls = rq->calc_pls ? B.take((size_t)g*4) : 0,
                d_pgls = rq->calc_phased_gls ? B.take((size_t)pg*8) : 0;
+  // the same three in the VCF order (only what is asked for travels)
+  const size_t v_gls = order && rq->calc_gls ? B.take((size_t)g*8) : 0, v_pls = order && rq->calc_pls ? B.take((size_t)g*4) : 0,
+               v_pgls = order && rq->calc_phased_gls ? B.take((size_t)pg*8) : 0;
   if (B.reserve(ctx, R.stream)) return 1;
   h.units = ar.at<hs_gt_unit_t>(o_units); h.h2a = ar.at<int32_t>(o_h2a); h.gmem = ar.at<int32_t>(o_gmem); h.goff = ar.at<int32_t>(o_goff);
   h.log_post = R.h.log_post; h.sample_total = R.h.sample_total; h.map_gt = R.h.map_gt;
@@ -1944,10 +1986,28 @@ int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hi
     HS_HIP(hipMemcpy(h.tot, h_tot.data(), sizeof(double)*(size_t)tot, hipMemcpyHostToDevice));
     h.tot_given = 1;
   }
+  if (order){
+    hp.units = h.units; hp.unit_var = ar.at<int32_t>(o_uvar); hp.new_to_old = ar.at<int32_t>(o_n2o); hp.old_to_new = ar.at<int32_t>(o_o2n);
+    hp.n2o_abs = ar.at<int32_t>(o_abs); hp.n_var = (int32_t)n_var;
+    hp.gls = h.gls; hp.pls = h.pls; hp.pgls = h.pgls; hp.best_gt = h.best_gt;
+    if (rq->calc_gls) hp.gls_out = B.dev<double>(v_gls);
+    if (rq->calc_pls) hp.pls_out = B.dev<int32_t>(v_pls);
+    if (rq->calc_phased_gls) hp.pgls_out = B.dev<double>(v_pgls);
+    if (order->allele_bp_diff){ hp.bp_in = ar.at<int32_t>(o_bp); hp.bp_out = B.dev<int32_t>(r_bp); }
+    if (order->allele_count){ hp.ac_in = ar.at<int32_t>(o_ac); hp.ac_out = B.dev<int32_t>(r_ac); }
+  }
   if (pd->foreign_stream) HS_HIP(hipDeviceSynchronize());          // the posterior kernel may still be running on a stream of the caller's
   if (ar.send(R.stream)) return 1;                                 // (the argument block is complete by now)
   hipLaunchKernelGGL(hs_genotype_kernel, dim3((unsigned)units.size()), dim3(256), 0, R.stream, (const hs_gt_dev_t*)ar.at<hs_gt_dev_t>(o_args));
   HS_HIP(hipGetLastError());
+  if (order){
+    hipLaunchKernelGGL(hs_gt_permute_kernel, dim3((unsigned)units.size()), dim3(256), 0, R.stream, (const hs_gt_perm_dev_t*)ar.at<hs_gt_perm_dev_t>(o_pargs));
+    HS_HIP(hipGetLastError());
+    if (order->allele_bp_diff || order->allele_count){
+      hipLaunchKernelGGL(hs_gt_gather_kernel, dim3((unsigned)((n_var + 255)/256)), dim3(256), 0, R.stream, (const hs_gt_perm_dev_t*)ar.at<hs_gt_perm_dev_t>(o_pargs));
+      HS_HIP(hipGetLastError());
+    }
+  }
   HS_HIP(hipMemcpyAsync(B.dev<char>(r_hap), R.h.map_gt, (size_t)so*2*4, hipMemcpyDeviceToDevice, R.stream));       // best_hap travels with the rest
   lap("setup");
   if (B.fetch()) return 1;
@@ -1957,18 +2017,27 @@ int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hi
   memcpy(out->log_phased_post, hf, (size_t)so*8); memcpy(out->log_unphased_post, hf + so, (size_t)so*8);
   if (host_libm)                                          // the exact pair log_sum_exp of the two phasings (mathops.cpp:52-57) with the host libm
     for (const hs_gt_unit_t& u : units){
-      const int ga = out->best_gt[2*u.samp_index], gb = out->best_gt[2*u.samp_index+1];
+      int ga = out->best_gt[2*u.samp_index], gb = out->best_gt[2*u.samp_index+1];
       if (ga < 0 || gb < 0 || ga == gb) continue;
+      if (order){ const int32_t* n2o = order->new_to_old + unit_var[u.samp_index]; ga = n2o[ga]; gb = n2o[gb]; }       // h_tot is in block-option order
       const double lp = h_tot[u.tot_off + (int64_t)u.n_variants*ga + gb], alt = h_tot[u.tot_off + (int64_t)u.n_variants*gb + ga];
       out->log_unphased_post[u.samp_index] = (lp > alt) ? lp + log(1 + exp(alt - lp)) : alt + log(1 + exp(lp - alt));
     }
   memcpy(out->hap_log_phased_post, hf + 2*(size_t)so, (size_t)so*8); memcpy(out->hap_log_unphased_post, hf + 3*(size_t)so, (size_t)so*8);
   if (any) memcpy(out->gl_diff, hf + 4*(size_t)so, (size_t)so*8);
-  if (rq->calc_gls && fetch_array(ctx, R.stream, out->gls, h.gls, (size_t)g*8)) return 1;
-  if (rq->calc_pls && fetch_array(ctx, R.stream, out->pls, h.pls, (size_t)g*4)) return 1;
-  if (rq->calc_phased_gls && fetch_array(ctx, R.stream, out->phased_gls, h.pgls, (size_t)pg*8)) return 1;
+  if (order && order->allele_bp_diff) memcpy(order->bp_diffs, B.host<char>(r_bp), n_var*4);
+  if (order && order->allele_count) memcpy(order->ac, B.host<char>(r_ac), n_var*4);
+  if (rq->calc_gls && fetch_array(ctx, R.stream, out->gls, order ? hp.gls_out : h.gls, (size_t)g*8)) return 1;
+  if (rq->calc_pls && fetch_array(ctx, R.stream, out->pls, order ? hp.pls_out : h.pls, (size_t)g*4)) return 1;
+  if (rq->calc_phased_gls && fetch_array(ctx, R.stream, out->phased_gls, order ? hp.pgls_out : h.pgls, (size_t)pg*8)) return 1;
   lap("fetch");
   return 0;
+}
+
+int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hipstr_gt_out_t* out){ return post_extract_run(pd, rq, NULL, out); }
+int hipstr_post_extract_vcf(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, const hipstr_gt_vcf_order_t* order, hipstr_gt_out_t* out){
+  if (!order) return fail("null argument");
+  return post_extract_run(pd, rq, order, out);
 }
 
 // ----------------------------------------------------------------------------- read assignment

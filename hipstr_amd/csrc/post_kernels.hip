@@ -426,3 +426,55 @@ extern "C" __global__ void __launch_bounds__(64) hs_fast_lse_vec_kernel(const do
   }
   out[r] = lse.finish();
 }
+
+// hipstr_post_extract_vcf: one workgroup per sample, behind hs_genotype_kernel on the same stream.  Pure copies: entry (i, j), j <= i, of the
+// VCF-ordered triangle comes from b(b+1)/2 + a with a <= b the two old indices (seq_stutter_genotyper.cpp:1450-1470); a haploid sample's
+// entry i from new_to_old[i] (:1436-1447); PHASEDGL (i, j) from new_to_old[i]*V + new_to_old[j] (:1472-1481).
+extern "C" __global__ void __launch_bounds__(256)
+hs_gt_permute_kernel(const hs_gt_perm_dev_t* __restrict__ dp){
+  const hs_gt_perm_dev_t& d = *dp;
+  const hs_gt_unit_t u = d.units[blockIdx.x];
+  const int V = u.n_variants, tid = threadIdx.x;
+  const int32_t* n2o = d.new_to_old + d.unit_var[blockIdx.x];
+  if (tid < 2){
+    const int g = d.best_gt[2*(int64_t)u.samp_index + tid];
+    if (g >= 0 && g < V) d.best_gt[2*(int64_t)u.samp_index + tid] = d.old_to_new[d.unit_var[blockIdx.x] + g];
+  }
+  if (u.haploid){
+    for (int i = tid; i < V; i += 256){
+      const int64_t to = u.gl_off + i, from = u.gl_off + n2o[i];
+      if (d.gls_out) d.gls_out[to] = d.gls[from];
+      if (d.pls_out) d.pls_out[to] = d.pls[from];
+      if (d.pgls_out) d.pgls_out[u.pgl_off + i] = d.pgls[u.pgl_off + n2o[i]];
+    }
+    return;
+  }
+  if (d.gls_out || d.pls_out){
+    const int64_t n = (int64_t)V*(V + 1)/2;
+    for (int64_t k = tid; k < n; k += 256){
+      const int i = hs_gt_tri_row(k), j = (int)(k - (int64_t)i*(i + 1)/2);
+      const int x = n2o[i], y = n2o[j], a = x < y ? x : y, b = x < y ? y : x;
+      const int64_t from = u.gl_off + (int64_t)b*(b + 1)/2 + a;
+      if (d.gls_out) d.gls_out[u.gl_off + k] = d.gls[from];
+      if (d.pls_out) d.pls_out[u.gl_off + k] = d.pls[from];
+    }
+  }
+  if (d.pgls_out){
+    const int64_t n = (int64_t)V*V;
+    for (int64_t k = tid; k < n; k += 256){
+      const int i = (int)(k/V), j = (int)(k - (int64_t)i*V);
+      d.pgls_out[u.pgl_off + k] = d.pgls[u.pgl_off + (int64_t)n2o[i]*V + n2o[j]];
+    }
+  }
+}
+
+// BPDIFFS and AC in the new order: one lane per variant
+extern "C" __global__ void __launch_bounds__(256)
+hs_gt_gather_kernel(const hs_gt_perm_dev_t* __restrict__ dp){
+  const hs_gt_perm_dev_t& d = *dp;
+  const int64_t v = (int64_t)blockIdx.x*256 + threadIdx.x;
+  if (v >= d.n_var) return;
+  const int from = d.n2o_abs[v];
+  if (d.bp_out) d.bp_out[v] = d.bp_in[from];
+  if (d.ac_out) d.ac_out[v] = d.ac_in[from];
+}

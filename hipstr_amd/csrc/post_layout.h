@@ -1,5 +1,6 @@
 // post_layout.h — device-side description of a posterior batch (post_kernels.hip, api.hip).
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -92,6 +93,28 @@ struct hs_gt_dev_t {
   double   log_thresh;
   int32_t  tot_given;            // HIPSTR_DEBUG_HOST_LIBM: `tot` (and log_unphased) come from the host
 };
+
+// hipstr_post_extract_vcf: the genotype kernel's GL / PL / PHASEDGL pieces gathered into the sorted allele order of the record
+// (seq_stutter_genotyper.cpp:1436-1481), best_gt renumbered in place, and the per-variant BPDIFFS / AC gathers
+struct hs_gt_perm_dev_t {
+  const hs_gt_unit_t* units;      // the genotype kernel's
+  const int32_t* unit_var;        // [n_units] where the unit's locus begins in the per-variant arrays
+  const int32_t *new_to_old, *old_to_new;      // [sum V], per locus
+  const int32_t* n2o_abs;         // [sum V] new_to_old plus the locus' begin
+  const double* gls; const int32_t* pls; const double* pgls;      // block-option order
+  double* gls_out; int32_t* pls_out; double* pgls_out;            // VCF order; NULL = not asked for
+  int32_t* best_gt;               // [2*n_samp]
+  const int32_t *bp_in, *ac_in;   // [sum V] or NULL
+  int32_t *bp_out, *ac_out;
+  int32_t n_var;
+};
+// row i of the lower triangle that holds entry k (k = i(i+1)/2 + j, j <= i): the square root is within one of it
+HS_POST_HD inline int hs_gt_tri_row(int64_t k){
+  int i = (int)((sqrt(8.0*(double)k + 1.0) - 1.0)*0.5);
+  if ((int64_t)(i + 1)*(i + 2)/2 <= k) i++;
+  if ((int64_t)i*(i + 1)/2 > k) i--;
+  return i;
+}
 
 // ---- read assignment (assign.hip, hipstr_post_assign): SeqStutterGenotyper::write_vcf_record's per-read loop (seq_stutter_genotyper.cpp:1079-1157)
 // and retrace_alignments' pick (:805-841) on the resident MAP pairs.  The unit is hs_post_unit_t again; lanes are reads.

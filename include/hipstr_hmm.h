@@ -360,6 +360,33 @@ int hipstr_gt_offsets(const hipstr_post_batch_t* pb, const hipstr_gt_request_t* 
 int hipstr_post_extract(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, hipstr_gt_out_t* out);
 
 /*
+ * hipstr_post_extract with its outputs in the allele order of the VCF record: SeqStutterGenotyper::write_vcf_record renumbers the
+ * genotypes and gathers every sample's GL / PL / PHASEDGL through reorder_alleles' maps (seq_stutter_genotyper.cpp:673-689, :1436-1481).
+ * The extraction kernel runs unchanged; a permutation kernel behind it on the same stream writes the requested arrays in the new order
+ * before they are fetched, so no host gather is left.  Per locus new_to_old is a permutation of [0, V) with new_to_old[0] == 0 (the
+ * reference allele stays first) and old_to_new its inverse.  Against hipstr_post_extract's outputs (same request):
+ *   best_gt            old_to_new[best_gt]; -1 stays
+ *   gls, pls diploid   entry i(i+1)/2 + j, j <= i, = the old entry b(b+1)/2 + a with a = min(new_to_old[i], new_to_old[j]), b = their max (:1450-1470)
+ *   gls, pls haploid   entry i = the old entry new_to_old[i]                                                                (:1436-1447)
+ *   phased_gls         entry i*V + j = the old entry new_to_old[i]*V + new_to_old[j]; haploid: entry i = old new_to_old[i]   (:1472-1481)
+ * Every double is a copy: its bits are hipstr_post_extract's.  best_hap and the per-sample posteriors and gl_diff do not depend on the
+ * order.  With allele_bp_diff / allele_count (block-option order; hipstr_record_fields' allele_count) the same call returns them in the new
+ * order: bp_diffs[i] = allele_bp_diff[new_to_old[i]] (BPDIFFS: the entries i >= 1, :1047-1050) and ac[i] = allele_count[new_to_old[i]]
+ * (AC: i >= 1; REFAC = ac[0] = allele_count[0], :1261-1266).  An identity order reproduces hipstr_post_extract byte for byte.
+ * Refused, nothing written: what hipstr_post_extract refuses, a null order, new_to_old[0] != 0, a new_to_old that is no permutation or
+ * an old_to_new that is not its inverse, allele_bp_diff without bp_diffs, allele_count without ac.
+ */
+typedef struct hipstr_gt_vcf_order {
+  const int32_t* new_to_old;      /* [sum V_l]                                                                        */
+  const int32_t* old_to_new;      /* [sum V_l]                                                                        */
+  const int32_t* allele_bp_diff;  /* [sum V_l] block-option order, or NULL                                            */
+  const int32_t* allele_count;    /* [sum V_l] block-option order, or NULL                                            */
+  int32_t*       bp_diffs;        /* [sum V_l] out, with allele_bp_diff                                               */
+  int32_t*       ac;              /* [sum V_l] out, with allele_count                                                 */
+} hipstr_gt_vcf_order_t;
+int hipstr_post_extract_vcf(hipstr_post_dev_t* pd, const hipstr_gt_request_t* rq, const hipstr_gt_vcf_order_t* order, hipstr_gt_out_t* out);
+
+/*
  * De novo stutter model: EMStutterGenotyper::train (em_stutter_genotyper.cpp:146-226) with its E-step
  * (calc_hap_aln_probs :146-150, Genotyper::calc_log_sample_posteriors under the allele-frequency priors of :129-144,
  * recalc_log_read_phase_posteriors :152-169) and M-step (recalc_log_gt_priors :22-57, recalc_stutter_model :64-127), batched
@@ -724,6 +751,129 @@ typedef struct hipstr_record_out {
 } hipstr_record_out_t;
 int hipstr_record_fields(hipstr_post_dev_t* pd, const hipstr_record_request_t* rq, hipstr_record_out_t* out);
 int hipstr_record_fields_host(const hipstr_post_batch_t* pb, const int32_t* map_gt, const hipstr_record_request_t* rq, hipstr_record_out_t* out);
+
+/*
+ * The alleles of a VCF record: SeqStutterGenotyper::get_alleles (seq_stutter_genotyper.cpp:691-769) and reorder_alleles (:673-689) on the
+ * options of block 1 of every locus of a batch (only n_loci, blk_start, blk_end, blk_nopts, opt_off and seq are read), with the base pair
+ * differences of :1047-1050 and, on request, the LFLANKS / RFLANKS option strings of :1018-1040.  chrom_seq is given as
+ * hipstr_hapgen_request_t gives it: window[win_off[l] + i] = chrom_seq[region_start - 40 + i], any case, win_off[l+1] - win_off[l] bytes
+ * (region_stop + 40 - (region_start - 40) in the middle of a chromosome); a position below 0 or not among those bytes is outside.  Per locus:
+ *   left trim    while start + left_trim < region_start: stop at the first option with left_trim + 1 >= size or a byte other than option
+ *                0's at left_trim (:703-713); right trim mirrored, every option indexed from its own end (:721-733)
+ *   flanks       left_flank = upper(chrom_seq[region_start, start)) only when the trimmed start >= region_start, right_flank =
+ *                upper(chrom_seq[end, region_stop)) only when the trimmed end <= region_stop (:738-739); pos = min(region_start, start)
+ *   pad          only with an empty left flank, when an option i >= 1 is empty or begins with another byte than option 0 (an empty
+ *                option 0 begins with 0): pos - 1, and upper(chrom_seq[pos]) in front of every allele (:745-758)
+ *   outputs      pos (1-based, :766); left_trim / right_trim = the returned pair (flank lengths and the pad subtracted, :741-742, :755);
+ *                the V strings left_flank + option + right_flank in block-option order at alleles[allele_off[..]]; allele_bp_diff =
+ *                size - size of allele 0; new_to_old / old_to_new: allele 0 first, the rest by (length, then bytes as unsigned char)
+ *                (stringops.cpp:35-39)
+ * status[l]: 0; HIPSTR_ALLELES_DUPLICATE: two equal allele strings (the reference's map loses an index there: no guess is made);
+ * HIPSTR_ALLELES_OUTSIDE_WINDOW: the rule would read chrom_seq outside the window or before base 0.  A failed locus has zero-length
+ * outputs (its V entries of allele_off repeat, its maps and bp_diffs hold -1 / 0, pos and trims 0).  With lflank_off / rflank_off given,
+ * the options of block 0 cut by, or extended with, the first left_trim bases of the reference STR option (:1020-1028), and those of block
+ * 2 likewise from the other end (:1032-1040); where an assert of :1015-1016, :1023, :1035 would fire, or right_trim < 0 (the reference's
+ * substr(trim) throws there), HIPSTR_ALLELES_FLANK_ASSERT is or-ed into status and the locus' flank strings are empty.
+ * Room: alleles needs sum over loci of V_l * (longest option of block 1 + window length + 1) bytes at most (cap_alleles is checked against
+ * what is written); lflanks / rflanks the options' bytes plus, per option, the reference STR option's length.
+ * The device form (hipstr_record_alleles) runs one wavefront per locus: lanes over the options for every position's test with a
+ * wave-wide AND, every option's rank by counting the options that sort before it; a locus of more than HIPSTR_ALLELES_DEVICE_OPTIONS
+ * options takes the host form inside the same call, and the flank strings are cut on the host in both forms.  Equal to
+ * hipstr_record_alleles_host (no device needed) byte for byte, which equals the compiled reference (tests/golden/record_alleles_*.npz).
+ * Refused, nothing written: null arguments, region_stop < region_start, a block 1 without options, offsets that do not ascend, a
+ * capacity that is too small.
+ */
+#define HIPSTR_ALLELES_DUPLICATE        1
+#define HIPSTR_ALLELES_OUTSIDE_WINDOW   2
+#define HIPSTR_ALLELES_FLANK_ASSERT     4
+#define HIPSTR_ALLELES_DEVICE_OPTIONS 256
+typedef struct hipstr_record_alleles_request {
+  const int32_t* region_start;    /* [n_loci]                                                                 */
+  const int32_t* region_stop;     /* [n_loci]                                                                 */
+  const int32_t* win_off;         /* [n_loci+1]                                                               */
+  const char*    window;
+} hipstr_record_alleles_request_t;
+typedef struct hipstr_record_alleles_out {
+  int32_t* status;                /* [n_loci]                                                                 */
+  int32_t* pos, *left_trim, *right_trim;          /* [n_loci]                                                 */
+  int32_t* allele_off;            /* [sum V + 1]                                                              */
+  char*    alleles;
+  int64_t  cap_alleles;
+  int32_t* allele_bp_diff, *old_to_new, *new_to_old;      /* [sum V]                                          */
+  int32_t* lflank_off;            /* [options of the blocks 0 + 1] or NULL                                    */
+  char*    lflanks;
+  int64_t  cap_lflanks;
+  int32_t* rflank_off;            /* [options of the blocks 2 + 1] or NULL                                    */
+  char*    rflanks;
+  int64_t  cap_rflanks;
+} hipstr_record_alleles_out_t;
+int hipstr_record_alleles(const hipstr_batch_t* batch, const hipstr_record_alleles_request_t* rq, hipstr_record_alleles_out_t* out);
+int hipstr_record_alleles_host(const hipstr_batch_t* batch, const hipstr_record_alleles_request_t* rq, hipstr_record_alleles_out_t* out);
+
+/*
+ * The per-read sizes of a VCF record and their per-sample histograms: ExtractCigar (extract_indels.cpp:18-90) for every read of a batch,
+ * and Genotyper::condense_read_counts (genotyper.h:50-63) for every sample — the ALLREADS and MALLREADS fields of
+ * SeqStutterGenotyper::write_vcf_record (seq_stutter_genotyper.cpp:1147-1154) without their text.  ExtractCigar is also all that lies
+ * between the reads and hipstr_em_train in GenotyperBamProcessor::learn_stutter_model (genotyper_bam_processor.cpp:104-139):
+ * hipstr_em_batch_from_bp_diffs is that loop.  Each device form equals its _host form (no device needed) byte for byte, and the host forms
+ * equal the compiled reference (tests/golden/record_reads_*.npz).
+ *
+ * hipstr_cigar_bp_diffs: per read r of locus l, with region_start' = region_start[l] - pad[l] and region_end' = region_stop[l] + pad[l]
+ * (both call sites pad with the period), span = the summed lengths of the runs that advance the reference (M = X D):
+ *   got[r] = 0 when region_start' < read_start[r] or region_end' >= read_start[r] + span                     (:39-40)
+ *   first  = the last M = X run among the runs that begin before region_start', 0 when there is none (last_match_index stays 0, :43-53);
+ *            got[r] = 0 when first == 0 and run 0 is not M = X                                                (:54-58)
+ *   last   = the lowest M = X run among the runs that end behind region_end' (the walk from the back stops at run 0, :64-75), the last run
+ *            when there is none; got[r] = 0 when last is the last run and that run is not M = X               (:76-80)
+ *   bp_diff[r] = sum of the I lengths minus the D lengths of the runs first..last (0 when first > last); 0 when got[r] == 0.
+ * Any SAM op letter (MIDNSHP=X) is accepted: learn_stutter_model runs on raw BAM CIGARs.  One lane per read; a read of more than
+ * HIPSTR_CIGAR_DEVICE_RUNS runs is done by the host form inside the same call.
+ * Refused, nothing written (the reference asserts or indexes out of a vector there): null arguments, offsets that do not ascend from 0,
+ * read_start < 0, a read without CIGAR runs, a run of non-positive length, another op byte, region_end' < region_start', and a read or
+ * region whose positions leave int32 (read_start plus ALL its run lengths, region_start - pad, region_stop + pad).
+ *
+ * hipstr_sample_histograms: for the sample layout of a posterior batch (only n_loci, n_samples, read_off and sample_label of `pb` are
+ * read; reads grouped by ascending sample as hipstr_post_upload requires) and one value per read, per sample (sample_total_ll's order)
+ * the distinct values other than `skip`, ascending as signed integers, with the number of reads that hold each:
+ *   sample s has the pairs [pair_off[s], pair_off[s+1]) of hist_value / hist_count; a sample without values has none (the reference
+ *   prints "."); pair_off[n_samp] pairs in all, never more than n_reads: hist_value and hist_count have room for n_reads.
+ * ALLREADS: value = bp_diff of hipstr_cigar_bp_diffs with the reads that have !got or seed < 0 (:1080) set to a skip value no read can
+ * hold (e.g. HIPSTR_NO_ML_BP); MALLREADS: value = ml_bp of hipstr_assign_trace_stats(_dev), skip = HIPSTR_NO_ML_BP.
+ * One wavefront per sample sorts the sample's values in LDS and counts the run heads, one scan over the samples gives pair_off, a third
+ * kernel writes the pairs; a sample of more than HIPSTR_HISTOGRAM_DEVICE_READS reads is condensed by the host form inside the same call.
+ * Refused, nothing written: null arguments, a negative sample count, read_off that does not ascend from 0, a label outside the locus'
+ * samples, reads not grouped by ascending label.
+ *
+ * hipstr_em_batch_from_bp_diffs (host only): learn_stutter_model's loop (:113-139) on hipstr_cigar_bp_diffs' output.  Per locus the reads
+ * with got[r] and bp_diff[r] >= -(region_stop - region_start + 1) enter, in order, with their label and log_p1 / log_p2 (0 and 0 when
+ * pb->log_p1 is NULL: no SNP information, :123-125); the walk over a locus' samples ends behind the sample during which the entered count
+ * passed 10000 (MAX_INF_READS, :131-132).  too_few[l] = the entered
+ * count is below min_total_reads (:135-139: the reference trains no model there; the reads stay in the batch and the caller passes by).
+ * em_read_off: [n_loci+1]; the four per-read arrays have room for every read of pb.  With period, haploid, n_samples = the caller's,
+ * read_off = em_read_off and ref_allele 0 they are a hipstr_em_batch_t for hipstr_em_train.  Refused as hipstr_sample_histograms refuses,
+ * and: region_stop < region_start, min_total_reads < 0, pb->log_p1 without pb->log_p2.
+ */
+#define HIPSTR_CIGAR_DEVICE_RUNS      4096
+#define HIPSTR_HISTOGRAM_DEVICE_READS 1024
+typedef struct hipstr_cigar_request {
+  int32_t        n_loci;
+  const int32_t* read_off;        /* [n_loci+1] reads of every locus                                          */
+  const int32_t* read_start;      /* [n_reads] 0-based position of the alignment (BamAlignment::Position())   */
+  const int32_t* cigar_off;       /* [n_reads+1] runs of every read                                           */
+  const uint8_t* cigar_op;        /* [cigar_off[n_reads]] SAM op letters                                      */
+  const int32_t* cigar_len;       /* [cigar_off[n_reads]]                                                     */
+  const int32_t* region_start, *region_stop, *pad;      /* [n_loci]                                           */
+} hipstr_cigar_request_t;
+int hipstr_cigar_bp_diffs(const hipstr_cigar_request_t* rq, uint8_t* got /*[n_reads]*/, int32_t* bp_diff /*[n_reads]*/);
+int hipstr_cigar_bp_diffs_host(const hipstr_cigar_request_t* rq, uint8_t* got, int32_t* bp_diff);
+int hipstr_sample_histograms(const hipstr_post_batch_t* pb, const int32_t* value /*[n_reads]*/, int32_t skip,
+                             int32_t* pair_off /*[n_samp+1]*/, int32_t* hist_value, int32_t* hist_count /* each [n_reads] capacity */);
+int hipstr_sample_histograms_host(const hipstr_post_batch_t* pb, const int32_t* value, int32_t skip,
+                                  int32_t* pair_off, int32_t* hist_value, int32_t* hist_count);
+int hipstr_em_batch_from_bp_diffs(const hipstr_post_batch_t* pb, const uint8_t* got, const int32_t* bp_diff /* [n_reads] */,
+                                  const int32_t* region_start, const int32_t* region_stop /* [n_loci] */, int32_t min_total_reads,
+                                  int32_t* em_read_off /*[n_loci+1]*/, int32_t* sample_label, int32_t* num_bps,
+                                  double* log_p1, double* log_p2 /* each [n_reads] capacity */, uint8_t* too_few /*[n_loci]*/);
 
 /*
  * The allele census between two rounds of SeqStutterGenotyper::genotype (seq_stutter_genotyper.cpp:603-671): what decides the next round's

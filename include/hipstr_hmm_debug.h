@@ -137,6 +137,14 @@ int hipstr_debug_flank_last(int64_t out[8], int32_t* flags, int32_t* sizes, int6
  * back.  A call that was refused, or that had nothing to do, leaves zeros.  Used by tests/test_record_gpu.py and
  * tools/record_fields_timing.py. */
 int hipstr_debug_record_last(int64_t out[4]);
+/* Diagnostics: the calling thread's last hipstr_cigar_bp_diffs or hipstr_sample_histograms: out[0] reads or samples, out[1] those the host
+ * twin did inside the call because they exceed HIPSTR_CIGAR_DEVICE_RUNS or HIPSTR_HISTOGRAM_DEVICE_READS, out[2] bytes sent to the device,
+ * out[3] bytes copied back.  A call that was refused, or that had nothing to do, leaves zeros.  Used by tests/test_record_reads_gpu.py
+ * and tools/record_alleles_timing.py. */
+int hipstr_debug_record_reads_last(int64_t out[4]);
+/* Diagnostics: the calling thread's last hipstr_record_alleles: out[0] loci, out[1] those the host twin did inside the call (more than
+ * HIPSTR_ALLELES_DEVICE_OPTIONS options), out[2] bytes sent to the device, out[3] bytes copied back.  Used by tests/test_record_alleles_gpu.py. */
+int hipstr_debug_record_alleles_last(int64_t out[4]);
 /* Diagnostics: the calling thread's last hipstr_pool_reads (or hipstr_pool_batch on the device): out[0] loci pooled on the device, out[1]
  * loci the host pooled for their size, out[2] loci the host redid after a hash collision, out[3..5] pools of the device's loci by median
  * route (copy, net, radix), out[6] chunks, out[7] reads uploaded.  hipstr_debug_pool_last_timing: out[0] milliseconds between HIP events

@@ -517,10 +517,65 @@ static int run_allele_cases(const char* in_path, FILE* out){
   return 0;
 }
 
+// [--record-cases IN --out OUT] the reference's own SeqStutterGenotyper::get_alleles and reorder_alleles (seq_stutter_genotyper.cpp:673-769)
+// on cases read from a text file (tests/golden/make_golden_record_alleles.py writes the file from tests/record_alleles_cases.py and stores
+// the records as tests/golden/record_alleles_*.npz):
+//   case NAME REGION_START REGION_STOP / chrom SEQ (the chromosome from base 0) / 3 x "block B START END N SEQ..."   ("-" = the empty string)
+// get_alleles reads one member, haplotype_: it is called on zeroed storage of the class' size with that member set (a genotyper cannot be
+// constructed without reads and a model).  Written: "case NAME", "pos P", "trim LEFT RIGHT", "alleles N SEQ...", "old_to_new ...",
+// "new_to_old ...".  Data only.
+static int run_record_cases(const char* in_path, FILE* out){
+  std::ifstream in(in_path);
+  if (!in){ perror(in_path); return 2; }
+  auto seq = [](const std::string& s){ return s == "-" ? std::string() : s; };
+  auto show = [](const std::string& s){ return s.empty() ? "-" : s.c_str(); };
+  std::string line;
+  while (std::getline(in, line)){
+    if (line.empty()) continue;
+    std::istringstream hd(line);
+    std::string word, name, chrom; int rs = 0, re = 0;
+    hd >> word >> name >> rs >> re;
+    if (word != "case" || !hd){ fprintf(stderr, "bad case line: %s\n", line.c_str()); return 2; }
+    std::getline(in, line);
+    { std::istringstream ls(line); ls >> word >> chrom; if (word != "chrom"){ fprintf(stderr, "bad chrom line\n"); return 2; } }
+    std::vector<HapBlock*> blocks;                 // (plain blocks: get_alleles reads their strings and coordinates only)
+    for (int b = 0; b < 3; b++){
+      std::getline(in, line);
+      std::istringstream ls(line);
+      int idx = 0, start = 0, end = 0, n = 0; std::string s;
+      ls >> word >> idx >> start >> end >> n;
+      if (word != "block" || idx != b || !ls || n < 1){ fprintf(stderr, "bad block line: %s\n", line.c_str()); return 2; }
+      ls >> s;
+      HapBlock* blk = new HapBlock(start, end, seq(s));
+      for (int o = 1; o < n; o++){ ls >> s; blk->add_alternate(seq(s)); }
+      blocks.push_back(blk);
+    }
+    Haplotype* haplotype = new Haplotype(blocks);
+    SeqStutterGenotyper* g = (SeqStutterGenotyper*)calloc(1, sizeof(SeqStutterGenotyper));
+    g->haplotype_ = haplotype;
+    Region region("chr", rs, re, 2);
+    int32_t pos = 0;
+    std::vector<std::string> alleles;
+    const std::pair<int, int> trims = g->get_alleles(region, 1, chrom, pos, alleles);
+    std::vector<int> old_to_new, new_to_old;
+    g->reorder_alleles(alleles, old_to_new, new_to_old);
+    fprintf(out, "case %s\npos %d\ntrim %d %d\nalleles %zu", name.c_str(), pos, trims.first, trims.second, alleles.size());
+    for (size_t i = 0; i < alleles.size(); i++) fprintf(out, " %s", show(alleles[i]));
+    fprintf(out, "\nold_to_new");
+    for (size_t i = 0; i < old_to_new.size(); i++) fprintf(out, " %d", old_to_new[i]);
+    fprintf(out, "\nnew_to_old");
+    for (size_t i = 0; i < new_to_old.size(); i++) fprintf(out, " %d", new_to_old[i]);
+    fprintf(out, "\n");
+    free(g); delete haplotype;
+    for (size_t i = 0; i < blocks.size(); i++) delete blocks[i];
+  }
+  return 0;
+}
+
 extern "C" int flow_main(int argc, char** argv){
   LocusParams lp; lp.seed = 1; lp.n_samples = 10; lp.reads_per_sample = 9; lp.period = 4; lp.recompute = false; lp.reassemble = true; lp.nw = false; lp.dump_inputs = NULL;
   const char* out_path = NULL; int n_loci = 0, n_threads = 1; bool use_stream = false, profile = false;
-  const char* debruijn_cases = NULL, *hapgen_cases = NULL, *allele_cases = NULL; int time_reps = 0;
+  const char* record_cases = NULL; const char* debruijn_cases = NULL, *hapgen_cases = NULL, *allele_cases = NULL; int time_reps = 0;
   for (int i = 1; i < argc; i++){
     if (!strcmp(argv[i], "--seed")) lp.seed = strtoull(argv[++i], NULL, 10);
     else if (!strcmp(argv[i], "--samples")) lp.n_samples = atoi(argv[++i]);
@@ -534,12 +589,20 @@ extern "C" int flow_main(int argc, char** argv){
     else if (!strcmp(argv[i], "--loci")) n_loci = atoi(argv[++i]);          // many loci (seeds seed, seed+1, ...; periods cycling 2..5) ...
     else if (!strcmp(argv[i], "--threads")) n_threads = atoi(argv[++i]);    // ... one SeqStutterGenotyper per host thread at a time
     else if (!strcmp(argv[i], "--profile")) profile = true;                 // many-loci form: where the host threads' time went (MI355X build: library and adapter buckets)
+    else if (!strcmp(argv[i], "--record-cases")) record_cases = argv[++i];      // the reference's get_alleles / reorder_alleles on cases of a text file (see run_record_cases)
     else if (!strcmp(argv[i], "--debruijn-cases")) debruijn_cases = argv[++i];  // the reference's DebruijnGraph on cases of a text file (see run_debruijn_cases)
     else if (!strcmp(argv[i], "--hapgen-cases")) hapgen_cases = argv[++i];      // the reference's HaplotypeGenerator on cases of a text file (see run_hapgen_cases)
     else if (!strcmp(argv[i], "--allele-cases")) allele_cases = argv[++i];      // the reference's HapBlock / Haplotype on cases of a text file (see run_allele_cases)
     else if (!strcmp(argv[i], "--time")) time_reps = atoi(argv[++i]);           // with --hapgen-cases: build every case that many times more and report the seconds
     else if (!strcmp(argv[i], "--stream")) use_stream = true;               // MI355X build: alignment rounds of the loci in flight share batches
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+  }
+  if (record_cases){
+    FILE* f = out_path ? fopen(out_path, "w") : stdout;
+    if (!f){ perror(out_path); return 2; }
+    const int rc = run_record_cases(record_cases, f);
+    if (out_path) fclose(f);
+    return rc;
   }
   if (debruijn_cases){
     FILE* f = out_path ? fopen(out_path, "w") : stdout;
