@@ -219,63 +219,65 @@ int calc_seed_base(const hipstr_batch_t* b, int l, int r){
 
 namespace {
 
-struct SideSeqs {                 // the three block sequences of one allele in one orientation
-  std::string s[3];
-  std::vector<int> lrun[3], rrun[3];
-  // Run-length tables of HapBlock::calc_homopolymer_lengths (HapBlock.cpp:7-30).  The reference
-  // does not reset its counter between the forward and the backward pass, so the backward
-  // ("right") lengths near the end of a block are inflated by the block's trailing run; the
-  // transition tables are indexed with those values, so the quirk is reproduced on purpose.
-  void index(){
-    for (int b = 0; b < 3; b++){
-      const std::string& q = s[b];
-      const int n = q.size();
-      lrun[b].assign(n, 0); rrun[b].assign(n, 0);
-      if (n == 0) continue;
-      int count = 0;
-      for (int j = 1; j < n; j++){ count = (q[j-1] == q[j]) ? count+1 : 0; lrun[b][j] = count; }
-      for (int j = n-2; j >= 0; j--){ count = (q[j+1] == q[j]) ? count+1 : 0; rrun[b][j] = count; }
-    }
-  }
-};
-
-// Haplotype::homopolymer_length with its neighbour-block extensions (Haplotype.cpp:239-287).
-int homopolymer_len(const SideSeqs& h, int bi, int pos){
-  const std::string& q = h.s[bi];
-  const char c = q[pos];
-  int l = h.lrun[bi][pos], r = h.rrun[bi][pos];
-  if (pos - l == 0){
-    for (int nb = bi-1; nb >= 0; nb--){
-      const int n = h.s[nb].size();
-      if (n == 0) continue;
-      if (h.s[nb][n-1] != c) break;
-      const int ll = h.lrun[nb][n-1];
-      l += 1 + ll;
-      if (ll != n) break;
-    }
-  }
-  if (pos + r == (int)q.size()-1){
-    for (int nb = bi+1; nb < 3; nb++){
-      const int n = h.s[nb].size();
-      if (n == 0) continue;
-      if (h.s[nb][0] != c) break;
-      const int rl = h.rrun[nb][0];
-      r += 1 + rl;
-      if (rl != n) break;
-    }
-  }
-  return l + r + 1;
+// ---- The homopolymer context of a flank block's rows.  (The only copy: prepare_locus and the traceback's fresh_flank_rows both build
+// their rows here.)
+//
+// A row carries the homopolymer length at its base, Haplotype::homopolymer_length (Haplotype.cpp:239-287): the block's own run-length
+// tables (HapBlock::calc_homopolymer_lengths, HapBlock.cpp:7-30) plus, where the run touches the block's boundary, an extension into
+// the neighbouring blocks.  The reference does not reset HapBlock's counter between the forward and the backward pass, so the backward
+// ("right") lengths near the end of a block are inflated by the block's trailing run — a block that is ONE run of n bases ends with
+// right length 2 (n - 1) at its first base; the transition tables are indexed with those values, so the quirk is reproduced on purpose.
+//
+// What a flank takes from its neighbours is one integer E, the same at every position it applies to (side orientation: leading flank,
+// STR block, trailing flank):
+//   leading flank:  only the right length extends, only where pos + rrun[pos] is the flank's last base c, by
+//                   E = 0 if the STR block does not start with c, else 1 + rr_first (the block's right length at its first base);
+//                   if rr_first equals the block's length — with the carried counter a TWO-base one-run block, the two-copy allele of a
+//                   homopolymer locus — and the far flank starts with c as well, 1 + the far flank's right length at its first base
+//                   on top (Haplotype.cpp:262-270: `if (rl != n) break`).  There are three blocks: nothing lies further.
+//   trailing flank: only the left length extends, only where pos - lrun[pos] is the flank's first base c, by
+//                   E = 1 + run_last (the STR block's left length at its last base) if the block ends with c, else 0; never further,
+//                   a left length is smaller than its block.
+struct Seq { const char* p; int n; };
+struct EndSig { char c_first, c_last; int run_first, run_last; };       // a block's end bases; HapBlock's right length at the first, left length at the last
+static void run_tables(const char* q, int n, int* lrun, int* rrun){     // HapBlock.cpp:7-30, `count` carried from the first loop into the second
+  for (int j = 0; j < n; j++){ lrun[j] = 0; rrun[j] = 0; }
+  int count = 0;
+  for (int j = 1; j < n; j++){ count = (q[j-1] == q[j]) ? count+1 : 0; lrun[j] = count; }
+  for (int j = n-2; j >= 0; j--){ count = (q[j+1] == q[j]) ? count+1 : 0; rrun[j] = count; }
 }
+static EndSig end_sig(const Seq& q){                                     // = { q[0], q[n-1], rrun[0], lrun[n-1] } of run_tables, from the two end runs alone
+  const int n = q.n;
+  int run_first = 0, run_last = 0;
+  while (run_first < n-1 && q.p[run_first+1] == q.p[0]) run_first++;
+  while (run_last < n-1 && q.p[n-2-run_last] == q.p[n-1]) run_last++;
+  return EndSig{ q.p[0], q.p[n-1], (run_first == n-1) ? 2*(n-1) : run_first, run_last };
+}
+static EndSig reversed(const EndSig& e, int n){                          // end_sig of the reversed block
+  return EndSig{ e.c_last, e.c_first, (e.run_last == n-1) ? 2*(n-1) : e.run_last, std::min(e.run_first, n-1) };
+}
+static int lead_extension(const EndSig& lead, const EndSig& str, int n_str, const EndSig& far){
+  if (str.c_first != lead.c_last) return 0;
+  int E = 1 + str.run_first;
+  if (str.run_first == n_str && far.c_first == lead.c_last) E += 1 + far.run_first;
+  return E;
+}
+static int trail_extension(const EndSig& str, const EndSig& trail){ return str.c_last == trail.c_first ? 1 + str.run_last : 0; }
 
-// rows of flank block `bi` (0 = lead, 2 = trail) under context h; u0 = compact index of its first row
-std::vector<hs_row_t> flank_rows(const SideSeqs& h, int bi, int u0){
-  const std::string& q = h.s[bi];
-  std::vector<hs_row_t> rows(q.size());
-  for (int i = 0; i < (int)q.size(); i++){
-    const int hl = std::min(HIPSTR_MAX_HOMOP_LEN, std::max(homopolymer_len(h, bi, i), homopolymer_len(h, bi, std::max(0, i-1))));
-    rows[i] = HS_ROW_VALID | ((uint32_t)(u0+i) << 12) | ((uint32_t)hl << 8) | (uint8_t)q[i];
+// Rows of one flank block: a pure function of its arguments — the flank in side orientation with its own run tables, which end it
+// borders the STR block with, the compact index u0 of its first row, and E.  (hl: scratch.)
+static void flank_rows(const Seq& q, const int* lrun, const int* rrun, bool trailing, int u0, int E, std::vector<int>& hl, std::vector<hs_row_t>& rows){
+  const int n = q.n;
+  if ((int)hl.size() < n) hl.resize(n);
+  rows.resize(n);
+  for (int i = 0; i < n; i++){
+    const bool at_boundary = trailing ? (i - lrun[i] == 0) : (i + rrun[i] == n-1);
+    hl[i] = lrun[i] + rrun[i] + 1 + (at_boundary ? E : 0);
   }
-  return rows;
+  for (int i = 0; i < n; i++){
+    const int v = std::min(HIPSTR_MAX_HOMOP_LEN, std::max(hl[i], hl[std::max(0, i-1)]));
+    rows[i] = HS_ROW_VALID | ((uint32_t)(u0+i) << 12) | ((uint32_t)v << 8) | (uint8_t)q.p[i];
+  }
 }
 
 inline hs_visit_t visit(int ni, int U, char ca, char cb, bool plain, double logU){
@@ -289,9 +291,6 @@ inline hs_visit_t visit(int ni, int U, char ca, char cb, bool plain, double logU
 struct Scratch {
   std::vector<int> up;                  // StutterAlignerClass's upstream-match run table of one shift (h:35-42)
   std::vector<hs_visit_t> vis;          // the visiting lists of the STR option being built
-  std::vector<char> rev;                // reversed block sequences of the locus being prepared
-  std::vector<int> lrun, rrun;          // HapBlock run lengths of the three blocks of one haplotype orientation
-  std::vector<hs_row_t> rows;           // rows of one flank block before they are interned
 };
 static Scratch& scratch(){ thread_local Scratch s; return s; }
 
@@ -707,11 +706,13 @@ void emit_stropt(const char* blk, const int B, int period, const double pmf13[HS
 
 // ---- helpers shared with the traceback path (trace.hip)
 void fresh_flank_rows(const std::string side_seqs[3], std::vector<hs_row_t>& lead, std::vector<hs_row_t>& trail){
-  SideSeqs h;
-  for (int j = 0; j < 3; j++) h.s[j] = side_seqs[j];
-  h.index();
-  lead = flank_rows(h, 0, 0);
-  trail = flank_rows(h, 2, (int)h.s[0].size() + 1);
+  Seq q[3]; EndSig sig[3];
+  for (int j = 0; j < 3; j++){ q[j] = Seq{ side_seqs[j].data(), (int)side_seqs[j].size() }; sig[j] = end_sig(q[j]); }
+  std::vector<int> run(2*(size_t)std::max(q[0].n, q[2].n)), hl;
+  run_tables(q[0].p, q[0].n, run.data(), run.data() + q[0].n);
+  flank_rows(q[0], run.data(), run.data() + q[0].n, false, 0, lead_extension(sig[0], sig[1], q[1].n, sig[2]), hl, lead);
+  run_tables(q[2].p, q[2].n, run.data(), run.data() + q[2].n);
+  flank_rows(q[2], run.data(), run.data() + q[2].n, true, q[0].n + 1, trail_extension(sig[1], sig[2]), hl, trail);
 }
 void append_stropt(const std::string& blk, int period, const double* stutter, Prepared& out){
   double pmf13[HS_NART]; stutter_pmf13(stutter, period, pmf13);
@@ -767,8 +768,59 @@ int validate_tables(const hipstr_batch_t* b, std::string& err){
   return 0;
 }
 
-// The conditions under which prepare_batch refuses a batch, without building anything (same order, same messages): used where a
-// bad locus must be turned away before it is merged with others (hipstr_stream_submit).
+// The shape of one locus, read off the tables, and every refusal that depends on the tables alone: the one copy that check_locus,
+// prepare_batch's setup and prepare_locus share.  opt0 = index of the locus' first block option in opt_off.
+struct LocusShape {
+  int32_t nopts[3], opt_first[3];
+  int32_t A;                       // candidate haplotypes = product of the option counts
+  int32_t longest_B;               // longest STR option (at least 1)
+  int n_options() const { return nopts[0] + nopts[1] + nopts[2]; }
+};
+static int locus_shape(const hipstr_batch_t* b, int l, int opt0, LocusShape& s, std::string& err){
+  if (b->period[l] < 1 || b->period[l] > 9){ err = "STR period must be in [1,9] (stutter_model.h:38)"; return 1; }
+  int64_t A = 1;
+  s.longest_B = 1;
+  for (int k = 0, c = opt0; k < 3; k++){
+    const int n = s.nopts[k] = b->blk_nopts[3*l+k];
+    if (n < 1){ err = "haplotype block without options"; return 1; }
+    if (n > 1024){ err = "more than 1024 options for a haplotype block are not supported"; return 1; }
+    s.opt_first[k] = c;
+    A *= n;
+    for (int o = 0; o < n; o++, c++){
+      const int len = b->opt_off[c+1] - b->opt_off[c];
+      if (len < 0){ err = "opt_off must not decrease"; return 1; }
+      if (len == 0){ err = k == 1 ? "empty STR allele is not supported" : "empty flank sequence"; return 1; }
+      if (k == 1 && len > HS_MAX_STR_BP){ err = "STR allele longer than 2047 bp is not supported"; return 1; }
+      if (len > (1 << 16)){ err = "haplotype block option longer than 65536 bases is not supported"; return 1; }
+      if (k == 1) s.longest_B = std::max(s.longest_B, len);
+    }
+  }
+  if (A != b->hap_off[l+1]-b->hap_off[l]){ err = "hap_off does not match the product of block options"; return 1; }
+  if (A >= (1 << 24)){ err = "more than 16 M candidate haplotypes for a locus are not supported"; return 1; }
+  s.A = (int32_t)A;
+  if (b->read_off[l+1] < b->read_off[l]){ err = "read_off must not decrease"; return 1; }
+  return 0;
+}
+// The sizes of a read the library does not take, realigned or not
+static int read_too_long(const hipstr_batch_t* b, int r, std::string& err){
+  if (b->base_off[r+1] - b->base_off[r] > (1 << 20)){ err = "read longer than 1 Mi bases is not supported"; return 1; }
+  if (b->cigar_off[r+1] - b->cigar_off[r] > (1 << 20)){ err = "CIGAR of more than 1 Mi runs is not supported"; return 1; }
+  return 0;
+}
+// The seed base of realigned read r — the caller's (HapAligner.h:83) or calc_seed_base's — and the refusals that hang on it
+static int read_seed(const hipstr_batch_t* b, int l, int r, int32_t given_seed, int* seed_out, std::string& err){
+  const int len = b->base_off[r+1] - b->base_off[r];
+  const bool given = given_seed != HIPSTR_SEED_AUTO;
+  const int s = given ? given_seed : calc_seed_base(b, l, r);
+  *seed_out = s;
+  if (s == -2){ err = "Invalid alignment seed or unrecognized CIGAR char (HapAligner.cpp:309,316)"; return 1; }
+  if (given && s != -1 && (s < 1 || s > len - 2)){ err = "seed base must leave at least one base on either side (HapAligner.cpp:316)"; return 1; }
+  if (s >= 0 && (s > HS_MAX_SIDE_FWD || len-s-1 > HS_MAX_SIDE_FWD)){ err = "read side longer than 1024 bases is not supported"; return 1; }
+  return 0;
+}
+
+// The conditions under which prepare_batch refuses a batch, without building anything — the same functions, so the same messages: used
+// where a bad locus must be turned away before it is merged with others (hipstr_stream_submit).
 int check_batch(const hipstr_batch_t* b, std::string& err){
   if (validate_tables(b, err)) return 1;
   int opt_cursor = 0;
@@ -807,49 +859,25 @@ double locus_cost(const hipstr_batch_t* b, int l, int opt0){
 
 // One locus of check_batch; *opt_cursor = index of the locus' first block option in opt_off, advanced past the locus.
 int check_locus(const hipstr_batch_t* b, int l, int* opt_cursor_io, std::string& err, int32_t* seeds_out, int* dims_out){
-  int opt_cursor = *opt_cursor_io;
-  {
-    const int period = b->period[l];
-    if (period < 1 || period > 9){ err = "STR period must be in [1,9] (stutter_model.h:38)"; return 1; }
-    int64_t A = 1;
-    for (int k = 0; k < 3; k++){
-      const int n = b->blk_nopts[3*l+k];
-      if (n < 1){ err = "haplotype block without options"; return 1; }
-      if (n > 1024){ err = "more than 1024 options for a haplotype block are not supported"; return 1; }
-      A *= n;
-      for (int o = 0; o < n; o++, opt_cursor++){
-        const int len = b->opt_off[opt_cursor+1] - b->opt_off[opt_cursor];
-        if (len < 0){ err = "opt_off must not decrease"; return 1; }
-        if (len > (1 << 16)){ err = "haplotype block option longer than 65536 bases is not supported"; return 1; }
-        if (k != 1 && len == 0){ err = "empty flank sequence"; return 1; }
-        if (k == 1 && len == 0){ err = "empty STR allele is not supported"; return 1; }
-        if (k == 1 && len > HS_MAX_STR_BP){ err = "STR allele longer than 2047 bp is not supported"; return 1; }
-      }
-    }
-    if (A != b->hap_off[l+1]-b->hap_off[l]){ err = "hap_off does not match the product of block options"; return 1; }
-    if (A >= (1 << 24)){ err = "more than 16 M candidate haplotypes for a locus are not supported"; return 1; }
-    if (b->read_off[l+1] < b->read_off[l]){ err = "read_off must not decrease"; return 1; }
-    int longest_B = 1, longest_read = 0;
-    for (int o = 0; o < b->blk_nopts[3*l+1]; o++){ const int c = *opt_cursor_io + b->blk_nopts[3*l] + o; longest_B = std::max(longest_B, b->opt_off[c+1] - b->opt_off[c]); }
-    for (int r = b->read_off[l]; r < b->read_off[l+1]; r++){
-      if (b->realign_read && !b->realign_read[r]){ if (seeds_out) seeds_out[r] = HIPSTR_SEED_AUTO; continue; }
-      const int len = b->base_off[r+1] - b->base_off[r];
-      if (len > (1 << 20)){ err = "read longer than 1 Mi bases is not supported"; return 1; }
-      if (b->cigar_off[r+1] - b->cigar_off[r] > (1 << 20)){ err = "CIGAR of more than 1 Mi runs is not supported"; return 1; }
-      longest_read = std::max(longest_read, len);
-      const int s = calc_seed_base(b, l, r);
-      if (seeds_out) seeds_out[r] = s;
-      if (s == -2){ err = "Invalid alignment seed or unrecognized CIGAR char (HapAligner.cpp:309,316)"; return 1; }
-      if (s >= 0 && (s > HS_MAX_SIDE_FWD || len-s-1 > HS_MAX_SIDE_FWD)){ err = "read side longer than 1024 bases is not supported"; return 1; }
-    }
-    // the per-read STR kernels keep a read's tables and the allele's block in LDS: a locus whose longest read and longest allele do not fit
-    // is turned away here, alone — not at upload time, where it would take the batch it shares down with it.  (The LDS is sized by the
-    // BATCH's longest read and longest allele: the stream and hipstr_hmm_process_reads_each close a batch before a locus that would push
-    // the combined figure over the limit — dims_out.)
-    if (dims_out){ dims_out[0] = longest_read; dims_out[1] = longest_B; }
-    if (hs_str_kernel_lds_bytes(longest_read, longest_B) > HS_LDS_LIMIT){ err = "reads and STR alleles this long need more than 160 KiB of LDS per workgroup (about 1.8 kb reads; less with alleles near 2 kb)"; return 1; }
+  LocusShape shape;
+  if (locus_shape(b, l, *opt_cursor_io, shape, err)) return 1;
+  int longest_read = 0;
+  for (int r = b->read_off[l]; r < b->read_off[l+1]; r++){
+    if (read_too_long(b, r, err)) return 1;
+    if (b->realign_read && !b->realign_read[r]){ if (seeds_out) seeds_out[r] = HIPSTR_SEED_AUTO; continue; }
+    longest_read = std::max(longest_read, b->base_off[r+1] - b->base_off[r]);
+    int s;
+    const int bad = read_seed(b, l, r, HIPSTR_SEED_AUTO, &s, err);
+    if (seeds_out) seeds_out[r] = s;
+    if (bad) return 1;
   }
-  *opt_cursor_io = opt_cursor;
+  // the per-read STR kernels keep a read's tables and the allele's block in LDS: a locus whose longest read and longest allele do not fit
+  // is turned away here, alone — not at upload time, where it would take the batch it shares down with it.  (The LDS is sized by the
+  // BATCH's longest read and longest allele: the stream and hipstr_hmm_process_reads_each close a batch before a locus that would push
+  // the combined figure over the limit — dims_out.)
+  if (dims_out){ dims_out[0] = longest_read; dims_out[1] = shape.longest_B; }
+  if (hs_str_kernel_lds_bytes(longest_read, shape.longest_B) > HS_LDS_LIMIT){ err = "reads and STR alleles this long need more than 160 KiB of LDS per workgroup (about 1.8 kb reads; less with alleles near 2 kb)"; return 1; }
+  *opt_cursor_io += shape.n_options();
   return 0;
 }
 
@@ -877,7 +905,6 @@ void prep_profile_print(){
 #define HS_LAP(k) do { if (g_lap_on){ const uint64_t now_ = __builtin_ia32_rdtsc(); g_lap_cycles[k] += now_ - lap_t; lap_t = now_; } } while (0)
 
 namespace {
-struct Seq { const char* p; int n; };
 inline bool seq_eq(const Seq& a, const Seq& b){ return a.n == b.n && memcmp(a.p, b.p, (size_t)a.n) == 0; }
 inline bool seq_less(const Seq& a, const Seq& b){        // std::string's order among sequences of one length
   return memcmp(a.p, b.p, (size_t)a.n) < 0;
@@ -893,190 +920,142 @@ template <class T, class Less> void stable_small_sort(T* v, int n, Less less){
 }
 // Scratch of prepare_locus, one per host thread (cleared per locus, capacity kept)
 struct LocusScratch {
-  std::vector<char> rev;                       // reversed STR options, then (per cache miss) the reversed flanks of one haplotype
-  std::vector<char> hbuf;
+  std::vector<char> rev;                       // reversed STR options
   std::vector<Seq> sblk[2];                    // STR options in side orientation
   std::vector<int32_t> str_opt_of, ks, opt_rank, os, cnt;
-  struct EndSig { char c_first, c_last; int run_first, run_last; };
-  struct RowsKey { int opt; char c; int run; int aux; int id; };
-  std::vector<EndSig> end_sig[2];
-  std::vector<RowsKey> lead_tab[2], trail_tab[2];
+  std::vector<EndSig> end_sig[2][3];           // [side][block, numbered as the caller gives them]: every option's signature in side orientation
+  // A flank option in side orientation with its run tables: a function of the option and the side alone, built when the first rows of
+  // that (side, option) are and kept for the rest of the locus.
+  struct FlankTab { int seq, run; };           // offsets: fseq (side 1: the reversed copy), run (lrun | rrun; < 0 = not built yet)
+  std::vector<FlankTab> flank[2][3];           // [side][block 0 or 2]
+  std::vector<char> fseq;
+  std::vector<int> run;
+  struct RowsKey { int opt, E, lead_len, id; };        // the row cache: flank_rows' arguments -> rowset id (lead_len: u0 - 1 of a trailing flank, 0 for a leading one)
+  std::vector<RowsKey> rows_tab[2][2];         // [side][trailing]
   std::vector<int32_t> lead_sets[2];
-  std::vector<int> run;                        // lrun | rrun of the three blocks of one orientation
   std::vector<int> hl;
   std::vector<hs_row_t> rows;
   std::vector<uint64_t> pairs;
 };
 static LocusScratch& locus_scratch(){ thread_local LocusScratch s; return s; }
 
-// One haplotype orientation: the three block sequences + HapBlock's run-length tables (see SideSeqs above; same quirk)
-struct SideView {
-  Seq s[3];
-  const int* lrun[3]; const int* rrun[3];
+// One locus in preparation: what the stages below share.  Every stage appends to `out`; the order of the appends is part of the layout
+// (tests/golden/prep_digests*.json).
+struct LocusPrep {
+  const hipstr_batch_t* b; int l;
+  const LocusShape& shape;
+  Prepared& out;
+  LocusScratch& S;
+  hs_locus_t loc;
+  int so_base;                 // the locus' STR options in out.stropts: forward orientation from here, the reversed ones behind them
+  int rowset_first;            // ... its rowsets (shared by content within the locus)
+  size_t allele_base;          // ... its alleles
+  int n_realigned;
+  bool one_flank() const { return shape.nopts[0] == 1 && shape.nopts[2] == 1; }      // (the usual locus: allele k is STR option k, the STR block is what changes)
+  Seq opt(int k, int o) const { const int c = shape.opt_first[k] + o; return Seq{ b->seq + b->opt_off[c], b->opt_off[c+1] - b->opt_off[c] }; }
 };
-static void index_side(SideView& h, std::vector<int>& store){
-  size_t tot = 0; for (int b = 0; b < 3; b++) tot += 2*(size_t)h.s[b].n;
-  if (store.size() < tot) store.resize(tot);
-  int* p = store.data();
-  for (int b = 0; b < 3; b++){
-    const int n = h.s[b].n; const char* q = h.s[b].p;
-    int* lr = p; int* rr = p + n; p += 2*n;
-    h.lrun[b] = lr; h.rrun[b] = rr;
-    if (n == 0) continue;
-    for (int j = 0; j < n; j++){ lr[j] = 0; rr[j] = 0; }
-    int count = 0;
-    for (int j = 1; j < n; j++){ count = (q[j-1] == q[j]) ? count+1 : 0; lr[j] = count; }
-    for (int j = n-2; j >= 0; j--){ count = (q[j+1] == q[j]) ? count+1 : 0; rr[j] = count; }
-  }
-}
-// Haplotype::homopolymer_length with its neighbour-block extensions (Haplotype.cpp:239-287)
-static int homopolymer_len_v(const SideView& h, int bi, int pos){
-  const Seq& q = h.s[bi];
-  const char c = q.p[pos];
-  int l = h.lrun[bi][pos], r = h.rrun[bi][pos];
-  if (pos - l == 0){
-    for (int nb = bi-1; nb >= 0; nb--){
-      const int n = h.s[nb].n;
-      if (n == 0) continue;
-      if (h.s[nb].p[n-1] != c) break;
-      const int ll = h.lrun[nb][n-1];
-      l += 1 + ll;
-      if (ll != n) break;
-    }
-  }
-  if (pos + r == q.n-1){
-    for (int nb = bi+1; nb < 3; nb++){
-      const int n = h.s[nb].n;
-      if (n == 0) continue;
-      if (h.s[nb].p[0] != c) break;
-      const int rl = h.rrun[nb][0];
-      r += 1 + rl;
-      if (rl != n) break;
-    }
-  }
-  return l + r + 1;
-}
-// rows of flank block `bi` (0 = lead, 2 = trail) under context h; u0 = compact index of its first row
-static void flank_rows_v(const SideView& h, int bi, int u0, std::vector<int>& hl, std::vector<hs_row_t>& rows){
-  const Seq& q = h.s[bi];
-  if ((int)hl.size() < q.n) hl.resize(q.n);
-  rows.resize(q.n);
-  for (int i = 0; i < q.n; i++) hl[i] = homopolymer_len_v(h, bi, i);
-  for (int i = 0; i < q.n; i++){
-    const int v = std::min(HIPSTR_MAX_HOMOP_LEN, std::max(hl[i], hl[std::max(0, i-1)]));
-    rows[i] = HS_ROW_VALID | ((uint32_t)(u0+i) << 12) | ((uint32_t)v << 8) | (uint8_t)q.p[i];
-  }
-}
 }  // namespace
 
-static int prepare_locus(const hipstr_batch_t* b, int l, int opt_cursor, const PrepShared& sh, Prepared& out, std::string& err){
-  const int32_t* seed_in = sh.seed_in;
-  uint64_t lap_t = g_lap_on ? __builtin_ia32_rdtsc() : 0;
-  LocusScratch& S = locus_scratch();
-  const int period = b->period[l];
-  if (period < 1 || period > 9){ err = "STR period must be in [1,9] (stutter_model.h:38)"; return 1; }
-  int32_t nopts[3], opt_first[3];
-  for (int k = 0; k < 3; k++){
-    nopts[k] = b->blk_nopts[3*l+k];
-    if (nopts[k] < 1){ err = "haplotype block without options"; return 1; }
-    if (nopts[k] > 1024){ err = "more than 1024 options for a haplotype block are not supported"; return 1; }      // (the sizes check_locus refuses, in its words)
-    opt_first[k] = opt_cursor; opt_cursor += nopts[k];
-  }
-  auto O = [&](int k, int o) -> Seq { const int c = opt_first[k] + o; return Seq{ b->seq + b->opt_off[c], b->opt_off[c+1] - b->opt_off[c] }; };
-  for (int k = 0; k < 3; k += 2)
-    for (int o = 0; o < nopts[k]; o++){
-      if (O(k, o).n == 0){ err = "empty flank sequence"; return 1; }
-      if (O(k, o).n > (1 << 16)){ err = "haplotype block option longer than 65536 bases is not supported"; return 1; }
-    }
-  for (int r = b->read_off[l]; r < b->read_off[l+1]; r++){
-    if (b->base_off[r+1] - b->base_off[r] > (1 << 20)){ err = "read longer than 1 Mi bases is not supported"; return 1; }
-    if (b->cigar_off[r+1] - b->cigar_off[r] > (1 << 20)){ err = "CIGAR of more than 1 Mi runs is not supported"; return 1; }
-  }
-  size_t str_total = 0;
-  for (int o = 0; o < nopts[1]; o++){
-    const int n = O(1, o).n;
-    if (n == 0){ err = "empty STR allele is not supported"; return 1; }
-    if (n > HS_MAX_STR_BP){ err = "STR allele longer than 2047 bp is not supported"; return 1; }
-    out.max_B = std::max(out.max_B, (int32_t)n);
-    str_total += (size_t)n;
-  }
-  const int64_t A64 = (int64_t)nopts[0]*nopts[1]*nopts[2];
-  if (A64 != b->hap_off[l+1]-b->hap_off[l]){ err = "hap_off does not match the product of block options"; return 1; }
-  if (A64 >= (1 << 24)){ err = "more than 16 M candidate haplotypes for a locus are not supported"; return 1; }
-  const int A = (int)A64;
-
-  HS_LAP(0);
-  hs_locus_t loc;
-  loc.out_off = sh.out_off[l]; loc.hap_begin = out.alleles.size(); loc.n_alleles = A;
-  loc.read_begin = b->read_off[l]; loc.n_reads = b->read_off[l+1]-b->read_off[l];
-  loc.period = period; loc.fused = 0;
-
-  // STR options: forward then reversed orientation
-  const int so_base = out.stropts.size();
-  double pmf13[HS_NART]; stutter_pmf13(b->stutter + 6*l, period, pmf13);
+// ---- stage 1: the STR options, forward then reversed orientation
+static void append_str_options(LocusPrep& C){
+  LocusScratch& S = C.S; Prepared& out = C.out;
+  const int n_str = C.shape.nopts[1], period = C.loc.period;
+  C.so_base = out.stropts.size();
+  double pmf13[HS_NART]; stutter_pmf13(C.b->stutter + 6*C.l, period, pmf13);
   const int pmf_off = (int)out.pmf13.size();
   out.pmf13.insert(out.pmf13.end(), pmf13, pmf13 + HS_NART);
+  out.max_B = std::max(out.max_B, C.shape.longest_B);
+  size_t str_total = 0;
+  for (int o = 0; o < n_str; o++) str_total += (size_t)C.opt(1, o).n;
   S.rev.resize(str_total);
   S.sblk[0].clear(); S.sblk[1].clear();
-  {
-    char* rp = S.rev.data();
-    for (int o = 0; o < nopts[1]; o++){
-      const Seq f = O(1, o);
-      S.sblk[0].push_back(f);
-      for (int i = 0; i < f.n; i++) rp[i] = f.p[f.n-1-i];
-      S.sblk[1].push_back(Seq{rp, f.n});
-      rp += f.n;
-    }
+  char* rp = S.rev.data();
+  for (int o = 0; o < n_str; o++){
+    const Seq f = C.opt(1, o);
+    S.sblk[0].push_back(f);
+    for (int i = 0; i < f.n; i++) rp[i] = f.p[f.n-1-i];
+    S.sblk[1].push_back(Seq{rp, f.n});
+    rp += f.n;
   }
   for (int side = 0; side < 2; side++)
-    for (int o = 0; o < nopts[1]; o++)
-      emit_stropt(S.sblk[side][o].p, S.sblk[side][o].n, period, pmf13, out, true, pmf_off, side ? so_base + o : -1);
-  HS_LAP(1);
-  S.str_opt_of.resize(A);                            // STR option of every allele
-  const bool one_flank = nopts[0] == 1 && nopts[2] == 1;          // (the usual locus: allele k is STR option k, the STR block is what changes)
-  if (one_flank) for (int k = 0; k < A; k++) S.str_opt_of[k] = k;
-  else for (int k = 0; k < A; k++){ int32_t o3[3]; allele_options(nopts, k, o3); S.str_opt_of[k] = o3[1]; }
+    for (int o = 0; o < n_str; o++)
+      emit_stropt(S.sblk[side][o].p, S.sblk[side][o].n, period, pmf13, out, true, pmf_off, side ? C.so_base + o : -1);
+}
 
-  // alleles in visit order, replaying the reference's row reuse (HapAligner.cpp:54-60, 612-634):
-  // the lead block of a side is (re)computed only when reuse is off or it is the block that changed;
-  // otherwise its rows — and the homopolymer context they were computed under — are inherited.
-  const int rowset_first = (int)out.rowsets.size();           // rowsets are shared (by content) within the locus
-  auto intern = [&](const std::vector<hs_row_t>& rows){
-    const int n = (int)rows.size();
-    // (the reference-order map of round 1-3 numbered distinct row vectors in order of first use: so does a scan of the locus' rowsets)
-    for (int id = rowset_first; id < (int)out.rowsets.size(); id++){
-      const hs_rowset_t& rs = out.rowsets[id];
-      if (rs.len == n && memcmp(out.rows.data() + rs.off, rows.data(), sizeof(hs_row_t)*(size_t)n) == 0) return id;
-    }
-    hs_rowset_t rs; rs.off = out.rows.size(); rs.len = n;
-    out.rows.insert(out.rows.end(), rows.begin(), rows.end());
-    out.rowsets.push_back(rs);
-    return (int)out.rowsets.size() - 1;
-  };
-  // boundary signature of every STR option per side: first base and HapBlock's right-run length there, last base and left-run length
-  // there (HapBlock.cpp:7-30, with its counter carried from the forward into the backward pass)
-  typedef LocusScratch::EndSig EndSig; typedef LocusScratch::RowsKey RowsKey;
-  for (int side = 0; side < 2; side++){
-    S.end_sig[side].clear(); S.lead_tab[side].clear(); S.trail_tab[side].clear(); S.lead_sets[side].clear();
-    for (int o = 0; o < nopts[1]; o++){
-      const Seq& q = S.sblk[side][o];
-      const int n = q.n;
-      // HapBlock's two passes (forward: count = run so far; backward: the same counter, NOT reset) leave, at the block's ends: the run
-      // ending at the last base and the run starting at the first one, each minus one — unless the block is one run, where the backward pass
-      // keeps counting from what the forward pass left: n - 1 and 2 (n - 1)
-      int run_first = 0, run_last = 0;
-      while (run_first < n-1 && q.p[run_first+1] == q.p[0]) run_first++;
-      while (run_last < n-1 && q.p[n-2-run_last] == q.p[n-1]) run_last++;
-      const int lr_last = run_last, rr_first = (run_first == n-1) ? 2*(n-1) : run_first;
-      S.end_sig[side].push_back(EndSig{ q.p[0], q.p[n-1], rr_first, lr_last });
+// ---- between the stages: the STR option of every allele, the end signature of every block option per side, and an empty row cache
+static void index_boundaries(LocusPrep& C){
+  LocusScratch& S = C.S;
+  const int32_t* nopts = C.shape.nopts; const int A = C.shape.A;
+  S.str_opt_of.resize(A);
+  if (C.one_flank()) for (int k = 0; k < A; k++) S.str_opt_of[k] = k;
+  else for (int k = 0; k < A; k++){ int32_t o3[3]; allele_options(nopts, k, o3); S.str_opt_of[k] = o3[1]; }
+  for (int k = 0; k < 3; k++){
+    S.end_sig[0][k].clear(); S.end_sig[1][k].clear();
+    for (int o = 0; o < nopts[k]; o++){
+      const Seq q = C.opt(k, o);
+      const EndSig e = end_sig(q);
+      S.end_sig[0][k].push_back(e); S.end_sig[1][k].push_back(reversed(e, q.n));
     }
   }
-  HS_LAP(2);
+  for (int side = 0; side < 2; side++){
+    for (int k = 0; k < 3; k += 2) S.flank[side][k].assign(nopts[k], LocusScratch::FlankTab{0, -1});
+    S.rows_tab[side][0].clear(); S.rows_tab[side][1].clear(); S.lead_sets[side].clear();
+  }
+  S.fseq.clear(); S.run.clear();
+}
+
+// The locus' rowset with these rows.  (The reference-order map of round 1-3 numbered distinct row vectors in order of first use: so does
+// a scan of the locus' rowsets.)
+static int intern_rows(LocusPrep& C, const std::vector<hs_row_t>& rows){
+  Prepared& out = C.out;
+  const int n = (int)rows.size();
+  for (int id = C.rowset_first; id < (int)out.rowsets.size(); id++){
+    const hs_rowset_t& rs = out.rowsets[id];
+    if (rs.len == n && memcmp(out.rows.data() + rs.off, rows.data(), sizeof(hs_row_t)*(size_t)n) == 0) return id;
+  }
+  hs_rowset_t rs; rs.off = out.rows.size(); rs.len = n;
+  out.rows.insert(out.rows.end(), rows.begin(), rows.end());
+  out.rowsets.push_back(rs);
+  return (int)out.rowsets.size() - 1;
+}
+
+// The rowset of option o of flank block k as `side`'s leading or trailing flank under boundary extension E.  The alleles of a locus mostly
+// share flanks and motif, so rows are built once per distinct argument list of flank_rows — the cache key is that list, nothing else.
+static int flank_rowset(LocusPrep& C, int side, int k, int o, bool trailing, int lead_len, int E){
+  LocusScratch& S = C.S;
+  typedef LocusScratch::RowsKey RowsKey;
+  std::vector<RowsKey>& tab = S.rows_tab[side][trailing];
+  for (const RowsKey& e : tab) if (e.opt == o && e.E == E && e.lead_len == lead_len) return e.id;
+  const Seq f = C.opt(k, o);
+  LocusScratch::FlankTab& t = S.flank[side][k][o];
+  if (t.run < 0){
+    t.run = (int)S.run.size(); S.run.resize((size_t)t.run + 2*(size_t)f.n);
+    t.seq = (int)S.fseq.size();
+    if (side){ S.fseq.resize((size_t)t.seq + f.n); for (int i = 0; i < f.n; i++) S.fseq[t.seq + i] = f.p[f.n-1-i]; }
+    run_tables(side ? S.fseq.data() + t.seq : f.p, f.n, S.run.data() + t.run, S.run.data() + t.run + f.n);
+  }
+  const Seq q{ side ? S.fseq.data() + t.seq : f.p, f.n };
+  const int* run = S.run.data() + t.run;
+  flank_rows(q, run, run + f.n, trailing, trailing ? lead_len + 1 : 0, E, S.hl, S.rows);
+  const RowsKey e{ o, E, lead_len, intern_rows(C, S.rows) };
+  tab.push_back(e);
+  return e.id;
+}
+
+// ---- stage 2: the alleles in visit order with their flank rows, replaying the reference's row reuse (HapAligner.cpp:54-60, 612-634):
+// the lead block of a side is (re)computed only when reuse is off or it is the block that changed; otherwise its rows — and the
+// homopolymer context they were computed under — are inherited.  (That is the reference's behaviour, not a cache: see flank_rowset.)
+static void append_allele_rows(LocusPrep& C){
+  const hipstr_batch_t* b = C.b; const int l = C.l;
+  LocusScratch& S = C.S; Prepared& out = C.out; hs_locus_t& loc = C.loc;
+  const int32_t* nopts = C.shape.nopts; const int A = C.shape.A;
+  const bool one_flank = C.one_flank();
+  C.rowset_first = (int)out.rowsets.size();
   bool reuse = false;
   int lead_id[2] = {-1, -1};
   int n_realigned = 0;
   loc.lt_stride = 0; loc.lead_flank[0] = loc.lead_flank[1] = 0;
-  const size_t allele_base = out.alleles.size();
+  const size_t allele_base = C.allele_base = out.alleles.size();
   out.alleles.resize(allele_base + (size_t)A);
   const size_t rh_base = out.realign_hap.size();
   out.realign_hap.resize(rh_base + (size_t)A);
@@ -1087,48 +1066,19 @@ static int prepare_locus(const hipstr_batch_t* b, int l, int opt_cursor, const P
     al.realign = realign ? 1 : 0;
     int32_t o3[3];
     if (one_flank){ o3[0] = 0; o3[1] = k; o3[2] = 0; } else allele_options(nopts, k, o3);
-    al.n_flank = O(0, o3[0]).n + O(2, o3[2]).n;
+    al.n_flank = C.opt(0, o3[0]).n + C.opt(2, o3[2]).n;
     out.max_flank = std::max(out.max_flank, al.n_flank);
     if (!realign){ reuse = false; out.alleles[allele_base + k] = al; continue; }
     al.re_ord = n_realigned++;
     loc.lt_stride = std::max(loc.lt_stride, al.n_flank);
     const int cb = k == 0 ? -1 : (one_flank ? 1 : changed_block(nopts, k));
     for (int side = 0; side < 2; side++){
-      // The rows of a flank block depend on the block and, through the homopolymer run that may cross the block boundary, on the
-      // STR block's first base and the run it starts (leading flank) or its last base and the run it ends (trailing flank) — never on
-      // more: the reference's extension stops after one non-empty neighbour (Haplotype.cpp:239-275).  The alleles of a locus mostly
-      // share flanks and motif, so the rows are built once per (flank option, boundary signature) and looked up afterwards.
-      const int o_lead = side ? o3[2] : o3[0], o_trail = side ? o3[0] : o3[2];
-      const int lead_len = O(side ? 2 : 0, o_lead).n;
-      const EndSig& es = S.end_sig[side][o3[1]];
-      SideView h; bool have_h = false;
-      auto need_h = [&](){
-        if (have_h) return;
-        if (!side){ h.s[0] = O(0, o3[0]); h.s[1] = S.sblk[0][o3[1]]; h.s[2] = O(2, o3[2]); }
-        else {
-          const Seq f0 = O(2, o3[2]), f2 = O(0, o3[0]);           // side order: [reversed right flank | reversed block | reversed left flank]
-          S.hbuf.resize((size_t)f0.n + f2.n);
-          char* p0 = S.hbuf.data(); char* p2 = p0 + f0.n;
-          for (int i = 0; i < f0.n; i++) p0[i] = f0.p[f0.n-1-i];
-          for (int i = 0; i < f2.n; i++) p2[i] = f2.p[f2.n-1-i];
-          h.s[0] = Seq{p0, f0.n}; h.s[1] = S.sblk[1][o3[1]]; h.s[2] = Seq{p2, f2.n};
-        }
-        index_side(h, S.run); have_h = true;
-      };
-      auto cached = [&](std::vector<RowsKey>& tab, const RowsKey& key, int bi, int u0) -> int {
-        for (const RowsKey& e : tab) if (e.opt == key.opt && e.c == key.c && e.run == key.run && e.aux == key.aux) return e.id;
-        need_h();
-        flank_rows_v(h, bi, u0, S.hl, S.rows);
-        RowsKey e = key; e.id = intern(S.rows);
-        tab.push_back(e);
-        return e.id;
-      };
+      const int k_lead = side ? 2 : 0, k_trail = 2 - k_lead;          // side 1 reads the haplotype from its right end
+      const int o_lead = o3[k_lead], o_trail = o3[k_trail];
+      const int lead_len = C.opt(k_lead, o_lead).n;
+      const EndSig& lead = S.end_sig[side][k_lead][o_lead], &str = S.end_sig[side][1][o3[1]], &trail = S.end_sig[side][k_trail][o_trail];
       const int side_changed = cb < 0 ? -1 : (side ? 2-cb : cb);
-      // (one case looks further: a neighbour that is ONE run whose table entry equals its length lets the extension go on into the block
-      //  behind it (Haplotype.cpp:262-270: `if (rl != n) break`) — with HapBlock's carried counter that is a two-base block, 2 (n - 1) == n:
-      //  a homopolymer locus' two-copy allele.  Its leading-flank rows also depend on the far flank: part of the key.)
-      const int lead_aux = (es.run_first == S.sblk[side][o3[1]].n) ? 1 + o_trail : 0;
-      if (!reuse || side_changed <= 0) lead_id[side] = cached(S.lead_tab[side], RowsKey{o_lead, es.c_first, es.run_first, lead_aux, 0}, 0, 0);
+      if (!reuse || side_changed <= 0) lead_id[side] = flank_rowset(C, side, k_lead, o_lead, false, 0, lead_extension(lead, str, S.sblk[side][o3[1]].n, trail));
       al.lead_rows[side]  = lead_id[side];
       {
         std::vector<int32_t>& ls = S.lead_sets[side];
@@ -1137,16 +1087,22 @@ static int prepare_locus(const hipstr_batch_t* b, int l, int opt_cursor, const P
         al.lead_slot[side] = (int32_t)slot;
         loc.lead_flank[side] = std::max(loc.lead_flank[side], (int32_t)lead_len);
       }
-      al.trail_rows[side] = cached(S.trail_tab[side], RowsKey{o_trail, es.c_last, es.run_last, lead_len, 0}, 2, lead_len + 1);
-      al.str_opt[side]    = so_base + side*nopts[1] + o3[1];
+      al.trail_rows[side] = flank_rowset(C, side, k_trail, o_trail, true, lead_len, trail_extension(str, trail));
+      al.str_opt[side]    = C.so_base + side*nopts[1] + o3[1];
     }
     reuse = true;
     out.alleles[allele_base + k] = al;
   }
-
-  HS_LAP(3);
-  loc.n_re = n_realigned;
+  C.n_realigned = loc.n_re = n_realigned;
   loc.n_lead[0] = S.lead_sets[0].size(); loc.n_lead[1] = S.lead_sets[1].size();
+}
+
+// ---- stage 3: per side the STR-kernel order of the realigned alleles, with the record and read-end-row descriptors of the tabulated ones
+static void append_str_order(LocusPrep& C){
+  LocusScratch& S = C.S; Prepared& out = C.out; hs_locus_t& loc = C.loc;
+  const int32_t* nopts = C.shape.nopts; const int A = C.shape.A;
+  const int period = loc.period, so_base = C.so_base, n_realigned = C.n_realigned;
+  const size_t allele_base = C.allele_base;
   for (int side = 0; side < 2; side++){
     // STR-kernel order: by STR option, options sorted by length; an option whose block (in side orientation) ends with the
     // previous option's block continues that option's match/deletion tables (StutterAlignerClass::load_read sums run
@@ -1222,7 +1178,12 @@ static int prepare_locus(const hipstr_batch_t* b, int l, int opt_cursor, const P
       prev = cur;
     }
   }
-  HS_LAP(4);
+}
+
+// ---- stage 4: the trailing-flank groups
+static void append_trailing_groups(LocusPrep& C){
+  LocusScratch& S = C.S; Prepared& out = C.out; hs_locus_t& loc = C.loc;
+  const int A = C.shape.A; const size_t allele_base = C.allele_base;
   for (int side = 0; side < 2; side++){      // alleles sharing a trailing-flank rowset run as lanes of one wavefront (<= 64 each)
     // groups in ascending rowset order, members in allele order: (rowset, allele) pairs, sorted
     S.pairs.clear();
@@ -1247,32 +1208,57 @@ static int prepare_locus(const hipstr_batch_t* b, int l, int opt_cursor, const P
     }
     loc.tg_count[side] = out.tgroups.size() - loc.tg_begin[side];
   }
-  HS_LAP(5);
+}
+
+// ---- stage 5: the leading-flank slots and the reads — records and seeds go straight to the batch-wide arrays, the active ones to `out`
+static int append_reads(LocusPrep& C, const PrepShared& sh, std::string& err){
+  const hipstr_batch_t* b = C.b; const int l = C.l;
+  Prepared& out = C.out; const hs_locus_t& loc = C.loc;
   for (int side = 0; side < 2; side++){
     out.lead_off.push_back((int32_t)out.lead_ids.size());
-    out.lead_ids.insert(out.lead_ids.end(), S.lead_sets[side].begin(), S.lead_sets[side].end());
+    out.lead_ids.insert(out.lead_ids.end(), C.S.lead_sets[side].begin(), C.S.lead_sets[side].end());
   }
   for (int r = loc.read_begin; r < loc.read_begin + loc.n_reads; r++){
+    if (read_too_long(b, r, err)) return 1;
     hs_read_t rd;
     rd.base_off = b->base_off[r]; rd.len = b->base_off[r+1]-b->base_off[r]; rd.locus = l; rd.seed = -1;
     const bool realign = b->realign_read ? b->realign_read[r] != 0 : true;
     sh.realign_read[r] = realign ? 1 : 0;
     if (realign){
-      const bool given = seed_in && seed_in[r] != HIPSTR_SEED_AUTO;
-      const int s = given ? seed_in[r] : calc_seed_base(b, l, r);
-      if (s == -2){ err = "Invalid alignment seed or unrecognized CIGAR char (HapAligner.cpp:309,316)"; return 1; }
-      if (given && s != -1 && (s < 1 || s > rd.len - 2)){ err = "seed base must leave at least one base on either side (HapAligner.cpp:316)"; return 1; }
+      int s;
+      if (read_seed(b, l, r, sh.seed_in ? sh.seed_in[r] : HIPSTR_SEED_AUTO, &s, err)) return 1;
       rd.seed = s;
       sh.seeds[r] = s;
       if (s >= 0){
-        if (s > HS_MAX_SIDE_FWD || rd.len-s-1 > HS_MAX_SIDE_FWD){ err = "read side longer than 1024 bases is not supported"; return 1; }
         out.active.push_back(r);
-        out.n_alignments += n_realigned;
+        out.n_alignments += C.n_realigned;
         out.max_read_len = std::max(out.max_read_len, rd.len);
       }
     }
     sh.reads[r] = rd;
   }
+  return 0;
+}
+
+static int prepare_locus(const hipstr_batch_t* b, int l, const LocusShape& shape, const PrepShared& sh, Prepared& out, std::string& err){
+  uint64_t lap_t = g_lap_on ? __builtin_ia32_rdtsc() : 0;
+  LocusPrep C{ b, l, shape, out, locus_scratch() };
+  hs_locus_t& loc = C.loc;
+  loc.out_off = sh.out_off[l]; loc.hap_begin = out.alleles.size(); loc.n_alleles = shape.A;
+  loc.read_begin = b->read_off[l]; loc.n_reads = b->read_off[l+1]-b->read_off[l];
+  loc.period = b->period[l]; loc.fused = 0;
+  HS_LAP(0);
+  append_str_options(C);
+  HS_LAP(1);
+  index_boundaries(C);
+  HS_LAP(2);
+  append_allele_rows(C);
+  HS_LAP(3);
+  append_str_order(C);
+  HS_LAP(4);
+  append_trailing_groups(C);
+  HS_LAP(5);
+  if (append_reads(C, sh, err)) return 1;
   HS_LAP(6);
   out.loci.push_back(loc);
   return 0;
@@ -1391,20 +1377,14 @@ int prepare_batch(const hipstr_batch_t* b, Prepared& out, std::string& err, int6
   out.realign_read.assign(n_reads_total, 1);
   out.reads.resize(n_reads_total);
   // per-locus starts in the option table and in the output, and a cost estimate to cut the loci into balanced fragments
-  std::vector<int> opt_start(b->n_loci + 1, 0);
+  std::vector<LocusShape> shape(b->n_loci);
   std::vector<int64_t> out_off_v(b->n_loci + 1, 0), cost(b->n_loci + 1, 0);
-  for (int l = 0; l < b->n_loci; l++){
-    int64_t A = 1; int no = 0;
-    for (int k = 0; k < 3; k++){
-      const int n = b->blk_nopts[3*l+k];
-      if (n < 1){ err = "haplotype block without options"; return 1; }
-      no += n; A *= n;
-    }
-    opt_start[l+1] = opt_start[l] + no;
-    const int64_t P = b->read_off[l+1] - b->read_off[l];
-    if (P < 0){ err = "read_off must not decrease"; return 1; }
+  for (int l = 0, opt0 = 0; l < b->n_loci; l++){
+    if (locus_shape(b, l, opt0, shape[l], err)) return 1;
+    opt0 += shape[l].n_options();
+    const int64_t P = b->read_off[l+1] - b->read_off[l], A = shape[l].A;
     out_off_v[l+1] = out_off_v[l] + P*A;
-    cost[l+1] = cost[l] + 64*(int64_t)b->blk_nopts[3*l+1] + 4*A + P;
+    cost[l+1] = cost[l] + 64*(int64_t)shape[l].nopts[1] + 4*A + P;
   }
   const int64_t out_off = out_off_v[b->n_loci];
   lap("setup", t_lap);
@@ -1413,7 +1393,7 @@ int prepare_batch(const hipstr_batch_t* b, Prepared& out, std::string& err, int6
   int n_threads = std::min(host_threads(), std::max(1, b->n_loci / 4));
   if (n_threads <= 1){
     for (int l = 0; l < b->n_loci; l++)
-      if (prepare_locus(b, l, opt_start[l], sh, out, err)) return 1;
+      if (prepare_locus(b, l, shape[l], sh, out, err)) return 1;
   } else {
     // fragments of consecutive loci with near-equal cost, a few per thread so that a slow fragment does not stall the rest
     const int n_frag = std::min(b->n_loci, n_threads*4);
@@ -1427,7 +1407,7 @@ int prepare_batch(const hipstr_batch_t* b, Prepared& out, std::string& err, int6
     std::vector<int> frag_rc(n_frag, 0);
     parallel_for(n_frag, n_threads, [&](int f){
       for (int l = cut[f]; l < cut[f+1] && !frag_rc[f]; l++)
-        frag_rc[f] = prepare_locus(b, l, opt_start[l], sh, frag[f], frag_err[f]);
+        frag_rc[f] = prepare_locus(b, l, shape[l], sh, frag[f], frag_err[f]);
     });
     lap("fragments", t_lap);
     for (int f = 0; f < n_frag; f++) if (frag_rc[f]){ err = frag_err[f]; return 1; }
