@@ -313,11 +313,35 @@ Ctx* current_ctx(){
 int bind(Ctx* c){ HS_HIP(hipSetDevice(c->device)); return 0; }
 }  // namespace
 
-hipError_t hipstr::wait_stream(hipStream_t st){
+namespace {
+// HIPSTR_WAIT: 0 spin (the driver's own wait), 1 yield then sleep, 2 sleep from the first poll
+int wait_mode(){
   static const int mode = []{ const char* e = getenv("HIPSTR_WAIT"); return !e ? 1 : !strcmp(e, "spin") ? 0 : !strcmp(e, "sleep") ? 2 : 1; }();
-  if (mode == 0) return hipStreamSynchronize(st);
+  return mode;
+}
+// the one polling loop of wait_stream and wait_event: `query` until it is no longer hipErrorNotReady
+template <typename Query> hipError_t poll_until_ready(Query query){
   const auto t0 = std::chrono::steady_clock::now();
-  bool slow = (mode == 2);
+  bool slow = (wait_mode() == 2);
+  for (unsigned n = 0;; n++){
+    const hipError_t e = query();
+    if (e != hipErrorNotReady) return e;
+    if (slow) usleep(50);
+    else {
+      sched_yield();
+      if ((n & 15) == 15 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) slow = true;
+    }
+  }
+}
+}  // namespace
+
+hipError_t hipstr::wait_event(hipEvent_t ev){
+  if (wait_mode() == 0) return hipEventSynchronize(ev);
+  return poll_until_ready([&]{ return hipEventQuery(ev); });
+}
+
+hipError_t hipstr::wait_stream(hipStream_t st){
+  if (wait_mode() == 0) return hipStreamSynchronize(st);
   // (round 6: an event recorded behind the stream's work and hipEventQuery — a hipStreamQuery that finds the stream busy leaves work for the
   //  HSA runtime's event thread: 0.45 s of its CPU per 3 s of polling against 0.03 with an event, profiles/r06_runtime_thread_probe.txt; sixteen host threads
   //  of one-shot calls share that one thread)
@@ -326,15 +350,10 @@ hipError_t hipstr::wait_stream(hipStream_t st){
   { int cur = -1; if (!c || hipGetDevice(&cur) != hipSuccess || cur != c->device) c = NULL; }
   hipEvent_t ev = c ? c->get_event(false) : NULL;
   if (ev && hipEventRecord(ev, st) != hipSuccess){ c->put_event(ev, false); ev = NULL; }
-  for (unsigned n = 0;; n++){
-    const hipError_t e = ev ? hipEventQuery(ev) : hipStreamQuery(st);
-    if (e != hipErrorNotReady){ if (ev) c->put_event(ev, false); return e; }
-    if (slow) usleep(50);
-    else {
-      sched_yield();
-      if ((n & 15) == 15 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) slow = true;
-    }
-  }
+  if (!ev) return poll_until_ready([&]{ return hipStreamQuery(st); });
+  const hipError_t e = poll_until_ready([&]{ return hipEventQuery(ev); });
+  c->put_event(ev, false);
+  return e;
 }
 
 namespace {
@@ -369,7 +388,8 @@ hipStream_t thread_stream(Ctx* c){
 
 // A second stream per (host thread, device): the tables the device builds for itself (expand_kernels.hip) are inputs of the STR-block kernels
 // only, so on the one-shot path they are built here while the caller's stream runs the column tables and the leading flanks (20 us of a
-// 190 us one-locus call).  NULL when it cannot be made: the expansion then stays on the upload's stream.
+// 190 us one-locus call).  NULL when it cannot be made: the expansion then stays on the upload's stream.  The stutter EM runs its
+// allele-frequency scans here (ctx_aux_stream; em.hip joins them into its own stream before it returns).
 hipStream_t thread_aux_stream(Ctx* c){
   thread_local std::map<Ctx*, hipStream_t> mine;
   auto it = mine.find(c);
@@ -895,6 +915,9 @@ void hipstr::free_landed(hipstr_dev_batch_t* dev, bool landed){
 double hipstr::batch_prepare_seconds(const hipstr_dev_batch_t* dev){ return dev ? dev->t_prepare : 0.0; }
 hipStream_t hipstr::ctx_stream(Ctx* c){ return c->stream; }
 int hipstr::ctx_device(Ctx* c){ return c->device; }
+hipStream_t hipstr::ctx_aux_stream(Ctx* c){ hipStream_t st = thread_aux_stream(c); if (!st) fail("hipStreamCreate failed"); return st; }
+hipEvent_t hipstr::event_get(Ctx* c){ hipEvent_t e = c->get_event(false); if (!e) fail("hipEventCreate failed"); return e; }
+void hipstr::event_put(Ctx* c, hipEvent_t e){ c->put_event(e, false); }
 int hipstr::ctx_record_table(Ctx* c, size_t count, void (*fill)(double*), const double** out){
   std::lock_guard<std::mutex> lock(c->rec_m);
   if (!c->rec_table){

@@ -37,6 +37,7 @@ int api_fail(const std::string& message);     // records hipstr_last_error(); re
 // yields the core between polls (sched_yield returns at once when nothing else is runnable: the single-thread latency stays what it was),
 // sleeping 50 us per poll once a wait has lasted 2 ms.  HIPSTR_WAIT=spin: the driver's own wait; =sleep: sleep from the first poll.
 hipError_t wait_stream(hipStream_t st);
+hipError_t wait_event(hipEvent_t ev);         // the same policy for an event the caller recorded
 
 void* dev_alloc(Ctx* ctx, size_t bytes);      // NULL + last error on failure
 void  dev_free(Ctx* ctx, void* p);
@@ -70,7 +71,7 @@ struct HostArena : HostPieces {
 // On the normal path the results were fetched through wait_stream already and that wait costs a few microseconds; hipStreamSynchronize
 // is the backstop of the error paths.
 
-// Cache blocks with one owner — the device scratch arrays of a chunked call (traceback, Needleman-Wunsch, the stutter EM), the blocks of a
+// Cache blocks with one owner — the device scratch arrays of a chunked call (traceback, Needleman-Wunsch), the blocks of a
 // resident handle (a posterior run, a read matrix): one cache block each, device or pinned, all of them back when the owner goes, behind
 // every stream it was told about.  release() gives one back earlier — the caller has waited for whatever used it — and replace() puts a
 // new block in its place; an owner that holds nothing any more has nothing to wait for.
@@ -235,6 +236,13 @@ void scatter_loci(const hipstr_dev_batch* dev, int l0, int l1, double* aln_probs
 void free_landed(hipstr_dev_batch* dev, bool landed);
 hipStream_t ctx_stream(Ctx* c);
 int ctx_device(Ctx* c);
+// the calling thread's second stream on c's device, for work beside its own stream (the forward pass' table expansion, the EM's
+// allele-frequency scans): lives until the process ends; NULL + last error when it could not be made.  Whoever queues work on it joins
+// that work into the stream of the call before the call returns.
+hipStream_t ctx_aux_stream(Ctx* c);
+// an untimed event of the context's pool (NULL + last error when the driver refuses a new one), and its way back
+hipEvent_t event_get(Ctx* c);
+void event_put(Ctx* c, hipEvent_t e);
 // record.hip's constant table: `count` doubles written by `fill` and uploaded on the context's first request, the context's from then on
 // (freed by hipstr_hmm_shutdown with its other tables); 1 + last error on failure
 int ctx_record_table(Ctx* c, size_t count, void (*fill)(double*), const double** out);

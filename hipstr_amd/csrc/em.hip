@@ -766,147 +766,188 @@ int em_prepare(const hipstr_em_batch_t* eb, bool host_loop, EmPrep& P){
   return 0;
 }
 
-// The loop of train() (:171-226) for a prepared batch: P's locus records and posterior units, and the seven per-read and per-allele arrays
-// they index, already on the device — uploaded from em_prepare's host arrays (hipstr_em_train) or built there (em_input.hip:
-// hipstr_em_train_dev).  Everything else the loop needs is allocated here, through `dev` (whose blocks outlive the loop's kernels).
-struct EmArrays { int32_t *bps, *obs, *lab, *w; double *p1, *p2, *gtp; };
-int em_loop(const hipstr::ApiTables& T, hipstr::ScratchBufs& dev, EmPrep& P, const EmArrays& in, int max_iter, double min_abs_change, double min_frac_change,
-            bool host_loop, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
-  const hipstr::HostTables& HT = hipstr::host_tables();
+// ---- The loop of train() (:171-226) for a prepared batch: P's locus records and posterior units, and the seven per-read and per-allele
+// arrays they index — uploaded with the rest from em_prepare's host arrays (hipstr_em_train) or built on the device (em_input.hip:
+// hipstr_em_train_dev).  em_loop below is the sequence of its stages.
+
+// The call's memory is ONE layout: every array of the loop is a piece of the device block of a hipstr::ResultBlocks (what comes home first,
+// then the workspace) or of the uploaded block of a hipstr::HostArena, sized from P's totals.  lay() names every array once, as a piece and
+// as the address the kernels get; it runs twice: without blocks the addresses are offsets and only the sizes count (em_blocks, and
+// hipstr_debug_em_plan's "blocks"), with them it fills the argument structs (em_arguments).  Each
+// run starts both piece lists afresh and must take the same branches: em_loop checks that the second arrives at the first's sizes.  Most pieces serve both loops; a piece that only
+// one loop's kernels touch is that loop's: the device loop's lists, counts, state and parameters; the host loop's masks (em_locus' `active`,
+// the posterior kernel's `unit_active`) and hs_em_mstep's new_ll / sums; the nine logs per locus are uploaded in the one and workspace in
+// the other.  tests/test_em_routes.py restates the list.
+constexpr int EM_NBUF = 4;          // rounds whose counts may be on their way home
+struct EmHostArrays { const int32_t *sample_label, *weight; const double *log_p1, *log_p2; size_t n_reads; };      // hipstr_em_train's own, beside P's bps / obs / gtp
+struct EmBlocks {
+  hipstr::ResultBlocks B; hipstr::HostArena ar;
+  bool device_loop = true, timing = false; int pieces = 0;
+  hs_em_dev_t h[2]; hs_post_dev_t ph[2];          // the argument structs: one pair for the host loop, two for the device loop (the lists swap roles)
+  const hs_em_dev_t* d_h = NULL; const hs_post_dev_t* d_ph = NULL;      // ... where they land
+  double* keep = NULL; int32_t* polled = NULL;   // hs_em_mstep_keepmax's maxima; the counts of EM_NBUF rounds (a results' piece for its pinned side: the device side is idle)
+  std::vector<int32_t> first_unit;
+  size_t round_off = 0, round_bytes = 0;          // the host loop's per-round upload within the arena
+  template <typename T> T* piece(size_t count){ pieces++; return (T*)((uintptr_t)B.d + B.take(count*sizeof(T))); }
+  template <typename T> T* sent(const T* src, size_t count){ pieces++; return (T*)((uintptr_t)ar.dev + ar.add(src, count*sizeof(T))); }
+  template <typename T> T* home(const T* p) const { return (T*)(B.h + ((const char*)p - B.d)); }             // a results' piece on the host, after fetch
+  template <typename T> T* staged(const T* p) const { return (T*)(ar.pin + ((const char*)p - ar.dev)); }      // an uploaded piece in the pinned block
+
+  void lay(const EmPrep& P, const EmHostArrays* up, const hipstr::EmDeviceArrays* on_device, const double* int_log, int max_iter, double min_abs_change, double min_frac_change){
+    const hipstr::HostTables& HT = hipstr::host_tables();
+    const size_t nl = P.loci.size(), nu = P.units.size(), ns = (size_t)P.samp_off, n_args = device_loop ? 2 : 1;
+    B.tot = B.res = 0; ar.pieces.clear(); ar.total = 0; pieces = 0;
+    hs_em_dev_t e; memset(&e, 0, sizeof e);
+    hs_post_dev_t p; memset(&p, 0, sizeof p);
+    // ---- what comes home: the device loop's four outputs and polled counts, or hs_em_mstep's for the host; a timed call's counters
+    if (device_loop){ e.state = piece<int32_t>(nl); e.n_iter = piece<int32_t>(nl); e.final_ll = piece<double>(nl); e.sp = piece<double>(6*nl); polled = piece<int32_t>(2*EM_NBUF); }
+    else { e.new_ll = piece<double>(nl); e.sums = piece<double>(7*nl); }
+    if (timing) e.dbg = piece<unsigned long long>(4);
+    B.end_results();
+    // ---- workspace
+    p.map_gt = piece<int32_t>(2*ns); e.ll = piece<double>(P.ll_off); e.prior = piece<double>(P.prior_off); p.log_post = piece<double>(P.post_off);
+    p.sample_total = piece<double>(ns); e.row_lse = piece<double>(P.post_off); e.cat = piece<int32_t>(P.ll_off); e.leff = piece<double>(P.ll_off);
+    e.part = piece<double>(7*(size_t)HS_EM_PARTS*nl); keep = piece<double>(7*nl); e.gmax = piece<double>(P.sa_off);
+    // ---- uploaded: locus records and units; hipstr_em_train's seven arrays (hipstr_em_train_dev's are on the device); the argument structs
+    e.loci = sent(P.loci.data(), nl); p.units = sent(P.units.data(), nu);
+    const hipstr::EmDeviceArrays in = !up ? *on_device : hipstr::EmDeviceArrays{
+      sent(P.bps.data(), P.bps.size()), sent(P.obs.data(), P.obs.size()), sent(up->sample_label, up->n_reads), sent(up->weight, up->n_reads),
+      sent(up->log_p1, up->n_reads), sent(up->log_p2, up->n_reads), sent(P.gtp.data(), P.gtp.size()) };
+    d_h = sent(h, n_args); d_ph = sent(ph, n_args);
+    // ---- one loop's own
+    int32_t *list[2] = {NULL, NULL}, *counts[2] = {NULL, NULL}, *ulist[2] = {NULL, NULL};
+    if (device_loop){
+      e.logp = e.logp_rw = piece<double>(9*nl);
+      for (int k = 0; k < 2; k++) list[k] = piece<int32_t>(nl);
+      for (int k = 0; k < 2; k++) counts[k] = piece<int32_t>(2);
+      for (int k = 0; k < 2; k++) ulist[k] = piece<int32_t>(nu);
+      e.next_unit_begin = piece<int32_t>(nl); e.iter = piece<int32_t>(nl); e.cur_ll = piece<double>(nl);
+      first_unit.resize(nl);
+      { int32_t u = 0; for (size_t l = 0; l < nl; l++){ first_unit[l] = u; u += P.loci[l].S; } }
+      e.unit_first = sent(first_unit.data(), nl);
+    } else {
+      // The host writes these three into the pinned block and sends [round_off, round_off + round_bytes) again every round: they must stay
+      // the arena's last pieces (em_loop checks it).  The first round writes them while send()'s copy of the whole block may still read
+      // the pinned bytes: whatever that copy carries of them, the round's own copy follows it on the same stream, ahead of the kernels.
+      round_off = ar.total;
+      e.active = sent<int32_t>(NULL, nl); p.unit_active = sent<int32_t>(NULL, nu); e.logp = sent<double>(NULL, 9*nl);
+      round_bytes = ar.total - round_off;
+    }
+    // ---- the structs
+    e.bps = in.bps; e.obs = in.obs; e.sample_label = in.sample_label; e.log_p1 = in.log_p1; e.log_p2 = in.log_p2; e.gtp = in.gtp; e.int_log = int_log;
+    e.post = p.log_post; e.sample_total = p.sample_total;
+    e.log_thresh = HT.log_thresh; e.log_half = HT.log_half; e.log_1p1 = device_loop ? cr_log(1.1) : log(1.1);
+    e.max_iter = max_iter; e.n_loci = (int32_t)nl; e.min_abs = min_abs_change; e.min_frac = min_frac_change;
+    p.log_aln_probs = e.ll; p.log_p1 = in.log_p1; p.log_p2 = in.log_p2; p.read_weight = in.weight; p.log_prior = e.prior;
+    p.log_thresh = HT.log_thresh; p.log_half = HT.log_half; p.sym_prior = 1;          // hs_em_fill: log f(a1) + log f(a2), or the haploid diagonal
+    for (int k = 0; k < 2; k++){        // (the two sets of lists: a round reads one and writes the other; NULL with the host loop)
+      h[k] = e; h[k].list = list[k]; h[k].counts = counts[k]; h[k].next_list = list[k ^ 1]; h[k].next_counts = counts[k ^ 1]; h[k].next_units = ulist[k ^ 1];
+      ph[k] = p; ph[k].unit_list = ulist[k]; ph[k].n_list = device_loop ? counts[k] + 1 : NULL;
+    }
+  }
+};
+
+// The calling thread's auxiliary stream as the side stream of a round (the allele-frequency scans), and pooled events: fork, join, and
+// the device loop's counts.  The call joins the side stream into its own before it waits for that; where it leaves between a fork and
+// that wait, the side stream is waited for here — before the blocks go back (EmBlocks is declared first, so it dies last).
+struct EmSide {
+  hipstr::Ctx* ctx; hipStream_t stream = NULL; bool busy = false;
+  hipEvent_t fork = NULL, join = NULL, counts[EM_NBUF] = {NULL, NULL, NULL, NULL};
+  explicit EmSide(hipstr::Ctx* c) : ctx(c) {}
+  ~EmSide(){
+    if (busy) hipStreamSynchronize(stream);
+    for (hipEvent_t e : {fork, join, counts[0], counts[1], counts[2], counts[3]}) hipstr::event_put(ctx, e);
+  }
+  int open(bool device_loop){            // 1 + the last error when the stream or an event is not to be had
+    bool ok = (stream = hipstr::ctx_aux_stream(ctx)) && (fork = hipstr::event_get(ctx)) && (join = hipstr::event_get(ctx));
+    for (int i = 0; ok && device_loop && i < EM_NBUF; i++) ok = (counts[i] = hipstr::event_get(ctx)) != NULL;
+    return ok ? 0 : 1;
+  }
+};
+
+// One round's launches.  The loops differ in the grids (a bound on the listed loci and units, or all of them), in who forms the next
+// parameters (hs_em_finish, or hs_em_mstep's sums for the host) and in the device loop's lists of the next round.
+int em_queue_round(hipStream_t st, EmSide& side, const hs_em_dev_t* H, const hs_post_dev_t* PH, double* keep, unsigned grid_loci, unsigned grid_units, bool device_loop){
+  hipLaunchKernelGGL(hs_em_fill, dim3(grid_loci), dim3(256), 0, st, H);
+  hipLaunchKernelGGL(hs_posterior_kernel, dim3(grid_units), dim3(256), 0, st, PH);
+  HS_HIP(hipEventRecord(side.fork, st));                             // posteriors are in place: the allele-frequency scans branch off
+  HS_HIP(hipStreamWaitEvent(side.stream, side.fork, 0));             // (beside the M-step on the side stream: 0.51 against 0.57 s per 10 000 loci in series, profiles/r05_notes.md)
+  side.busy = true;
+  hipLaunchKernelGGL(hs_em_gt_priors, dim3(grid_loci), dim3(HS_EM_THREADS), hs_em_lds_doubles()*sizeof(double), side.stream, H);
+  HS_HIP(hipEventRecord(side.join, side.stream));
+  hipLaunchKernelGGL(hs_em_gmax, dim3(grid_loci), dim3(256), 0, st, H);
+  hipLaunchKernelGGL(hs_em_mstep_part<0>, dim3(grid_loci, HS_EM_PARTS), dim3(256), 0, st, H, (const double*)NULL);
+  hipLaunchKernelGGL(hs_em_mstep_keepmax, dim3(grid_loci), dim3(64), 0, st, H, keep);
+  hipLaunchKernelGGL(hs_em_mstep_part<1>, dim3(grid_loci, HS_EM_PARTS), dim3(256), 0, st, H, (const double*)keep);
+  if (device_loop) hipLaunchKernelGGL(hs_em_finish, dim3(grid_loci), dim3(64), 0, st, H, (const double*)keep);
+  else hipLaunchKernelGGL(hs_em_mstep, dim3(grid_loci), dim3(256), 0, st, H, (const double*)keep);
+  HS_HIP(hipStreamWaitEvent(st, side.join, 0));                      // the new allele frequencies: the next round's hs_em_fill reads them, or the host this round's results
+  if (device_loop){
+    hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(HS_EM_COMPACT_THREADS), 0, st, H);
+    hipLaunchKernelGGL(hs_em_units, dim3(grid_loci), dim3(HS_EM_UNITS_THREADS), 0, st, H);
+  }
+  return 0;
+}
+
+// HIPSTR_TIMING's stopwatch: a lap is printed, or added to a sum
+struct EmClock {
   const bool timing = getenv("HIPSTR_TIMING") != NULL;
-  auto t_prev = std::chrono::steady_clock::now();
-  double t_gpu = 0.0, t_host = 0.0;
-  auto lap = [&](const char* what, double* into){
+  std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+  void lap(const char* what, double* into){
     const auto now = std::chrono::steady_clock::now();
     const double dt = std::chrono::duration<double>(now - t_prev).count();
     t_prev = now;
     if (into) *into += dt; else if (timing) fprintf(stderr, "hipstr_em_train: %s %.3f ms\n", what, 1e3*dt);
-  };
-  std::vector<hs_em_locus_t>& loci = P.loci; std::vector<hs_post_unit_t>& units = P.units;
-  std::vector<int32_t>& unit_locus = P.unit_locus;
-  const int nl = (int)loci.size();
-  const int64_t post_off = P.post_off, ll_off = P.ll_off, prior_off = P.prior_off, sa_off = P.sa_off; const int samp_off = P.samp_off;
-  // ---- device state
-  hs_em_dev_t h; memset(&h, 0, sizeof h);
-  hs_post_dev_t ph; memset(&ph, 0, sizeof ph);
-  hs_em_locus_t* d_loci; hs_post_unit_t* d_units; int32_t *d_active, *d_unit_active, *d_mapgt;
-  int32_t* const d_bps = in.bps, * const d_obs = in.obs, * const d_lab = in.lab, * const d_w = in.w;
-  double* const d_p1 = in.p1, * const d_p2 = in.p2, * const d_gtp = in.gtp;
-  double *d_logp, *d_ll, *d_prior, *d_post, *d_tot, *d_newll, *d_sums, *d_rowlse, *d_leff, *d_part, *d_keep, *d_gmax; int32_t* d_cat;
-  if (dev.put(&d_loci, loci.data(), loci.size()) || dev.put(&d_units, units.data(), units.size()) || dev.alloc(&d_active, nl) ||
-      dev.alloc(&d_unit_active, units.size()) || dev.alloc(&d_mapgt, 2*(size_t)samp_off) ||
-      dev.alloc(&d_logp, 9*(size_t)nl) || dev.alloc(&d_ll, ll_off) || dev.alloc(&d_prior, prior_off) || dev.alloc(&d_post, post_off) ||
-      dev.alloc(&d_tot, samp_off) || dev.alloc(&d_newll, nl) || dev.alloc(&d_sums, 7*(size_t)nl) || dev.alloc(&d_rowlse, post_off) ||
-      dev.alloc(&d_cat, ll_off) || dev.alloc(&d_leff, ll_off) || dev.alloc(&d_part, 7*(size_t)HS_EM_PARTS*nl) || dev.alloc(&d_keep, 7*(size_t)nl) || dev.alloc(&d_gmax, sa_off)) return 1;
-  h.loci = d_loci; h.active = d_active; h.logp = d_logp; h.bps = d_bps; h.obs = d_obs; h.sample_label = d_lab; h.log_p1 = d_p1; h.log_p2 = d_p2;
-  h.gtp = d_gtp; h.ll = d_ll; h.prior = d_prior; h.post = d_post; h.sample_total = d_tot; h.int_log = T.int_log; h.new_ll = d_newll; h.sums = d_sums; h.row_lse = d_rowlse; h.cat = d_cat; h.leff = d_leff; h.part = d_part; h.gmax = d_gmax;
-  unsigned long long* d_dbg = NULL;
-  if (timing){ if (dev.alloc(&d_dbg, 4)) return 1; HS_HIP(hipMemset(d_dbg, 0, 4*sizeof(unsigned long long))); }
-  h.dbg = d_dbg;
-  h.log_thresh = HT.log_thresh; h.log_half = HT.log_half; h.log_1p1 = host_loop ? log(1.1) : cr_log(1.1);
-  ph.units = d_units; ph.log_aln_probs = d_ll; ph.log_p1 = d_p1; ph.log_p2 = d_p2; ph.read_weight = d_w; ph.log_prior = d_prior;
-  ph.unit_active = d_unit_active; ph.log_post = d_post; ph.sample_total = d_tot; ph.map_gt = d_mapgt;
-  ph.log_thresh = HT.log_thresh; ph.log_half = HT.log_half; ph.sym_prior = 1;          // hs_em_fill: log f(a1) + log f(a2), or the haploid diagonal
-  hs_em_dev_t* d_h; hs_post_dev_t* d_ph;
-  if (dev.put(&d_h, &h, 1) || dev.put(&d_ph, &ph, 1)) return 1;
-
-  lap("device state", NULL);
-  struct SideStream {                 // a second stream for the allele-frequency scans of an iteration
-    hipStream_t stream = NULL; hipEvent_t ev_fork = NULL, ev_join = NULL;
-    ~SideStream(){ if (stream) hipStreamSynchronize(stream); if (ev_fork) hipEventDestroy(ev_fork); if (ev_join) hipEventDestroy(ev_join); if (stream) hipStreamDestroy(stream); }
-  } side;
-  HS_HIP(hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking));
-  HS_HIP(hipEventCreateWithFlags(&side.ev_fork, hipEventDisableTiming));
-  HS_HIP(hipEventCreateWithFlags(&side.ev_join, hipEventDisableTiming));
-  if (!host_loop){
-    // ---- the device-resident loop: state, the two sets of lists (a round reads one and writes the other), two argument blocks each for
-    // the EM kernels and the posterior kernel that differ only in which set is which
-    const size_t n_units = units.size();
-    std::vector<int32_t> unit_first(nl);
-    { int32_t u = 0; for (int l = 0; l < nl; l++){ unit_first[l] = u; u += loci[l].S; } }
-    int32_t *d_list[2], *d_counts[2], *d_ulist[2], *d_ubegin, *d_ufirst, *d_iter, *d_state, *d_niter; double *d_sp, *d_curll, *d_fll;
-    if (dev.alloc(&d_list[0], nl) || dev.alloc(&d_list[1], nl) || dev.alloc(&d_counts[0], 2) || dev.alloc(&d_counts[1], 2) || dev.alloc(&d_ulist[0], n_units) ||
-        dev.alloc(&d_ulist[1], n_units) || dev.alloc(&d_ubegin, nl) || dev.put(&d_ufirst, unit_first.data(), unit_first.size()) || dev.alloc(&d_iter, nl) ||
-        dev.alloc(&d_state, nl) || dev.alloc(&d_niter, nl) || dev.alloc(&d_sp, 6*(size_t)nl) || dev.alloc(&d_curll, nl) || dev.alloc(&d_fll, nl)) return 1;
-    hs_em_dev_t hb[2]; hs_post_dev_t pb2[2];
-    for (int k = 0; k < 2; k++){
-      hb[k] = h; hb[k].active = NULL;
-      hb[k].list = d_list[k]; hb[k].counts = d_counts[k]; hb[k].next_list = d_list[k ^ 1]; hb[k].next_counts = d_counts[k ^ 1]; hb[k].next_units = d_ulist[k ^ 1];
-      hb[k].next_unit_begin = d_ubegin; hb[k].unit_first = d_ufirst; hb[k].logp_rw = d_logp; hb[k].sp = d_sp; hb[k].cur_ll = d_curll; hb[k].iter = d_iter;
-      hb[k].state = d_state; hb[k].n_iter = d_niter; hb[k].final_ll = d_fll; hb[k].max_iter = max_iter; hb[k].n_loci = nl;
-      hb[k].min_abs = min_abs_change; hb[k].min_frac = min_frac_change;
-      pb2[k] = ph; pb2[k].unit_active = NULL; pb2[k].unit_list = d_ulist[k]; pb2[k].n_list = d_counts[k] + 1;
-    }
-    hs_em_dev_t* d_hb; hs_post_dev_t* d_pb;
-    if (dev.put(&d_hb, hb, 2) || dev.put(&d_pb, pb2, 2)) return 1;
-    struct Pinned { hipstr::Ctx* ctx; int32_t* p; ~Pinned(){ if (p) hipstr::pin_free(ctx, p); } } pin{T.ctx, NULL};
-    constexpr int NBUF = 4;
-    pin.p = (int32_t*)hipstr::pin_alloc(T.ctx, NBUF*2*sizeof(int32_t));
-    if (!pin.p) return 1;
-    hipEvent_t ev_cnt[NBUF] = {NULL, NULL, NULL, NULL};
-    struct EvGuard { hipEvent_t* e; int n; ~EvGuard(){ for (int i = 0; i < n; i++) if (e[i]) hipEventDestroy(e[i]); } } evg{ev_cnt, NBUF};
-    for (int i = 0; i < NBUF; i++) HS_HIP(hipEventCreateWithFlags(&ev_cnt[i], hipEventDisableTiming));
-    auto wait_event = [&](hipEvent_t e) -> hipError_t {           // without burning a core (hipEventSynchronize spins: tools/wait_probe.hip)
-      for (unsigned n = 0;; n++){
-        const hipError_t q = hipEventQuery(e);
-        if (q != hipErrorNotReady) return q;
-        if (n < 2000) sched_yield(); else usleep(20);
-      }
-    };
-    lap("device-loop state", NULL);
-    const unsigned g_loci = hs_em_init_blocks(nl);
-    // the starting state, and the lists of round 0 (written through block 1, whose "next" set is block 0's current one)
-    hipLaunchKernelGGL(hs_em_init, dim3(g_loci), dim3(HS_EM_INIT_THREADS), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
-    hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(HS_EM_COMPACT_THREADS), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
-    hipLaunchKernelGGL(hs_em_units, dim3(nl), dim3(HS_EM_UNITS_THREADS), 0, T.stream, (const hs_em_dev_t*)(d_hb + 1));
-    unsigned bound_l = (unsigned)nl, bound_u = (unsigned)n_units;
-    int rounds = 0;
-    for (int r = 0; r <= hs_em_last_round(max_iter); r++){
-      const hs_em_dev_t* H = d_hb + (r & 1); const hs_post_dev_t* PH = d_pb + (r & 1);
-      if (bound_l > 0){
-        hipLaunchKernelGGL(hs_em_fill, dim3(bound_l), dim3(256), 0, T.stream, H);
-        hipLaunchKernelGGL(hs_posterior_kernel, dim3(std::max(1u, bound_u)), dim3(256), 0, T.stream, PH);
-        HS_HIP(hipEventRecord(side.ev_fork, T.stream));                  // posteriors are in place: the allele-frequency scans branch off
-        HS_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));        // (beside the M-step on the side stream: 0.51 against 0.57 s per 10 000 loci in series, profiles/r05_notes.md)
-        hipLaunchKernelGGL(hs_em_gt_priors, dim3(bound_l), dim3(HS_EM_THREADS), hs_em_lds_doubles()*sizeof(double), side.stream, H);
-        HS_HIP(hipEventRecord(side.ev_join, side.stream));
-        hipLaunchKernelGGL(hs_em_gmax, dim3(bound_l), dim3(256), 0, T.stream, H);
-        hipLaunchKernelGGL(hs_em_mstep_part<0>, dim3(bound_l, HS_EM_PARTS), dim3(256), 0, T.stream, H, (const double*)NULL);
-        hipLaunchKernelGGL(hs_em_mstep_keepmax, dim3(bound_l), dim3(64), 0, T.stream, H, d_keep);
-        hipLaunchKernelGGL(hs_em_mstep_part<1>, dim3(bound_l, HS_EM_PARTS), dim3(256), 0, T.stream, H, (const double*)d_keep);
-        hipLaunchKernelGGL(hs_em_finish, dim3(bound_l), dim3(64), 0, T.stream, H, (const double*)d_keep);
-        HS_HIP(hipStreamWaitEvent(T.stream, side.ev_join, 0));            // the next round's hs_em_fill reads the new allele frequencies
-        hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(HS_EM_COMPACT_THREADS), 0, T.stream, H);
-        hipLaunchKernelGGL(hs_em_units, dim3(bound_l), dim3(HS_EM_UNITS_THREADS), 0, T.stream, H);
-        rounds++;
-      }
-      HS_HIP(hipMemcpyAsync(pin.p + 2*(r % NBUF), d_counts[(r & 1) ^ 1], 2*sizeof(int32_t), hipMemcpyDeviceToHost, T.stream));
-      HS_HIP(hipEventRecord(ev_cnt[r % NBUF], T.stream));
-      HS_HIP(hipGetLastError());
-      if (r >= 1){
-        // what round r - 1 left: the loci (and units) of round r — a bound for the grids of round r + 1, and the stop signal — while
-        // round r is already queued
-        HS_HIP(wait_event(ev_cnt[(r - 1) % NBUF]));
-        bound_l = (unsigned)pin.p[2*((r - 1) % NBUF)]; bound_u = (unsigned)pin.p[2*((r - 1) % NBUF) + 1];
-        if (bound_l == 0) break;
-      }
-    }
-    HS_HIP(hipstr::wait_stream(T.stream));
-    lap("device loop", &t_gpu);
-    std::vector<int32_t> state(nl), niter(nl);
-    HS_HIP(hipMemcpy(state.data(), d_state, nl*sizeof(int32_t), hipMemcpyDeviceToHost));
-    HS_HIP(hipMemcpy(niter.data(), d_niter, nl*sizeof(int32_t), hipMemcpyDeviceToHost));
-    HS_HIP(hipMemcpy(final_ll, d_fll, nl*sizeof(double), hipMemcpyDeviceToHost));
-    HS_HIP(hipMemcpy(stutter, d_sp, 6*(size_t)nl*sizeof(double), hipMemcpyDeviceToHost));
-    for (int l = 0; l < nl; l++){ trained[l] = state[l] == 1 ? 1 : 0; n_iter[l] = niter[l]; }
-    if (timing){
-      unsigned long long c[4] = {0, 0, 0, 0};
-      if (d_dbg) hipMemcpy(c, d_dbg, sizeof c, hipMemcpyDeviceToHost);
-      fprintf(stderr, "hipstr_em_train: device-resident loop, %d rounds queued: %.3f ms; M-step rows walked: maxima pass %llu of %llu, sums pass %llu of %llu\n", rounds, 1e3*t_gpu, c[0], c[1], c[2], c[3]);
-    }
-    return 0;
   }
-  // ---- the EM loop of train() (:171-226), all loci in lock step, converged loci masked out
+};
+
+// The device-resident loop: the host queues round r + 1 while the counts of round r - 1 travel.  Returns the rounds queued in *rounds.
+int em_run_device(const hipstr::ApiTables& T, const EmPrep& P, EmBlocks& M, EmSide& side, int max_iter, int* rounds){
+  const int nl = (int)P.loci.size();
+  hipStream_t st = T.stream;
+  int32_t* const polled = M.home(M.polled);
+  // the starting state, and the lists of round 0 (written through block 1, whose "next" set is block 0's current one)
+  hipLaunchKernelGGL(hs_em_init, dim3(hs_em_init_blocks(nl)), dim3(HS_EM_INIT_THREADS), 0, st, M.d_h + 1);
+  hipLaunchKernelGGL(hs_em_compact, dim3(1), dim3(HS_EM_COMPACT_THREADS), 0, st, M.d_h + 1);
+  hipLaunchKernelGGL(hs_em_units, dim3(nl), dim3(HS_EM_UNITS_THREADS), 0, st, M.d_h + 1);
+  unsigned bound_l = (unsigned)nl, bound_u = (unsigned)P.units.size();
+  for (int r = 0; r <= hs_em_last_round(max_iter); r++){
+    if (bound_l > 0){
+      if (em_queue_round(st, side, M.d_h + (r & 1), M.d_ph + (r & 1), M.keep, bound_l, std::max(1u, bound_u), true)) return 1;
+      (*rounds)++;
+    }
+    HS_HIP(hipMemcpyAsync(polled + 2*(r % EM_NBUF), M.h[r & 1].next_counts, 2*sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HS_HIP(hipEventRecord(side.counts[r % EM_NBUF], st));
+    HS_HIP(hipGetLastError());
+    if (r >= 1){
+      // what round r - 1 left: the loci (and units) of round r — a bound for the grids of round r + 1, and the stop signal — while
+      // round r is already queued
+      HS_HIP(hipstr::wait_event(side.counts[(r - 1) % EM_NBUF]));
+      bound_l = (unsigned)polled[2*((r - 1) % EM_NBUF)]; bound_u = (unsigned)polled[2*((r - 1) % EM_NBUF) + 1];
+      if (bound_l == 0) break;
+    }
+  }
+  return 0;
+}
+// ... and its results: one copy home
+int em_results(EmBlocks& M, int nl, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
+  if (M.B.fetch()) return 1;
+  const hs_em_dev_t& h = M.h[0];
+  const int32_t* state = M.home(h.state);
+  for (int l = 0; l < nl; l++) trained[l] = state[l] == 1 ? 1 : 0;
+  memcpy(n_iter, M.home(h.n_iter), nl*sizeof(int32_t)); memcpy(final_ll, M.home(h.final_ll), nl*sizeof(double));
+  memcpy(stutter, M.home(h.sp), 6*(size_t)nl*sizeof(double));
+  return 0;
+}
+
+// The round-4 loop (HIPSTR_EM_HOST_LOOP=1), the yardstick of the device loop: the EM loop of train() (:171-226) with all loci in lock
+// step, converged loci masked out, the parameters formed on the host with its libm.  The masks and the nine logs go up from the arena's
+// pinned block, new_ll and sums come home as the results, every round.
+int em_run_host(const hipstr::ApiTables& T, const EmPrep& P, EmBlocks& M, EmSide& side, EmClock& clock, int max_iter, double min_abs_change, double min_frac_change,
+                uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
+  const hipstr::HostTables& HT = hipstr::host_tables();
+  const int nl = (int)P.loci.size(); const size_t n_units = P.units.size();
+  double t_gpu = 0.0, t_host = 0.0;
   struct State { double sp[6]; double LL; int it; bool done, ok; };
   std::vector<State> st(nl);
   for (int l = 0; l < nl; l++){
@@ -915,8 +956,9 @@ int em_loop(const hipstr::ApiTables& T, hipstr::ScratchBufs& dev, EmPrep& P, con
     st[l].LL = -DBL_MAX; st[l].it = 1; st[l].done = false; st[l].ok = false;
     n_iter[l] = 0; final_ll[l] = 0; trained[l] = 0;
   }
-  std::vector<int32_t> active(nl), unit_active(units.size());
-  std::vector<double> logp(9*(size_t)nl), newll(nl), sums(7*(size_t)nl);
+  int32_t* const active = M.staged(M.h[0].active); int32_t* const unit_active = M.staged(M.ph[0].unit_active);
+  double* const logp = M.staged(M.h[0].logp);
+  const double* const newll = M.home(M.h[0].new_ll); const double* const sums = M.home(M.h[0].sums);
   for (;;){
     int n_active = 0;
     for (int l = 0; l < nl; l++){
@@ -930,28 +972,14 @@ int em_loop(const hipstr::ApiTables& T, hipstr::ScratchBufs& dev, EmPrep& P, con
       q[8] = log(1-sp[1]-sp[2]-sp[4]-sp[5]);
     }
     if (n_active == 0) break;
-    for (size_t u = 0; u < units.size(); u++) unit_active[u] = active[unit_locus[u]];
-    lap("", &t_host);
-    HS_HIP(hipMemcpy(d_active, active.data(), nl*sizeof(int32_t), hipMemcpyHostToDevice));
-    HS_HIP(hipMemcpy(d_unit_active, unit_active.data(), units.size()*sizeof(int32_t), hipMemcpyHostToDevice));
-    HS_HIP(hipMemcpy(d_logp, logp.data(), logp.size()*sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(hs_em_fill, dim3(nl), dim3(256), 0, T.stream, d_h);
-    hipLaunchKernelGGL(hs_posterior_kernel, dim3((unsigned)units.size()), dim3(256), 0, T.stream, (const hs_post_dev_t*)d_ph);
-    HS_HIP(hipEventRecord(side.ev_fork, T.stream));                      // posteriors are in place: the allele-frequency scans branch off
-    HS_HIP(hipStreamWaitEvent(side.stream, side.ev_fork, 0));
-    hipLaunchKernelGGL(hs_em_gt_priors, dim3(nl), dim3(HS_EM_THREADS), hs_em_lds_doubles()*sizeof(double), side.stream, d_h);
-    HS_HIP(hipEventRecord(side.ev_join, side.stream));
-    hipLaunchKernelGGL(hs_em_gmax, dim3(nl), dim3(256), 0, T.stream, d_h);
-    hipLaunchKernelGGL(hs_em_mstep_part<0>, dim3(nl, HS_EM_PARTS), dim3(256), 0, T.stream, d_h, (const double*)NULL);
-    hipLaunchKernelGGL(hs_em_mstep_keepmax, dim3(nl), dim3(64), 0, T.stream, d_h, d_keep);
-    hipLaunchKernelGGL(hs_em_mstep_part<1>, dim3(nl, HS_EM_PARTS), dim3(256), 0, T.stream, d_h, (const double*)d_keep);
-    hipLaunchKernelGGL(hs_em_mstep, dim3(nl), dim3(256), 0, T.stream, d_h, (const double*)d_keep);
-    HS_HIP(hipStreamWaitEvent(T.stream, side.ev_join, 0));                // ... and join before the host reads this iteration's results
+    for (size_t u = 0; u < n_units; u++) unit_active[u] = active[P.unit_locus[u]];
+    clock.lap("", &t_host);
+    HS_HIP(hipMemcpyAsync(M.ar.dev + M.round_off, M.ar.pin + M.round_off, M.round_bytes, hipMemcpyHostToDevice, T.stream));
+    if (em_queue_round(T.stream, side, M.d_h, M.d_ph, M.keep, (unsigned)nl, (unsigned)n_units, false)) return 1;
     HS_HIP(hipGetLastError());
-    HS_HIP(hipstr::wait_stream(T.stream));
-    HS_HIP(hipMemcpy(newll.data(), d_newll, nl*sizeof(double), hipMemcpyDeviceToHost));
-    HS_HIP(hipMemcpy(sums.data(), d_sums, sums.size()*sizeof(double), hipMemcpyDeviceToHost));
-    lap("", &t_gpu);
+    if (M.B.fetch()) return 1;
+    side.busy = false;
+    clock.lap("", &t_gpu);
     for (int l = 0; l < nl; l++){
       State& s = st[l];
       if (!active[l]) continue;
@@ -978,7 +1006,7 @@ int em_loop(const hipstr::ApiTables& T, hipstr::ScratchBufs& dev, EmPrep& P, con
       s.LL = new_LL; s.it++;
     }
   }
-  if (timing) fprintf(stderr, "hipstr_em_train: iterations: copies + kernels %.3f ms, host updates %.3f ms\n", 1e3*t_gpu, 1e3*t_host);
+  if (clock.timing) fprintf(stderr, "hipstr_em_train: iterations: copies + kernels %.3f ms, host updates %.3f ms\n", 1e3*t_gpu, 1e3*t_host);
   for (int l = 0; l < nl; l++){
     trained[l] = st[l].ok ? 1 : 0;
     memcpy(stutter + 6*(size_t)l, st[l].sp, 6*sizeof(double));
@@ -986,24 +1014,50 @@ int em_loop(const hipstr::ApiTables& T, hipstr::ScratchBufs& dev, EmPrep& P, con
   return 0;
 }
 
-// hipstr_em_train on the device of T: em_prepare on the host, its arrays uploaded, the loop.
+// `up`: the host arrays that go up with the rest (hipstr_em_train), or NULL: the seven arrays are on the device already, `on_device`
+int em_loop(const hipstr::ApiTables& T, const EmPrep& P, const EmHostArrays* up, const hipstr::EmDeviceArrays* on_device, int max_iter, double min_abs_change,
+            double min_frac_change, bool host_loop, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
+  EmClock clock;
+  const int nl = (int)P.loci.size();
+  EmBlocks M;
+  M.device_loop = !host_loop; M.timing = clock.timing;
+  auto lay = [&]{ M.lay(P, up, on_device, T.int_log, max_iter, min_abs_change, min_frac_change); };
+  lay();                                                                    // em_blocks: the sizes, then the blocks
+  const size_t tot = M.B.tot, res = M.B.res, sent = M.ar.total;
+  if (M.ar.reserve(T.ctx) || M.B.reserve(T.ctx, T.stream)) return 1;
+  lay();                                                                    // em_arguments: the same pass on the blocks' addresses
+  if (M.B.tot != tot || M.B.res != res || M.ar.total != sent || (host_loop && M.round_off + M.round_bytes != sent))
+    return hipstr::api_fail("hipstr_em_train: the layout's two passes disagree, or a piece follows the host loop's per-round upload");
+  if (M.ar.send(T.stream)) return 1;
+  if (M.timing) HS_HIP(hipMemsetAsync(M.h[0].dbg, 0, 4*sizeof(unsigned long long), T.stream));
+  clock.lap("device state", NULL);
+  EmSide side(T.ctx);
+  if (side.open(!host_loop)) return 1;
+  if (host_loop) return em_run_host(T, P, M, side, clock, max_iter, min_abs_change, min_frac_change, trained, stutter, n_iter, final_ll);
+  clock.lap("device-loop state", NULL);
+  int rounds = 0; double t_gpu = 0.0;
+  if (em_run_device(T, P, M, side, max_iter, &rounds) || em_results(M, nl, trained, stutter, n_iter, final_ll)) return 1;
+  side.busy = false;
+  clock.lap("device loop", &t_gpu);
+  if (M.timing){
+    const unsigned long long* c = M.home(M.h[0].dbg);
+    fprintf(stderr, "hipstr_em_train: device-resident loop, %d rounds queued: %.3f ms; M-step rows walked: maxima pass %llu of %llu, sums pass %llu of %llu\n", rounds, 1e3*t_gpu, c[0], c[1], c[2], c[3]);
+  }
+  return 0;
+}
+
+// hipstr_em_train on the device of T: em_prepare on the host, its arrays uploaded with the loop's own, the loop.
 int em_train_on(const hipstr::ApiTables& T, const hipstr_em_batch_t* eb, uint8_t* trained, double* stutter, int32_t* n_iter, double* final_ll){
-  const int nl = eb->n_loci;
-  const int n_reads = eb->read_off[nl];
+  const size_t n_reads = (size_t)eb->read_off[eb->n_loci];
   const bool host_loop = getenv("HIPSTR_EM_HOST_LOOP") && atoi(getenv("HIPSTR_EM_HOST_LOOP")) != 0;       // the round-4 loop: host libm, every locus in every round
   const auto t0 = std::chrono::steady_clock::now();
   // ---- alleles, read -> allele index, initial allele frequencies, (locus, sample) units; the refusals
   EmPrep P;
   if (em_prepare(eb, host_loop, P)) return 1;
   if (getenv("HIPSTR_TIMING")) fprintf(stderr, "hipstr_em_train: %s %.3f ms\n", "alleles and units", 1e3*std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-  hipstr::ScratchBufs dev;
-  dev.ctx = T.ctx; dev.runs_on(T.stream);
-  EmArrays in;
-  std::vector<int32_t> ones(n_reads, 1);
-  if (dev.put(&in.bps, P.bps.data(), P.bps.size()) || dev.put(&in.obs, P.obs.data(), P.obs.size()) || dev.put(&in.lab, eb->sample_label, n_reads) ||
-      dev.put(&in.w, ones.data(), ones.size()) || dev.put(&in.p1, eb->log_p1, n_reads) || dev.put(&in.p2, eb->log_p2, n_reads) ||
-      dev.put(&in.gtp, P.gtp.data(), P.gtp.size())) return 1;
-  return em_loop(T, dev, P, in, eb->max_iter, eb->min_ll_abs_change, eb->min_ll_frac_change, host_loop, trained, stutter, n_iter, final_ll);
+  const std::vector<int32_t> ones(n_reads, 1);
+  const EmHostArrays up = { eb->sample_label, ones.data(), eb->log_p1, eb->log_p2, n_reads };
+  return em_loop(T, P, &up, NULL, eb->max_iter, eb->min_ll_abs_change, eb->min_ll_frac_change, host_loop, trained, stutter, n_iter, final_ll);
 }
 
 }  // namespace
@@ -1043,10 +1097,7 @@ int hipstr::em_train_prepared(const ApiTables& T, int n_loci, const EmLocusFacts
     em_push_locus(P, l, F.A, F.S, F.read_begin, F.R, F.period, F.haploid, F.bps_off, reads_of_sample + so);
     so += F.S;
   }
-  hipstr::ScratchBufs dev;
-  dev.ctx = T.ctx; dev.runs_on(T.stream);
-  const EmArrays in = { arr.bps, arr.obs, arr.sample_label, arr.weight, arr.log_p1, arr.log_p2, arr.gtp };
-  return em_loop(T, dev, P, in, max_iter, min_abs_change, min_frac_change, false, trained, stutter, n_iter, final_ll);
+  return em_loop(T, P, NULL, &arr, max_iter, min_abs_change, min_frac_change, false, trained, stutter, n_iter, final_ll);
 }
 
 #ifndef HIPSTR_NO_DEBUG_ABI
@@ -1130,7 +1181,12 @@ extern "C" int hipstr_debug_em_plan(const hipstr_em_batch_t* eb, char* json, int
       nl, ib, cc, nl > 0 ? nl - (cc - 1)*HS_EM_COMPACT_THREADS : 0, max_S, passes);
   bool first = true;
   for (int i = 0; i < EM_N_ROUTES; i++) if (hit[i]){ put("%s\"%s\"", first ? "" : ", ", kEmRoutes[i]); first = false; }
-  o += "]}";
+  // the memory of the call: EmBlocks' layout for the device loop of hipstr_em_train (untimed) — the device block and how much of it comes
+  // home, the uploaded block (pinned and device, each), and the arrays that are pieces of the two
+  EmBlocks M;
+  const EmHostArrays up = { NULL, NULL, NULL, NULL, nl > 0 ? (size_t)eb->read_off[nl] : 0 };
+  M.lay(P, &up, NULL, NULL, eb->max_iter, eb->min_ll_abs_change, eb->min_ll_frac_change);
+  put("], \"blocks\": {\"device_bytes\": %zu, \"result_bytes\": %zu, \"upload_bytes\": %zu, \"pieces\": %d}}", M.B.tot, M.B.res, M.ar.total, M.pieces);
   if (json && cap > 0){ const size_t m = std::min(o.size(), (size_t)cap - 1); memcpy(json, o.data(), m); json[m] = 0; }
   return (int)o.size();
 }

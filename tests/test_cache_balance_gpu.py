@@ -319,3 +319,24 @@ def test_em_train(hmm):
     kw = em_case(7, n_loci=2, samples=(3, 4), reads_per_sample=(2, 3))
     with balanced(hmm, "hipstr_em_train"):
         assert len(capi.run_em(hmm, "hipstr_", **kw)[0]) == 2
+
+
+def test_em_train_other_exits(hmm, monkeypatch):
+    """The same two loci through the round-4 host loop, and with max_iter = 0 (no locus trains: the call takes its blocks, its side stream and
+    its events, and gives them back); a repeated call finds every block in the caches, eight in a row as well."""
+    kw = em_case(7, n_loci=2, samples=(3, 4), reads_per_sample=(2, 3))
+    monkeypatch.setenv("HIPSTR_EM_HOST_LOOP", "1")
+    with balanced(hmm, "hipstr_em_train, HIPSTR_EM_HOST_LOOP=1"):
+        host = capi.run_em(hmm, "hipstr_", **kw)
+    monkeypatch.delenv("HIPSTR_EM_HOST_LOOP")
+    with balanced(hmm, "hipstr_em_train, max_iter = 0"):
+        none = capi.run_em(hmm, "hipstr_", **dict(kw, max_iter=0))
+    assert not none[0].any() and not none[2].any()
+    first = capi.run_em(hmm, "hipstr_", **kw)
+    allocs = hmm.hipstr_debug_driver_allocs()
+    with balanced(hmm, "hipstr_em_train, eight calls in a row"):
+        for _ in range(8):
+            again = capi.run_em(hmm, "hipstr_", **kw)
+            assert all(np.array_equal(a, b) for a, b in zip(again, first))
+    assert hmm.hipstr_debug_driver_allocs() == allocs
+    assert np.array_equal(host[0], first[0]) and np.array_equal(host[2], first[2])

@@ -40,6 +40,38 @@ def test_plan_shows_what_the_case_names(hmm_host, lim, cases, name):
     assert set(plan["routes_hit"]) <= set(plan["routes"])
 
 
+def em_pieces(loci, parts):
+    """The arrays of hipstr_em_train's device loop as (results, workspace, uploaded) lists of byte counts, restated from em.hip's EmBlocks:
+    every array is a piece of one device block (results first) or of the one uploaded block.  Struct sizes: hs_em_locus_t 8 x int32 +
+    4 x int64; hs_post_unit_t 3 x int64 + 4 x int32 + 2 x double; hs_em_dev_t 36 pointers + 5 doubles + 2 x int32; hs_post_dev_t 12
+    pointers + 2 doubles + 2 x int32, each of the two padded to 8."""
+    LOCUS, UNIT, EM_ARGS, POST_ARGS, NBUF = 64, 56, 336, 128, 4
+    nl = len(loci)
+    ns = sum(L["S"] for L in loci)                       # samples = (locus, sample) units
+    na = sum(L["A"] for L in loci)
+    nr = sum(L["R"] for L in loci)
+    post = sum(L["S"] * L["A"] ** 2 for L in loci); ll = sum(L["R"] * L["A"] for L in loci)
+    prior = sum(L["A"] ** 2 for L in loci); sa = sum(L["S"] * L["A"] for L in loci)
+    results = [4 * nl, 4 * nl, 8 * nl, 6 * 8 * nl, NBUF * 2 * 4]                        # state, n_iter, final_ll, sp, the counts the host polls
+    workspace = [2 * 4 * ns, 8 * ll, 8 * prior, 8 * post, 8 * ns, 8 * post, 4 * ll, 8 * ll, 7 * parts * 8 * nl, 7 * 8 * nl, 8 * sa,   # map_gt, ll, prior, post, sample totals, row_lse, cat, leff, part, keep, gmax
+                 9 * 8 * nl, 4 * nl, 4 * nl, 8, 8, 4 * ns, 4 * ns, 4 * nl, 4 * nl, 8 * nl]   # logp, 2 lists, 2 counts, 2 unit lists, unit_begin, iter, cur_ll
+    uploaded = [LOCUS * nl, UNIT * ns, 4 * na, 4 * nr, 4 * nr, 4 * nr, 8 * nr, 8 * nr, 8 * na,   # loci, units; bps, obs, sample_label, weight, log_p1, log_p2, gtp
+                2 * EM_ARGS, 2 * POST_ARGS, 4 * nl]                                              # the two pairs of argument structs, unit_first
+    return results, workspace, uploaded
+
+
+@pytest.mark.parametrize("name", ec.CASE_NAMES)
+def test_plan_reports_the_calls_blocks(hmm_host, lim, cases, name):
+    """Pieces lie back to back in steps of 256 bytes, an empty piece taking one step (block_pieces.h)."""
+    plan = capi.em_plan(hmm_host, **cases[name].kw)
+    step = lambda n: (max(n, 1) + 255) // 256 * 256
+    results, workspace, uploaded = em_pieces(plan["loci"], lim["HS_EM_PARTS"])
+    b = plan["blocks"]
+    assert b == dict(device_bytes=sum(map(step, results + workspace)), result_bytes=sum(map(step, results)), upload_bytes=sum(map(step, uploaded)),
+                     pieces=len(results) + len(workspace) + len(uploaded))
+    assert b["result_bytes"] <= b["device_bytes"]
+
+
 def test_every_route_has_a_case_or_a_reason(hmm_host, lim, cases):
     """The union of the cases' routes is every route the plan can name, except UNREACHABLE — which is exactly the set of routes without a
     case, each with its reason: a route added to the plan without a case fails here."""
