@@ -776,8 +776,20 @@ struct LocusShape {
   int32_t longest_B;               // longest STR option (at least 1)
   int n_options() const { return nopts[0] + nopts[1] + nopts[2]; }
 };
+const char* stutter_model_refusal(const double* sp){
+  for (int i = 0; i < 6; i++){         // on the bits: the build tells the compiler that there are no NaNs (-fno-honor-nans)
+    uint64_t u; memcpy(&u, sp + i, 8);
+    if (((u >> 52) & 0x7ff) == 0x7ff) return "stutter model value is not finite (stutter_model.h:35-39)";
+  }
+  if (!(sp[0] > 0.0 && sp[0] < 1.0) || !(sp[3] > 0.0 && sp[3] < 1.0)) return "stutter model geometric parameters must lie inside (0, 1) (stutter_model.h:35-39)";
+  if (!(sp[1] > 0.0 && sp[2] > 0.0 && sp[4] > 0.0 && sp[5] > 0.0)) return "stutter model up and down probabilities must be positive (stutter_model.h:35-39)";
+  if (!(sp[1] + sp[2] + sp[4] + sp[5] < 1.0)) return "stutter model up and down probabilities must sum to less than 1 (stutter_model.h:35-39)";
+  return NULL;
+}
+
 static int locus_shape(const hipstr_batch_t* b, int l, int opt0, LocusShape& s, std::string& err){
   if (b->period[l] < 1 || b->period[l] > 9){ err = "STR period must be in [1,9] (stutter_model.h:38)"; return 1; }
+  if (const char* why = stutter_model_refusal(b->stutter + 6*l)){ err = why; return 1; }
   int64_t A = 1;
   s.longest_B = 1;
   for (int k = 0, c = opt0; k < 3; k++){

@@ -115,6 +115,10 @@ double locus_cost(const hipstr_batch_t* b, int l, int opt0);
 // dims_out (optional): [0] = the longest realigned read, [1] = the longest STR allele of the locus — what the per-read STR kernels' LDS is
 // sized by, batch-wide (layout.h hs_str_kernel_lds_bytes): whoever puts loci into one batch keeps the combined figure within HS_LDS_LIMIT
 int check_locus(const hipstr_batch_t* b, int locus, int* opt_cursor_io, std::string& err, int32_t* seeds_out = NULL, int* dims_out = NULL);
+// The six numbers of a locus' stutter model (in-frame geom, up, down, out-of-frame geom, up, down) against StutterModel's constructor
+// asserts (stutter_model.h:35-39): NULL if the reference would take them, else the refusal.  A value that is not finite is refused too
+// (NaN fails every one of the reference's comparisons; an infinite one fails the one it takes part in).
+const char* stutter_model_refusal(const double* sp);
 
 // HapAligner::calc_seed_base (HapAligner.cpp:238-318).  Returns -2 on the inputs the reference dies on.
 int calc_seed_base(const hipstr_batch_t* b, int locus, int read);

@@ -1243,7 +1243,7 @@ AsmDense asm_dense(const hs_adev_t& a){
 
 // ---- what a request list means: the one walk, for the call and for both plans.  It makes every refusal that depends on the batch and the
 // list alone, in this order: per locus the period, then blocks without options; per request the read, the allele, the seed (trace_seed_of),
-// and for a (locus, allele) pair not seen before its blocks in order, then the flanks' total.
+// and for a (locus, allele) pair not seen before its locus' stutter model (stutter_model.h:35-39), its blocks in order, then the flanks' total.
 struct TracePair { int32_t locus, allele, opt[3], len[3]; };      // a distinct pair: the option (counted over the batch) and the bases of each block
 struct TraceRequests {
   std::vector<int32_t> locus, seed, len, pair, compact_off;       // per request; compact_off: its read among the requested reads, first come first
@@ -1282,6 +1282,7 @@ const char* trace_resolve(const hipstr_batch_t* b, int32_t n_req, const int32_t*
     const int64_t key = ((int64_t)l << 32) | (uint32_t)k;
     std::map<int64_t, int>::iterator hit = slot.find(key);
     if (hit == slot.end()){
+      if (const char* why = hipstr::stutter_model_refusal(b->stutter + 6*l)) return why;     // (a locus no request names is never read)
       TracePair p; p.locus = l; p.allele = k;
       int32_t oi[3];
       hipstr::allele_options(nopts, k, oi);

@@ -127,6 +127,68 @@ def _synth(**kw):
     return lambda: synth_to_batch(capi.SynthBatch(**kw))
 
 
+# ---- per-locus, asymmetric stutter models (tests/stutter_models.py): six loci each, one non-default model per locus
+def _model_case(first, **kw):
+    """A generator batch of six loci under the non-default models NON_DEFAULT[first], [first + 1], ... (the generator's switches are set
+    for the draw and put back)."""
+    import stutter_models as sm
+    return lambda: sm.synth(sm.rotate(sm.NON_DEFAULT, first)[:6], **kw)
+
+
+def _reads_of_alleles(lf, strs, rf, picks, flank=22):
+    """Reads that span the STR block: (source allele, bases of left flank, bases of right flank) each, with the CIGAR of an alignment
+    to allele 0 (the repeat-count difference as one insertion or deletion at the end of the block)."""
+    reads = []
+    for pick in picks:
+        s, nl, nr = pick if isinstance(pick, tuple) else (pick, flank, flank)
+        seq = lf[len(lf) - nl:] + strs[s] + rf[:nr]
+        d = len(strs[s]) - len(strs[0]); common = min(len(strs[s]), len(strs[0]))
+        cig = [("=", nl + common)] + ([("I", d)] if d > 0 else [("D", -d)] if d < 0 else []) + [("=", nr)]
+        reads.append((seq, None, len(lf) - nl, True, cig))
+    return reads
+
+
+def stutter_models_edges():
+    """Hand-built loci under asymmetric models throughout: period 1 and period 9; alleles shorter than the largest deletions (fewer
+    than six deletion sizes: the LARGE_NEGATIVE substitution meets unequal up / down values); a read inside the STR only (no seed);
+    -1 and +1 repeat stutter reads; reads drawn from every allele so that the tracebacks against the other alleles carry stutter
+    artifacts of both signs."""
+    import stutter_models as sm
+    b = capi.Batch()
+    M = sm.MODELS
+    # period 1: homopolymers down to one base
+    homo = ["A" * 12, "A" * 11, "A" * 14, "A" * 3, "A", "A" * 13]
+    lf1, rf1 = LF[:-1] + "C", "G" + RF[1:]
+    simple_locus(lf1, homo, rf1, 1, _reads_of_alleles(lf1, homo, rf1, [0, 1, 2, 5, (1, 30, 18), (2, 17, 31), (3, 25, 25), 0]),
+                 start=500, batch=b, stutter=M["down_heavy"])
+    # period 9
+    m9 = "ACGGTTCAG"
+    nine = [m9 * 5, m9 * 4, m9 * 6, m9 * 7, m9 * 2 + "ACGGTTCAT" + m9 * 2, m9 * 3]
+    simple_locus(LF, nine, RF, 9, _reads_of_alleles(LF, nine, RF, [0, 1, 2, 3, 4, 5, (1, 30, 19), (2, 18, 33)]),
+                 start=1500, batch=b, stutter=M["up_heavy"])
+    # period 6, alleles of less than one unit up to five: every deletion count from 0 to 5
+    six = ["ACGGTC" * 3, "ACGGTC" * 2, "ACGGTC", "ACGG", "AC", "ACGGTC" * 5, "ACGGTC" * 4]
+    hap6 = LF + six[0] + RF
+    reads6 = _reads_of_alleles(LF, six, RF, [0, 1, 2, 5, 6, (3, 28, 26), (4, 31, 30), (1, 19, 34)])
+    reads6.append((six[0][2:16], None, len(LF) + 2, True))                          # inside the STR only -> seed -1
+    simple_locus(LF, six, RF, 6, reads6, start=2500, batch=b, stutter=M["heavy"])
+    # period 3: a -1 and a +1 repeat stutter read next to reads of the alleles themselves
+    cag = ["CAG" * 8, "CAG" * 9, "CAG" * 7, "CAG" * 4 + "CAA" + "CAG" * 4, "CAG" * 12, "CAG" * 2]
+    reads3 = _reads_of_alleles(LF, cag, RF, [0, 1, 2, 3, 4, (5, 33, 32)])
+    reads3.append((LF[5:] + "CAG" * 7 + RF[:30], None, 5, True, [("=", 30), ("D", 3), ("=", 21 + 30)]))     # -1 repeat
+    reads3.append((LF[7:] + "CAG" * 9 + RF[:28], None, 7, True, [("=", 28 + 24), ("I", 3), ("=", 28)]))     # +1 repeat
+    reads3.append((cag[0][3:21], None, len(LF) + 3, True))                          # inside the STR only -> seed -1
+    simple_locus(LF, cag, RF, 3, reads3, start=3500, batch=b, stutter=M["flat_geom"])
+    # period 2 under the model whose step is the threshold itself, period 4 under the model with the smallest artifacts
+    gt = ["GT" * 10, "GT" * 9, "GT" * 12, "GT" * 7, "GT" * 2, "GT" * 5 + "GA" + "GT" * 5]
+    simple_locus(LF, gt, RF, 2, _reads_of_alleles(LF, gt, RF, [0, 1, 2, 3, 5, (4, 34, 30), (1, 20, 29), (2, 27, 18)]),
+                 start=4500, batch=b, stutter=M["em_clamp"])
+    agat = ["AGAT" * 6, "AGAT" * 7, "AGAT" * 5, "AGAT" * 3, "AGAT", "AGAT" * 9]
+    simple_locus(LF, agat, RF, 4, _reads_of_alleles(LF, agat, RF, [0, 1, 2, 3, 5, (4, 35, 35), (1, 24, 31), (2, 30, 20)]),
+                 start=5500, batch=b, stutter=M["tiny"])
+    return b.finalize()
+
+
 CASES = {
     "kat_survey": kat_survey,
     "edge_reads": edge_reads,
@@ -145,6 +207,11 @@ CASES = {
     # round 6: 4 x 60 x 4 = 960 candidate haplotypes, next to MAX_TOTAL_HAPLOTYPES = 1000 (genotyper_bam_processor.h:110, enforced at
     # seq_stutter_genotyper.cpp:610-614); fixtures by make_golden.py's "sizes" section
     "many_haplotypes": _synth(n_loci=1, reads_per_locus=12, n_str_alleles=60, n_flank_opts=4, seed=11),
+    # per-locus stutter models: periodic, interrupted (_pw) and inherited-interruption (_rp) generator batches, hand-built edges
+    "stutter_models_periodic": _model_case(0, n_loci=6, reads_per_locus=12, n_str_alleles=8, seed=301),
+    "stutter_models_interrupted": _model_case(3, imperfect=1.0, n_loci=6, reads_per_locus=12, n_str_alleles=8, n_flank_opts=2, mask_rate=0.2, seed=302),
+    "stutter_models_inherited": _model_case(6, inherit=2, n_loci=6, reads_per_locus=10, n_str_alleles=16, seed=303),
+    "stutter_models_edges": stutter_models_edges,
 }
 
 BIGPOST_STRIDE = 101

@@ -92,7 +92,7 @@ def cigar_vs_ref(read, hap_ref, offset):
     return [(o, n) for o, n in ops]
 
 
-def simple_locus(lf, str_opts, rf, period, reads, start=500, lf_opts=None, rf_opts=None, realign_hap=None, batch=None):
+def simple_locus(lf, str_opts, rf, period, reads, start=500, lf_opts=None, rf_opts=None, realign_hap=None, batch=None, stutter=STUTTER):
     """reads: list of (sequence, quals or None, offset into the reference haplotype, realign flag[, cigar])."""
     b = batch if batch is not None else capi.Batch()
     ref_hap = lf + str_opts[0] + rf
@@ -104,7 +104,7 @@ def simple_locus(lf, str_opts, rf, period, reads, start=500, lf_opts=None, rf_op
     blocks = [(start, start + len(lf), [lf] + (lf_opts or [])),
               (start + len(lf), start + len(lf) + len(str_opts[0]), list(str_opts)),
               (start + len(lf) + len(str_opts[0]), start + len(ref_hap), [rf] + (rf_opts or []))]
-    A = b.add_locus(blocks, period, STUTTER, rds, realign_hap=realign_hap)
+    A = b.add_locus(blocks, period, stutter, rds, realign_hap=realign_hap)
     return b, A
 
 
